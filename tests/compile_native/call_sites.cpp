@@ -16,8 +16,8 @@
 #error "the native-types branch was not selected: the stand-in headers are not on the include path"
 #endif
 
-// State, LidarMeasurement, LidarMeasurementPtr: the reference's own include/ESKF_LIO/Types.hpp (on the include path
-// of this check only; it is read where it lies, never copied)
+// State, LidarMeasurement, LidarMeasurementPtr: a stand-in for the reference's include/ESKF_LIO/Types.hpp
+// (stubs/ESKF_LIO/Types.hpp, on the include path of this check only)
 
 Eigen::Isometry3d filter_update(  // the part of ErrorStateKF::update that touches the path (src/ErrorStateKF.cpp:126-130)
   const std::shared_ptr<ESKF_LIO::ICP> & icp_, const ESKF_LIO::LidarMeasurement & lidar,

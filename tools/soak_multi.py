@@ -5,7 +5,7 @@ that give every thread several points), random round counts, converging and forc
 scans, interleaved with map mutations (replicated insert / erase) and the resident frame calls — every align compared
 with a single-device context on the same map: identical correspondence counts, normal equations and pose to rounding
 (sharding only regroups the sums), and the same bits when the multi-device align is repeated.
-usage: GPU_MAX_HW_QUEUES=24 python tools/soak_multi.py [seconds] [N]"""
+usage: python tools/soak_multi.py [seconds] [N]"""
 import os
 import sys
 import time
