@@ -100,15 +100,8 @@ __device__ __forceinline__ void fold_swap(double (&v)[kSlots]) {
 // the chain; a quarter of the dependent instructions of the IEEE division.
 __device__ __forceinline__ double rcp_newton(double d) {
   const double y = __builtin_amdgcn_rcp(d);
-#if defined(VGICP_RCP_TWO_STEPS)   // developer A/B: two second-order steps (what rounds 1-4 shipped): 4 dependent operations
-  double e = fma(-d, y, 1.0);
-  const double y1 = fma(y, e, y);
-  e = fma(-d, y1, 1.0);
-  return fma(y1, e, y1);
-#else
   const double e = fma(-d, y, 1.0);
   return fma(y, fma(e, e, e), y);
-#endif
 }
 
 // Fallback of the 6x6 solve: vgicp_math.h's ldlt6_solve — Eigen's pivoted LDLT with pseudo-inverted D, the
@@ -258,11 +251,7 @@ constexpr double kSmallAngle2 = 0x1.19799812dea10p-40;   // 9.999999999999998e-1
 __device__ __forceinline__ void se3_exp_device(const double* xi, Pose& T) {
   const double px = xi[0], py = xi[1], pz = xi[2], rx = xi[3], ry = xi[4], rz = xi[5];
   const double n2 = rx * rx + ry * ry + rz * rz;
-#if defined(VGICP_EXP_ANGLE_AXIS)   // developer A/B (tools/ab_build.sh): the angle-axis form for every step
-  if (true) {
-#else
   if (n2 > 0.25) {  // uniform on the solver wave
-#endif
     se3_exp_angle(xi, T);
     return;
   }
@@ -797,13 +786,7 @@ __device__ __forceinline__ unsigned long long publishable(double v) {
   return b == kRowUnset ? kRowNaN : b;
 }
 
-// Lanes <= kCountSlot (lane = slot): wait until the 16 consecutive rows at src are published and return
-// the sum of their words as the pairwise tree over ascending rows (tree_sum<16>, as the folds of iterate_kernel
-// do; rows that belong to no workgroup hold +0.0 for good).  All 64 lanes of the wave call it; false when
-// spin_limit polls did not suffice.  The 16 loads are in flight together (one address, immediate offsets).
-#ifndef VGICP_L2_DELAY
-#define VGICP_L2_DELAY 64      // s_sleep units (64 clocks each) a workgroup that is no folder waits before its first poll of the parts
-#endif
+constexpr int kL2Delay = 64;   // s_sleep units (64 clocks each) a workgroup that is no folder waits before its first poll of the parts
 // Lanes <= kCountSlot (lane = slot) end with the sum over the 16 consecutive rows at src, as the pairwise tree over
 // ascending rows (tree_sum<16>, as the folds of iterate_kernel do; rows that belong to no workgroup hold +0.0 for
 // good).  All 64 lanes of the wave call it; false when spin_limit polls did not suffice.
@@ -812,7 +795,7 @@ __device__ __forceinline__ unsigned long long publishable(double v) {
 // registers and half the loads per lane.  ONE poll of the eight words is in flight: two, three or four of them, issued a
 // fraction of a memory round trip apart so that a word which lands just after a poll has passed need not wait a whole
 // round trip for the next, made every round SLOWER (C2 +0.3 / +0.9 / +1.5 us: the polls of 256 workgroups queue at the
-// memory side, profiles/NOTES_dropped_experiments.md) — which is what led to VGICP_L2_DELAY: poll LESS.
+// memory side, profiles/NOTES_dropped_experiments.md) — which is what led to kL2Delay: poll LESS.
 template <bool SYSTEM>
 __device__ __forceinline__ bool poll_and_sum(const double* src, uint32_t lane, uint32_t spin_limit, double& sum) {
   constexpr int H = kFolders / 2;
@@ -1150,7 +1133,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a) {
         // ~1.5 us): polling the parts from the start only puts 240 workgroups' loads into the queues the 16 folders'
         // polls and stores go through.  One point per thread (C2): 6.82 -> 6.55 us per round with 64 units (50: 6.63,
         // 60 - 70: 6.55, 85: 6.9, 100: 7.1); several points per thread (C5): no gain, not delayed.
-        if (VGICP_L2_DELAY > 0 && !MANY && !folder) __builtin_amdgcn_s_sleep(VGICP_L2_DELAY);
+        if (!MANY && !folder) __builtin_amdgcn_s_sleep(kL2Delay);
         if (ok) ok = poll_and_sum<false>(parts, lane, a.spin_limit, tot);
       } else {
         // ---- several GPUs: workgroup 0 adds the parts to this rank's total and stores it into the mailbox

@@ -9,8 +9,8 @@
 //                contraction, same evaluation order), voxel key, find-or-CLAIM the voxel's slot
 //                (claims race through a CAS; same-key racers spin on the LOCKED word until the winner,
 //                which finishes its critical section inside the same loop iteration, publishes FULL)
-//   2. sort      stable radix sort of (slot, point index) by slot (hipCUB): the points of one voxel
-//                become one segment, still in scan order
+//   2. sort      stable sort of (slot, point index) by slot (rocPRIM's merge sort): the points of one
+//                voxel become one segment, still in scan order
 //   3. apply     the thread at the head of a segment walks it and applies the constructor / addPoint
 //                arithmetic of the reference sequentially, in registers, one record write at the end
 // Arithmetic is bit-exact with the CPU path (tests compare means, covariances and counts with `==`).
@@ -24,7 +24,8 @@
 //   2. apply     the leader walks the list, takes the points in ascending index = scan order (a register buffer of
 //                kListChunk indices per walk; longer lists take several walks: correct for any length, quadratic
 //                beyond the buffer, which is why arbitrary scans keep the sort), applies them, empties the list.
-#include <hipcub/hipcub.hpp>
+#include <cstring>   // rocprim/iterator/texture_cache_iterator.hpp calls memset without including it
+
 #include <rocprim/rocprim.hpp>
 
 #include "vgicp_device.h"
@@ -59,8 +60,8 @@ struct InsertScratch {
   uint32_t* slot_out;  // n (sorted)
   uint32_t* idx_in;    // n
   uint32_t* idx_out;   // n (sorted)
-  void* cub;           // radix sort temp storage
-  size_t cub_bytes;
+  void* temp;          // the sort's temporary storage
+  size_t temp_bytes;
 };
 
 __host__ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
@@ -80,7 +81,7 @@ __host__ inline size_t sort_temp_bytes(uint32_t n) {
   return bytes;
 }
 
-__host__ inline InsertScratch carve(void* base, uint32_t n, size_t cub_bytes) {
+__host__ inline InsertScratch carve(void* base, uint32_t n, size_t temp_bytes) {
   char* p = static_cast<char*>(base);
   InsertScratch s;
   s.wpts = reinterpret_cast<double*>(p); p += align256((size_t)n * 3 * sizeof(double));
@@ -89,8 +90,8 @@ __host__ inline InsertScratch carve(void* base, uint32_t n, size_t cub_bytes) {
   s.slot_out = reinterpret_cast<uint32_t*>(p); p += align256((size_t)n * sizeof(uint32_t));
   s.idx_in = reinterpret_cast<uint32_t*>(p); p += align256((size_t)n * sizeof(uint32_t));
   s.idx_out = reinterpret_cast<uint32_t*>(p); p += align256((size_t)n * sizeof(uint32_t));
-  s.cub = p;
-  s.cub_bytes = cub_bytes;
+  s.temp = p;
+  s.temp_bytes = temp_bytes;
   return s;
 }
 
@@ -350,8 +351,7 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
                              size_t scratch_bytes, uint32_t* counters, bool short_lists) {
   if (n == 0) return hipSuccess;
   if (scratch_bytes < map_insert_scratch_bytes(n)) return hipErrorInvalidValue;
-  size_t cub_bytes = sort_temp_bytes(n);
-  InsertScratch w = carve(scratch, n, cub_bytes);
+  InsertScratch w = carve(scratch, n, sort_temp_bytes(n));
   Pose12 pose;
   for (int k = 0; k < 12; ++k) pose.v[k] = pose12[k];
   if (short_lists) {
@@ -369,7 +369,7 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // stable: equal slots keep ascending point index = scan order
-  e = sort_slots(w.cub, cub_bytes, w.slot_in, w.slot_out, w.idx_in, w.idx_out, n, s);
+  e = sort_slots(w.temp, w.temp_bytes, w.slot_in, w.slot_out, w.idx_in, w.idx_out, n, s);
   if (e != hipSuccess) return e;
   for (uint64_t run = 2048; ; run <<= 1) {  // rocPRIM's merge sort: one block sort + one merge launch per doubling
     ++g_kernel_launches;

@@ -7,8 +7,8 @@
 // Here:
 //   1. every point gets the 60-bit Morton code of its cell on a grid of voxel_size / 4 (so that
 //      code >> 6 is the Morton code of the voxel, the same floor(p / h) as the map keys); ONE stable
-//      sort (rocPRIM merge sort) of (code, index) orders the scan so that the cells of every octree
-//      level — h/4, h/2, h, 2h, ... — are contiguous runs
+//      sort (vgicp_sort.h: wave tiles, then rank merges) of (code, index) orders the scan so that the cells of
+//      every octree level — h/4, h/2, h, 2h, ... — are contiguous runs
 //   2. the lowest index of every voxel-level run is the first point of its voxel: that is the
 //      down-sampling. One segmented scan over the sorted order yields, at the last point of every run,
 //      the voxel's rank, its kept point and that point's sorted position (the query list in Morton
@@ -18,16 +18,16 @@
 //      an octree whose nodes are contiguous runs of the sorted points (by the workgroups behind the scan's tiles
 //      in the same launch); query_split_body (keep_and_split_kernel) then puts the queries of sparse neighbourhoods -- the expensive
 //      ones -- at the head of the search's launch
-//   4. ONE WAVE per kept point (control flow is uniform, lanes share the work): the k-list starts
-//      full with sorted-order neighbours of the query; the finest own cell with >= k points ("home")
+//   4. ONE WAVE per kept point (control flow is uniform, lanes share the work): the candidates start
+//      with sorted-order neighbours of the query; the finest own cell with >= k points ("home")
 //      is measured first, and the k-th distance after it picks the level whose 27-cell block covers
 //      the ball; those cells seed a pool; the wave repeatedly takes the nearest cell of the pool
 //      (best-first), and either lets its lanes look up the 64 cells two levels below (one each) or,
-//      for a short run, lets them measure its points (one each); passing points are inserted into the
-//      sorted k-list the lanes hold in registers. It stops when the nearest cell left is farther than
-//      the k-th distance: the result is the EXACT k nearest neighbours, ties broken by index, for
-//      work proportional to what lies inside that ball (DESIGN.md §9 has the measurements behind
-//      every choice in this kernel)
+//      for a short run, lets them measure its points (one each); passing points join an unordered
+//      candidate buffer, whose bound a radix select tightens; the order is made once, at the end. It
+//      stops when the nearest cell left is farther than the k-th distance: the result is the EXACT k
+//      nearest neighbours, ties broken by index, for work proportional to what lies inside that ball
+//      (DESIGN.md §9 has the measurements behind every choice in this kernel)
 //   5. one THREAD per kept point: cumulants in ascending-distance order, Open3D's cumulant covariance, then
 //      svd.matrixU() diag(1,1,1e-2) svd.matrixV()^T with Eigen 3.4's two-sided JacobiSVD restated in its
 //      published operation order (U != V where an eigenvalue of the — in floating point possibly indefinite —
@@ -37,10 +37,6 @@
 // distances, sums and rotations round as they do on the CPU.
 #include <cstring>
 #include <string.h>
-
-#ifdef VGICP_SORT_ROCPRIM
-#include <rocprim/rocprim.hpp>
-#endif
 
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
@@ -64,26 +60,13 @@ constexpr int kPool = 256;             // cells waiting per query
 // (frame sweep, 29 151 queries: 128 -> 203 us, longest query 168 us; 256 -> 160 / 126; 512 -> 148 / 99; 1024 -> 153 / 98;
 // 64 -> +13 % on 128.  profiles/r10_knn_leaf.txt).  Round 6, with the candidates kept unordered (a point that passes costs
 // an append, not an insertion): 256 -> 115 us, 512 -> 95.5, **1024 -> 89.8**, 1536 -> 90.4, 2048 -> 91.5, 4096 -> 95.0.
-#ifndef VGICP_LEAF_POINTS
-#define VGICP_LEAF_POINTS 1024
-#endif
-constexpr uint32_t kLeafPoints = VGICP_LEAF_POINTS;
-// The neighbour search keeps its candidates unordered and makes the order once (round 6, knn_search_kernel);
-// -DVGICP_KNN_EAGER builds rounds 2-5's sorted k-list with one insertion per candidate instead (A/B: 104.9 -> 101.3 us
-// per 60 000-point sweep, the same bits; tools/soak_preprocess.py: 817 random scans against the oracle, no mismatch).
-#ifndef VGICP_KNN_EAGER
-#define VGICP_KNN_LAZY 1
-#endif
-#ifndef VGICP_KNN_TIGHTEN_AT
-#define VGICP_KNN_TIGHTEN_AT 40   // entries in the candidate buffer (of 64) at which the bound is tightened
-#endif
-#ifndef VGICP_KNN_SELECT_LOW
-#define VGICP_KNN_SELECT_LOW 15   // the select resolves bits 30 .. this one of the single-precision key (16 steps)
-#endif
-#ifndef VGICP_HOME_POINTS
-#define VGICP_HOME_POINTS 128
-#endif
-constexpr uint32_t kHomePoints = VGICP_HOME_POINTS;  // the query's own cell is measured whole when it holds at most this many
+constexpr uint32_t kLeafPoints = 1024;
+// The neighbour search keeps its candidates unordered and makes the order once (round 6, knn_search_kernel), against
+// rounds 2-5's sorted k-list with one insertion per candidate: 104.9 -> 101.3 us per 60 000-point sweep, the same bits
+// (tools/soak_preprocess.py: 817 random scans against the oracle, no mismatch).
+constexpr uint32_t kKnnTightenAt = 40;   // entries in the candidate buffer (of 64) at which the bound is tightened
+constexpr int kKnnSelectLow = 15;        // the select resolves bits 30 .. this one of the single-precision key (16 steps)
+constexpr uint32_t kHomePoints = 128;    // the query's own cell is measured whole when it holds at most this many
 constexpr int kCovBlock = 128;
 constexpr unsigned long long kEmptyCell = ~0ull;
 constexpr unsigned long long kKeyMask = (1ull << 60) - 1;
@@ -449,12 +432,7 @@ constexpr int kScanThreads = 256;
 // eight (run_scan_kernel at 60 000 points: 20.2 us with 8, 17.6 with 4, 16.7 with 2; keep_scan_kernel 5.5 / 5.1 / 5.1).
 constexpr int kScanItemsSmall = 4, kScanItemsLarge = 8;
 inline int scan_items_for(uint32_t n) {
-#ifdef VGICP_SCAN_ITEMS_LARGE_ONLY   // developer builds: the > 4 M-point variant at test sizes (tools/ab_build.sh items8 -DVGICP_SCAN_ITEMS_LARGE_ONLY)
-  (void)n;
-  return kScanItemsLarge;
-#else
   return (uint64_t)n <= (uint64_t)kMaxScanTiles * kScanThreads * kScanItemsSmall ? kScanItemsSmall : kScanItemsLarge;
-#endif
 }
 constexpr uint32_t kScanSpinLimit = 1u << 22;
 
@@ -810,14 +788,8 @@ __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) 
 // durations: frame sweep 147 -> 136 us, 100k-point sweep 244 -> 216 us, profiles/r10_knn_leaf.txt), the others follow in
 // (nearly) Morton order -- a workgroup's 1 024 queries stay together, the workgroups' blocks land in the order their atomics do.
 // The order of the queries changes nothing in what the search writes: every query owns its output slot.
-#ifndef VGICP_HEAVY_BELOW
-#define VGICP_HEAVY_BELOW 4
-#endif
-#ifndef VGICP_HEAVY_LEVEL
-#define VGICP_HEAVY_LEVEL 4
-#endif
-constexpr int kHeavyLevel = VGICP_HEAVY_LEVEL;
-constexpr uint32_t kHeavyBelow = VGICP_HEAVY_BELOW;
+constexpr int kHeavyLevel = 4;
+constexpr uint32_t kHeavyBelow = 4;
 constexpr int kSplitBlock = 1024;  // one atomic per list and workgroup: same-address atomics cost ~20 ns apiece
 __device__ __forceinline__ void query_split_body(uint32_t block, const double* __restrict__ spts, uint32_t n, double h,
                                                  const CellEntry* __restrict__ table, uint32_t mask,
@@ -895,10 +867,8 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
   __shared__ unsigned long long pool_key[kSearchBlock / 64][kPool];
   __shared__ uint32_t pool_start[kSearchBlock / 64][kPool];
   __shared__ uint32_t pool_end[kSearchBlock / 64][kPool];
-#ifdef VGICP_KNN_LAZY
   __shared__ double cand_d[kSearchBlock / 64][64];     // the candidates still in the race (at most 64), unordered
   __shared__ uint32_t cand_i[kSearchBlock / 64][64];
-#endif
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2: give every XCD one contiguous
@@ -943,16 +913,9 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
                qz = uniform_f64(spts[4 * (size_t)qj + 2]);
   const int K = knn < (int)n ? knn : (int)n;
   const uint64_t t_begin = debug >= 2 ? wall_clock64() : 0;
-#ifdef VGICP_PREP_TRACE
-  const uint64_t t_trace = wall_clock64();
-#endif
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
 
-  uint32_t batches = 0, pops = 0, spills = 0, inserts = 0;
-#ifdef VGICP_PREP_TRACE
-  uint32_t opens = 0, home_batches = 0;
-#endif
-  [[maybe_unused]] const unsigned long long list_lanes = K >= 64 ? ~0ull : (1ull << K) - 1ull;
+  uint32_t batches = 0, pops = 0, spills = 0;
 
   // squared distance to sorted point j and, from the same record, its original index
   auto dist2 = [&](uint32_t j, uint32_t& id) {
@@ -984,14 +947,11 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
   // sorted order costs more insertions than the best-first search needs; 64: 270 us, 128 / 256: 250 us, no cap: 308 us)
   const bool has_home = enough != 0 && home_end - home_start <= kHomePoints;
 
-  // The k-list: lane l < K holds the l-th nearest so far, by (distance, index). It starts FULL, from consecutive points
-  // of the sorted order around the query (inside home when there is one): real points and usually near ones. The
-  // search skips the points it has measured here when it meets them again (sorted positions skip_start ..
-  // skip_start + skip_count - 1).  (-DVGICP_KNN_SEEDS_ONLY keeps the opening of rounds 2-5 for A/B runs: K seeds.)
-#ifdef VGICP_KNN_LAZY
-  // ---- round 6: the candidates are kept UNORDERED until the end ---------------------------------------------------
-  // What the search needs while it runs is one number, an upper bound of the K-th distance so far (it filters points
-  // and prunes cells); the ORDER of the K nearest is needed once, at the end.  Rounds 2-5 kept a sorted list and paid
+  // The candidates start from up to 64 consecutive points of the sorted order around the query (inside home when there
+  // is one): real points and usually near ones. The search skips the points it has measured here when it meets them
+  // again (sorted positions skip_start .. skip_start + skip_count - 1).
+  // They are kept UNORDERED until the end (round 6).  What the search needs while it runs is one number, an upper bound
+  // of the K-th distance so far (it filters points and prunes cells); the ORDER of the K nearest is needed once, at the end.  Rounds 2-5 kept a sorted list and paid
   // ~15 instructions per candidate that passed (27 per query) plus an all-pairs ranking of the 64-point opening window
   // (~200).  Here the candidates that pass the bound are appended to a buffer of at most 64 (lane l mirrors entry l),
   // and after every batch that brought any the bound is tightened by a RADIX SELECT over single-precision keys rounded
@@ -1011,17 +971,17 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
   uint32_t cnt = 0;               // uniform
   double kth = INFINITY;          // uniform: an upper bound of the K-th smallest distance among the points seen so far
   // K-th smallest single-precision key (distances rounded UP; non-negative floats order as unsigned integers) among the
-  // cnt entries, to its 16 leading bits (VGICP_KNN_SELECT_LOW), rounded up: the new bound.  Entries above it leave the buffer.
+  // cnt entries, to its 16 leading bits (kKnnSelectLow), rounded up: the new bound.  Entries above it leave the buffer.
   auto tighten = [&]() {
     const uint32_t fkey = (uint32_t)lane < cnt ? __builtin_bit_cast(uint32_t, __double2float_ru(ld)) : 0xFFFFFFFFu;
     uint32_t prefix = 0;
 #pragma unroll
-    for (int bit = 30; bit >= VGICP_KNN_SELECT_LOW; --bit) {
+    for (int bit = 30; bit >= kKnnSelectLow; --bit) {
       const uint32_t trial = prefix | (1u << bit);
       const uint32_t below = (uint32_t)__builtin_popcountll(__ballot(fkey < trial));
       if (below < (uint32_t)K) prefix = trial;   // the K-th key has this bit set
     }
-    const uint32_t top = prefix | ((1u << VGICP_KNN_SELECT_LOW) - 1u);
+    const uint32_t top = prefix | ((1u << kKnnSelectLow) - 1u);
     const bool keep = fkey <= top;
     const unsigned long long who = __ballot(keep);
     const uint32_t kept = (uint32_t)__builtin_popcountll(who);
@@ -1072,9 +1032,9 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
       kth = uniform_f64(mx);
     }
   }
-  uint32_t kth_id = 0xFFFFFFFFu;   // (ties at the bound are admitted: the order is settled at the end)
   double bound = kth;
-  // every lane brings one candidate (valid, d, id, j); the ones at or below the bound join the buffer
+  // every lane brings one candidate (valid, d, id, j); the ones at or below the bound join the buffer (ties at the bound
+  // are admitted: the order is settled at the end)
   auto offer = [&](bool valid, double d, uint32_t id, uint32_t j) {
     ++batches;
     bool pass = valid & (j - skip_start >= skip_count) & (d <= kth);
@@ -1084,14 +1044,12 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
       const uint32_t ahead = (uint32_t)__builtin_popcountll(todo & lanes_below);
       const bool now = pass && ahead < room;
       if (now) { cdv[cnt + ahead] = d; civ[cnt + ahead] = id; }
-      const uint32_t took = (uint32_t)__builtin_popcountll(__ballot(now));
-      inserts += took;
-      cnt += took;
+      cnt += (uint32_t)__builtin_popcountll(__ballot(now));
       // ... but not after every batch: a select costs ~35 vector instructions, a candidate that slips in under a stale
-      // bound ~2.  The bound is tightened when the buffer holds VGICP_KNN_TIGHTEN_AT entries, or when candidates of this
+      // bound ~2.  The bound is tightened when the buffer holds kKnnTightenAt entries, or when candidates of this
       // batch are still waiting for room (A/B on the 60 000-point frame sweep: after every batch 100.4 us; at 40 / 48 /
       // 56 / 64 entries 95.8 / 96.6 / 95.1 / 96.3; at 40 with 16 instead of 20 bits of the key: 94.7)
-      if (cnt > (uint32_t)K && (cnt >= (uint32_t)VGICP_KNN_TIGHTEN_AT || (todo & ~__ballot(now)) != 0ull)) {
+      if (cnt > (uint32_t)K && (cnt >= kKnnTightenAt || (todo & ~__ballot(now)) != 0ull)) {
         wave_sync();   // (the lanes' mirror of the buffer is brought up to date only where somebody reads it)
         if ((uint32_t)lane < cnt) { ld = cdv[lane]; li = civ[lane]; }
         tighten();
@@ -1100,154 +1058,8 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
       todo = __ballot(pass);
     }
   };
-  (void)kth_id;
-#else
-#ifndef VGICP_KNN_SEEDS_ONLY
-  // The opening window: up to 64 consecutive points of the sorted order around the query (inside home when there is
-  // one), one per lane.  All of them are ranked against each other at once -- every lane counts the keys below its
-  // own, the keys read one after the other from this wave's (still empty) pool: one LDS broadcast read, one compare
-  // and one add per key -- and the K lowest are the list.  (Rounds 2-5 ranked K seeds with three v_readlane per key
-  // and inserted the rest of home one candidate at a time: 38 insertions of ~16 instructions per query.)
-  const uint32_t span_lo = has_home ? home_start : 0u, span_hi = has_home ? home_end : n;
-  const uint32_t W = span_hi - span_lo < 64u ? span_hi - span_lo : 64u;   // >= K: home holds K points, and K <= n
-  uint32_t w0 = qj > W / 2 ? qj - W / 2 : 0;
-  if (w0 < span_lo) w0 = span_lo;
-  if (w0 + W > span_hi) w0 = span_hi - W;
-  uint32_t skip_start = w0, skip_count = W;
-  double ld = INFINITY;
-  uint32_t li = 0xFFFFFFFFu;
-  {
-    const bool mine = (uint32_t)lane < W;
-    uint32_t id = 0xFFFFFFFFu;
-    double d = INFINITY;
-    if (mine) d = dist2(w0 + (uint32_t)lane, id);
-    if (!(d < INFINITY)) d = INFINITY;  // a NaN / infinite point is a placeholder that everything finite displaces
-    // squared distances are non-negative: their bit patterns order as unsigned integers
-    const unsigned long long key = (unsigned long long)__double_as_longlong(d);
-    pk[lane] = key;
-    ps[lane] = id;
-    wave_sync();
-    uint32_t rank = 0;
-#pragma unroll 16
-    for (int s = 0; s < 64; ++s) rank += pk[s] < key ? 1u : 0u;
-    // equal distances (rare) give equal ranks: found out by two lanes claiming one slot, settled by the index
-    if (mine) pe[rank] = (uint32_t)lane;
-    wave_sync();
-    const bool clash = mine && pe[rank] != (uint32_t)lane;
-    if (__ballot(clash)) {
-      rank = 0;
-      for (int s = 0; s < 64; ++s) {
-        const unsigned long long ks = pk[s];
-        const uint32_t is = ps[s];
-        rank += ((ks < key) | ((ks == key) & (is < id))) ? 1u : 0u;
-      }
-    }
-    wave_sync();   // every lane has read all keys: the slots can be rewritten in rank order
-    if (mine) {
-      pk[rank] = key;
-      ps[rank] = id;
-    }
-    wave_sync();
-    if (lane < K) {
-      ld = __longlong_as_double((long long)pk[lane]);
-      li = ps[lane];
-    }
-    wave_sync();
-  }
-#else
-  const uint32_t half = (uint32_t)K / 2;
-  uint32_t w0 = qj > half ? qj - half : 0;
-  if (has_home) {
-    if (w0 < home_start) w0 = home_start;
-    if (w0 + (uint32_t)K > home_end) w0 = home_end - (uint32_t)K;
-  } else if (w0 + (uint32_t)K > n) {
-    w0 = n - (uint32_t)K;
-  }
-  uint32_t skip_start = w0, skip_count = (uint32_t)K;
-  double ld = INFINITY;
-  uint32_t li = 0xFFFFFFFFu;
-  {
-    const bool mine = lane < K;
-    uint32_t id = 0xFFFFFFFFu;
-    double d = INFINITY;
-    if (mine) d = dist2(w0 + (uint32_t)lane, id);
-    if (!(d < INFINITY)) d = INFINITY;  // a NaN / infinite point is a placeholder that everything finite displaces
-    // rank of every seed among the seeds (all distinct by index), then one trip through this wave's (still
-    // empty) pool to put lane l's entry into lane rank(l)
-    uint32_t rank = 0;
-    for (int s = 0; s < K; ++s) {
-      const double sd = readlane_f64(d, s);
-      const uint32_t si = (uint32_t)__builtin_amdgcn_readlane((int)id, s);
-      rank += ((sd < d) | ((sd == d) & (si < id))) ? 1u : 0u;
-    }
-    if (mine) {
-      pk[rank] = (unsigned long long)__double_as_longlong(d);
-      ps[rank] = id;
-    }
-    wave_sync();
-    if (mine) {
-      ld = __longlong_as_double((long long)pk[lane]);
-      li = ps[lane];
-    }
-    wave_sync();
-  }
-#endif
-  double kth = readlane_f64(ld, K - 1);
-  uint32_t kth_id = (uint32_t)__builtin_amdgcn_readlane((int)li, K - 1);
-  double bound = kth;
-
-  // every lane brings one candidate (valid, d, id, j); the passing ones are inserted one after the other
-  auto offer = [&](bool valid, double d, uint32_t id, uint32_t j) {
-    ++batches;
-    const bool pass = valid & (j - skip_start >= skip_count) & (d <= bound) & ((d < kth) | ((d == kth) & (id < kth_id)));
-    unsigned long long todo = __ballot(pass);
-    bool moved = false;
-    while (todo) {
-      const int src = __builtin_ctzll(todo);
-      todo &= todo - 1;
-      const double cd = readlane_f64(d, src);
-      const uint32_t ci = (uint32_t)__builtin_amdgcn_readlane((int)id, src);
-      // how many entries come before the candidate (scalar mask arithmetic; equal distances are rare and take
-      // the uniform branch). Lanes >= K hold whatever was pushed out and are masked off.
-      unsigned long long before = __ballot(ld < cd);
-      const unsigned long long same = __ballot(ld == cd) & list_lanes;
-      if (same) before |= same & __ballot(li < ci);
-      const int p = __builtin_popcountll(before & list_lanes);
-      if (p >= K) continue;  // the list moved on since the batch was filtered
-      ++inserts;
-      // lanes above p take the entry of the lane below (one DPP select per dword, lanes <= p keep theirs), then
-      // lane p is overwritten from the scalar registers (v_writelane): 7 VALU instructions for the whole
-      // shift-and-insert. (A DPP operand written by the instruction before needs two wait states: s_nop 1.)
-      uint32_t lo = (uint32_t)__double_as_longlong(ld), hi = (uint32_t)((unsigned long long)__double_as_longlong(ld) >> 32);
-      const unsigned long long cbits = (unsigned long long)__double_as_longlong(cd);
-      uint32_t m0_saved;
-      asm volatile(
-          "s_nop 1\n\t"
-          "v_cmp_ge_u32_e32 vcc, %4, %5\n\t"
-          "s_mov_b32 %3, m0\n\t"
-          "s_mov_b32 m0, %4\n\t"
-          "v_cndmask_b32_dpp %0, %0, %0, vcc wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-          "v_cndmask_b32_dpp %1, %1, %1, vcc wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-          "v_cndmask_b32_dpp %2, %2, %2, vcc wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-          "v_writelane_b32 %0, %6, m0\n\t"
-          "v_writelane_b32 %1, %7, m0\n\t"
-          "v_writelane_b32 %2, %8, m0\n\t"
-          "s_mov_b32 m0, %3"
-          : "+v"(lo), "+v"(hi), "+v"(li), "=&s"(m0_saved)
-          : "s"(p), "v"(lane), "s"((uint32_t)cbits), "s"((uint32_t)(cbits >> 32)), "s"(ci)
-          : "vcc");
-      ld = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-      moved = true;
-    }
-    if (moved) {  // the k-th entry is read back once per batch: inside the loop the list itself decides (p >= K)
-      kth = readlane_f64(ld, K - 1);
-      kth_id = (uint32_t)__builtin_amdgcn_readlane((int)li, K - 1);
-    }
-  };
-#endif  // VGICP_KNN_LAZY
   if (has_home) {
     // the rest of home, then home as a whole is what the search skips; all K are now within home's diagonal
-#ifndef VGICP_KNN_SEEDS_ONLY
     const uint32_t rest = (home_end - home_start) - skip_count;   // home's points outside the opening window
     for (uint32_t base = 0; base < rest; base += 64u) {
       const uint32_t t = base + (uint32_t)lane;
@@ -1259,19 +1071,6 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
       if (valid) d = dist2(j, id);
       offer(valid, d, id, j);
     }
-#else
-    for (uint32_t base = home_start; base < home_end; base += 64u) {
-      const uint32_t j = base + (uint32_t)lane;
-      const bool valid = j < home_end;
-      uint32_t id = 0xFFFFFFFFu;
-      double d = INFINITY;
-      if (valid) d = dist2(j, id);
-      offer(valid, d, id, j);
-    }
-#endif
-#ifdef VGICP_PREP_TRACE
-    home_batches = batches;
-#endif
     skip_start = home_start;
     skip_count = home_end - home_start;
     bound = fmin(bound, kth);
@@ -1421,9 +1220,6 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
       const unsigned long long mk = key & kKeyMask;
             bool measure = l == 0 || end - start <= kLeafPoints;
       if (!measure) {  // one lane per cell two levels down (one level above the finest)
-#ifdef VGICP_PREP_TRACE
-        ++opens;
-#endif
         const int step = l >= 2 ? 2 : 1;
         const int fan = 1 << (3 * step);
         const unsigned long long cm = (mk << (3 * step)) | (unsigned long long)lane;
@@ -1479,7 +1275,6 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
   if (lane == 0 && spills && debug) atomicAdd(&counters[2], 1u);
   const uint32_t qi = uniform_u32(sorted_idx[qj]);
   const uint32_t o = uniform_u32(slot_of_index[qi]);
-#ifdef VGICP_KNN_LAZY
   {
     // the order, once: rank of every survivor by (distance, index) among the survivors (all distinct by index)
     wave_sync();
@@ -1493,27 +1288,10 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
     }
     if ((uint32_t)lane < cnt && rank < (uint32_t)K) nbr[(size_t)o * kMaxKnn + rank] = li;
   }
-#else
-  if (lane < kMaxKnn) nbr[(size_t)o * kMaxKnn + lane] = li;  // original indices: the list carries nothing else
-#endif
   if (lane == 0) {
     out_pts[3 * (size_t)o] = qx; out_pts[3 * (size_t)o + 1] = qy; out_pts[3 * (size_t)o + 2] = qz;
     if (soa) { soa[o] = qx; soa[soa_stride + o] = qy; soa[2 * soa_stride + o] = qz; }  // the planes the registration reads
     out_idx[o] = qi;
-#ifdef VGICP_PREP_TRACE  // developer build only (tools/ab_build.sh trace -DVGICP_PREP_TRACE): the index output carries a trace record
-    {
-      // the 10-bit field: cells taken (1), insertions (2), points in the query's own level-5 / level-4 cell (4 / 6), the
-      // finest level whose own cell holds K points (5)
-      const uint32_t trace_field = VGICP_PREP_TRACE == 2 ? inserts : VGICP_PREP_TRACE == 7 ? batches : VGICP_PREP_TRACE == 8 ? opens
-                                 : VGICP_PREP_TRACE == 9 ? home_batches
-                                 : VGICP_PREP_TRACE == 4 ? (uint32_t)__builtin_amdgcn_readlane((int)(own_end - own_start), 5)
-                                 : VGICP_PREP_TRACE == 6 ? (uint32_t)__builtin_amdgcn_readlane((int)(own_end - own_start), 4)
-                                 : VGICP_PREP_TRACE == 5 ? (enough ? (uint32_t)home_level : 15u) : pops;
-      const uint64_t t_end = wall_clock64();
-      uint64_t dt = t_end - t_trace; if (dt > 0xFFFFFu) dt = 0xFFFFFu;
-      out_idx[o] = (dt << 44) | ((uint64_t)(trace_field > 1023u ? 1023u : trace_field) << 34) | ((uint64_t)((VGICP_PREP_TRACE == 3 ? (int)(blockIdx.x % 8u) : level) & 15) << 30) | ((t_trace / 10u) & 0x3FFFFFFFu);
-    }
-#endif
     if (debug) {
       atomicAdd(&counters[3], batches);
       atomicMax(&counters[4], batches);
@@ -1953,37 +1731,12 @@ __host__ inline uint64_t pow2_at_least(uint64_t v) { uint64_t p = 1; while (p < 
 //   points           28k   33k   60k   65k   66k  100k  130k  150k  250k  300k
 //   2 048 per block  35.5  50.8  50.9  51.3  48.7  50.1  52.7  70.8 108.1 115.8
 //   4 096 per block  43.8  42.3  43.7  43.1  59.1  60.2  62.0  60.5  93.9 119.3
-// -DVGICP_SORT_ROCPRIM builds that one again (A/B measurements only).
-#ifdef VGICP_SORT_ROCPRIM
-inline bool sort_in_large_blocks(uint32_t n) { return (n > 32768u && n <= 65536u) || (n > 131072u && n <= 262144u); }
-inline hipError_t sort_codes_rocprim(void* temp, size_t& temp_bytes, const unsigned long long* codes_in,
-                                     unsigned long long* codes_out, const uint32_t* idx_in, uint32_t* idx_out, uint32_t n,
-                                     hipStream_t s) {
-  if (sort_in_large_blocks(n)) {
-    using Large = rocprim::merge_sort_config<512, 1024, 4>;
-    return rocprim::merge_sort<Large>(temp, temp_bytes, codes_in, codes_out, idx_in, idx_out, (size_t)n,
-                                      rocprim::less<unsigned long long>(), s);
-  }
-  using Config = rocprim::merge_sort_config<512, 512, 4>;
-  return rocprim::merge_sort<Config>(temp, temp_bytes, codes_in, codes_out, idx_in, idx_out, (size_t)n,
-                                     rocprim::less<unsigned long long>(), s);
-}
-#endif
-
 struct Layout {
-  size_t codes_in, codes_out, idx_in, idx_out, spts, keep_i, rank_i, queries, nbr, cub, total;
-  size_t cub_bytes;
+  size_t codes_in, codes_out, idx_in, idx_out, spts, keep_i, rank_i, queries, nbr, split, total;
 };
 
 __host__ inline Layout layout_for(uint32_t n) {
   Layout L;
-  size_t sort_pairs = 0;
-#ifdef VGICP_SORT_ROCPRIM
-  (void)sort_codes_rocprim(nullptr, sort_pairs, nullptr, nullptr, nullptr, nullptr, n, nullptr);
-#else
-  sort_pairs = sortk::split_bytes(n, sizeof(unsigned long long));   // the runs' splitters; the pairs alternate between the in and out buffers
-#endif
-  L.cub_bytes = sort_pairs;
   size_t off = 0;
   L.codes_in = off; off += align256((size_t)n * 8);
   L.codes_out = off; off += align256((size_t)n * 8);
@@ -1994,7 +1747,8 @@ __host__ inline Layout layout_for(uint32_t n) {
   L.rank_i = off; off += align256((size_t)n * 4);
   L.queries = off; off += align256((size_t)n * 4);
   L.nbr = off; off += align256((size_t)n * kMaxKnn * 4);
-  L.cub = off; off += align256(L.cub_bytes);
+  // the sort's splitters; the pairs alternate between the in and out buffers
+  L.split = off; off += align256(sortk::split_bytes(n, sizeof(unsigned long long)));
   L.total = off + 256;
   return L;
 }
@@ -2018,19 +1772,6 @@ size_t preprocess_cell_bytes(uint64_t entries) { return entries * sizeof(CellEnt
 size_t preprocess_tile_bytes() {   // tile slots of the two scans + the prologue's look-back slots
   return (size_t)kMaxScanTiles * (sizeof(TileSlot) + sizeof(unsigned long long)) + (size_t)kFusedBoundsBlocksMax * sizeof(unsigned long long);
 }
-
-namespace {
-// launches of the sort
-uint32_t merge_sort_launches(uint32_t n) {
-#ifdef VGICP_SORT_ROCPRIM
-  uint32_t launches = 1;
-  for (uint64_t run = sort_in_large_blocks(n) ? 4096 : 2048; run < n; run <<= 1) ++launches;
-  return launches;
-#else
-  return sortk::launches_for(n);
-#endif
-}
-}  // namespace
 
 hipError_t launch_fetch(hipStream_t s, const double* aos_pts, const double* aos_cov, const uint32_t* counters, uint32_t epoch,
                         uint32_t n_cap, char* stage, uint32_t* flags, unsigned long long* hdr_done, uint32_t seq,
@@ -2057,8 +1798,7 @@ struct PrepareBuffers {
   uint32_t mask;
   TileSlot* tiles_a;
   unsigned long long* tiles_b;
-  char* cub;
-  size_t cub_bytes;
+  char* split;
 };
 PrepareBuffers prepare_buffers(const PrepareArgs& a) {
   const Layout L = layout_for(a.n);
@@ -2077,8 +1817,7 @@ PrepareBuffers prepare_buffers(const PrepareArgs& a) {
   B.mask = (uint32_t)(a.table_entries - 1);
   B.tiles_a = static_cast<TileSlot*>(a.tiles);
   B.tiles_b = reinterpret_cast<unsigned long long*>(static_cast<char*>(a.tiles) + (size_t)kMaxScanTiles * sizeof(TileSlot));
-  B.cub = b + L.cub;
-  B.cub_bytes = L.cub_bytes;
+  B.split = b + L.split;
   return B;
 }
 }  // namespace
@@ -2171,14 +1910,9 @@ hipError_t launch_prepare_tail(hipStream_t s, const PrepareArgs& a) {
   unsigned long long* tiles_b = B.tiles_b;
 
   // ---- the one sort ----
-#ifdef VGICP_SORT_ROCPRIM
-  size_t cub_bytes = B.cub_bytes;
-  hipError_t e = sort_codes_rocprim(B.cub, cub_bytes, codes_in, codes_out, idx_in, idx_out, n, s);
-#else
-  hipError_t e = sortk::sort_pairs(codes_in, idx_in, codes_out, idx_out, B.cub, n, s);   // the inputs are scratch from here on
-#endif
+  hipError_t e = sortk::sort_pairs(codes_in, idx_in, codes_out, idx_out, B.split, n, s);   // the inputs are scratch from here on
   if (e != hipSuccess) return e;
-  g_kernel_launches += merge_sort_launches(n);
+  g_kernel_launches += sortk::launches_for(n);
 
   // ---- runs, kept points, query list (one launch); output slots in scan order (one launch) ----
   const uint32_t items = (uint32_t)scan_items_for(n);

@@ -20,7 +20,7 @@
 //      Every step is taken for all other runs at once, so a wave waits for four loads in a row whatever G is; what G
 //      costs is instructions: measured 4 us + 0.85 .. 1.3 us per other run and level (60 000 pairs, one wave per SIMD:
 //      nothing hides anything), i.e. 5.2 / 6.5 / 11.4 / 24 us per level for G = 2 / 4 / 8 / 16, and 60 000 pairs need
-//      8 / 4 / 3 / 2 levels: G = 4 it is (tools/ab_sort.sh; -DVGICP_SORT_MAX_GROUP=8 or 16 builds the others).
+//      8 / 4 / 3 / 2 levels: G = 4 it is (tools/ab_sort.sh).
 // 60 000 pairs: 8 + 4 x 6.5 = 34 us in the frame chain against 42.5 us (same session, tools/ab_kernel.sh).
 //
 // The two buffers alternate; sort_pairs says where the result is wanted and starts on the side that ends there.
@@ -32,10 +32,8 @@
 namespace vgicp {
 namespace sortk {
 
-#ifndef VGICP_SORT_MAX_GROUP
-#define VGICP_SORT_MAX_GROUP 4
-#endif
-constexpr int kMaxGroup = VGICP_SORT_MAX_GROUP;   // runs merged by one launch, at most (2, 4, 8 or 16)
+constexpr int kMaxGroup = 4;               // runs merged by one launch, at most (2 or 4)
+static_assert(kMaxGroup == 4, "sort_pairs launches rank_merge_kernel<K, 2> and <K, 4> only");
 constexpr uint32_t kTile = 256;            // pairs a wave sorts
 constexpr uint32_t kTileThreads = 256;     // four waves, four tiles per block
 constexpr uint32_t kMergeThreads = 256;
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(kMergeThreads) void rank_merge_kernel(const K* __re
   unsigned long long start[R];
 #pragma unroll
   for (int j = 0; j < R; ++j) start[j] = group_start + ((unsigned long long)((uint32_t)j + ((uint32_t)j >= own ? 1u : 0u)) << run_log2);
-#define VGICP_SORT_BEFORE(j, m, x) ((uint32_t)(j) < own ? !((x) < (m)) : (m) < (x))
+#define SORTK_BEFORE(j, m, x) ((uint32_t)(j) < own ? !((x) < (m)) : (m) < (x))
   // --- where the wave's first and last key fall in every other run: pf[j] <= every lane's count <= pl[j] ---
   uint32_t pf[R], pl[R];
   uint32_t range = run >> 6;                                    // what is left to search after the splitters
@@ -173,8 +171,8 @@ __global__ __launch_bounds__(kMergeThreads) void rank_merge_kernel(const K* __re
     }
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-      pf[j] = (uint32_t)__builtin_popcountll(__ballot(VGICP_SORT_BEFORE(j, sv[j], k_first))) * range;
-      pl[j] = (uint32_t)__builtin_popcountll(__ballot(VGICP_SORT_BEFORE(j, sv[j], k_last))) * range;
+      pf[j] = (uint32_t)__builtin_popcountll(__ballot(SORTK_BEFORE(j, sv[j], k_first))) * range;
+      pl[j] = (uint32_t)__builtin_popcountll(__ballot(SORTK_BEFORE(j, sv[j], k_last))) * range;
     }
   }
   while (range > 64u) {                                         // runs beyond 4 096: every (range / 64)-th key of the part
@@ -190,8 +188,8 @@ __global__ __launch_bounds__(kMergeThreads) void rank_merge_kernel(const K* __re
     }
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-      pf[j] += (uint32_t)__builtin_popcountll(__ballot(VGICP_SORT_BEFORE(j, a[j], k_first))) * st;
-      pl[j] += (uint32_t)__builtin_popcountll(__ballot(VGICP_SORT_BEFORE(j, b[j], k_last))) * st;
+      pf[j] += (uint32_t)__builtin_popcountll(__ballot(SORTK_BEFORE(j, a[j], k_first))) * st;
+      pl[j] += (uint32_t)__builtin_popcountll(__ballot(SORTK_BEFORE(j, b[j], k_last))) * st;
     }
     range = st;
   }
@@ -207,8 +205,8 @@ __global__ __launch_bounds__(kMergeThreads) void rank_merge_kernel(const K* __re
     }
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-      pf[j] += (uint32_t)__builtin_popcountll(__ballot(VGICP_SORT_BEFORE(j, a[j], k_first)));
-      pl[j] += (uint32_t)__builtin_popcountll(__ballot(VGICP_SORT_BEFORE(j, b[j], k_last)));
+      pf[j] += (uint32_t)__builtin_popcountll(__ballot(SORTK_BEFORE(j, a[j], k_first)));
+      pl[j] += (uint32_t)__builtin_popcountll(__ballot(SORTK_BEFORE(j, b[j], k_last)));
     }
   }
   // --- the windows [pf, pl) of all other runs, one behind the other, in LDS; every lane counts inside them ---
@@ -267,37 +265,43 @@ __global__ __launch_bounds__(kMergeThreads) void rank_merge_kernel(const K* __re
 #pragma unroll
     for (int j = 0; j < R; ++j) {
       const uint32_t half = rem[j] >> 1;
-      const bool right = rem[j] > 0u && VGICP_SORT_BEFORE(j, m[j], key);
+      const bool right = rem[j] > 0u && SORTK_BEFORE(j, m[j], key);
       p[j] = right ? p[j] + half + 1u : p[j];
       rem[j] = right ? rem[j] - half - 1u : half;
     }
   }
 #pragma unroll
   for (int j = 0; j < R; ++j) rank += p[j];
-#undef VGICP_SORT_BEFORE
+#undef SORTK_BEFORE
   if (!valid) return;
   const unsigned long long to = group_start + rank;
   keys_out[to] = key;
   idx_out[to] = my_idx;
   if (split_out) {                                               // the merged run's splitters: S = G run / 64
-    constexpr uint32_t g_log2 = G == 2 ? 1u : G == 4 ? 2u : G == 8 ? 3u : 4u;
+    constexpr uint32_t g_log2 = G == 2 ? 1u : 2u;
     const uint32_t s_log2 = run_log2 + g_log2 - 6u;
     if ((to & ((1ull << s_log2) - 1u)) == (1ull << s_log2) - 1u) split_out[to >> s_log2] = key;
   }
 }
 
-// how the runs of a scan of n pairs are merged: the group sizes of the levels (each 2, 4, 8 or 16), fewest levels first,
-// then the smallest groups that still finish in that many
+// how the runs of a scan of n pairs are merged: the group sizes of the levels (each 2 or 4), fewest levels first, then
+// the smallest groups that still finish in that many
+constexpr int levels_for(uint64_t runs) {
+  int levels = 0;
+  for (uint64_t reach = 1; reach < runs; reach *= kMaxGroup) ++levels;
+  return levels;
+}
+constexpr int kMaxLevels = 12;             // the largest n: 2^32 / 256 = 4^12 tiles
+static_assert(levels_for((0xFFFFFFFFull + kTile - 1) / kTile) <= kMaxLevels, "Plan::group cannot hold the levels of the largest scan");
 struct Plan {
   int levels;
-  int group[8];
+  int group[kMaxLevels];
 };
 inline Plan plan_for(uint32_t n) {
   Plan p;
   p.levels = 0;
   uint64_t runs = ((uint64_t)n + kTile - 1) / kTile;
-  int levels = 0;
-  for (uint64_t reach = 1; reach < runs; reach *= kMaxGroup) ++levels;
+  const int levels = levels_for(runs);
   for (int l = 0; l < levels; ++l) {
     const int left = levels - l;                 // levels still to come, this one included
     int g = 2;
@@ -338,11 +342,9 @@ inline hipError_t sort_pairs(K* keys_a, uint32_t* idx_a, K* keys_b, uint32_t* id
     K* to_s = l + 1 < p.levels ? (from_s == split_0 ? split_1 : split_0) : static_cast<K*>(nullptr);
     switch (p.group[l]) {
       case 2: hipLaunchKernelGGL((rank_merge_kernel<K, 2>), dim3(blocks), dim3(kMergeThreads), 0, s, from_k, from_i, from_s, to_k, to_i, to_s, n, run_log2); break;
-      case 4: hipLaunchKernelGGL((rank_merge_kernel<K, 4>), dim3(blocks), dim3(kMergeThreads), 0, s, from_k, from_i, from_s, to_k, to_i, to_s, n, run_log2); break;
-      case 8: hipLaunchKernelGGL((rank_merge_kernel<K, 8>), dim3(blocks), dim3(kMergeThreads), 0, s, from_k, from_i, from_s, to_k, to_i, to_s, n, run_log2); break;
-      default: hipLaunchKernelGGL((rank_merge_kernel<K, 16>), dim3(blocks), dim3(kMergeThreads), 0, s, from_k, from_i, from_s, to_k, to_i, to_s, n, run_log2); break;
+      default: hipLaunchKernelGGL((rank_merge_kernel<K, 4>), dim3(blocks), dim3(kMergeThreads), 0, s, from_k, from_i, from_s, to_k, to_i, to_s, n, run_log2); break;
     }
-    run_log2 += p.group[l] == 2 ? 1u : p.group[l] == 4 ? 2u : p.group[l] == 8 ? 3u : 4u;
+    run_log2 += p.group[l] == 2 ? 1u : 2u;
     from_k = to_k;
     from_i = to_i;
     from_s = to_s;

@@ -9,7 +9,7 @@
 int main() {
   using namespace vgicp::sortk;
   unsigned long long checked = 0;
-  for (unsigned long long n = 1; n <= 20000000ull; n = n < 5000 ? n + 1 : n + n / 97 + 1) {
+  for (unsigned long long n = 1; n <= 0xFFFFFFFFull; n = n < 5000 ? n + 1 : n + n / 97 + 1) {
     const Plan p = plan_for((uint32_t)n);
     const unsigned long long tiles = (n + kTile - 1) / kTile;
     unsigned long long reach = 1;
@@ -33,7 +33,8 @@ int main() {
     if (split_bytes((uint32_t)n, 8) / 2 < (n / 4 + 1) * 8) { std::printf("n = %llu: too little room for the splitters\n", n); return 1; }
     ++checked;
   }
-  if (launches_for(0) != 0u || launches_for(60000) != 5u || launches_for(256) != 1u || launches_for(257) != 2u) { std::printf("known plans differ\n"); return 1; }
+  if (launches_for(0) != 0u || launches_for(60000) != 5u || launches_for(256) != 1u || launches_for(257) != 2u ||
+      launches_for(0xFFFFFFFFu) != 1u + (uint32_t)kMaxLevels) { std::printf("known plans differ\n"); return 1; }
   std::printf("ok %llu sizes\n", checked);
   return 0;
 }

@@ -280,7 +280,7 @@ def test_dropin_resident_check_hash_on_the_cpu(tmp_path):
 
 def test_sort_plan_of_the_preparation_on_the_cpu(tmp_path):
     """Host logic of the hand-written sort (eskf_lio_amd/csrc/vgicp_sort.h: which groups of runs the merge levels take,
-    how many launches that is, how much room the splitters need) for sizes up to 20 M pairs: tests/native/sort_plan.hip,
+    how many launches that is, how much room the splitters need) for sizes up to 2^32 - 1 pairs: tests/native/sort_plan.hip,
     compiled by hipcc (it cross-compiles without a GPU) and run on the CPU — no device call.  The sort itself is checked on
     the GPU against std::stable_sort (tests/native/sort_check.hip, test_gpu_parity.py)."""
     exe = tmp_path / "sort_plan"
