@@ -72,6 +72,8 @@ def load() -> C.CDLL:
     lib.oracle_preprocess_ex.argtypes = [sz, dp, C.c_double, C.c_int, dp, dp, up, up]
     lib.oracle_preprocess_ordered.restype = sz
     lib.oracle_preprocess_ordered.argtypes = [sz, dp, C.c_double, C.c_int, C.c_int, dp, dp, up, up]
+    lib.oracle_preprocess_queries.restype = None
+    lib.oracle_preprocess_queries.argtypes = [sz, dp, C.c_double, C.c_int, sz, up, dp]
     lib.oracle_jacobi_svd3.restype = C.c_int
     lib.oracle_jacobi_svd3.argtypes = [dp, dp, dp, dp]
     lib.oracle_regularize.restype = C.c_int
@@ -275,6 +277,19 @@ def preprocess_ex(points, voxel_size: float, knn: int = 30):
     m = load().oracle_preprocess_ex(n, _dp(points), float(voxel_size), int(knn), _dp(op), _dp(oc),
                                     ix.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(bad))
     return op[:m].copy(), oc[:m].copy(), ix[:m].copy(), int(bad.value)
+
+
+def preprocess_queries(points, voxel_size: float, knn: int, query_index):
+    """The covariances preprocess() gives the kept points query_index (input indices), m x 9, without computing the
+    others: for scans too large to check whole."""
+    points = _f64(points, 3)
+    q = np.ascontiguousarray(query_index, dtype=np.uint64).reshape(-1)
+    if q.size and int(q.max()) >= points.shape[0]:
+        raise IndexError("query index out of range")
+    oc = np.zeros((q.size, 9))
+    load().oracle_preprocess_queries(points.shape[0], _dp(points), float(voxel_size), int(knn), q.size,
+                                     q.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(oc))
+    return oc
 
 
 def jacobi_svd3(A):

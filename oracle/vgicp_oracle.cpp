@@ -812,6 +812,49 @@ extern "C" size_t oracle_preprocess_ex(size_t n, const double* points, double vo
   return oracle_preprocess_ordered(n, points, voxel_size, knn, ORACLE_ORDER_ASCENDING, out_points, out_covs, out_index, indefinite);
 }
 
+namespace {
+// One kept point's regularised covariance (src/CloudPreprocessor.cpp:100-123): its K nearest of all n points, then
+// open3d::utility::ComputeCovariance over them in search order, then regularize.  The reference orders the neighbours
+// by a partial_sort of (distance², index) pairs; a bounded max-heap of K pairs keeps the same K pairs (the comparison
+// is a strict total order: the indices differ) and sort_heap leaves them in the same ascending order, with K pairs of
+// memory per query instead of n.  heap: scratch of at least K pairs.
+M3 query_covariance(size_t n, const V3* P, const V3& q, size_t K, std::pair<double, size_t>* heap, int* negated) {
+  const auto far = heap + K;
+  for (size_t j = 0; K > 0 && j < n; ++j) {
+    const double dx = P[j].x - q.x, dy = P[j].y - q.y, dz = P[j].z - q.z;
+    const std::pair<double, size_t> c{dx * dx + dy * dy + dz * dz, j};
+    if (j < K) {
+      heap[j] = c;
+      if (j + 1 == K) std::make_heap(heap, far);
+    } else if (c < heap[0]) {
+      std::pop_heap(heap, far);
+      heap[K - 1] = c;
+      std::push_heap(heap, far);
+    }
+  }
+  std::sort_heap(heap, far);  // ascending distance, then index
+  M3 cov = identity3();
+  if (K >= 3) {
+    // open3d::utility::ComputeCovariance: cumulants over the neighbours in search order
+    double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t k = 0; k < K; ++k) {
+      const V3& p = P[heap[k].second];
+      c[0] += p.x; c[1] += p.y; c[2] += p.z;
+      c[3] += p.x * p.x; c[4] += p.x * p.y; c[5] += p.x * p.z;
+      c[6] += p.y * p.y; c[7] += p.y * p.z; c[8] += p.z * p.z;
+    }
+    for (double& v : c) v /= static_cast<double>(K);
+    cov(0, 0) = c[3] - c[0] * c[0];
+    cov(1, 1) = c[6] - c[1] * c[1];
+    cov(2, 2) = c[8] - c[2] * c[2];
+    cov(0, 1) = cov(1, 0) = c[4] - c[0] * c[1];
+    cov(0, 2) = cov(2, 0) = c[5] - c[0] * c[2];
+    cov(1, 2) = cov(2, 1) = c[7] - c[1] * c[2];
+  }
+  return regularize(cov, negated);
+}
+}  // namespace
+
 // order: ORACLE_ORDER_ASCENDING — the kept points in ascending input index (what the HIP path emits, order-independent
 // by construction); ORACLE_ORDER_REFERENCE_HASH — in the iteration order of the reference's own container
 // (src/CloudPreprocessor.cpp:85-99: std::unordered_map<Vector3i, int, open3d::utility::hash_eigen> filled in scan
@@ -835,35 +878,12 @@ extern "C" size_t oracle_preprocess_ordered(size_t n, const double* points, doub
   const size_t K = std::min<size_t>(static_cast<size_t>(knn > 0 ? knn : 0), n);
 #pragma omp parallel reduction(+ : flipped)
   {
-    std::vector<std::pair<double, size_t>> dist(n);
+    std::vector<std::pair<double, size_t>> heap(K);
 #pragma omp for schedule(dynamic, 16)
     for (size_t o = 0; o < m; ++o) {
       const V3 q = P[kept[o]];
-      for (size_t j = 0; j < n; ++j) {
-        const double dx = P[j].x - q.x, dy = P[j].y - q.y, dz = P[j].z - q.z;
-        dist[j] = {dx * dx + dy * dy + dz * dz, j};
-      }
-      std::partial_sort(dist.begin(), dist.begin() + K, dist.end());  // ascending distance, then index
-      M3 cov = identity3();
-      if (K >= 3) {
-        // open3d::utility::ComputeCovariance: cumulants over the neighbours in search order
-        double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (size_t k = 0; k < K; ++k) {
-          const V3& p = P[dist[k].second];
-          c[0] += p.x; c[1] += p.y; c[2] += p.z;
-          c[3] += p.x * p.x; c[4] += p.x * p.y; c[5] += p.x * p.z;
-          c[6] += p.y * p.y; c[7] += p.y * p.z; c[8] += p.z * p.z;
-        }
-        for (double& v : c) v /= static_cast<double>(K);
-        cov(0, 0) = c[3] - c[0] * c[0];
-        cov(1, 1) = c[6] - c[1] * c[1];
-        cov(2, 2) = c[8] - c[2] * c[2];
-        cov(0, 1) = cov(1, 0) = c[4] - c[0] * c[1];
-        cov(0, 2) = cov(2, 0) = c[5] - c[0] * c[2];
-        cov(1, 2) = cov(2, 1) = c[7] - c[1] * c[2];
-      }
       int negated = 0;
-      const M3 R = regularize(cov, &negated);
+      const M3 R = query_covariance(n, P, q, K, heap.data(), &negated);
       if (negated > 0) ++flipped;
       std::memcpy(out_points + 3 * o, &q, 24);
       std::memcpy(out_covs + 9 * o, R.a, 72);
@@ -872,6 +892,26 @@ extern "C" size_t oracle_preprocess_ordered(size_t n, const double* points, doub
   }
   if (indefinite) *indefinite = flipped;
   return m;
+}
+
+// The covariance of oracle_preprocess for the listed input indices only (each must be a kept point for the result
+// to be one of oracle_preprocess's): checks a scan too large for the brute-force entry above by sampling it.
+// voxel_size does not enter a kept point's covariance; it is taken so that the call reads like the others.
+extern "C" void oracle_preprocess_queries(size_t n, const double* points, double voxel_size, int knn, size_t m,
+                                          const uint64_t* query_index, double* out_covs) {
+  (void)voxel_size;
+  const V3* P = reinterpret_cast<const V3*>(points);
+  const size_t K = std::min<size_t>(static_cast<size_t>(knn > 0 ? knn : 0), n);
+#pragma omp parallel
+  {
+    std::vector<std::pair<double, size_t>> heap(K);
+#pragma omp for schedule(dynamic, 1)
+    for (size_t o = 0; o < m; ++o) {
+      int negated = 0;
+      const M3 R = query_covariance(n, P, P[query_index[o]], K, heap.data(), &negated);
+      std::memcpy(out_covs + 9 * o, R.a, 72);
+    }
+  }
 }
 
 // ---- CloudPreprocessor::deskew (src/CloudPreprocessor.cpp:25-74) ----------------------------------

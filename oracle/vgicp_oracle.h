@@ -114,6 +114,10 @@ size_t oracle_preprocess_ex(size_t n, const double* points, double voxel_size, i
 enum { ORACLE_ORDER_ASCENDING = 0, ORACLE_ORDER_REFERENCE_HASH = 1 };
 size_t oracle_preprocess_ordered(size_t n, const double* points, double voxel_size, int knn, int order,
                                  double* out_points, double* out_covs, uint64_t* out_index, uint64_t* indefinite);
+/* The out_covs of oracle_preprocess for the m input indices query_index[] only (m x 9, column-major), each computed
+ * as oracle_preprocess computes a kept point's.  For checking scans too large for the brute-force entries whole. */
+void oracle_preprocess_queries(size_t n, const double* points, double voxel_size, int knn, size_t m,
+                               const uint64_t* query_index, double* out_covs);
 /* Test hooks. oracle_jacobi_svd3: the JacobiSVD restatement on ANY real 3x3 (column-major in and out):
  * A = U diag(sv) V^T, sv descending; returns the number of columns with U.col(k) . V.col(k) < 0 (negative
  * eigenvalues of a symmetric A), -1 for a non-finite input.

@@ -1,5 +1,5 @@
 // GPU check of the preparation's sort (eskf_lio_amd/csrc/vgicp_sort.h) against std::stable_sort: sizes around every
-// boundary of the plan (one tile, a tile's end, a group's end, a level more), keys with long runs of equal values (a
+// boundary of the plan (one tile, a tile's end, a group's end, a level more, up to the 8 M-point limit of a scan), keys with long runs of equal values (a
 // scan's voxel codes), all equal, already sorted, reversed, and random 63-bit keys.  Built by the module's Makefile
 // (`make sort_check`) into eskf_lio_amd/lib/, run by tests/test_gpu_parity.py.
 #include <hip/hip_runtime.h>
@@ -53,8 +53,9 @@ int main(int argc, char** argv) {
     return 0;
   }
   const uint32_t sizes[] = {1, 2, 3, 255, 1023, 1024, 1025, 2048, 2049, 4097, 8191, 8192, 8193, 10131, 16385, 60000, 65535, 65536,
-                            65537, 100000, 131073, 262144, 262145, 300001, 1000003, 1048577};
-  const uint32_t cap = 1048577 + 8;
+                            65537, 100000, 131073, 262144, 262145, 300001, 1000003, 1048577,
+                            4194304, 4194305, 6000001, 8388608};   // 8 merge levels: the sizes of a scan on the 8-item branch
+  const uint32_t cap = 8388608 + 8;
   unsigned long long *ka, *kb;
   uint32_t *ia, *ib;
   CK(hipMalloc(&ka, cap * 8ull)); CK(hipMalloc(&kb, cap * 8ull)); CK(hipMalloc(&ia, cap * 4ull)); CK(hipMalloc(&ib, cap * 4ull));

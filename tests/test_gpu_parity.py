@@ -1144,6 +1144,20 @@ def test_the_preparations_sort_equals_a_stable_sort():
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
 
 
+def _assert_fetch_sums(sums, fp, fc, what):
+    """The checksums vgicp_scan_fetch_sums reports (per array, 16 lanes of a plain and a position-weighted sum of the
+    64-bit words) against the ones of the bytes scan_fetch delivered."""
+    for arr, buf in enumerate((fp, fc)):
+        w = np.ascontiguousarray(buf).view(np.uint64).reshape(-1)
+        idx = np.arange(len(w), dtype=np.uint64)
+        for lane in range(16):
+            wl = w[lane::16]
+            m = np.uint64(len(wl))
+            with np.errstate(over="ignore"):
+                assert sums[arr, 0, lane] == wl.sum(dtype=np.uint64), (what, arr, lane)
+                assert sums[arr, 1, lane] == ((m - (idx[lane::16] >> np.uint64(4))) * wl).sum(dtype=np.uint64), (what, arr, lane)
+
+
 def test_scan_fetch_returns_the_prepared_scan_without_a_copy_command(oracle):
     """vgicp_scan_fetch_begin / _end (ABI 6): the host copy of an ENQUEUED preparation, written into page-locked memory by a
     kernel behind it and copied out piece by piece — equal to vgicp_scan_info + vgicp_scan_download bit for bit (and so to
@@ -1166,16 +1180,7 @@ def test_scan_fetch_returns_the_prepared_scan_without_a_copy_command(oracle):
             dp, dc = b.scan_download()
             assert kept == len(fp) == len(dp) and np.array_equal(fp, dp) and np.array_equal(fc, dc), n
             # vgicp_scan_fetch_sums: the checksums the kernel made while writing equal the ones of the delivered bytes
-            sums = a.scan_fetch_sums()
-            for arr, buf in enumerate((fp, fc)):
-                w = np.ascontiguousarray(buf).view(np.uint64).reshape(-1)
-                idx = np.arange(len(w), dtype=np.uint64)
-                for lane in range(16):
-                    wl = w[lane::16]
-                    m = np.uint64(len(wl))
-                    with np.errstate(over="ignore"):
-                        assert sums[arr, 0, lane] == wl.sum(dtype=np.uint64), (n, arr, lane)
-                        assert sums[arr, 1, lane] == ((m - (idx[lane::16] >> np.uint64(4))) * wl).sum(dtype=np.uint64), (n, arr, lane)
+            _assert_fetch_sums(a.scan_fetch_sums(), fp, fc, n)
             if k == 2:   # against the oracle chain once
                 moved, _ = oracle.transform(raw, np.tile(np.eye(3).reshape(9), (n, 1)), ext)
                 desk, _ = oracle.deskew(moved, tt, st)
@@ -2181,3 +2186,198 @@ def test_preprocess_survives_non_finite_points(gpu_ctx, oracle):
     orig = np.flatnonzero(keep)[ri.astype(np.int64)]
     common, ia, ib = np.intersect1d(gi.astype(np.int64), orig, return_indices=True)
     assert len(common) > 0.99 * len(ri) and np.array_equal(gc[ia], rc[ib])
+
+
+# ---- scans on the 8-item branch of the preparation (more than 4 194 304 points) and the 8 M-point limit -------------
+# Up to 4 096 x 256 x 4 = 4 194 304 points the kept points are found by run_scan_kernel / keep_and_split_kernel with 4 items
+# per thread; above, by their 8-item instantiations (2 048-point tiles, a look-back over up to 4 096 tile slots), up to
+# 4 096 x 2 048 = 8 388 608 points, the largest scan any preparation entry point accepts.
+SCAN_ITEMS_SWITCH = 4_194_304
+SCAN_LIMIT = 8_388_608
+# Covariances of a scan this large are checked on a sample (oracle_preprocess_queries: K nearest of all n points, brute
+# force).  Besides the first and last 256 kept points and every kept point in three small windows, LARGE_SCAN_SAMPLE
+# kept points drawn uniformly.  The oracle answers ~1 850 queries a second at 8 M points on 16 CPU threads (4 000 at 4 M):
+# about 42 000 queries are 23 s at the limit and 11 s at the switch, well inside a minute per size.
+LARGE_SCAN_SAMPLE = 40_000
+
+
+def _first_point_of_every_voxel(oracle, pts, voxel_size):
+    """The kept points of a preparation, independently: the first input index of every voxel, ascending (integer work:
+    the oracle's floor() keys packed into one integer, np.unique's first occurrences)."""
+    k = oracle.voxel_index(voxel_size, pts).astype(np.int64)
+    assert np.abs(k).max() < 1 << 20
+    code = ((k[:, 0] + (1 << 20)) << 42) | ((k[:, 1] + (1 << 20)) << 21) | (k[:, 2] + (1 << 20))
+    _, first = np.unique(code, return_index=True)
+    return np.sort(first).astype(np.uint64)
+
+
+def _covariance_sample(kept_pts, seed):
+    """Positions in the kept list: the first and last 256, every kept point inside three 3 m x 3 m columns (the crowded
+    ground next to the sensor, a stretch of wall, clutter far out where neighbourhoods are sparse) and LARGE_SCAN_SAMPLE
+    more drawn uniformly."""
+    m = len(kept_pts)
+    x, y = kept_pts[:, 0], kept_pts[:, 1]
+    windows = [(np.abs(x) < 1.5) & (np.abs(y) < 1.5),
+               (x > 10.0) & (x < 13.0) & (np.abs(y - 7.5) < 0.5),
+               (x > 45.0) & (x < 48.0) & (y > 45.0) & (y < 48.0)]
+    for w in windows:
+        assert w.sum() >= 20, "a window without kept points checks nothing"
+    rng = np.random.default_rng(seed)
+    parts = [np.arange(min(256, m)), np.arange(max(m - 256, 0), m), rng.choice(m, min(LARGE_SCAN_SAMPLE, m), replace=False)]
+    return np.unique(np.concatenate(parts + [np.flatnonzero(w) for w in windows]))
+
+
+@pytest.mark.timeout(300)   # measured: 12 s / 12 s / 28 s
+@pytest.mark.parametrize("n", [SCAN_ITEMS_SWITCH, SCAN_ITEMS_SWITCH + 1, SCAN_LIMIT])
+def test_preprocess_past_the_scan_items_switch_and_at_the_limit(gpu_ctx, oracle, n):
+    """The last size on the 4-item branch (every tile slot used), the first on the 8-item branch, and the largest size
+    accepted (every tile slot used again): the kept points of the WHOLE scan exactly (the first point of every voxel,
+    ascending), the covariances of a sample of several thousand kept points bit for bit against the oracle."""
+    import time
+    from eskf_lio_amd import synth
+    pts = synth.make_lidar_scan(n, seed=n % 997, extent=60.0)
+    gp, gc, gi = gpu_ctx.preprocess(pts, 0.3, 30)
+    kept = _first_point_of_every_voxel(oracle, pts, 0.3)
+    assert len(gi) == len(kept) and np.array_equal(gi, kept)
+    assert np.array_equal(gp, pts[kept.astype(np.int64)])
+    sel = _covariance_sample(gp, seed=n)
+    t0 = time.perf_counter()
+    ref = oracle.preprocess_queries(pts, 0.3, 30, kept[sel])
+    spent = time.perf_counter() - t0
+    wrong = np.flatnonzero((gc[sel] != ref).any(axis=1))
+    assert len(wrong) == 0, (len(wrong), sel[wrong[:10]])
+    assert np.allclose(np.linalg.svd(_cov_mats(gc[sel]), compute_uv=False), [1.0, 1.0, 1e-2], atol=1e-9)
+    print(f"n = {n}: {len(kept)} kept, {len(sel)} covariances checked in {spent:.1f} s on {oracle.max_threads()} threads")
+
+
+@pytest.mark.timeout(180)   # measured: 2 s
+def test_one_far_point_more_takes_the_scan_to_the_eight_item_branch(oracle):
+    """A cloud A of 4 194 304 points (4-item branch) and B = A + one point at (2 000, 2 000, 2 000) m (8-item branch): the
+    point is inside the search grid but among nobody's 30 nearest, so B's prepared scan is A's followed by that point,
+    bit for bit over the whole output: every kept point of the 8-item branch checked at the cost of two preparations.
+    The same through the chain with the deskew (vgicp_scan_prepare_async + vgicp_scan_fetch: ~850 pieces of 64 KB),
+    whose copy equals vgicp_scan_download and whose checksums the fetch kernel's."""
+    from eskf_lio_amd import capi, synth
+    n = SCAN_ITEMS_SWITCH
+    far = np.array([[2000.0, 2000.0, 2000.0]])
+    A = synth.make_lidar_scan(n, seed=4242, extent=60.0)
+    B = np.concatenate([A, far])
+    with capi.Context(0) as ctx:
+        pa, ca, ia = ctx.preprocess(A, 0.3, 30)
+        pb, cb, ib = ctx.preprocess(B, 0.3, 30)
+    assert len(ib) == len(ia) + 1 and ib[-1] == n
+    assert np.array_equal(ib[:-1], ia) and np.array_equal(pb[:-1], pa) and np.array_equal(cb[:-1], ca)
+    assert np.array_equal(pb[-1:], far) and np.array_equal(cb[-1:], oracle.preprocess_queries(B, 0.3, 30, [n]))
+    del pa, ca, ia, pb, cb, ib
+    # the chain: extrinsic, deskew (the extra point taken at the sweep's last capture time), preparation, fetch
+    st = synth.make_imu_states(48, seed=5)
+    ext = synth.se3_to_SE3([0.01, -0.02, 0.03, 0.002, -0.001, 0.003])
+    tA = synth.make_point_times(n, st[1, 0] + 1e-4, st[-3, 0] + 0.4 / 400.0, seed=13)
+    tB = np.concatenate([tA, tA[-1:]])
+    fetched = []
+    with capi.Context(0) as a, capi.Context(0) as b:
+        for cloud, t in ((A, tA), (B, tB)):
+            a.scan_prepare_async(cloud, t, st, ext, 0.3, 30)
+            fp, fc = a.scan_fetch()
+            _assert_fetch_sums(a.scan_fetch_sums(), fp, fc, len(cloud))
+            b.scan_prepare_async(cloud, t, st, ext, 0.3, 30)
+            kept, moved, _ = b.scan_info()
+            dp, dc = b.scan_download()
+            assert kept == len(fp) and moved > 0 and np.array_equal(fp, dp) and np.array_equal(fc, dc), len(cloud)
+            assert 96 * kept > 500 * 65536                                # hundreds of 64 KB pieces
+            fetched.append((fp, fc))
+            del dp, dc
+    (fa, ca), (fb, cb) = fetched
+    assert len(fb) == len(fa) + 1 and np.array_equal(fb[:-1], fa) and np.array_equal(cb[:-1], ca)
+    assert np.linalg.norm(fb[-1]) > 1000.0
+
+
+@pytest.mark.timeout(120)   # measured: 0.2 s
+def test_every_preparation_entry_refuses_one_point_over_the_limit():
+    """8 388 609 points: vgicp_preprocess, vgicp_scan_prepare, vgicp_scan_prepare_async (then vgicp_scan_fetch) and
+    vgicp_sweep_stage + vgicp_scan_prepare_staged_async each return VGICP_ERR_BAD_ARGUMENT at once, enqueue nothing and
+    leave the resident scan as it was; after each refusal the same context prepares a 60 000-point sweep to the bits of a
+    fresh context.  (8 388 608 points are accepted: test_preprocess_past_the_scan_items_switch_and_at_the_limit.)"""
+    import time
+    from eskf_lio_amd import capi, synth
+    big = np.random.default_rng(5).uniform(-50.0, 50.0, size=(SCAN_LIMIT + 1, 3))
+    sweep = synth.make_lidar_scan(60_000, seed=61)
+    with capi.Context(0) as fresh:
+        hp, hc, hi = fresh.preprocess(sweep, 0.3, 30)
+        fresh.scan_prepare(sweep, None, None, None, 0.3, 30)
+        rp, rc = fresh.scan_download()
+    assert np.array_equal(rp, hp) and np.array_equal(rc, hc)
+
+    def refused(call):
+        t0 = time.perf_counter()
+        with pytest.raises(capi.VgicpError) as e:
+            call()
+        spent = time.perf_counter() - t0
+        assert e.value.code == capi.ERR_BAD_ARGUMENT and "more than 8 M points" in str(e.value), str(e.value)
+        assert spent <= 1.0, spent
+
+    with capi.Context(0) as ctx:
+        refused(lambda: ctx.preprocess(big, 0.3, 30))
+        gp, gc, gi = ctx.preprocess(sweep, 0.3, 30)
+        assert np.array_equal(gi, hi) and np.array_equal(gp, hp) and np.array_equal(gc, hc)
+
+        refused(lambda: ctx.scan_prepare(big, None, None, None, 0.3, 30))
+        with pytest.raises(capi.VgicpError) as e:                        # nothing resident yet: nothing was made of it
+            ctx.scan_download()
+        assert e.value.code == capi.ERR_NOT_READY
+        assert ctx.scan_prepare(sweep, None, None, None, 0.3, 30)[0] == len(rp)
+        gp, gc = ctx.scan_download()
+        assert np.array_equal(gp, rp) and np.array_equal(gc, rc)
+
+        refused(lambda: ctx.scan_prepare_async(big, None, None, None, 0.3, 30))
+        t0 = time.perf_counter()
+        gp, gc = ctx.scan_fetch()                                         # the sweep before, untouched; nothing to wait for
+        assert time.perf_counter() - t0 <= 1.0
+        assert np.array_equal(gp, rp) and np.array_equal(gc, rc)
+        ctx.scan_prepare_async(sweep, None, None, None, 0.3, 30)
+        gp, gc = ctx.scan_fetch()
+        assert np.array_equal(gp, rp) and np.array_equal(gc, rc)
+
+        ticket = ctx.sweep_stage(big)                                     # staging copies, it does not prepare
+        refused(lambda: ctx.scan_prepare_staged_async(ticket, None, None, 0.3, 30))
+        with pytest.raises(capi.VgicpError) as e:                        # the ticket is used up all the same
+            ctx.scan_prepare_staged_async(ticket, None, None, 0.3, 30)
+        assert e.value.code == capi.ERR_BAD_ARGUMENT and "no sweep staged" in str(e.value)
+        gp, gc = ctx.scan_fetch()
+        assert np.array_equal(gp, rp) and np.array_equal(gc, rc)
+        ctx.scan_prepare_staged_async(ctx.sweep_stage(sweep), None, None, 0.3, 30)
+        gp, gc = ctx.scan_fetch()
+        assert np.array_equal(gp, rp) and np.array_equal(gc, rc)
+
+
+@pytest.mark.timeout(180)   # measured: 2.3 s
+def test_the_largest_prepared_scan_feeds_the_registration():
+    """The 8 388 608-point scan prepared resident (the SoA planes written by the 8-item branch at stride = scan_capacity):
+    three rounds of vgicp_align_resident against a map of the scan's first 1 000 000 points give the counts and the pose
+    of vgicp_align on the downloaded copy bit for bit, and the counts of the launch-per-round loop (FLAG_NO_PERSISTENT)
+    with its pose to rounding."""
+    from eskf_lio_amd import capi, synth
+    raw = synth.make_lidar_scan(SCAN_LIMIT, seed=SCAN_LIMIT % 997, extent=60.0)
+    guess = synth.se3_to_SE3([0.03, -0.02, 0.01, 0.001, -0.002, 0.004])
+    with capi.Context(0) as ctx:
+        ctx.map_reset(0.3, 0)
+        p0, c0, _ = ctx.preprocess(raw[:1_000_000], 0.3, 30)
+        ctx.map_insert_scan(p0, c0, np.eye(4), 20)
+        del p0, c0
+        hp, hc, _ = ctx.preprocess(raw, 0.3, 30)                          # checked against the oracle by the test above
+        kept, _ = ctx.scan_prepare(raw, None, None, None, 0.3, 30)
+        del raw
+        sp, sc = ctx.scan_download()
+        assert kept == len(hp) and np.array_equal(sp, hp) and np.array_equal(sc, hc)
+        del hp, hc
+        # a cosine threshold no step meets: exactly three rounds
+        res = ctx.align_resident(guess, 3, 0.0, 2.0)
+        up = ctx.align(sp, sc, guess, 3, 0.0, 2.0)
+        loop = ctx.align(sp, sc, guess, 3, 0.0, 2.0, flags=capi.FLAG_NO_PERSISTENT)
+    assert res.iterations == up.iterations == loop.iterations == 3
+    assert np.array_equal(res.corr_count, up.corr_count) and np.array_equal(res.corr_count, loop.corr_count)
+    assert res.corr_count.min() > 0.2 * kept                          # (the map holds an eighth of the points)
+    assert np.array_equal(res.pose, up.pose), np.abs(res.pose - up.pose).max()   # the same kernel on the same planes
+    assert np.abs(res.pose - loop.pose).max() <= 1e-11, np.abs(res.pose - loop.pose).max()
+    print(f"align on {kept} kept points: |resident - uploaded| = {np.abs(res.pose - up.pose).max():.3e}, "
+          f"|resident - loop| = {np.abs(res.pose - loop.pose).max():.3e}, launches {res.launches} / {loop.launches}")

@@ -499,6 +499,61 @@ def test_preprocess_degenerate_neighbourhoods(oracle):
     assert len(ix) == 1 and bad == 0 and np.array_equal(_cov_mats(oc)[0], np.diag([1.0, 1.0, 1e-2]))
 
 
+def _restated_query_covariances(pts, query, knn):
+    """oracle_preprocess's covariance of the kept points `query`, restated: the K smallest (distance², index) pairs by a
+    lexicographic sort, the cumulants summed in that order, then the oracle's regulariser on the result."""
+    K = min(knn, len(pts))
+    out = np.zeros((len(query), 9))
+    for o, q in enumerate(query):
+        d = pts - pts[q]
+        d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+        nb = pts[np.lexsort((np.arange(len(pts)), d2))[:K]]
+        C = np.eye(3)
+        if K >= 3:
+            c = np.zeros(9)
+            for p in nb:                                                  # one term at a time, as the reference adds them
+                c += [p[0], p[1], p[2], p[0] * p[0], p[0] * p[1], p[0] * p[2], p[1] * p[1], p[1] * p[2], p[2] * p[2]]
+            c /= K
+            C = np.array([[c[3] - c[0] * c[0], c[4] - c[0] * c[1], c[5] - c[0] * c[2]],
+                          [c[4] - c[0] * c[1], c[6] - c[1] * c[1], c[7] - c[1] * c[2]],
+                          [c[5] - c[0] * c[2], c[7] - c[1] * c[2], c[8] - c[2] * c[2]]])
+        out[o] = _regularized(C)
+    return out
+
+
+def _regularized(C):
+    from oracle import binding
+    return binding.regularize(C)[0].T.reshape(9)                         # column-major, as out_covs
+
+
+def test_preprocess_queries_equal_the_whole_preparation(oracle):
+    """oracle_preprocess_queries (the sampled checker of scans too large for the brute-force entry) gives every kept
+    point's covariance of oracle_preprocess bit for bit, in any query order and with repeats; its bounded top-K keeps the
+    pairs a lexicographic sort of (distance², index) keeps: a lattice where every distance occurs many times (the K-th
+    place is decided by the index), a pile of exact duplicates (all at distance zero), and a LiDAR-like scan."""
+    rng = np.random.default_rng(29)
+    g = np.arange(-6, 7) * 0.125
+    lattice = np.stack(np.meshgrid(g, g, g[:4], indexing="ij"), axis=-1).reshape(-1, 3)    # exact in binary
+    lattice = np.ascontiguousarray(lattice[rng.permutation(len(lattice))])
+    pile = np.concatenate([np.tile([[0.51, -0.23, 0.07]], (90, 1)), np.tile([[0.52, -0.23, 0.07]], (45, 1)),
+                           rng.normal(size=(200, 3)) * 0.4, np.tile([[3.0, 3.0, 3.0]], (2, 1))])
+    pile = np.ascontiguousarray(pile[rng.permutation(len(pile))])
+    scan = synth.make_lidar_scan(4_000, seed=31)
+    for name, pts, knn in (("lattice", lattice, 30), ("lattice", lattice, 7), ("pile", pile, 30), ("scan", scan, 30),
+                           ("few", scan[:2], 30)):
+        _, oc, ix = oracle.preprocess(pts, 0.3, knn)
+        got = oracle.preprocess_queries(pts, 0.3, knn, ix)
+        assert np.array_equal(got, oc), (name, knn)
+        shuffled = rng.permutation(len(ix))
+        again = np.concatenate([shuffled, shuffled[:5]])
+        assert np.array_equal(oracle.preprocess_queries(pts, 0.3, knn, ix[again]), oc[again]), (name, knn)
+        some = np.unique(np.concatenate([np.arange(min(40, len(ix))), rng.choice(len(ix), min(40, len(ix)), replace=False)]))
+        assert np.array_equal(_restated_query_covariances(pts, ix[some].astype(np.int64), knn), oc[some]), (name, knn)
+    assert oracle.preprocess_queries(scan, 0.3, 30, np.zeros(0, dtype=np.uint64)).shape == (0, 9)
+    with pytest.raises(IndexError):
+        oracle.preprocess_queries(scan, 0.3, 30, [len(scan)])
+
+
 # ---- deskew (SURVEY.md 8(f) N4): oracle vs the numpy restatement ------------------------------------
 def _deskew_case(n=5_000, states=48, jitter=0.0, seed=9):
     st = synth.make_imu_states(states, seed=seed)
