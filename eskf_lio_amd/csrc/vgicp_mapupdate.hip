@@ -9,8 +9,8 @@
 //                contraction, same evaluation order), voxel key, find-or-CLAIM the voxel's slot
 //                (claims race through a CAS; same-key racers spin on the LOCKED word until the winner,
 //                which finishes its critical section inside the same loop iteration, publishes FULL)
-//   2. sort      stable sort of (slot, point index) by slot (rocPRIM's merge sort): the points of one
-//                voxel become one segment, still in scan order
+//   2. sort      stable sort of (slot, point index) by slot (vgicp_sort.h, the library's one sort): the points of
+//                one voxel become one segment, still in scan order
 //   3. apply     the thread at the head of a segment walks it and applies the constructor / addPoint
 //                arithmetic of the reference sequentially, in registers, one record write at the end
 // Arithmetic is bit-exact with the CPU path (tests compare means, covariances and counts with `==`).
@@ -24,17 +24,16 @@
 //   2. apply     the leader walks the list, takes the points in ascending index = scan order (a register buffer of
 //                kListChunk indices per walk; longer lists take several walks: correct for any length, quadratic
 //                beyond the buffer, which is why arbitrary scans keep the sort), applies them, empties the list.
-#include <cstring>   // rocprim/iterator/texture_cache_iterator.hpp calls memset without including it
-
-#include <rocprim/rocprim.hpp>
-
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
+#include "vgicp_sort.h"
 
 namespace vgicp {
 namespace {
 
-constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+// table full: after every slot (2^31 slots of 128 B are already 256 GiB), and not 0xFFFFFFFF, the key the sort pads
+// with and keeps every key below (vgicp_sort.h)
+constexpr uint32_t kNoSlot = 0xFFFFFFFEu;
 
 // C <- R C R^T evaluated as Eigen evaluates (R * C) * R^T: left to right, every product and sum
 // rounded once.
@@ -60,28 +59,12 @@ struct InsertScratch {
   uint32_t* slot_out;  // n (sorted)
   uint32_t* idx_in;    // n
   uint32_t* idx_out;   // n (sorted)
-  void* temp;          // the sort's temporary storage
-  size_t temp_bytes;
+  void* split;         // the sort's splitters: sortk::split_bytes(n, 4)
 };
 
 __host__ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
-// (slot, point index) pairs, stable. rocPRIM's merge sort with 2 048-item blocks: at scan sizes a launch costs as
-// much as the work it does, and hipCUB's radix-sort front end picks the same sort with half the block and one more
-// merge pass (see vgicp_preprocess.hip).
-__host__ inline hipError_t sort_slots(void* temp, size_t& temp_bytes, const uint32_t* slot_in, uint32_t* slot_out,
-                                      const uint32_t* idx_in, uint32_t* idx_out, uint32_t n, hipStream_t s) {
-  using Config = rocprim::merge_sort_config<512, 512, 4>;
-  return rocprim::merge_sort<Config>(temp, temp_bytes, slot_in, slot_out, idx_in, idx_out, (size_t)n,
-                                     rocprim::less<uint32_t>(), s);
-}
-__host__ inline size_t sort_temp_bytes(uint32_t n) {
-  size_t bytes = 0;
-  (void)sort_slots(nullptr, bytes, nullptr, nullptr, nullptr, nullptr, n, nullptr);
-  return bytes;
-}
-
-__host__ inline InsertScratch carve(void* base, uint32_t n, size_t temp_bytes) {
+__host__ inline InsertScratch carve(void* base, uint32_t n) {
   char* p = static_cast<char*>(base);
   InsertScratch s;
   s.wpts = reinterpret_cast<double*>(p); p += align256((size_t)n * 3 * sizeof(double));
@@ -90,8 +73,7 @@ __host__ inline InsertScratch carve(void* base, uint32_t n, size_t temp_bytes) {
   s.slot_out = reinterpret_cast<uint32_t*>(p); p += align256((size_t)n * sizeof(uint32_t));
   s.idx_in = reinterpret_cast<uint32_t*>(p); p += align256((size_t)n * sizeof(uint32_t));
   s.idx_out = reinterpret_cast<uint32_t*>(p); p += align256((size_t)n * sizeof(uint32_t));
-  s.temp = p;
-  s.temp_bytes = temp_bytes;
+  s.split = p;
   return s;
 }
 
@@ -342,7 +324,7 @@ inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((w
 size_t map_insert_scratch_bytes(uint32_t n) {
   const uint32_t m = n ? n : 1;
   return align256((size_t)m * 3 * sizeof(double)) + align256((size_t)m * 9 * sizeof(double)) +
-         4 * align256((size_t)m * sizeof(uint32_t)) + align256(sort_temp_bytes(m)) + 256;
+         4 * align256((size_t)m * sizeof(uint32_t)) + align256(sortk::split_bytes(m, sizeof(uint32_t))) + 256;
 }
 
 hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, double voxel_size,
@@ -351,7 +333,7 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
                              size_t scratch_bytes, uint32_t* counters, bool short_lists) {
   if (n == 0) return hipSuccess;
   if (scratch_bytes < map_insert_scratch_bytes(n)) return hipErrorInvalidValue;
-  InsertScratch w = carve(scratch, n, sort_temp_bytes(n));
+  InsertScratch w = carve(scratch, n);
   Pose12 pose;
   for (int k = 0; k < 12; ++k) pose.v[k] = pose12[k];
   if (short_lists) {
@@ -368,13 +350,10 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
                      counters);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // stable: equal slots keep ascending point index = scan order
-  e = sort_slots(w.temp, w.temp_bytes, w.slot_in, w.slot_out, w.idx_in, w.idx_out, n, s);
+  // stable: equal slots keep ascending point index = scan order (the inputs are scratch from here on)
+  e = sortk::sort_pairs(w.slot_in, w.idx_in, w.slot_out, w.idx_out, w.split, n, s);
   if (e != hipSuccess) return e;
-  for (uint64_t run = 2048; ; run <<= 1) {  // rocPRIM's merge sort: one block sort + one merge launch per doubling
-    ++g_kernel_launches;
-    if (run >= n) break;
-  }
+  g_kernel_launches += sortk::launches_for(n);
   ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, w.slot_out,
                      w.idx_out, n, w.wpts, w.wcovs, max_points);
   return hipGetLastError();

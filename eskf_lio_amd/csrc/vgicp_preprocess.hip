@@ -1724,13 +1724,7 @@ inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((w
 __host__ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 __host__ inline uint64_t pow2_at_least(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
 
-// The one sort: (Morton code, index) pairs, stable — vgicp_sort.h (every wave sorts 256 pairs in registers, then groups
-// of four runs are merged per launch: five launches, 34 us for a sweep of 60 000 points).  Until round 6 this was
-// rocPRIM's merge sort, one launch per doubling of the run length (42.5 us there; launches of one preparation's sort,
-// us, profiles/r10_knn_leaf.txt):
-//   points           28k   33k   60k   65k   66k  100k  130k  150k  250k  300k
-//   2 048 per block  35.5  50.8  50.9  51.3  48.7  50.1  52.7  70.8 108.1 115.8
-//   4 096 per block  43.8  42.3  43.7  43.1  59.1  60.2  62.0  60.5  93.9 119.3
+// (Morton code, index) pairs, stable: vgicp_sort.h (the sort it replaced, and the timings of both: profiles/README.md, r17).
 struct Layout {
   size_t codes_in, codes_out, idx_in, idx_out, spts, keep_i, rank_i, queries, nbr, split, total;
 };

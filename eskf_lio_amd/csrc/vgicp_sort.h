@@ -1,10 +1,16 @@
-// The preparation's one sort, hand-written for gfx950: (key, index) pairs, keys ascending, equal keys in ascending
-// index order — the result of a stable sort when the indices come in ascending (the prologue writes idx[i] = i).
+// The library's one sort, hand-written for gfx950: (key, index) pairs, keys ascending, equal keys in ascending
+// index order — the result of a stable sort when the indices come in ascending (both callers write idx[i] = i first).
+// Two callers, one key type each, and each key type is instantiated in ONE translation unit only (the two objects are
+// separate code objects; keep it that way):
+//   - vgicp_preprocess.hip: unsigned long long Morton codes of a scan's points;
+//   - vgicp_mapupdate.hip:  uint32_t voxel slots of the map insertion.
+// Keys must lie below ~K(0).  That value pads partial tiles and stands for every place past the end of a run; where a
+// wave searches a run before its own (`<=`), a key equal to it would count that padding as pairs.
 //
 // A scan is 10^4 .. 10^6 pairs: small enough that a sort is paid for in LAUNCHES and in loads that wait for one another,
-// not in bytes (60 000 pairs are 720 KB).  rocPRIM's merge sort, which this replaces, took one block sort (19 us: 15
-// blocks of 4 096 on 256 CUs) and one merge launch per doubling of the run length (4 x 5.9 us): 42.5 us for 60 000
-// pairs (profiles/r16_frame_kernel_stats.csv).  Here:
+// not in bytes (60 000 pairs are 720 KB).  The library merge sort this replaced took one block sort (19 us: 15 blocks
+// of 4 096 on 256 CUs) and one merge launch per doubling of the run length (4 x 5.9 us): 42.5 us for 60 000 pairs
+// (profiles/r16_frame_kernel_stats.csv).  Here:
 //   1. tile_sort_kernel: every WAVE sorts 256 pairs, four per lane, with a bitonic network over (key, index) — the index
 //      breaks ties, which makes the order total and lets an unstable network give the stable result.  Exchanges at
 //      distance 1 and 2 are inside a lane, the others are lane shuffles: no LDS, no barrier.  235 waves, 8 us.
@@ -22,6 +28,8 @@
 //      nothing hides anything), i.e. 5.2 / 6.5 / 11.4 / 24 us per level for G = 2 / 4 / 8 / 16, and 60 000 pairs need
 //      8 / 4 / 3 / 2 levels: G = 4 it is (tools/ab_sort.sh).
 // 60 000 pairs: 8 + 4 x 6.5 = 34 us in the frame chain against 42.5 us (same session, tools/ab_kernel.sh).
+// The map insertion's 32-bit slots against the library sort it used before (rocprofv3, same session, this / before):
+// 12 000 pairs 23 / 36 us, 100 000 40 / 47 us, 300 000 67 / 104 us, 1 000 000 (a map built in one call) 156 / 167 us.
 //
 // The two buffers alternate; sort_pairs says where the result is wanted and starts on the side that ends there.
 #pragma once
@@ -37,7 +45,11 @@ static_assert(kMaxGroup == 4, "sort_pairs launches rank_merge_kernel<K, 2> and <
 constexpr uint32_t kTile = 256;            // pairs a wave sorts
 constexpr uint32_t kTileThreads = 256;     // four waves, four tiles per block
 constexpr uint32_t kMergeThreads = 256;
-constexpr uint32_t kFlat = 4096;           // keys of the other runs' windows a wave keeps in LDS (beyond: per-lane searches)
+// keys of the other runs' windows a wave keeps in LDS (beyond: per-lane searches).  64-bit keys: 4 096, 128 KB a block,
+// one block per CU (a scan of 60 000 points has about one wave per SIMD anyway).  32-bit keys: 1 024, 16 KB a block, so
+// that 8 waves per SIMD fit in the CU's 160 KB: with 4 096 only 2 did, and 1 M pairs took 43 instead of 24 us a level
+template <typename K>
+constexpr uint32_t flat_keys() { return sizeof(K) == 8 ? 4096u : 1024u; }
 
 template <typename K>
 struct Pair {
@@ -133,6 +145,7 @@ __global__ __launch_bounds__(kMergeThreads) void rank_merge_kernel(const K* __re
                                                                    uint32_t run_log2) {
   constexpr int R = G - 1;
   const uint32_t run = 1u << run_log2;
+  constexpr uint32_t kFlat = flat_keys<K>();
   __shared__ K flat_sh[kMergeThreads / 64][kFlat + 8];
   K* flat = flat_sh[threadIdx.x >> 6];
   const uint32_t lane = threadIdx.x & 63u;

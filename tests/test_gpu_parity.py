@@ -901,6 +901,53 @@ def test_device_map_insert_edge_cases(gpu_ctx, oracle):
     assert np.array_equal(gpu_ctx.map_export()[0], _sorted_oracle_export(om)[0])
 
 
+@pytest.mark.parametrize("n", [1, 200, 257, 3_000, 12_000, 50_000, 200_000])
+def test_map_insertion_sort_is_bit_exact_at_every_merge_depth(gpu_ctx, oracle, n):
+    """map_insert_scan orders each voxel's points with vgicp_sort.h on 32-bit slots.  These sizes take 0, 0, 1, 2, 3, 4
+    and 5 merge levels (both parities of the buffer swap).  Points repeat, so voxels get segments of several points
+    and the cap of 5 bites.  Two scans with different poses: the second one also updates existing voxels.  The map
+    equals the reference's serial loop with ==."""
+    from eskf_lio_amd import synth
+    rng = np.random.default_rng(n)
+    cap = 5
+    gpu_ctx.map_reset(0.3, 0)
+    om = oracle.OracleMap(0.3, cap)
+    base = rng.uniform(-20.0, 20.0, size=(n // 6 + 1, 3))
+    for T in (synth.se3_to_SE3([0.1, -0.2, 0.05, 0.01, 0.0, 0.03]), synth.se3_to_SE3([-0.3, 0.1, 0.0, 0.0, 0.02, -0.05])):
+        p = base[rng.integers(0, len(base), n)] + rng.normal(scale=0.02, size=(n, 3))
+        c = np.tile(np.eye(3).reshape(1, 9), (n, 1)) * rng.uniform(0.01, 1.0, size=(n, 1))
+        gpu_ctx.map_insert_scan(p, c, T, cap)
+        om.insert(*oracle.transform(p, c, T))
+    got = gpu_ctx.map_export()
+    ref = _sorted_oracle_export(om)
+    for a, b in zip(got, ref):
+        assert np.array_equal(a, b)
+    assert n < 200 or ref[3].max() == cap
+
+
+@pytest.mark.parametrize("voxels", [1, 3])
+def test_map_insertion_sort_of_segments_longer_than_the_lds_window(gpu_ctx, oracle, voxels):
+    """70 000 / 75 000 points in one / three voxels, in scan order at random, no cap: every mean and covariance depends
+    on the order of all the voxel's points.  One voxel: every key is equal, so every merge window is empty and the
+    order is the index order alone.  Three voxels of ~25 000 points: a merging wave whose 64 keys straddle two segments
+    has windows as long as a segment's share of each other run, far beyond the keys it keeps in LDS, so the upper
+    merge levels search the runs themselves."""
+    rng = np.random.default_rng(70 + voxels)
+    n, cap = (70_000 if voxels == 1 else 75_000), 1 << 20
+    p = 0.15 + 0.1 * rng.random((n, 3))
+    p[:, 0] += 0.3 * rng.integers(0, voxels, n)
+    c = np.tile(np.eye(3).reshape(1, 9), (n, 1)) * rng.random((n, 1))
+    gpu_ctx.map_reset(0.3, 0)
+    om = oracle.OracleMap(0.3, cap)
+    om.insert(p, c)
+    assert gpu_ctx.map_insert_scan(p, c, np.eye(4), cap) == voxels
+    got = gpu_ctx.map_export()
+    ref = _sorted_oracle_export(om)
+    assert len(ref[0]) == voxels and ref[3].sum() == n and ref[3].min() > 20_000
+    for a, b in zip(got, ref):
+        assert np.array_equal(a, b)
+
+
 def test_device_map_eviction_matches_the_reference_rule(gpu_ctx, c1_inputs):
     vmap, _, _ = c1_inputs
     gpu_ctx.map_reset(vmap.voxel_size, 0)
@@ -1132,10 +1179,13 @@ def test_sweep_staged_on_arrival_prepares_to_the_same_bits(oracle):
 
 
 def test_the_preparations_sort_equals_a_stable_sort():
-    """eskf_lio_amd/csrc/vgicp_sort.h (tile sort in LDS + whole groups of runs merged per launch) against std::stable_sort
-    over (key, index) pairs: sizes around every boundary of the plan, voxel-code-like keys with long runs of equal values,
-    all-equal / sorted / reversed / random 63-bit keys, nothing written past the end (tests/native/sort_check.hip, built
-    by `make sort_check`)."""
+    """eskf_lio_amd/csrc/vgicp_sort.h (tile sort in registers + whole groups of runs merged per launch) against
+    std::stable_sort over (key, index) pairs, for both key types the library sorts: 64-bit Morton codes (the scan
+    preparation) and 32-bit voxel slots (the map insertion).  Sizes around every boundary of the plan, voxel-code-like
+    keys with long runs of equal values, all-equal / sorted / reversed / random keys of the full width (63 or 32 bits),
+    few distinct keys in the high and low bits, the largest key the sort accepts (the insertion's table-full slot)
+    mixed in and last, where a partial tile's padding is; nothing written past the end (tests/native/sort_check.hip,
+    built by `make sort_check`)."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "eskf_lio_amd", "lib", "sort_check")
