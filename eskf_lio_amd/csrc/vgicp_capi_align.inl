@@ -171,15 +171,13 @@ int ensure_dense(vgicp_ctx* ctx, bool* usable) {
   return VGICP_OK;
 }
 
-// The whole align in one launch (single GPU). Returns VGICP_OK and *ran = true when the kernel
-// completed; *ran = false when it gave up (the caller then uses launches).
-int run_align_persistent(vgicp_ctx* ctx, const double* guess, const vgicp_params* params,
-                         AlignState* result, bool* ran, float* device_ms) {
-  *ran = false;
+// The arguments of the single persistent launch, and the header row of the pinned log reset for it: everything the
+// host does before the launch (never allocates; the dense copy is rebuilt only when the map changed).
+int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, PersistArgs* out) {
   static_assert(sizeof(AlignState) <= kSlots * sizeof(double), "the state must fit the log's header row");
   const uint32_t grid = ctx->persist_grid;  // always the same, all resident: the exchange buffers rely on it
   const int max_it = params->max_iteration;
-  PersistArgs a;
+  PersistArgs& a = *out;
   std::memset(&a, 0, sizeof a);
   a.scan = ctx->d_scan;
   a.stride = ctx->stride;
@@ -227,7 +225,19 @@ int run_align_persistent(vgicp_ctx* ctx, const double* guess, const vgicp_params
   AlignState* header = reinterpret_cast<AlignState*>(ctx->h_log - kSlots);
   header->abort_seq = 0;
   header->outcome = kOutcomeNone;
-  { const int rc_copy = fetch_insert_totals(ctx); if (rc_copy != VGICP_OK) return rc_copy; }   // normally carried by the preparation's copy
+  return fetch_insert_totals(ctx);   // normally carried by the preparation's copy
+}
+
+// The whole align in one launch (single GPU). Returns VGICP_OK and *ran = true when the kernel
+// completed; *ran = false when it gave up (the caller then uses launches).
+int run_align_persistent(vgicp_ctx* ctx, const double* guess, const vgicp_params* params,
+                         AlignState* result, bool* ran, float* device_ms) {
+  *ran = false;
+  const uint32_t grid = ctx->persist_grid;
+  PersistArgs a;
+  { const int rc_args = persistent_args(ctx, guess, params, &a); if (rc_args != VGICP_OK) return rc_args; }
+  const bool multi = a.world > 1;
+  AlignState* header = reinterpret_cast<AlignState*>(ctx->h_log - kSlots);
   // one launch, one synchronisation
   static const bool trace_align = std::getenv("VGICP_TRACE_ALIGN") != nullptr;   // developer aid: where the host time of an align goes
   const double ta0 = trace_align ? now_seconds() : 0.0;
@@ -308,8 +318,10 @@ int run_align_persistent(vgicp_ctx* ctx, const double* guess, const vgicp_params
   return VGICP_OK;
 }
 
+// loop_only: the fused align's launch has just given up and been counted (fallback and cooldown are set): this align
+// goes to the launch-per-round loop without touching the cooldown.
 int run_align(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, double* out_pose,
-              vgicp_stats* stats) {
+              vgicp_stats* stats, bool loop_only = false) {
   const double t0 = now_seconds();
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
@@ -324,7 +336,7 @@ int run_align(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, d
 
   const bool peer_path = ctx->peers_connected && ctx->peer_enabled && ctx->peer_world > 1;
   const bool alone = ctx->world_size == 1;  // also a communicator of one rank: nothing to exchange
-  const bool single_launch = !(ctx->persistent_cooldown > 0 && !peer_path) && ctx->persistent_enabled &&
+  const bool single_launch = !loop_only && !(ctx->persistent_cooldown > 0 && !peer_path) && ctx->persistent_enabled &&
                              (alone || peer_path) && !profile && max_it > 0 &&
                              (params->flags & VGICP_FLAG_NO_PERSISTENT) == 0;
   if (ctx->owner && ctx->peer_world > 1 && !single_launch) return vgicp_internal::kNeedGroupLoop;  // the group's host-summed loop
@@ -334,7 +346,8 @@ int run_align(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, d
     if (rc != VGICP_OK) return rc;
     if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
   }
-  if (ctx->persistent_cooldown > 0 && !peer_path) --ctx->persistent_cooldown;
+  if (loop_only) {
+  } else if (ctx->persistent_cooldown > 0 && !peer_path) --ctx->persistent_cooldown;
   else if (single_launch) {
     bool ran = false;
     float ms = 0.f;

@@ -116,6 +116,7 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
   if (const char* dp = std::getenv("VGICP_DEBUG_PREP")) ctx->dev.debug_prep = std::atoi(dp);
   if (const char* ps = std::getenv("VGICP_PACK_SPIN_LIMIT")) ctx->dev.pack_spin_limit = (uint32_t)std::strtoul(ps, nullptr, 10);
   if (const char* dd = std::getenv("VGICP_DEBUG_UPLOAD_DELAY_US")) ctx->dev.debug_upload_delay_us = std::atol(dd);
+  ctx->dev.no_fused = std::getenv("VGICP_NO_FUSED_ALIGN") != nullptr;   // A/B: the pack launch, then the persistent one
   {
     // the in-kernel exchange needs every workgroup resident: one 512-thread workgroup with the LARGEST dynamic LDS
     // a launch plan asks for (memo + parked points of a scan bigger than the grid: 150 KB) must fit a CU — checked
@@ -138,6 +139,13 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
   if (const char* dbg = std::getenv("VGICP_DEBUG_STAMPS"); dbg && (dbg[0] == '1' || dbg[0] == '2')) {
     VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_stamps), (32 + kExchangeRows) * sizeof(uint64_t)));
     VG_CREATE(hipMemset(ctx->d_stamps, 0, (32 + kExchangeRows) * sizeof(uint64_t)));
+  }
+  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_unit_clock), sizeof(unsigned long long)));
+  VG_CREATE(hipMemset(ctx->d_unit_clock, 0, sizeof(unsigned long long)));
+  {
+    int khz = 0;
+    VG_CREATE(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device));
+    ctx->wall_clock_hz = khz > 0 ? khz * 1e3 : 0.0;
   }
   VG_CREATE(hipEventCreate(&ctx->ev_begin));
   VG_CREATE(hipEventCreate(&ctx->ev_end));
@@ -176,6 +184,7 @@ int vgicp_destroy(vgicp_ctx* ctx) {
   close_peers(ctx);
   if (ctx->d_mail) (void)hipFree(ctx->d_mail);
   if (ctx->d_mail_table) (void)hipFree(ctx->d_mail_table);
+  if (ctx->d_unit_clock) (void)hipFree(ctx->d_unit_clock);
   if (ctx->comm && ctx->rccl.CommDestroy) ctx->rccl.CommDestroy(ctx->comm);
   if (ctx->d_stamps) {
     uint64_t h[32] = {0};

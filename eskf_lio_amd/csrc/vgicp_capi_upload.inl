@@ -52,7 +52,28 @@ int ensure_upload_stage(vgicp_ctx* ctx, size_t bytes) {
   return VGICP_OK;
 }
 
-int scan_upload_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const double* covs) {
+// Whether scan_upload_enqueue stages this scan through the copy threads (else the runtime copies it in place).
+bool upload_is_staged(const vgicp_ctx* ctx, size_t n, const double* points, const double* covs) {
+  static const bool stage_off = std::getenv("VGICP_STAGE_LIMIT") && std::atoll(std::getenv("VGICP_STAGE_LIMIT")) == 0;
+  const size_t bytes = n * kScanPlanes * sizeof(double);
+  const size_t whole_bytes = ctx->upload_whole_hint ? ctx->upload_whole_hint : bytes;
+  return !stage_off && whole_bytes <= ctx->upload_stage_limit && bytes > (256u << 10) &&
+         !(is_pagelocked(points) && is_pagelocked(covs));
+}
+
+// A scan upload in three steps — stage (everything up to the copy), post + copy (the copy threads), finish — so that the
+// fused align can put its launch between the first two (vgicp_align).
+struct UploadJob {
+  bool staged = false;         // false: scan_upload_stage did the whole upload (n == 0 or the runtime's copy)
+  bool helpers = false;
+  uint32_t job = 0;
+  double t0 = 0.0, t_post = 0.0;
+};
+
+// The scan's bookkeeping; a staged upload's memory and the copy job's fields (not posted yet).  A scan that is not staged
+// is enqueued here whole (copies + pack_scan_kernel).
+int scan_upload_stage(vgicp_ctx* ctx, size_t n, const double* points, const double* covs, UploadJob* up) {
+  *up = UploadJob{};
   if (n > 0 && (!points || !covs)) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL scan pointer");
   if (n > 0xFFFFFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "scan too large");
   VG_HIP(ctx, hipSetDevice(ctx->device));
@@ -67,73 +88,101 @@ int scan_upload_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const do
   ctx->n = (uint32_t)n;
   ctx->stride = ctx->scan_capacity;
   if (n == 0) return VGICP_OK;
-  const double t0 = now_seconds();
+  up->t0 = now_seconds();
   double* aos_pts = ctx->d_scan_aos;
   double* aos_cov = ctx->d_scan_aos + 3 * ctx->scan_capacity;
   if (++ctx->scan_seq == 0) ++ctx->scan_seq;
   ctx->scan_sym_known = true;
   const size_t bytes = n * kScanPlanes * sizeof(double);
-  static const bool stage_off = std::getenv("VGICP_STAGE_LIMIT") && std::atoll(std::getenv("VGICP_STAGE_LIMIT")) == 0;
-  const size_t whole_bytes = ctx->upload_whole_hint ? ctx->upload_whole_hint : bytes;
-  const bool staged = !stage_off && whole_bytes <= ctx->upload_stage_limit && bytes > (256u << 10) &&
-                      !(is_pagelocked(points) && is_pagelocked(covs));
-  if (staged) {
-    const uint32_t unit = pack_arena_unit(), units = (uint32_t)((n + unit - 1) / unit);
-    const size_t pb = (n * 3 * sizeof(double) + 255 + 16) & ~size_t(255), cb = (n * 9 * sizeof(double) + 255 + 16) & ~size_t(255);
-    rc = ensure_upload_stage(ctx, pb + cb);
-    if (rc != VGICP_OK) return rc;
-    if (!ctx->ev_upload) VG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
-    // the kernel that read the staging memory last has long finished (every align ends in a synchronisation); make sure
-    if (ctx->upload_in_flight && hipEventQuery(ctx->ev_upload) != hipSuccess) VG_HIP(ctx, hipEventSynchronize(ctx->ev_upload));
-    ctx->upload_in_flight = false;
-    const bool want_helpers = ctx->upload_threads > 1 && bytes >= (2u << 20);
-    if (!ctx->crew) ctx->crew = new CopyCrew;
-    CopyCrew* crew = ctx->crew;
-    if (want_helpers && crew->th.empty()) crew->start(ctx->upload_threads - 1);
-    crew->pts = reinterpret_cast<const char*>(points);
-    crew->cov = reinterpret_cast<const char*>(covs);
-    crew->flags = reinterpret_cast<uint32_t*>(ctx->h_upload);
-    crew->apts = ctx->h_upload + ctx->upload_flag_bytes;
-    crew->acov = crew->apts + pb;
-    crew->n = (uint32_t)n;
-    crew->unit = unit;
-    crew->units = units;
-    crew->seq = ctx->scan_seq;
-    crew->size_a = 3 * sizeof(double);
-    crew->size_b = 9 * sizeof(double);
-    crew->copy = stage_copy;
-    crew->copy_b_form = stage_cov_unit;
-    const double t_post = now_seconds();
-    const uint32_t job = crew->post(want_helpers);
-    // the launch first (it starts reading as soon as unit 0 is published), then this thread copies too
-    // test aids: a pack kernel with little patience and a copy thread that is held up (the repeat below is then what counts)
-    const uint32_t spin_limit = ctx->dev.pack_spin_limit ? ctx->dev.pack_spin_limit : kPackSpinLimit;
-    const long debug_delay_us = ctx->dev.debug_upload_delay_us;
-    const hipError_t e_launch = launch_pack_arena(ctx->stream, crew->apts, crew->acov, (uint32_t)n, crew->flags, true, ctx->scan_seq,
-                                                  spin_limit, aos_pts, aos_cov, ctx->d_scan, ctx->stride,
-                                                  ctx->d_ins_counters + 2);
-    if (debug_delay_us > 0 && !want_helpers) std::this_thread::sleep_for(std::chrono::microseconds(debug_delay_us));
-    crew->work(job);
-    const bool crew_done = crew->finish();   // always: the caller's buffers must not be in use on return
-    if (e_launch != hipSuccess) return fail_hip(ctx, e_launch, "launch_pack_arena");
-    if (!crew_done) return crew_gave_up(ctx);
-    if (now_seconds() - t_post > kCrewSlowSeconds) {
-      // the copy threads were held up for so long that a workgroup of the launch may have stopped waiting: everything
-      // is staged now, pack it again behind the launch (no flags to wait for)
-      ++ctx->upload_slow;
-      VG_HIP(ctx, launch_pack_arena(ctx->stream, crew->apts, crew->acov, (uint32_t)n, crew->flags, false, ctx->scan_seq, 0, aos_pts,
-                                    aos_cov, ctx->d_scan, ctx->stride, ctx->d_ins_counters + 2));
-    }
-    VG_HIP(ctx, hipEventRecord(ctx->ev_upload, ctx->stream));
-    ctx->upload_in_flight = true;
-  } else {
+  if (!upload_is_staged(ctx, n, points, covs)) {
     VG_HIP(ctx, hipMemcpyAsync(aos_pts, points, n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     VG_HIP(ctx, hipMemcpyAsync(aos_cov, covs, n * 9 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     VG_HIP(ctx, launch_pack_scan(ctx->stream, aos_pts, aos_cov, (uint32_t)n, ctx->d_scan, ctx->stride,
                                  ctx->d_ins_counters + 2, ctx->scan_seq));
+    ctx->upload_bytes += bytes;
+    ctx->upload_seconds += now_seconds() - up->t0;  // host side: the copy calls + the enqueue of the pack kernel
+    return VGICP_OK;
   }
-  ctx->upload_bytes += bytes;
-  ctx->upload_seconds += now_seconds() - t0;  // host side: the staging copy (or the copy calls) + the enqueue of the pack kernel
+  const uint32_t unit = pack_arena_unit(), units = (uint32_t)((n + unit - 1) / unit);
+  const size_t pb = (n * 3 * sizeof(double) + 255 + 16) & ~size_t(255), cb = (n * 9 * sizeof(double) + 255 + 16) & ~size_t(255);
+  rc = ensure_upload_stage(ctx, pb + cb);
+  if (rc != VGICP_OK) return rc;
+  if (!ctx->ev_upload) VG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
+  // the kernel that read the staging memory last has long finished (every align ends in a synchronisation); make sure
+  if (ctx->upload_in_flight && hipEventQuery(ctx->ev_upload) != hipSuccess) VG_HIP(ctx, hipEventSynchronize(ctx->ev_upload));
+  ctx->upload_in_flight = false;
+  up->staged = true;
+  up->helpers = ctx->upload_threads > 1 && bytes >= (2u << 20);
+  if (!ctx->crew) ctx->crew = new CopyCrew;
+  CopyCrew* crew = ctx->crew;
+  if (up->helpers && crew->th.empty()) crew->start(ctx->upload_threads - 1);
+  crew->pts = reinterpret_cast<const char*>(points);
+  crew->cov = reinterpret_cast<const char*>(covs);
+  crew->flags = reinterpret_cast<uint32_t*>(ctx->h_upload);
+  crew->apts = ctx->h_upload + ctx->upload_flag_bytes;
+  crew->acov = crew->apts + pb;
+  crew->n = (uint32_t)n;
+  crew->unit = unit;
+  crew->units = units;
+  crew->seq = ctx->scan_seq;
+  crew->size_a = 3 * sizeof(double);
+  crew->size_b = 9 * sizeof(double);
+  crew->copy = stage_copy;
+  crew->copy_b_form = stage_cov_unit;
+  return VGICP_OK;
+}
+
+// The copy threads start on the staged job.
+void scan_upload_post(vgicp_ctx* ctx, UploadJob* up) {
+  up->t_post = now_seconds();
+  up->job = ctx->crew->post(up->helpers);
+}
+
+// This thread copies too, then waits for the helpers: the caller's buffers are free again on return.  *slow: the copy
+// threads were held up for so long (kCrewSlowSeconds) that a kernel waiting for their units may have stopped waiting —
+// counted here, once.  A helper that never delivers ends the upload (crew_gave_up).
+int scan_upload_copy(vgicp_ctx* ctx, const UploadJob& up, bool* slow) {
+  *slow = false;
+  // test aid: a copy thread that is held up
+  const long debug_delay_us = ctx->dev.debug_upload_delay_us;
+  if (debug_delay_us > 0 && !up.helpers) std::this_thread::sleep_for(std::chrono::microseconds(debug_delay_us));
+  ctx->crew->work(up.job);
+  if (!ctx->crew->finish()) return crew_gave_up(ctx);   // always: the caller's buffers must not be in use on return
+  if (now_seconds() - up.t_post > kCrewSlowSeconds) {
+    *slow = true;
+    ++ctx->upload_slow;
+  }
+  return VGICP_OK;
+}
+
+// pack_arena_kernel over the staging memory of the current scan (wait: behind the copy threads, with the pack's patience)
+hipError_t launch_pack_staged(vgicp_ctx* ctx, bool wait) {
+  const uint32_t spin_limit = ctx->dev.pack_spin_limit ? ctx->dev.pack_spin_limit : kPackSpinLimit;
+  CopyCrew* crew = ctx->crew;
+  return launch_pack_arena(ctx->stream, crew->apts, crew->acov, ctx->n, crew->flags, wait, ctx->scan_seq, wait ? spin_limit : 0,
+                           ctx->d_scan_aos, ctx->d_scan_aos + 3 * ctx->scan_capacity, ctx->d_scan, ctx->stride,
+                           ctx->d_ins_counters + 2);
+}
+
+// The whole upload, enqueued: the pack kernel (and whatever the caller enqueues next) runs in stream order.
+int scan_upload_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const double* covs) {
+  UploadJob up;
+  int rc = scan_upload_stage(ctx, n, points, covs, &up);
+  if (rc != VGICP_OK || !up.staged) return rc;
+  scan_upload_post(ctx, &up);
+  // the launch first (it starts reading as soon as unit 0 is published), then this thread copies too
+  const hipError_t e_launch = launch_pack_staged(ctx, true);
+  bool slow = false;
+  rc = scan_upload_copy(ctx, up, &slow);
+  if (e_launch != hipSuccess) return fail_hip(ctx, e_launch, "launch_pack_arena");
+  if (rc != VGICP_OK) return rc;
+  // the copy threads were held up for so long that a workgroup of the launch may have stopped waiting: everything is
+  // staged now, pack it again behind the launch (no flags to wait for)
+  if (slow) VG_HIP(ctx, launch_pack_staged(ctx, false));
+  VG_HIP(ctx, hipEventRecord(ctx->ev_upload, ctx->stream));
+  ctx->upload_in_flight = true;
+  ctx->upload_bytes += n * kScanPlanes * sizeof(double);
+  ctx->upload_seconds += now_seconds() - up.t0;  // host side: the staging copy + the enqueue of the pack kernel
   return VGICP_OK;
 }
 }  // namespace

@@ -311,6 +311,7 @@ struct vgicp_ctx {
     int debug_prep = 0;
     uint32_t pack_spin_limit = 0;     // 0 = the module's default
     long debug_upload_delay_us = 0;
+    bool no_fused = false;            // A/B: vgicp_align keeps the pack launch in front of the persistent one
   } dev;
   CopyCrew* crew = nullptr;          // the upload's copy threads, created with the first upload that wants a helper
   int upload_threads = 3;            // threads that copy a scan into the staging memory, the caller's included (VGICP_UPLOAD_THREADS).
@@ -407,6 +408,8 @@ struct vgicp_ctx {
   double* h_log_dev = nullptr;  // the same memory as the device addresses it (the persistent launch writes state + log there)
   int log_capacity = 0;     // iterations
   uint64_t* d_stamps = nullptr;  // only with VGICP_DEBUG_STAMPS=1
+  unsigned long long* d_unit_clock = nullptr;  // FusedUpload::unit_clock
+  double wall_clock_hz = 0.0;    // the device's constant clock (s_memrealtime)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   hipEvent_t ev_chunk[kMaxChunksInFlight] = {nullptr, nullptr};
   std::vector<hipEvent_t> ev_prof;

@@ -53,6 +53,9 @@ struct AlignState {
   // persistent launch only (the host zeroes both before the launch)
   uint32_t abort_seq; // = PersistArgs::seq when ANY workgroup gave up waiting (whatever workgroup 0 concluded)
   uint32_t outcome;   // workgroup 0's verdict: kOutcome*
+  // fused align only: device constant-clock ticks (s_memrealtime) from the moment the last workgroup had its staged
+  // points in LDS to workgroup 0's commit, the launch's device time without the upload it waited for
+  uint64_t unit_to_end_ticks;
 };
 // AlignState::outcome of a persistent launch
 constexpr uint32_t kOutcomeNone = 0;         // workgroup 0 gave up inside a round (or never ran)
@@ -155,9 +158,28 @@ struct PersistArgs {
   uint64_t* stamps;
 };
 
+// The fused align (vgicp_align, one point per thread, one device): the persistent launch is enqueued BEFORE the copy
+// threads stage the scan, and every workgroup reads its own 448 points out of the page-locked staging memory as the
+// units are published — what pack_arena_kernel reads and writes for them, in the same layout (see that kernel).
+struct FusedUpload {
+  const char* apts;          // staged points, 24 bytes per point
+  const char* acov;          // staged covariances: unit u starts at acov + 72 * u * unit, compact (48 B) or full (72 B)
+  const uint32_t* flags;     // flags[16 * u] == seq: unit u is staged; flags[16 * u + 1]: its form (kArenaCompact / kArenaFull)
+  uint32_t unit;             // points per unit (pack_arena_unit())
+  uint32_t seq;
+  uint32_t spin_limit;       // the pack's patience: polls of a unit's flag, and of round 0's exchange
+  double* soa;               // out: the 12 SoA planes (PersistArgs::scan), stride PersistArgs::stride
+  double* aos_pts;           // out: the device's AoS copy of the scan
+  double* aos_cov;
+  uint32_t* asym;            // out: = seq when some covariance is not bitwise symmetric
+  unsigned long long* unit_clock;  // device word: the latest s_memrealtime at which a workgroup had its points in LDS
+};
+
 // ---- launchers (defined in vgicp_kernels.hip) ----
 // The whole ICP::align loop in one launch (512-thread workgroups, at most one per CU).
 hipError_t launch_persistent(hipStream_t s, const PersistArgs& args, uint32_t grid);
+// The same launch with the scan's upload fused into round 0 (single device, args.n <= grid x 448, no stamps).
+hipError_t launch_persistent_fused(hipStream_t s, const PersistArgs& args, const FusedUpload& up, uint32_t grid);
 // How launch_persistent splits the CU's LDS for a scan of n points on `grid` workgroups: points per
 // thread beyond the first that get a memo (last key + slot, 16 B) and that are parked whole (96 B).
 void persistent_lds_plan(uint32_t n, uint32_t grid, uint32_t* memo_points, uint32_t* stash_points, uint32_t* stash_bytes,

@@ -840,14 +840,112 @@ __device__ __forceinline__ uint64_t pinned_clock(double (&x)[N]) {
   return t;
 }
 
+// The fused align's round-0 load (all threads of the workgroup; one point per worker thread).  The workgroup's 448
+// points lie in one or two staged units: thread 0 waits for their flags with system-scope loads and the pack's patience,
+// then the workgroup reads the points and the covariances over PCIe as pack_arena_kernel does — contiguous 16-byte
+// non-temporal loads into LDS (`lds`: 18 x 448 doubles, the neighbour-prefetch area, unused before round 0), the
+// compact or full form per unit, the odd-count tail read whole (the staging areas are padded).  It leaves behind what
+// the pack left for these points: the 12 SoA planes, the AoS device copy and the asymmetry word.  Each worker thread
+// returns its point in q0, as load_point would have read it from the planes.  false: a unit did not arrive in time.
+__device__ __forceinline__ bool fused_round0_load(const FusedUpload& f, uint64_t stride, uint32_t n_pts, double* lds,
+                                                  double (&q0)[kScanPlanes]) {
+  typedef int v4i __attribute__((ext_vector_type(4)));
+  constexpr uint32_t B = 512, W = B - 64;   // the persistent workgroup and its worker threads
+  __shared__ uint32_t ok_sh, form_sh[2];
+  const uint32_t tid = threadIdx.x, p0 = blockIdx.x * W;
+  const uint32_t cnt = p0 < n_pts ? min(W, n_pts - p0) : 0u;  // uniform
+  if (cnt == 0) return true;
+  const uint32_t ua = p0 / f.unit, ub = (p0 + cnt - 1) / f.unit;  // W < unit: at most two units
+  const uint32_t split = min(p0 + cnt, (ua + 1) * f.unit);         // the first point of unit ub (p0 + cnt: one unit)
+  if (tid == 0) {
+    uint32_t good = 1;
+    for (uint32_t u = ua; u <= ub && good; ++u)
+      for (uint32_t spins = 0; __hip_atomic_load(f.flags + 16 * u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != f.seq; ++spins) {
+        if (spins >= f.spin_limit) { good = 0; break; }
+        __builtin_amdgcn_s_sleep(20);
+      }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    ok_sh = good;
+    if (good) {
+      form_sh[0] = __hip_atomic_load(f.flags + 16 * ua + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      form_sh[1] = __hip_atomic_load(f.flags + 16 * ub + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+  __syncthreads();
+  if (!ok_sh) return false;  // uniform
+  double* lp = lds;             // points: 3 x W
+  double* lc = lds + 3 * W;     // covariances, whole records: 9 x W
+  double* lq = lds + 12 * W;    // compact records as staged: 6 x W
+  {
+    const v4i* sp = reinterpret_cast<const v4i*>(f.apts + (size_t)p0 * 24);
+    const uint32_t np = (cnt * 24 + 15) / 16;
+    for (uint32_t k = tid; k < np; k += B) reinterpret_cast<v4i*>(lp)[k] = __builtin_nontemporal_load(sp + k);
+  }
+  for (uint32_t s = 0; s < 2; ++s) {
+    // a segment starts at p0 or at a unit's start, both even: 16-byte aligned in the staging memory and in LDS
+    const uint32_t s0 = s ? split : p0, s1 = s ? p0 + cnt : split, u = s ? ub : ua;  // uniform
+    if (s0 >= s1) continue;
+    if (form_sh[s] == kArenaCompact) {
+      const v4i* sc = reinterpret_cast<const v4i*>(f.acov + (size_t)u * f.unit * 72 + (size_t)(s0 - u * f.unit) * 48);
+      v4i* dst = reinterpret_cast<v4i*>(lq + 6 * (s0 - p0));
+      for (uint32_t k = tid; k < (s1 - s0) * 3; k += B) dst[k] = __builtin_nontemporal_load(sc + k);
+    } else {
+      const v4i* sc = reinterpret_cast<const v4i*>(f.acov + (size_t)s0 * 72);
+      v4i* dst = reinterpret_cast<v4i*>(lc + 9 * (s0 - p0));
+      const uint32_t nc = ((s1 - s0) * 72 + 15) / 16;
+      for (uint32_t k = tid; k < nc; k += B) dst[k] = __builtin_nontemporal_load(sc + k);
+    }
+  }
+  __syncthreads();
+  if (tid < cnt && form_sh[p0 + tid >= split ? 1 : 0] == kArenaCompact) {  // the three mirrored entries are made here
+    const double* q = lq + 6 * tid;
+    const double a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4], a5 = q[5];
+    double* c = lc + 9 * tid;
+    c[0] = a0; c[1] = a1; c[2] = a2; c[3] = a1; c[4] = a3; c[5] = a4; c[6] = a2; c[7] = a4; c[8] = a5;
+  }
+  __syncthreads();
+  // the workgroup's points have crossed the link: where the registration's device time starts (the two-launch path's
+  // persistent launch starts with every point packed)
+  if (tid == 0) atomicMax(f.unit_clock, (unsigned long long)wall_clock64());
+  // the AoS device copy, coalesced out of LDS (an odd count leaves one double at the end of each array)
+  {
+    const uint32_t wp = 3 * cnt, wc = 9 * cnt;
+    v4i* dp = reinterpret_cast<v4i*>(f.aos_pts + 3 * (size_t)p0);
+    v4i* dc = reinterpret_cast<v4i*>(f.aos_cov + 9 * (size_t)p0);
+    for (uint32_t k = tid; k < wp / 2; k += B) dp[k] = reinterpret_cast<const v4i*>(lp)[k];
+    for (uint32_t k = tid; k < wc / 2; k += B) dc[k] = reinterpret_cast<const v4i*>(lc)[k];
+    if (tid == 0 && (cnt & 1u)) {
+      f.aos_pts[3 * (size_t)p0 + wp - 1] = lp[wp - 1];
+      f.aos_cov[9 * (size_t)p0 + wc - 1] = lc[wc - 1];
+    }
+  }
+  const uint32_t wt = tid - 64u;
+  if (tid >= 64u && wt < cnt) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q0[k] = lp[3 * wt + k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) q0[3 + k] = lc[9 * wt + k];
+    const size_t i = p0 + wt;
+#pragma unroll
+    for (int k = 0; k < kScanPlanes; ++k) f.soa[k * stride + i] = q0[k];
+    const bool same = __double_as_longlong(q0[4]) == __double_as_longlong(q0[6]) &&
+                      __double_as_longlong(q0[5]) == __double_as_longlong(q0[9]) &&
+                      __double_as_longlong(q0[8]) == __double_as_longlong(q0[10]);
+    if (!same) *f.asym = f.seq;
+  }
+  return true;
+}
+
 // MULTI: several GPUs (the rank totals cross xGMI through mailboxes); STAMPS: in-kernel phase clocks
 // (VGICP_DEBUG_STAMPS=1).  Separate instantiations: the single-GPU production kernel carries neither.
 // MANY: a thread owns several points (scan larger than grid x 448), wave 0 included; every point has a memo in LDS, the
 // thread's first point stays in registers (its voxel record does not), some more are parked in LDS.  !MANY: one point
 // per thread (waves 1..7), kept in registers together with the
 // voxel record it used, plus the neighbour prefetch.  Separate instantiations keep both within 256 VGPRs.
-template <int BLOCK, bool MULTI, bool STAMPS, bool MANY>
-__device__ __forceinline__ void persistent_body(const PersistArgs& a) {
+// FUSED: round 0's points arrive through the staging memory of the upload (fused_round0_load), !MANY, !MULTI, !STAMPS.
+template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool FUSED = false>
+__device__ __forceinline__ void persistent_body(const PersistArgs& a, const FusedUpload& up) {
+  static_assert(!FUSED || (!MULTI && !STAMPS && !MANY), "the fused upload serves the single-device one-point-per-thread body");
   static_assert(BLOCK / kSlots == kFolders, "the exchange reproduces the fold order of iterate_kernel<512>");
   constexpr int kWaves = BLOCK / 64;
   constexpr int kWorkers = BLOCK - 64;
@@ -918,7 +1016,14 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a) {
 #pragma unroll
   for (int k = 0; k < kScanPlanes; ++k) q0[k] = 0.0;
   const bool have = first < end_pts;
-  if (have) load_point(a.scan, a.stride, first, q0);
+  if constexpr (FUSED) {
+    if (!fused_round0_load(up, a.stride, n_pts, reinterpret_cast<double*>(dyn_lds), q0)) {
+      if (tid == 0) a.state->abort_seq = a.seq;   // a unit never came: the host re-packs and re-runs the align
+      return;
+    }
+  } else if (have) {
+    load_point(a.scan, a.stride, first, q0);
+  }
 
   // what the first point used last round: key, hit flag, voxel payload (raw)
   bool spec = false, hit = false;
@@ -1120,9 +1225,11 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a) {
         store_through_bits(rows + (size_t)my_row * kSlots + lane, publishable(row_sum));
       }
       bool ok = true;
+      // the fused align's round 0: some workgroups publish a whole upload before the last one has its points
+      const uint32_t spin_limit = (FUSED && it == 0 && up.spin_limit > a.spin_limit) ? up.spin_limit : a.spin_limit;
       if (folder) {  // uniform
         double part = 0.0;
-        ok = poll_and_sum<false>(rows + (size_t)blk * kFolders * kSlots, lane, a.spin_limit, part);
+        ok = poll_and_sum<false>(rows + (size_t)blk * kFolders * kSlots, lane, spin_limit, part);
         if (ok && lane <= (uint32_t)kCountSlot) store_through_bits(parts + (size_t)blk * kSlots + lane, publishable(part));
       }
       if (STAMPS) { const uint64_t n = wall_clock64(); acc_l1 += n - t_mark; t_mark = n; }
@@ -1134,7 +1241,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a) {
         // polls and stores go through.  One point per thread (C2): 6.82 -> 6.55 us per round with 64 units (50: 6.63,
         // 60 - 70: 6.55, 85: 6.9, 100: 7.1); several points per thread (C5): no gain, not delayed.
         if (!MANY && !folder) __builtin_amdgcn_s_sleep(kL2Delay);
-        if (ok) ok = poll_and_sum<false>(parts, lane, a.spin_limit, tot);
+        if (ok) ok = poll_and_sum<false>(parts, lane, spin_limit, tot);
       } else {
         // ---- several GPUs: workgroup 0 adds the parts to this rank's total and stores it into the mailbox
         // of every rank (its own included); every workgroup then adds the ranks' totals in rank order ----
@@ -1265,6 +1372,8 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a) {
         out->converged = conv_keep ? 1 : 0;   // (the last increment itself, AlignState::step, is not reported by this launch)
         out->done = 1;
         out->pad = 0;
+        if constexpr (FUSED)
+          out->unit_to_end_ticks = wall_clock64() - __hip_atomic_load(up.unit_clock, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         out->seq = a.seq;
       }
     }
@@ -1289,14 +1398,22 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a) {
 // does not wait returns the bits of the one that does, whatever the sweep's raw size.
 template <int BLOCK, bool MULTI, bool STAMPS, bool MANY>
 __global__ __launch_bounds__(BLOCK) void persistent_kernel(PersistArgs a) {
+  const FusedUpload none{};
   if constexpr (MANY) {
     const uint32_t n_pts = a.n_dev ? (*a.n_dev < a.n ? *a.n_dev : a.n) : a.n;  // uniform
     if (n_pts <= gridDim.x * (uint32_t)(BLOCK - 64)) {
-      persistent_body<BLOCK, MULTI, STAMPS, false>(a);
+      persistent_body<BLOCK, MULTI, STAMPS, false>(a, none);
       return;
     }
   }
-  persistent_body<BLOCK, MULTI, STAMPS, MANY>(a);
+  persistent_body<BLOCK, MULTI, STAMPS, MANY>(a, none);
+}
+
+// The fused align: the upload's packing happens inside round 0 (a separate kernel, so that the production
+// instantiations above keep their code).
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void persistent_fused_kernel(PersistArgs a, FusedUpload up) {
+  persistent_body<BLOCK, false, false, false, true>(a, up);
 }
 
 // Multi-GPU only: fold this rank's rows into one row (fixed order) so the all-reduce moves 256 B.
@@ -1761,6 +1878,7 @@ constexpr uint32_t kMemoBytesPerPoint = kPersistWide * sizeof(int4);  // 8 192
 constexpr uint32_t kPersistDynLds = 150 * 1024;
 constexpr uint32_t kMaxMemoPoints = 12;  // beyond that a thread's points are looked up every round
 constexpr uint32_t kPrefetchBytes = kPersistWorkers * (sizeof(int4) + 6 * sizeof(double2));  // 50 176
+constexpr uint32_t kFusedLoadBytes = kPersistWorkers * 18 * sizeof(double);  // fused_round0_load: 64 512
 }  // namespace
 
 // The plan is made from n, which may be an upper bound of the scan's size (a scan prepared on the device): it is
@@ -1828,7 +1946,9 @@ hipError_t raise_lds_limit() {
 // call that may wait for the device — with several sub-contexts on one device another sub-context's launch is
 // already running (and waiting for this one) by then.
 hipError_t persistent_prepare_device() {
-  hipError_t e = raise_lds_limit<false, false, false>();
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&persistent_fused_kernel<512>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
+  if (e == hipSuccess) e = raise_lds_limit<false, false, false>();
   if (e == hipSuccess) e = raise_lds_limit<false, false, true>();
   if (e == hipSuccess) e = raise_lds_limit<false, true, false>();
   if (e == hipSuccess) e = raise_lds_limit<false, true, true>();
@@ -1862,6 +1982,16 @@ hipError_t launch_persistent(hipStream_t s, const PersistArgs& args, uint32_t gr
                            : launch_persistent_as<true, false, false>(s, args, grid, dyn, device);
   return stamps ? launch_persistent_as<false, true, false>(s, args, grid, dyn, device)
                 : launch_persistent_as<false, false, false>(s, args, grid, dyn, device);
+}
+
+hipError_t launch_persistent_fused(hipStream_t s, const PersistArgs& args, const FusedUpload& up, uint32_t grid) {
+  // one point per thread only: no memo, no stash; the round-0 load borrows the neighbour-prefetch area
+  if (args.memo_points != 0 || args.stash_bytes != 0 || args.world > 1 || args.stamps != nullptr || args.n_dev != nullptr ||
+      (uint64_t)args.n > (uint64_t)grid * kPersistWorkers || up.unit < kPersistWorkers)
+    return hipErrorInvalidValue;
+  const size_t dyn = std::max<size_t>(args.prefetch_margin > 0.0 ? kPrefetchBytes : 0u, kFusedLoadBytes);
+  ++g_kernel_launches; hipLaunchKernelGGL(persistent_fused_kernel<512>, dim3(grid), dim3(512), dyn, s, args, up);
+  return hipGetLastError();
 }
 
 // Whether `grid` 512-thread workgroups of the persistent kernel with this much dynamic LDS can all be
