@@ -510,6 +510,21 @@ class Context:
         assert n.value == kept.value
         return pts, covs
 
+    def scan_fetch_begin(self) -> int:
+        """vgicp_scan_fetch_begin alone: the fetch kernel enqueued behind the pending preparation -> the kept count."""
+        kept = C.c_size_t(0)
+        self._check(self._lib.vgicp_scan_fetch_begin(self._h, C.byref(kept)))
+        return kept.value
+
+    def scan_fetch_end(self, capacity: int):
+        """vgicp_scan_fetch_end alone, into arrays of `capacity` points -> (points, covs) of the delivered size."""
+        cap = int(capacity)
+        pts, covs = np.zeros((cap, 3)), np.zeros((cap, 9))
+        n = C.c_size_t(0)
+        self._check(self._lib.vgicp_scan_fetch_end(self._h, cap, _dp(pts) if cap else None, _dp(covs) if cap else None,
+                                                  C.byref(n)))
+        return pts[:n.value].copy(), covs[:n.value].copy()
+
     def scan_fetch_sums(self) -> np.ndarray:
         """vgicp_scan_fetch_sums: the device-made checksums of the last scan_fetch -> uint64[2][2][16] (array, A / B, lane)."""
         out = np.zeros(64, dtype=np.uint64)

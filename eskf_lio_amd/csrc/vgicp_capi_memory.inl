@@ -245,6 +245,13 @@ int ensure_scan(vgicp_ctx* ctx, size_t n) {
   return VGICP_OK;
 }
 
+// The resident scan is replaced, or a new preparation is enqueued: a fetch opened for the old scan (vgicp_scan_fetch_begin)
+// would copy the old bytes, and the checksums of the last fetch describe the old scan.  Both are void from here on.
+void forget_fetch(vgicp_ctx* ctx) {
+  ctx->fetch_open = false;
+  ctx->fetch_sums_valid = false;
+}
+
 int ensure_log(vgicp_ctx* ctx, int iterations) {
   if (iterations <= ctx->log_capacity) return VGICP_OK;
   if (ctx->d_log) VG_HIP(ctx, hipFree(ctx->d_log - kSlots));

@@ -30,6 +30,7 @@ int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it) {
     if (rc != VGICP_OK) return rc;
     ctx->scan_ready = false;   // whatever was resident went with the old buffers
     ctx->n = 0;
+    forget_fetch(ctx);
   }
   return ensure_log(ctx, std::max(max_it, 1));
 }
@@ -211,6 +212,7 @@ int adopt_device_scan(vgicp_ctx* ctx, int src_device, const double* d_points, co
   rc = ensure_scan(ctx, n);
   if (rc != VGICP_OK) return rc;
   ++ctx->scan_generation;
+  forget_fetch(ctx);
   ctx->scan_ready = false;
   ctx->prep_voxel = prep_voxel;
   ctx->prep_with_deskew = false;

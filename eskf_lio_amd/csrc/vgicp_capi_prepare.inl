@@ -546,6 +546,7 @@ int scan_prepare_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const d
   rc = ensure_scan(ctx, n);
   if (rc != VGICP_OK) return rc;
   ++ctx->scan_generation;
+  forget_fetch(ctx);
   ctx->scan_ready = false;
   ctx->scan_pending = false;
   ctx->n = 0;
@@ -692,7 +693,6 @@ int scan_prepare_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const d
                  (tr1 - tr0) * 1e3, (tr2 - tr1) * 1e3, (now_seconds() - tr2) * 1e3);
   if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[1], ctx->stream)); ctx->ev_stage_set[1] = true; }
   ctx->n_upper = (uint32_t)n;
-  ctx->fetch_sums_valid = false;
   ctx->scan_sym_known = false;   // covariances made on the device: all twelve planes are read
   ctx->n = (uint32_t)n;          // an upper bound until the pending scan is settled
   ctx->scan_pending = true;
@@ -840,18 +840,24 @@ int vgicp_scan_prepare_staged_async(vgicp_ctx* ctx, uint64_t ticket, size_t num_
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
   if (ctx->multi) return vgicp_multi_api::scan_prepare(ctx, 0, nullptr, nullptr, num_states, states, extrinsic, voxel_size, knn, nullptr, nullptr, true, ticket);
   vgicp_ctx::AheadSlot* slot = nullptr;
+  bool without_times = false;
   {
+    // the slot is taken under the lock that finds it: from here on vgicp_sweep_unstage / vgicp_sweep_stage on another
+    // thread cannot free or refill the memory the preparation reads
     std::lock_guard<std::mutex> lk(ctx->ahead_mutex);
     for (auto& s : ctx->ahead)
-      if (s.state == 1 && s.ticket == ticket) { slot = &s; break; }
+      if (ticket != 0 && s.state == 1 && s.ticket == ticket) { slot = &s; break; }
+    without_times = slot && num_states > 0 && !slot->has_times;
+    if (slot && !without_times) slot->state = 4;
   }
-  if (!slot || ticket == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "no sweep staged under this ticket (staged by vgicp_sweep_stage, used once)");
-  if (num_states > 0 && !slot->has_times) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the sweep was staged without capture times");
-  VG_HIP(ctx, hipSetDevice(ctx->device));
-  if (!slot->done) VG_HIP(ctx, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
-  const int rc = scan_prepare_enqueue(ctx, slot->n, reinterpret_cast<const double*>(slot->mem),
-                                      reinterpret_cast<const double*>(slot->mem + slot->times_at), num_states, states, extrinsic,
-                                      voxel_size, knn, slot);
+  if (!slot) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "no sweep staged under this ticket (staged by vgicp_sweep_stage, used once)");
+  if (without_times) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the sweep was staged without capture times");
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess && !slot->done) e = hipEventCreateWithFlags(&slot->done, hipEventDisableTiming);
+  const int rc = e != hipSuccess ? fail_hip(ctx, e, "vgicp_scan_prepare_staged_async")
+                                 : scan_prepare_enqueue(ctx, slot->n, reinterpret_cast<const double*>(slot->mem),
+                                                        reinterpret_cast<const double*>(slot->mem + slot->times_at), num_states,
+                                                        states, extrinsic, voxel_size, knn, slot);
   std::lock_guard<std::mutex> lk(ctx->ahead_mutex);
   // whatever the outcome the ticket is used up; the slot is free again once the kernels that read it are through
   // (an enqueue that failed before it launched anything left `done` as it was: an old, completed event)
@@ -954,7 +960,14 @@ int vgicp_scan_fetch_begin(vgicp_ctx* ctx, size_t* kept) {
   const double t0 = now_seconds();
   for (uint32_t spins = 0;; ++spins) {
     const unsigned long long k = __atomic_load_n(ctx->h_fetch_hdr, __ATOMIC_ACQUIRE);
-    if ((uint32_t)(k >> 32) == ctx->prep_epoch) { ctx->fetch_kept = (uint32_t)k; break; }
+    if ((uint32_t)(k >> 32) == ctx->prep_epoch) {
+      if ((uint32_t)k == 0) {   // a scan of n > 0 points keeps none only when it was refused (or gave up): say why now
+        ctx->fetch_open = false;
+        return vgicp_scan_info(ctx, kept, nullptr, nullptr);
+      }
+      ctx->fetch_kept = (uint32_t)k;
+      break;
+    }
     const unsigned long long d = __atomic_load_n(ctx->h_fetch_hdr + 8, __ATOMIC_ACQUIRE);
     if ((uint32_t)(d >> 32) == ctx->fetch_seq) {   // the fetch kernel has started: the preparation ended without a count
       ctx->fetch_open = false;
@@ -988,6 +1001,12 @@ int vgicp_scan_fetch_end(vgicp_ctx* ctx, size_t capacity, double* points, double
     const double t0 = now_seconds();
     for (uint32_t piece = 0; piece < pieces && rc_copy == VGICP_OK; ++piece) {
       for (uint32_t spins = 0; __atomic_load_n(flags + 16u * piece, __ATOMIC_ACQUIRE) != ctx->fetch_seq; ++spins) {
+        // the fetch kernel found the preparation refused: it writes no piece, settle() below says why
+        const unsigned long long d = __atomic_load_n(ctx->h_fetch_hdr + 8, __ATOMIC_ACQUIRE);
+        if ((uint32_t)(d >> 32) == ctx->fetch_seq && (d & 1ull)) {
+          rc_copy = fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the preparation was refused: no prepared scan to fetch");
+          break;
+        }
         __builtin_ia32_pause();
         if ((spins & 4095u) == 4095u && now_seconds() - t0 > kFetchPatienceSeconds) {
           rc_copy = fail(ctx, VGICP_ERR_TIMEOUT, "the prepared scan did not arrive within 5 s");

@@ -80,6 +80,7 @@ int scan_upload_stage(vgicp_ctx* ctx, size_t n, const double* points, const doub
   int rc = ensure_scan(ctx, n);
   if (rc != VGICP_OK) return rc;
   ++ctx->scan_generation;
+  forget_fetch(ctx);
   ctx->scan_ready = false;
   ctx->prep_voxel = 0.0;
   ctx->prep_with_deskew = false;   // what vgicp_scan_info reports belongs to a PREPARED scan, not to this one

@@ -377,7 +377,8 @@ struct vgicp_ctx {
     bool has_times = false;
     uint32_t step = 0, off[3] = {0, 0, 0};   // != 0: sensor records (vgicp_sweep_stage_cloud2), float32 x y z at these offsets
     size_t times_at = 0;           // byte offset of the capture times (n doubles) inside mem
-    int state = 0;                 // 0 free, 1 staged, 2 handed to the device (`done` recorded behind its readers), 3 being filled
+    int state = 0;                 // 0 free, 1 staged, 2 handed to the device (`done` recorded behind its readers), 3 being filled,
+                                   // 4 being handed to the device (vgicp_scan_prepare_staged_async is enqueuing its readers)
     hipEvent_t done = nullptr;
   };
   AheadSlot ahead[3];

@@ -511,6 +511,9 @@ __global__ __launch_bounds__(kScanThreads) void run_scan_kernel(
   if (tid == 0) tile_sh = atomicAdd(&counters[kTicketA], 1u);
   __syncthreads();
   const uint32_t tile = tile_sh;
+  // set by the prologue (an earlier launch) when a point lies beyond the search grid: read early, where the loads below hide
+  // its latency, and kept in a scalar register (the kernel's register count stays as it was)
+  const bool refused = (uint32_t)__builtin_amdgcn_readfirstlane((int)counters[kBeyondGrid]) == epoch;
   const uint32_t j0 = tile * kScanTile + tid * kScanItems;  // this thread's kScanItems consecutive sorted positions
   // Every load below is unconditional, from a clamped place, and masked afterwards: a load under a condition becomes a
   // branch, and the eight items' chains (index -> point -> store) then run one after the other — thirty tiles are one
@@ -631,11 +634,14 @@ __global__ __launch_bounds__(kScanThreads) void run_scan_kernel(
     if (j + 1 < n && (c[k + 2] >> (3 * kFineShift)) == (c[k + 1] >> (3 * kFineShift))) continue;
     const RunMin v = op(base_prefix, e[k]);
     if (j + 1 == n) {
-      counters[0] = v.count;
-      counters[1] = v.runs;
+      // a refused scan (the prologue found a point beyond the search grid) keeps nothing, as a scan that gave up: the
+      // host waiting for the count learns at once that there is nothing to fetch
+      const uint32_t count = refused ? 0u : v.count;
+      counters[0] = count;
+      counters[1] = refused ? 0u : v.runs;
       // the host may be waiting for exactly this number (vgicp_scan_fetch_begin: it sizes its vectors while the
       // neighbour search runs): one posted write into page-locked memory, tagged with the call's epoch
-      if (host_kept) __hip_atomic_store(host_kept, ((unsigned long long)epoch << 32) | v.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (host_kept) __hip_atomic_store(host_kept, ((unsigned long long)epoch << 32) | count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     queries[v.count - 1u] = (uint32_t)v.packed;
     keep_by_index[(uint32_t)(v.packed >> 32)] = 1u;

@@ -319,7 +319,11 @@ int vgicp_scan_info(vgicp_ctx* ctx, size_t* kept, int64_t* deskewed, uint64_t* i
  * with hipEventQuery (outside the mutex).  At most three sweeps can be staged ahead (VGICP_ERR_NOT_READY beyond); a
  * ticket is used once — by vgicp_scan_prepare_staged_async, or by vgicp_sweep_unstage for a sweep that is dropped
  * unprepared (a measurement the caller discards: src/Odometry.cpp:43-48 may pop several and keep one), which frees its
- * slot; a ticket that is never used either way keeps its slot for the life of the context. */
+ * slot; a ticket that is never used either way keeps its slot for the life of the context.  The two uses exclude each
+ * other: once vgicp_scan_prepare_staged_async has found the ticket, a vgicp_sweep_unstage of it (from any thread) fails
+ * with VGICP_ERR_BAD_ARGUMENT and no vgicp_sweep_stage reuses its slot before the preparation's readers are through; once
+ * vgicp_sweep_unstage has dropped it, the preparation fails.  The preparation uses the ticket up whatever its outcome,
+ * except when it is refused because the sweep was staged without capture times and num_states > 0. */
 int vgicp_sweep_stage(vgicp_ctx* ctx, size_t n, const double* points, const double* point_time, uint64_t* ticket);
 int vgicp_sweep_unstage(vgicp_ctx* ctx, uint64_t ticket);
 int vgicp_scan_prepare_staged_async(vgicp_ctx* ctx, uint64_t ticket, size_t num_states, const double* states,
@@ -341,8 +345,14 @@ int vgicp_map_insert_resident_async(vgicp_ctx* ctx, const double transform[16], 
  *                            has reported how many points it keeps (*kept) — while the neighbour search and the
  *                            covariances are still running: the caller sizes its vectors in that time;
  *   vgicp_scan_fetch_end     copies the pieces into points (kept x 3) / covs (kept x 9, column-major) as they arrive and
- *                            brings the context up to date as vgicp_scan_info does (a refused scan fails this call).
- * Without a pending preparation (or on a multi-device context) the pair is vgicp_scan_info + vgicp_scan_download. */
+ *                            brings the context up to date as vgicp_scan_info does.
+ * A refused scan (a point beyond the search grid) fails vgicp_scan_fetch_begin as soon as the down-sampling is through,
+ * as vgicp_scan_info would (VGICP_ERR_BAD_ARGUMENT, *kept = 0); vgicp_scan_fetch_end then answers as
+ * vgicp_scan_download does.  Neither call waits for a piece that a refused scan never writes.
+ * Without a pending preparation (or on a multi-device context) the pair is vgicp_scan_info + vgicp_scan_download.  So is
+ * vgicp_scan_fetch_end without a vgicp_scan_fetch_begin, or after anything that replaced the resident scan since the
+ * begin (a new preparation, vgicp_scan_upload, vgicp_align): it always delivers the scan resident when it is called.
+ * vgicp_scan_fetch_begin twice fetches once, through the second kernel. */
 int vgicp_scan_fetch_begin(vgicp_ctx* ctx, size_t* kept);
 int vgicp_scan_fetch_end(vgicp_ctx* ctx, size_t capacity, double* points, double* covs, size_t* n);
 /* Checksums of what the last vgicp_scan_fetch_end delivered, made BY THE DEVICE while it wrote the pieces — for a caller
@@ -351,7 +361,8 @@ int vgicp_scan_fetch_end(vgicp_ctx* ctx, size_t capacity, double* points, double
  * mod 16, k = index / 16); sums[32 a + lane] = the sum of the lane's words, sums[32 a + 16 + lane] = the sum of
  * (m_lane - k) x word with m_lane the lane's word count, both mod 2^64; a = 0 the points, 1 the covariances.  That is
  * what the loop  s1 += w; s2 += s1  over a lane's words ends with, up to its start values.  VGICP_ERR_NOT_READY when
- * the last host copy did not come through the fetch kernel (nothing pending, a multi-device context). */
+ * the last host copy did not come through the fetch kernel (nothing pending, a multi-device context), when it failed,
+ * or when the resident scan has been replaced since. */
 int vgicp_scan_fetch_sums(vgicp_ctx* ctx, uint64_t sums[64]);
 
 /* What the calls of THIS HOST THREAD into the module (whatever the context) have cost the host since this context's

@@ -7,6 +7,7 @@ actually reach (1e-9), so drift is caught early.  Integer work (voxel keys, matc
 is compared bit-exactly.
 """
 import os
+import time
 
 import numpy as np
 import pytest
@@ -1252,9 +1253,12 @@ def test_scan_fetch_returns_the_prepared_scan_without_a_copy_command(oracle):
         bad = synth.make_lidar_scan(5_000, seed=3).copy()
         bad[17, 0] = 1e9
         a.scan_prepare_async(bad, None, None, None, 0.3, 30)
+        t0 = time.perf_counter()
         with pytest.raises(capi.VgicpError) as e:
             a.scan_fetch()
+        seconds = time.perf_counter() - t0
         assert e.value.code == capi.ERR_BAD_ARGUMENT
+        assert seconds <= 1.0, seconds              # no wait for pieces a refused scan never writes
         a.scan_prepare_async(raw, None, None, ext, 0.3, 30)          # and the context recovers
         assert len(a.scan_fetch()[0]) > 0
 
