@@ -63,3 +63,284 @@ class OracleBackend:
             self.removed.append(self.map.evict(transform[:3, 3], self.evict[1]))
             self.updates_since_evict = 0
         self.prev = transform.copy()
+
+
+# ---- lockstep: the device chain and the oracle chain from the same state every frame (teacher forcing) -------------
+JTJ_RTOL = 1e-9          # per-round normal equations, relative to the round's largest entry
+LOCKSTEP_POSE_TOL = 1e-9  # TIGHT_POSE_TOL of tests/conftest.py
+
+
+def _pose_delta(A, B):
+    dt = float(np.linalg.norm(A[:3, 3] - B[:3, 3]))
+    R = A[:3, :3].T @ B[:3, :3]
+    c = max(-1.0, min(1.0, 0.5 * (np.trace(R) - 1.0)))
+    s = 0.5 * np.linalg.norm([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return dt, float(np.arctan2(s, c))
+
+
+def first_difference(dev, ora, rtol=JTJ_RTOL):
+    """The first Gauss-Newton round in which two aligns from the same map, scan and guess part -> (round, why), or None.
+    A round differs in its correspondence count or in a JTJ entry beyond rtol x the round's scale; after the common
+    rounds, in the round count or the converged flag."""
+    nd, no = int(dev.iterations), int(ora.iterations)
+    cd, co = np.asarray(dev.corr_count)[:nd], np.asarray(ora.corr_count)[:no]
+    Jd, Jo = np.asarray(dev.JTJ)[:nd], np.asarray(ora.JTJ)[:no]
+    for k in range(min(nd, no)):
+        if int(cd[k]) != int(co[k]):
+            return k, f"round {k}: {int(cd[k])} correspondences on the device, {int(co[k])} in the oracle"
+        scale = float(np.abs(Jo[k]).max())
+        err = float(np.abs(Jd[k] - Jo[k]).max())
+        if err > rtol * scale:
+            return k, f"round {k}: JTJ differs by {err:.3e} at scale {scale:.3e}"
+    if nd != no or bool(dev.converged) != bool(ora.converged):
+        return min(nd, no), f"rounds {nd} (converged {bool(dev.converged)}) on the device, {no} " \
+                            f"(converged {bool(ora.converged)}) in the oracle"
+    return None
+
+
+def certify_divergence(oracle, voxel_size, points, guess, dev, ora, rerun_dev, rerun_ora, reg, diff=None):
+    """Whether two aligns that part (first_difference) may legitimately do so: the same inputs, and either
+    (a) a voxel-face tie: under the two poses entering the first differing round r (each align re-run with
+        max_iteration = r), oracle.voxel_index bins at least one point differently, every such point lies within
+        10 x its displacement between the poses + 1e-12 m of the face it crossed, the correspondence counts of round r
+        differ by no more than the number of such points, and the entry poses agree to 1e-9; or
+    (b) a threshold tie: the round counts (or converged flags) differ, the entry poses agree to 1e-9, and the oracle's
+        last common step lies within 1e-9 (relative) of the translation or the cosine threshold.
+    points: the scan (sensor frame); rerun_dev / rerun_ora: max_iteration -> that side's align result from `guess`.
+    -> dict(accepted, kind, round, points, distances, why)."""
+    diff = diff or first_difference(dev, ora)
+    out = dict(accepted=False, kind=None, round=None, points=[], distances=[], why="")
+    if diff is None:
+        out["why"] = "the rounds do not differ"
+        return out
+    r, why = diff
+    out["round"] = r
+    if r:
+        pd, po = rerun_dev(r).pose, rerun_ora(r).pose
+    else:                                                       # both enter round 0 at the guess
+        pd = po = np.asarray(guess, dtype=np.float64)
+    dt, dr = _pose_delta(pd, po)
+    if max(dt, dr) > LOCKSTEP_POSE_TOL:
+        out["why"] = f"{why}; the poses entering round {r} are {dt:.3e} m / {dr:.3e} rad apart"
+        return out
+    nd, no = int(dev.iterations), int(ora.iterations)
+    if r < min(nd, no):                                         # (a): a round both sides ran
+        eye = np.tile(np.eye(3).reshape(9), (len(points), 1))
+        xd, _ = oracle.transform(points, eye, pd)
+        xo, _ = oracle.transform(points, eye, po)
+        kd, ko = oracle.voxel_index(voxel_size, xd), oracle.voxel_index(voxel_size, xo)
+        moved = np.nonzero((kd != ko).any(axis=1))[0]
+        if len(moved) == 0:
+            out["why"] = f"{why}; no point changes voxel between the two entry poses"
+            return out
+        dists, slack = [], []
+        for i in moved:
+            axes = np.nonzero(kd[i] != ko[i])[0]
+            face = np.maximum(kd[i, axes], ko[i, axes]).astype(np.float64) * voxel_size
+            dists.append(float(np.abs(xo[i, axes] - face).max()))
+            slack.append(10.0 * float(np.linalg.norm(xd[i] - xo[i])) + 1e-12)
+        out["points"], out["distances"] = moved.tolist(), dists
+        gap = abs(int(np.asarray(dev.corr_count)[r]) - int(np.asarray(ora.corr_count)[r]))
+        if any(d > s for d, s in zip(dists, slack)):
+            out["why"] = f"{why}; a point that changes voxel lies {max(dists):.3e} m from its face"
+            return out
+        if gap > len(moved):
+            out["why"] = f"{why}; {gap} correspondences apart but only {len(moved)} points near a face"
+            return out
+        out.update(accepted=True, kind="voxel face", why=why)
+        return out
+    # (b): one side stopped after round r - 1, the other did not (or the flags differ)
+    k = r - 1
+    if k < 0:
+        out["why"] = f"{why}; no common step"
+        return out
+    xi, _ = oracle.solve_step(np.asarray(ora.JTJ)[k], np.asarray(ora.JTr)[k])
+    step = oracle.se3_to_SE3(xi)
+    tsq = float(step[:3, 3] @ step[:3, 3])
+    cosine = 0.5 * (float(np.trace(step[:3, :3])) - 1.0)
+    t_thr, c_thr = float(reg["translation_sq_threshold"]), float(reg["cosine_threshold"])
+    near_t = abs(tsq - t_thr) <= 1e-9 * t_thr
+    near_c = abs(cosine - c_thr) <= 1e-9 * abs(c_thr)
+    out["distances"] = [abs(tsq - t_thr) / t_thr, abs(cosine - c_thr) / abs(c_thr)]
+    stopped = oracle.convergence_check(step, c_thr, t_thr)
+    if stopped != (no == r and bool(ora.converged)):
+        out["why"] = f"{why}; the oracle's own step {k} does not explain its stop"
+        return out
+    if not (near_t or near_c):
+        out["why"] = f"{why}; the last common step is {out['distances'][0]:.3e} / {out['distances'][1]:.3e} " \
+                     "(relative) from the thresholds"
+        return out
+    out.update(accepted=True, kind="threshold", why=why)
+    return out
+
+
+def reference_prepare(oracle, T_il, voxel, states, points, pointTime, reference_order=False):
+    """CloudPreprocessor::process as oracle calls: transform(T_il) -> deskew -> preprocess (or, under
+    VGICP_OPTION_REFERENCE_ORDER, preprocess_ordered(..., ORDER_REFERENCE_HASH)) -> (points, covs)."""
+    eye = np.tile(np.eye(3).reshape(9), (len(points), 1))
+    pts, _ = oracle.transform(points, eye, T_il)
+    if states is not None and len(states):
+        pts, done = oracle.deskew(pts, pointTime, states)
+        assert done >= 0, "IMU states do not bracket the sweep"
+    if reference_order:
+        p, c, _ = oracle.preprocess_ordered(pts, voxel, 30, oracle.ORDER_REFERENCE_HASH)
+    else:
+        p, c, _ = oracle.preprocess(pts, voxel, 30)
+    return p, c
+
+
+class LockstepBackend:
+    """The device chain and the oracle chain run side by side, from the same state every frame (teacher forcing).
+
+    device: anything with a capi.Context-like `ctx` (replay.DeviceBackend: its context is driven here, call by call).
+    Per frame: the device prepares the sweep and hands its prepared scan back (scan_download, or scan_fetch in the
+    enqueued form); that copy is the oracle's input, and on sampled frames (0, 1, the first after each eviction, the
+    largest raw sweep, the last) the oracle's own preparation must equal it bit for bit, order included.  Both align
+    from the same guess and must agree round by round (counts exactly, JTJ to 1e-9 x scale) and in the pose (1e-9);
+    the ORACLE's pose goes back to the filter.  Both insert with that pose, evict on the same schedule (removed counts
+    equal), and hold the same number of voxels after every frame; their exports are compared bit for bit after every
+    eviction, every change of the table size (a rehash) and at the end.  A frame whose aligns part is accepted only
+    with a certificate (certify_divergence), at most `max_accepted` per run."""
+
+    def __init__(self, config, oracle, device, enqueued=False, reference_order=False, prepare=None, max_accepted=2,
+                 log=print):
+        self.o = oracle
+        self.ctx = device.ctx
+        lm = config["local_map"]
+        self.map_voxel = float(lm["voxel_size"])
+        self.cap = int(lm["max_num_points_per_voxel"])
+        self.map = oracle.OracleMap(self.map_voxel, self.cap)
+        self.gate = (lm["translation_sq_threshold"], lm["cosine_threshold"])
+        self.evict = (bool(lm["remove_distant_points"]), float(lm["distance_threshold"]), int(lm.get("remove_every_updates", 0)))
+        assert not self.evict[0] or self.evict[2] > 0, "lockstep evicts by a count of map updates"
+        self.reg = config["registration"]
+        self.voxel = config["cloud_preprocessor"]["voxel_size"]
+        self.T_il = np.asarray(config["lidar_extrinsic"], dtype=np.float64)
+        self.enqueued, self.reference_order = bool(enqueued), bool(reference_order)
+        self.prepare = prepare or (lambda states, points, pointTime: reference_prepare(
+            oracle, self.T_il, self.voxel, states, points, pointTime, self.reference_order))
+        self.max_accepted, self.log = int(max_accepted), log
+        if self.reference_order:
+            from eskf_lio_amd import capi
+            self.ctx.set_option(capi.OPTION_REFERENCE_ORDER, 1)
+        self.ctx.map_reset(self.map_voxel, 0)
+        self.prev = None
+        self.updates_since_evict = 0
+        self.frame = -1
+        self.sample_next = False
+        self.pending = {}                                       # "largest" / "last": (frame, raw inputs, device scan)
+        self.iterations, self.kept, self.removed = [], [], []
+        self.slots_seen, self.slots_last = set(), None
+        self.map_checks = []                                    # (frame, why) of every export comparison
+        self.prep_checks = []                                   # frames whose preparation was compared
+        self.pose_diff = []                                     # per aligned frame: max(dt, dr) device vs oracle
+        self.accepted = []
+
+    # -- the three backend calls ---------------------------------------------------------------------------------
+    def preprocess(self, states, points, pointTime):
+        self.frame += 1
+        f = self.frame
+        if self.enqueued:
+            self.ctx.scan_prepare_async(points, pointTime, states, self.T_il, self.voxel, 30)
+            p, c = self.ctx.scan_fetch()
+            kept = self.ctx.scan_info()[0]
+        else:
+            kept, _ = self.ctx.scan_prepare(points, pointTime, states, self.T_il, self.voxel, 30)
+            p, c = self.ctx.scan_download()
+        assert kept == len(p) == len(c), f"frame {f}: kept {kept}, scan of {len(p)} points"
+        self.kept.append(int(kept))
+        raw = (None if states is None else np.array(states), np.array(points), np.array(pointTime))
+        if f <= 1 or self.sample_next:
+            self._check_preparation(f, raw, p, c)
+            self.sample_next = False
+        elif "largest" not in self.pending or len(points) > len(self.pending["largest"][1][1]):
+            self.pending["largest"] = (f, raw, p.copy(), c.copy())
+        self.pending["last"] = (f, raw, p.copy(), c.copy())
+        return p, c
+
+    def align(self, points, covs, guess):
+        f = self.frame
+        args = (self.reg["max_iteration"], self.reg["translation_sq_threshold"], self.reg["cosine_threshold"])
+        rd = self.ctx.align_resident(guess, *args)
+        ro = self.map.align(points, covs, guess, *args)
+        self.iterations.append(int(ro.iterations))
+        diff = first_difference(rd, ro)
+        if diff is None:
+            dt, dr = _pose_delta(rd.pose, ro.pose)
+            self.pose_diff.append(max(dt, dr))
+            assert max(dt, dr) <= LOCKSTEP_POSE_TOL, f"frame {f}: the same rounds, poses {dt:.3e} m / {dr:.3e} rad apart"
+            return ro.pose
+        cert = certify_divergence(self.o, self.map_voxel, points, guess, rd, ro,
+                                  lambda k: self.ctx.align_resident(guess, k, *args[1:]),
+                                  lambda k: self.map.align(points, covs, guess, k, *args[1:]), self.reg, diff)
+        if not cert["accepted"]:
+            raise AssertionError(f"frame {f}: {cert['why']} (not certified)")
+        self.accepted.append(dict(frame=f, **cert))
+        self.log(f"lockstep: frame {f} accepted ({cert['kind']}), round {cert['round']}: {cert['why']}; points "
+                 f"{cert['points'][:8]}, distances {['%.3e' % d for d in cert['distances'][:8]]}")
+        assert len(self.accepted) <= self.max_accepted, f"{len(self.accepted)} accepted divergences: {self.accepted}"
+        return ro.pose
+
+    def update_map(self, points, covs, transform, initialize):
+        if not initialize and self.prev is not None:                     # LocalMap::needsMapUpdate, once for both
+            moved = np.linalg.inv(self.prev) @ transform
+            cosine = 0.5 * (np.trace(moved[:3, :3]) - 1.0)
+            if not (cosine < self.gate[1] or float(moved[:3, 3] @ moved[:3, 3]) > self.gate[0]):
+                self.prev = transform.copy()
+                return
+        self._watch_table()                                              # what the previous insertion left
+        if self.enqueued:
+            self.ctx.map_insert_resident_async(transform, self.cap)
+        else:
+            self.ctx.map_insert_resident(transform, self.cap)
+        self.map.insert(*self.o.transform(points, covs, transform))
+        self.updates_since_evict += 1
+        if self.evict[0] and self.updates_since_evict >= self.evict[2]:
+            nd = self.ctx.map_evict(transform[:3, 3], self.evict[1])
+            no = self.map.evict(transform[:3, 3], self.evict[1])
+            assert nd == no, f"frame {self.frame}: eviction removed {nd} voxels on the device, {no} in the oracle"
+            self.removed.append(int(no))
+            self.updates_since_evict = 0
+            self.sample_next = True
+            self.compare_maps("eviction")
+        self.prev = transform.copy()
+
+    # -- checks ------------------------------------------------------------------------------------------------
+    def _watch_table(self):
+        voxels, slots = self.ctx.map_size()
+        assert voxels == len(self.map), f"frame {self.frame}: {voxels} voxels on the device, {len(self.map)} in the oracle"
+        self.slots_seen.add(int(slots))
+        if slots != self.slots_last:
+            if self.slots_last is not None:
+                self.compare_maps("rehash")
+            self.slots_last = slots
+
+    def _check_preparation(self, f, raw, p, c):
+        rp, rc = self.prepare(*raw)
+        assert len(rp) == len(p), f"frame {f}: the device kept {len(p)} points, the oracle {len(rp)}"
+        bad = np.nonzero((p != rp).any(axis=1) | (c != rc).any(axis=1))[0]
+        assert len(bad) == 0, f"frame {f}: prepared scans differ in {len(bad)} rows, first {bad[:4].tolist()}"
+        self.prep_checks.append(f)
+
+    def compare_maps(self, why):
+        dk, dm, dc, dn = self.ctx.map_export()
+        ok, om, oc, on = self.map.export()
+        order = np.lexsort(ok.T)
+        ok, om, oc, on = ok[order], om[order], oc[order], on[order]
+        where = f"frame {self.frame} ({why})"
+        assert len(dk) == len(ok), f"{where}: {len(dk)} voxels exported by the device, {len(ok)} by the oracle"
+        for name, a, b in (("keys", dk, ok), ("means", dm, om), ("covariances", dc, oc), ("counts", dn, on)):
+            rows = np.nonzero((a.reshape(len(a), -1) != b.reshape(len(b), -1)).any(axis=1))[0]
+            assert len(rows) == 0, f"{where}: {name} differ in {len(rows)} voxels, first key {ok[rows[0]].tolist()}"
+        self.map_checks.append((self.frame, why))
+
+    def finish(self):
+        """End of the drive: the table's last state, the final map, and the deferred preparation samples."""
+        self._watch_table()
+        self.compare_maps("final")
+        done = set(self.prep_checks)
+        for f, raw, p, c in self.pending.values():
+            if f not in done:
+                self._check_preparation(f, raw, p, c)
+                done.add(f)
+        return self
