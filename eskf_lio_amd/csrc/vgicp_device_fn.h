@@ -6,11 +6,13 @@
 namespace vgicp {
 namespace {
 
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+// The table's hash (murmur3's finaliser over the three keys).  Host code may call it too: tests/native/voxel_hash.hip
+// prints it for a fixed key list, and the test suite crafts colliding keys from a numpy restatement checked against it.
+__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
   h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
   return h;
 }
-__device__ __forceinline__ uint32_t voxel_hash(int32_t x, int32_t y, int32_t z) {
+__host__ __device__ __forceinline__ uint32_t voxel_hash(int32_t x, int32_t y, int32_t z) {
   uint32_t h = fmix32((uint32_t)x * 0x9E3779B1u + 0x7F4A7C15u);
   h = fmix32(h ^ ((uint32_t)y * 0x85EBCA77u));
   h = fmix32(h ^ ((uint32_t)z * 0xC2B2AE3Du));
@@ -86,17 +88,20 @@ __device__ __forceinline__ void transform_point(const double* R, const double* t
   q[2] = ((R[2] * x + R[5] * y) + R[8] * z) + t[2];
 }
 
-// Probe for the voxel that contains the key. Returns the record or nullptr.
+// Probe for the voxel that contains the key. Returns the record or nullptr.  The host keeps at least half of the slots
+// EMPTY (ensure_table), so a walk ends at an EMPTY slot long before it has seen every slot; the bound of mask + 1
+// probes only means that a broken invariant costs a wrong answer ("absent"), never a wave that spins forever.
 __device__ __forceinline__ const VoxelRecord* find_voxel(const VoxelRecord* table, uint32_t mask,
                                                          int32_t kx, int32_t ky, int32_t kz) {
   uint32_t slot = voxel_hash(kx, ky, kz) & mask;
-  for (;;) {
+  for (uint32_t probes = 0; probes <= mask; ++probes) {
     const VoxelRecord* rec = table + slot;
     const int4 ks = *reinterpret_cast<const int4*>(rec);
     if (ks.w == SLOT_EMPTY) return nullptr;
     if (ks.w == SLOT_FULL && ks.x == kx && ks.y == ky && ks.z == kz) return rec;
     slot = (slot + 1) & mask;
   }
+  return nullptr;
 }
 
 }  // namespace
