@@ -39,6 +39,9 @@ EXPORTS = (
     "vgicp_peer_export", "vgicp_peer_connect", "vgicp_peer_disconnect",
 )
 
+# every symbol include/vgicp_hip_map_points.h declares (an extension header: EXPORTS stays the main header's list)
+MAP_POINTS_EXPORTS = ("vgicp_map_points_size", "vgicp_map_points_export")
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -61,6 +64,7 @@ class FrameStats(C.Structure):
 OPTION_STAGE_EVENTS = 1
 OPTION_UPLOAD_STAGE_KB = 2   # scans up to this many KiB are staged through page-locked memory of the context; 0 = in place (vgicp_hip.h)
 OPTION_REFERENCE_ORDER = 3   # != 0: scan preparations emit the kept points in the reference's unordered_map order (vgicp_hip.h)
+OPTION_MAP_RAW_POINTS = 4    # != 0: the map keeps every voxel's raw points on the device (vgicp_hip_map_points.h)
 COUNTER_UPLOAD_SLOW = 6
 
 
@@ -138,7 +142,9 @@ def load_library() -> C.CDLL:
     lib.vgicp_peer_export.argtypes = [vp, vp]
     lib.vgicp_peer_connect.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.vgicp_peer_disconnect.argtypes = [vp]
-    for name in EXPORTS:
+    lib.vgicp_map_points_size.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    lib.vgicp_map_points_export.argtypes = [vp, sz, ip, dp, C.POINTER(sz)]
+    for name in EXPORTS + MAP_POINTS_EXPORTS:
         fn = getattr(lib, name)
         if name not in ("vgicp_last_error", "vgicp_peer_status"):
             fn.restype = C.c_int
@@ -329,6 +335,25 @@ class Context:
         assert w.value == n
         order = np.lexsort(keys.T)
         return keys[order], means[order], covs[order], counts[order]
+
+    def map_points_size(self):
+        """(raw points the map keeps, entries the device store holds before it grows); VgicpError (NOT_READY) while
+        OPTION_MAP_RAW_POINTS is off."""
+        p, c = C.c_size_t(), C.c_size_t()
+        self._check(self._lib.vgicp_map_points_size(self._h, C.byref(p), C.byref(c)))
+        return p.value, c.value
+
+    def map_points_export(self):
+        """(keys n x 3 int32, points n x 3) of every raw point the map keeps: a voxel's points contiguous, in insertion
+        order; the voxels in the library's (unspecified) order."""
+        n = self.map_points_size()[0]
+        keys = np.zeros((n, 3), dtype=np.int32)
+        pts = np.zeros((n, 3))
+        w = C.c_size_t()
+        self._check(self._lib.vgicp_map_points_export(self._h, n, keys.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      _dp(pts), C.byref(w)))
+        assert w.value == n, (w.value, n)
+        return keys, pts
 
     # -- registration --
     def scan_upload(self, points, covs):

@@ -65,19 +65,21 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
   VG_CREATE(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   // the insertion's running totals (4 words) sit right behind the counter block: ONE copy after a preparation brings
   // both back, so a deferred insertion needs no copy of its own in the frame chain
-  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_counters), (kCounterWords + 4) * sizeof(uint32_t)));
+  // ... and behind those the raw-point log's words (kInsertWords: 4 + 4)
+  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_counters), (kCounterWords + kInsertWords) * sizeof(uint32_t)));
   VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_counters), kCounterWords * sizeof(uint32_t), 0));
-  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_prep), (kCounterWords + 4) * sizeof(uint32_t), 0));
+  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_prep), (kCounterWords + kInsertWords) * sizeof(uint32_t), 0));
+  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_raw_ctr), 4 * sizeof(uint32_t), 0));
   VG_CREATE(hipMalloc(&ctx->d_tiles, preprocess_tile_bytes()));
   VG_CREATE(hipMemset(ctx->d_tiles, 0, preprocess_tile_bytes()));
-  VG_CREATE(hipMemset(ctx->d_counters, 0, (kCounterWords + 4) * sizeof(uint32_t)));
+  VG_CREATE(hipMemset(ctx->d_counters, 0, (kCounterWords + kInsertWords) * sizeof(uint32_t)));
   ctx->d_ins_counters = ctx->d_counters + kCounterWords;
   VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_fetch_hdr), 640, 0));
   std::memset(ctx->h_fetch_hdr, 0, 640);
   VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_fetch_sums), 65 * sizeof(unsigned long long)));
   VG_CREATE(hipMemset(ctx->d_fetch_sums, 0, 65 * sizeof(unsigned long long)));
   { void* dev = nullptr; VG_CREATE(hipHostGetDevicePointer(&dev, ctx->h_fetch_hdr, 0)); ctx->h_fetch_hdr_dev = static_cast<unsigned long long*>(dev); }
-  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_ins_counters), 4 * sizeof(uint32_t), 0));
+  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_ins_counters), kInsertWords * sizeof(uint32_t), 0));
   ctx->h_ins_counters[0] = ctx->h_ins_counters[1] = 0;
   if (const char* se = std::getenv("VGICP_STAGE_EVENTS"); se && se[0] == '1') {
     for (auto& e : ctx->ev_stage) VG_CREATE(hipEventCreate(&e));
@@ -231,6 +233,8 @@ int vgicp_destroy(vgicp_ctx* ctx) {
     (void)hipFree(ctx->d_stamps);
   }
   (void)hipFree(ctx->table);
+  (void)hipFree(ctx->d_raw);
+  (void)hipHostFree(ctx->h_raw_ctr);
   (void)hipFree(ctx->d_dense);
   (void)hipFree(ctx->d_dense_counts);
   (void)hipFree(ctx->d_counters);
@@ -359,6 +363,28 @@ int vgicp_set_option(vgicp_ctx* ctx, int option, int value) {
     case VGICP_OPTION_REFERENCE_ORDER:
       ctx->reference_order = value != 0;
       return VGICP_OK;
+    case VGICP_OPTION_MAP_RAW_POINTS: {
+      { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+      if (ctx->voxels != 0)
+        return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the raw-point store is switched only while the map holds no voxel");
+      VG_HIP(ctx, hipSetDevice(ctx->device));
+      if (value == 0) {
+        if (ctx->d_raw) VG_HIP(ctx, hipFree(ctx->d_raw));
+        ctx->d_raw = nullptr;
+        ctx->raw_capacity = 0;
+        ctx->raw_used_upper = 0;
+        ctx->raw_on = false;
+        return VGICP_OK;
+      }
+      if (ctx->raw_on) return VGICP_OK;
+      ctx->raw_on = true;
+      if (ctx->table) {   // else vgicp_map_reset makes the store
+        const int rc = raw_reset(ctx);
+        if (rc != VGICP_OK) ctx->raw_on = false;
+        return rc;
+      }
+      return VGICP_OK;
+    }
     default:
       return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "unknown option");
   }

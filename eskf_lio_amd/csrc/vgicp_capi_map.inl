@@ -1,6 +1,20 @@
 // vgicp_capi_map.inl — part of vgicp_capi.hip.
 // The device mirror of LocalMap's voxel grid (reset / upsert / erase / size / export) and LocalMap::updateLocalMap on the
 // device (insertion of a scan or of the resident scan, eviction).
+namespace {
+// The tail of a synchronous insertion (launched with d_counters): its counts, and the raw-point log's fill.
+int finish_insert(vgicp_ctx* ctx, size_t* new_voxels) {
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (ctx->raw_on)
+    VG_HIP(ctx, hipMemcpyAsync(ctx->h_raw_ctr, ctx->d_ins_counters + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->voxels += ctx->h_counters[0];
+  if (new_voxels) *new_voxels = ctx->h_counters[0];
+  if (ctx->h_counters[1] != 0) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table probe sequence exhausted");
+  return raw_note(ctx, ctx->h_raw_ctr);
+}
+}  // namespace
+
 extern "C" {
 
 int vgicp_map_reset(vgicp_ctx* ctx, double voxel_size, size_t capacity_hint) {
@@ -16,10 +30,15 @@ int vgicp_map_reset(vgicp_ctx* ctx, double voxel_size, size_t capacity_hint) {
   ctx->slots = ctx->voxels = ctx->tombstones = 0;
   ++ctx->map_version;
   ctx->voxel_size = voxel_size;
+  ctx->raw_hint = capacity_hint;
   const uint64_t slots = next_pow2(std::max<uint64_t>(kMinSlots, (uint64_t)capacity_hint * 4));
   int rc = alloc_table(ctx, slots, &ctx->table);
   if (rc != VGICP_OK) return rc;
   ctx->slots = slots;
+  if (ctx->raw_on) {   // the store empties with the map
+    rc = raw_reset(ctx);
+    if (rc != VGICP_OK) return rc;
+  }
   rc = reserve_dense(ctx);
   if (rc != VGICP_OK) return rc;
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -32,6 +51,7 @@ int vgicp_map_upsert(vgicp_ctx* ctx, size_t n, const int32_t* keys, const double
   if (ctx->multi) return vgicp_multi_api::map_upsert(ctx, n, keys, means, covs);
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
+  if (ctx->raw_on) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the map keeps raw points (VGICP_OPTION_MAP_RAW_POINTS): a mirror batch carries none");
   if (n == 0) return VGICP_OK;
   if (!keys || !means || !covs) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL batch pointer");
   if (n > 0xFFFFFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "batch too large");
@@ -107,9 +127,12 @@ int vgicp_map_insert_scan(vgicp_ctx* ctx, size_t n, const double* points, const 
   if (n == 0) return VGICP_OK;
   if (!points || !covs || !transform) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pointer");
   if (max_points_per_voxel == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be >= 1");
+  if (ctx->raw_on && max_points_per_voxel > 0xFFFFFFFFull)
+    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be < 2^32 while the map keeps raw points");
   if (n > 0x7FFFFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "scan too large");
   VG_HIP(ctx, hipSetDevice(ctx->device));
   int rc = ensure_table(ctx, n);  // every point may open a voxel
+  if (rc == VGICP_OK) rc = ensure_raw(ctx, n);  // ... and be kept
   if (rc != VGICP_OK) return rc;
   const size_t pb = ((n * 3 * sizeof(double)) + 255) & ~size_t(255);
   const size_t cb = ((n * 9 * sizeof(double)) + 255) & ~size_t(255);
@@ -127,13 +150,8 @@ int vgicp_map_insert_scan(vgicp_ctx* ctx, size_t n, const double* points, const 
   VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size,
                                 reinterpret_cast<const double*>(base), reinterpret_cast<const double*>(base + pb),
                                 (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, base + pb + cb, sb,
-                                ctx->d_counters));
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->voxels += ctx->h_counters[0];
-  if (new_voxels) *new_voxels = ctx->h_counters[0];
-  if (ctx->h_counters[1] != 0) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table probe sequence exhausted");
-  return VGICP_OK;
+                                ctx->d_counters, false, raw_log(ctx)));
+  return finish_insert(ctx, new_voxels);
 }
 
 namespace {
@@ -157,11 +175,14 @@ int vgicp_map_insert_resident(vgicp_ctx* ctx, const double transform[16], size_t
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
   if (!transform) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pointer");
   if (max_points_per_voxel == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be >= 1");
+  if (ctx->raw_on && max_points_per_voxel > 0xFFFFFFFFull)
+    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be < 2^32 while the map keeps raw points");
   if ((ctx->comm || ctx->peers_connected) && !ctx->owner) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "resident scan is a shard: use vgicp_map_insert_scan with the whole scan");
   const size_t n = ctx->n;
   if (n == 0) return VGICP_OK;
   VG_HIP(ctx, hipSetDevice(ctx->device));
   int rc = ensure_table(ctx, n);
+  if (rc == VGICP_OK) rc = ensure_raw(ctx, n);
   if (rc != VGICP_OK) return rc;
   const size_t sb = map_insert_scratch_bytes((uint32_t)n);
   rc = ensure_stage(ctx, sb);
@@ -173,13 +194,8 @@ int vgicp_map_insert_resident(vgicp_ctx* ctx, const double transform[16], size_t
   VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size,
                                 ctx->d_scan_aos, ctx->d_scan_aos + 3 * ctx->scan_capacity, (uint32_t)n, pose12,
                                 (uint64_t)max_points_per_voxel, ctx->d_stage, sb, ctx->d_counters,
-                                insertion_lists_stay_short(ctx)));
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->voxels += ctx->h_counters[0];
-  if (new_voxels) *new_voxels = ctx->h_counters[0];
-  if (ctx->h_counters[1] != 0) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table probe sequence exhausted");
-  return VGICP_OK;
+                                insertion_lists_stay_short(ctx), raw_log(ctx)));
+  return finish_insert(ctx, new_voxels);
 }
 
 int vgicp_map_insert_resident_async(vgicp_ctx* ctx, const double transform[16], size_t max_points_per_voxel) {
@@ -189,6 +205,8 @@ int vgicp_map_insert_resident_async(vgicp_ctx* ctx, const double transform[16], 
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
   if (!transform) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pointer");
   if (max_points_per_voxel == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be >= 1");
+  if (ctx->raw_on && max_points_per_voxel > 0xFFFFFFFFull)
+    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be < 2^32 while the map keeps raw points");
   if ((ctx->comm || ctx->peers_connected) && !ctx->owner) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "resident scan is a shard: use vgicp_map_insert_scan with the whole scan");
   // the scan's size has to be known (the align that registered it has settled it); an insertion still pending
   // from an earlier frame is settled by the same synchronisation
@@ -198,6 +216,7 @@ int vgicp_map_insert_resident_async(vgicp_ctx* ctx, const double transform[16], 
   if (n == 0) return VGICP_OK;
   VG_HIP(ctx, hipSetDevice(ctx->device));
   rc = ensure_table(ctx, n);  // every point may open a voxel (grows / rehashes with a synchronisation when it has to)
+  if (rc == VGICP_OK) rc = ensure_raw(ctx, n);  // ... and be kept (the log likewise)
   if (rc != VGICP_OK) return rc;
   const size_t sb = map_insert_scratch_bytes((uint32_t)n);
   rc = ensure_stage(ctx, sb);
@@ -209,11 +228,12 @@ int vgicp_map_insert_resident_async(vgicp_ctx* ctx, const double transform[16], 
   VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size,
                                 ctx->d_scan_aos, ctx->d_scan_aos + 3 * ctx->scan_capacity, (uint32_t)n, pose12,
                                 (uint64_t)max_points_per_voxel, ctx->d_stage, sb, ctx->d_ins_counters,
-                                insertion_lists_stay_short(ctx)));
+                                insertion_lists_stay_short(ctx), raw_log(ctx)));
   if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[5], ctx->stream)); ctx->ev_stage_set[5] = true; }
   ctx->insert_pending = true;
   ctx->ins_copy_enqueued = false;   // the next preparation's counter copy carries the totals (or settle() fetches them)
   ctx->insert_pending_upper = n;
+  if (ctx->raw_on) ctx->raw_used_upper += n;
   return VGICP_OK;
 }
 
@@ -266,6 +286,77 @@ int vgicp_map_export(vgicp_ctx* ctx, size_t capacity, int32_t* keys, double* mea
   VG_RC(user_d2h(ctx, means, b + kb, cap * 3 * sizeof(double)));
   VG_RC(user_d2h(ctx, covs, b + kb + mb, cap * 9 * sizeof(double)));
   VG_RC(user_d2h(ctx, counts, b + kb + mb + cb, cap * sizeof(uint64_t)));
+  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  user_copies_finish(ctx);
+  *written = cap;
+  return VGICP_OK;
+}
+
+// ---- the raw points of the map (include/vgicp_hip_map_points.h) ----
+int vgicp_map_points_size(const vgicp_ctx* ctx, size_t* points, size_t* capacity) {
+  if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
+  if (ctx->multi) {
+    vgicp_ctx* lead = vgicp_multi_api::first(ctx);
+    const int rc = vgicp_map_points_size(lead, points, capacity);
+    if (rc != VGICP_OK) ctx->err = lead->err;
+    return rc;
+  }
+  vgicp_ctx* c = const_cast<vgicp_ctx*>(ctx);
+  { const int rc_settle = settle(c); if (rc_settle != VGICP_OK) return rc_settle; }
+  if (!c->raw_on) return fail(c, VGICP_ERR_NOT_READY, "the map keeps no raw points: set VGICP_OPTION_MAP_RAW_POINTS");
+  { const int rc = raw_refuse_if_broken(c); if (rc != VGICP_OK) return rc; }
+  size_t total = 0;
+  if (c->table && c->voxels > 0) {
+    VG_HIP(c, hipSetDevice(c->device));
+    VG_HIP(c, hipMemsetAsync(c->d_counters, 0, 4 * sizeof(uint32_t), c->stream));
+    VG_HIP(c, launch_raw_offsets(c->stream, c->table, c->slots, nullptr, c->d_counters));
+    VG_HIP(c, hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    VG_HIP(c, hipStreamSynchronize(c->stream));
+    total = c->h_counters[0];
+  }
+  if (points) *points = total;
+  if (capacity) *capacity = c->raw_capacity;
+  return VGICP_OK;
+}
+
+int vgicp_map_points_export(vgicp_ctx* ctx, size_t capacity, int32_t* keys, double* points, size_t* written) {
+  if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
+  if (ctx->multi) {
+    vgicp_ctx* lead = vgicp_multi_api::first(ctx);
+    const int rc = vgicp_map_points_export(lead, capacity, keys, points, written);
+    if (rc != VGICP_OK) ctx->err = lead->err;
+    return rc;
+  }
+  if (!written) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "written is NULL");
+  *written = 0;
+  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  if (!ctx->raw_on) return fail(ctx, VGICP_ERR_NOT_READY, "the map keeps no raw points: set VGICP_OPTION_MAP_RAW_POINTS");
+  { const int rc = raw_refuse_if_broken(ctx); if (rc != VGICP_OK) return rc; }
+  if (!ctx->table || capacity == 0 || ctx->voxels == 0 || ctx->raw_used_upper == 0) return VGICP_OK;
+  if (!keys || !points) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL array pointer");
+  VG_HIP(ctx, hipSetDevice(ctx->device));
+  // the live points are at most the entries appended (exact after the settle): room for that many, or for capacity
+  const uint32_t used = (uint32_t)std::min<uint64_t>(ctx->raw_used_upper, ctx->raw_capacity);
+  const size_t room = std::min<size_t>(capacity, used);
+  const size_t ob = (ctx->slots * sizeof(uint32_t) + 255) & ~size_t(255);
+  const size_t kb = (room * 3 * sizeof(int32_t) + 255) & ~size_t(255);
+  int rc = ensure_stage(ctx, ob + kb + room * 3 * sizeof(double));
+  if (rc != VGICP_OK) return rc;
+  char* b = static_cast<char*>(ctx->d_stage);
+  uint32_t* offsets = reinterpret_cast<uint32_t*>(b);
+  // 1. every voxel's place in the output (its count points from there) and the total
+  VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
+  VG_HIP(ctx, launch_raw_offsets(ctx->stream, ctx->table, ctx->slots, offsets, ctx->d_counters));
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t cap = std::min<size_t>(room, ctx->h_counters[0]);
+  if (cap == 0) return VGICP_OK;
+  // 2. every live entry to its voxel's place + ordinal
+  VG_HIP(ctx, launch_raw_scatter(ctx->stream, ctx->d_raw, used, ctx->d_ins_counters + 4, ctx->table, ctx->slots, offsets, (uint32_t)cap,
+                                 reinterpret_cast<int32_t*>(b + ob), reinterpret_cast<double*>(b + ob + kb)));
+  arena_reset(ctx);
+  VG_RC(user_d2h(ctx, keys, b + ob, cap * 3 * sizeof(int32_t)));
+  VG_RC(user_d2h(ctx, points, b + ob + kb, cap * 3 * sizeof(double)));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   user_copies_finish(ctx);
   *written = cap;

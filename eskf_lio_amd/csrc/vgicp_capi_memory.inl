@@ -197,6 +197,105 @@ int alloc_table(vgicp_ctx* ctx, uint64_t slots, VoxelRecord** out) {
   return VGICP_OK;
 }
 
+// ---- the raw-point store (VGICP_OPTION_MAP_RAW_POINTS) ----
+RawLog raw_log(const vgicp_ctx* ctx) {
+  RawLog r;
+  if (ctx->raw_on) {
+    r.entries = ctx->d_raw;
+    r.capacity = ctx->raw_capacity;
+    r.ctr = ctx->d_ins_counters + 4;
+  }
+  return r;
+}
+
+// An empty log of `entries` in place of the current one (the stream is idle as far as the old one goes: hipFree).
+int raw_replace(vgicp_ctx* ctx, uint64_t entries) {
+  if (ctx->d_raw) VG_HIP(ctx, hipFree(ctx->d_raw));
+  ctx->d_raw = nullptr;
+  ctx->raw_capacity = 0;
+  ctx->raw_used_upper = 0;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->d_raw), entries * sizeof(RawPoint));
+  if (e != hipSuccess) {
+    ctx->d_raw = nullptr;
+    return fail(ctx, VGICP_ERR_TABLE_FULL, std::string("hipMalloc(raw-point log): ") + hipGetErrorString(e));
+  }
+  ctx->raw_capacity = (uint32_t)entries;
+  ctx->raw_broken = false;
+  VG_HIP(ctx, hipMemsetAsync(ctx->d_ins_counters + 4, 0, 3 * sizeof(uint32_t), ctx->stream));
+  return VGICP_OK;
+}
+// sized from the map's capacity hint like the table: 4 entries per voxel hinted
+int raw_reset(vgicp_ctx* ctx) {
+  return raw_replace(ctx, std::min(kRawMaxEntries, next_pow2(std::max<uint64_t>(kRawMinEntries, (uint64_t)ctx->raw_hint * 4))));
+}
+
+// An append that did not fit leaves entries counted that nobody wrote: from then on the store refuses every call that
+// would read or extend it, until vgicp_map_reset (or the option switched on again) makes it anew.
+int raw_overflowed(vgicp_ctx* ctx) {
+  ctx->raw_broken = true;
+  return fail(ctx, VGICP_ERR_TABLE_FULL, "raw-point log overflowed: points of the map were not kept (vgicp_map_reset starts it anew)");
+}
+int raw_refuse_if_broken(vgicp_ctx* ctx) {
+  return ctx->raw_on && ctx->raw_broken ? raw_overflowed(ctx) : VGICP_OK;
+}
+
+// The log's device words as a synchronisation brought them to the host: the exact fill, and whether an append failed.
+int raw_note(vgicp_ctx* ctx, const uint32_t* words) {
+  if (!ctx->raw_on) return VGICP_OK;
+  ctx->raw_used_upper = std::min<uint64_t>(words[0], ctx->raw_capacity);
+  if (words[1] != 0) return raw_overflowed(ctx);
+  return VGICP_OK;
+}
+
+// Room for the points an insertion of n may accept (all of them).  Only when the bound says the log could fill: one
+// synchronisation, the live entries (slot FULL) compacted into a fresh log that is twice as large as needed, geometric.
+int ensure_raw(vgicp_ctx* ctx, uint64_t n) {
+  if (!ctx->raw_on) return VGICP_OK;
+  { const int rc = raw_refuse_if_broken(ctx); if (rc != VGICP_OK) return rc; }
+  if (ctx->raw_used_upper + n <= ctx->raw_capacity) return VGICP_OK;
+  uint32_t* ctr = ctx->d_ins_counters + 4;
+  RawPoint* tmp = nullptr;
+  VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)ctx->raw_capacity * sizeof(RawPoint)));
+  VG_HIP(ctx, hipMemsetAsync(ctr + 2, 0, sizeof(uint32_t), ctx->stream));
+  VG_HIP(ctx, launch_raw_compact(ctx->stream, ctx->d_raw, (uint32_t)std::min<uint64_t>(ctx->raw_used_upper, ctx->raw_capacity),
+                                 ctr, ctx->table, ctx->slots, nullptr, tmp, ctx->raw_capacity, ctr + 2));
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_raw_ctr, ctr, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->h_raw_ctr[1] != 0) {
+    (void)hipFree(tmp);
+    return raw_overflowed(ctx);
+  }
+  const uint64_t live = ctx->h_raw_ctr[2];
+  uint64_t cap = ctx->raw_capacity;
+  while (cap < kRawMaxEntries && 2 * (live + n) > cap) cap *= 2;
+  if (live + n > cap) {
+    (void)hipFree(tmp);
+    return fail(ctx, VGICP_ERR_TABLE_FULL, "raw-point log would exceed 2^31 points");
+  }
+  VG_HIP(ctx, hipMemcpyAsync(ctr, ctr + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  if (cap == ctx->raw_capacity) {
+    VG_HIP(ctx, hipFree(ctx->d_raw));
+    ctx->d_raw = tmp;
+  } else {
+    RawPoint* grown = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&grown), cap * sizeof(RawPoint));
+    if (e != hipSuccess) {
+      (void)hipFree(tmp);
+      return fail(ctx, VGICP_ERR_TABLE_FULL, std::string("hipMalloc(raw-point log): ") + hipGetErrorString(e));
+    }
+    if (live) {
+      VG_HIP(ctx, hipMemcpyAsync(grown, tmp, live * sizeof(RawPoint), hipMemcpyDeviceToDevice, ctx->stream));
+      VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    VG_HIP(ctx, hipFree(tmp));
+    VG_HIP(ctx, hipFree(ctx->d_raw));
+    ctx->d_raw = grown;
+    ctx->raw_capacity = (uint32_t)cap;
+  }
+  ctx->raw_used_upper = live;
+  return VGICP_OK;
+}
+
 int reserve_dense(vgicp_ctx* ctx);
 // Keep load (FULL + TOMB + incoming) <= 1/2 at all times; size new tables for load <= 1/4.
 int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
@@ -206,17 +305,50 @@ int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
   VoxelRecord* fresh = nullptr;
   int rc = alloc_table(ctx, slots, &fresh);
   if (rc != VGICP_OK) return rc;
+  int rc_raw = VGICP_OK;
   if (ctx->table) {
     if (ctx->voxels > 0) {
       // one scratch word per OLD slot between the claim and the write launch (its own allocation: the staging area may
-      // hold the batch that made the table grow)
+      // hold the batch that made the table grow); with the raw-point store, the log the live entries move to
       uint32_t* claimed = nullptr;
-      VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&claimed), ctx->slots * sizeof(uint32_t)));
-      VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
-      VG_HIP(ctx, launch_rehash(ctx->stream, ctx->table, ctx->slots, fresh, (uint32_t)(slots - 1),
-                                ctx->d_counters, claimed));
-      VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      RawPoint* moved = nullptr;
+      uint32_t* ctr = ctx->d_ins_counters + 4;
+      // a failure on the way keeps nothing of the new table (what was enqueued is waited for before it is freed)
+      auto give_up = [&](hipError_t e, const char* what) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(claimed);
+        (void)hipFree(moved);
+        (void)hipFree(fresh);
+        return fail_hip(ctx, e, what);
+      };
+#define VG_REHASH(call)                                                   \
+  do {                                                                    \
+    const hipError_t e__ = (call);                                        \
+    if (e__ != hipSuccess) return give_up(e__, #call);                    \
+  } while (0)
+      VG_REHASH(hipMalloc(reinterpret_cast<void**>(&claimed), ctx->slots * sizeof(uint32_t)));
+      if (ctx->raw_on) VG_REHASH(hipMalloc(reinterpret_cast<void**>(&moved), (size_t)ctx->raw_capacity * sizeof(RawPoint)));
+      VG_REHASH(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
+      VG_REHASH(launch_rehash(ctx->stream, ctx->table, ctx->slots, fresh, (uint32_t)(slots - 1), ctx->d_counters, claimed));
+      // the raw points follow their voxels to the new slots (claimed maps old -> new); the dead ones stay behind
+      if (ctx->raw_on) {
+        VG_REHASH(hipMemsetAsync(ctr + 2, 0, sizeof(uint32_t), ctx->stream));
+        VG_REHASH(launch_raw_compact(ctx->stream, ctx->d_raw, (uint32_t)std::min<uint64_t>(ctx->raw_used_upper, ctx->raw_capacity),
+                                     ctr, ctx->table, ctx->slots, claimed, moved, ctx->raw_capacity, ctr + 2));
+        VG_REHASH(hipMemcpyAsync(ctr, ctr + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        VG_REHASH(hipMemcpyAsync(ctx->h_raw_ctr, ctr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+      }
+      VG_REHASH(hipStreamSynchronize(ctx->stream));
+#undef VG_REHASH
       VG_HIP(ctx, hipFree(claimed));
+      if (ctx->raw_on) {
+        VG_HIP(ctx, hipFree(ctx->d_raw));
+        ctx->d_raw = moved;
+        rc_raw = raw_note(ctx, ctx->h_raw_ctr);
+      }
+    } else if (ctx->raw_on) {   // no voxel left: every entry is dead, and the new table's slots will be claimed afresh
+      VG_HIP(ctx, hipMemsetAsync(ctx->d_ins_counters + 4, 0, sizeof(uint32_t), ctx->stream));
+      ctx->raw_used_upper = 0;
     }
     VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     VG_HIP(ctx, hipFree(ctx->table));
@@ -225,7 +357,8 @@ int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
   ctx->slots = slots;
   ctx->tombstones = 0;
   ++ctx->map_version;
-  return reserve_dense(ctx);   // the dense copy's storage follows the table's size here, never inside an align
+  rc = reserve_dense(ctx);   // the dense copy's storage follows the table's size here, never inside an align
+  return rc != VGICP_OK ? rc : rc_raw;
 }
 
 int ensure_scan(vgicp_ctx* ctx, size_t n) {

@@ -247,12 +247,15 @@ int map_insert_device(vgicp_ctx* ctx, const double* d_points, const double* d_co
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
   if (!transform) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pointer");
   if (max_points_per_voxel == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be >= 1");
+  if (ctx->raw_on && max_points_per_voxel > 0xFFFFFFFFull)
+    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be < 2^32 while the map keeps raw points");
   if (n > 0x7FFFFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "scan too large");
   VG_HIP(ctx, hipSetDevice(ctx->device));
   int rc = (ctx->scan_pending || ctx->insert_pending) ? settle(ctx) : VGICP_OK;
   if (rc != VGICP_OK) return rc;
   if (n == 0) return VGICP_OK;
   rc = ensure_table(ctx, n);
+  if (rc == VGICP_OK) rc = ensure_raw(ctx, n);
   if (rc != VGICP_OK) return rc;
   const size_t sb = map_insert_scratch_bytes((uint32_t)n);
   rc = ensure_stage(ctx, sb);
@@ -264,23 +267,20 @@ int map_insert_device(vgicp_ctx* ctx, const double* d_points, const double* d_co
     ++ctx->map_version;
   VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size, d_points, d_covs,
                                   (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, ctx->d_stage, sb, ctx->d_ins_counters,
-                                  short_lists));
+                                  short_lists, raw_log(ctx)));
     if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[5], ctx->stream)); ctx->ev_stage_set[5] = true; }
     ctx->insert_pending = true;
     ctx->ins_copy_enqueued = false;
     ctx->insert_pending_upper = n;
+    if (ctx->raw_on) ctx->raw_used_upper += n;
     return VGICP_OK;
   }
   VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
   ++ctx->map_version;
   VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size, d_points, d_covs,
-                                (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, ctx->d_stage, sb, ctx->d_counters, short_lists));
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->voxels += ctx->h_counters[0];
-  if (new_voxels) *new_voxels = ctx->h_counters[0];
-  if (ctx->h_counters[1] != 0) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table probe sequence exhausted");
-  return VGICP_OK;
+                                (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, ctx->d_stage, sb, ctx->d_counters, short_lists,
+                                raw_log(ctx)));
+  return finish_insert(ctx, new_voxels);
 }
 
 }  // namespace vgicp_internal

@@ -153,7 +153,9 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
     if (staged->done) VG_HIP(ctx, hipEventRecord(staged->done, ctx->stream));
     VG_HIP(ctx, launch_prepare_tail(ctx->stream, a));
   }
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_prep, ctx->d_counters, (kCounterWords + 4) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  // (+ the raw-point log's words when the map keeps raw points)
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_prep, ctx->d_counters, (kCounterWords + (ctx->raw_on ? kInsertWords : 4)) * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, ctx->stream));
   if (ctx->insert_pending && !ctx->ins_copy_enqueued) {   // the deferred insertion's totals travel with this copy
     ctx->ins_copy_enqueued = true;
     ctx->ins_from_prep = true;
@@ -191,7 +193,8 @@ int resolve_prepare(vgicp_ctx* ctx, uint32_t* kept) {
 // A deferred insertion whose totals no copy has picked up yet (no preparation followed it): a copy of its own, now.
 int fetch_insert_totals(vgicp_ctx* ctx) {
   if (!ctx->insert_pending || ctx->ins_copy_enqueued) return VGICP_OK;
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_ins_counters, ctx->d_ins_counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_ins_counters, ctx->d_ins_counters, (ctx->raw_on ? 6 : 2) * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, ctx->stream));
   ctx->ins_copy_enqueued = true;
   ctx->ins_from_prep = false;
   return VGICP_OK;
@@ -209,7 +212,7 @@ int settle_insert(vgicp_ctx* ctx) {
   ctx->ins_seen[1] = totals[1];
   ctx->voxels += created;
   if (failed) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table probe sequence exhausted (deferred map insertion)");
-  return VGICP_OK;
+  return raw_note(ctx, totals + 4);
 }
 
 // A pending scan's size and verdict, once the stream has been synchronised.

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/vgicp_hip.h"
+#include "../../include/vgicp_hip_map_points.h"
 #include "vgicp_device.h"
 
 using namespace vgicp;
@@ -73,6 +74,11 @@ inline uint64_t next_pow2(uint64_t v) {
 }
 
 constexpr uint64_t kMinSlots = 1024;
+// words behind the counter block (d_ins_counters): [0] [1] the deferred insertion's running totals, [2] [3] the
+// resident scan's symmetry verdicts, [4] [5] [6] the raw-point log (RawLog::ctr), [7] spare
+constexpr int kInsertWords = 8;
+constexpr uint64_t kRawMinEntries = 4096;
+constexpr uint64_t kRawMaxEntries = 1ull << 31;   // 64 GiB of raw points; ordinals and offsets stay 32-bit
 constexpr int kDefaultChunk = 4;
 constexpr int kMaxChunksInFlight = 2;
 constexpr int kPersistentCooldownAligns = 8;  // aligns on the per-launch loop after the single launch gave up
@@ -398,6 +404,17 @@ struct vgicp_ctx {
   bool ins_copy_enqueued = false;    // some device-to-host copy behind the pending insertion carries its totals ...
   bool ins_from_prep = false;        // ... in the tail of h_prep (the next preparation's counter copy) rather than h_ins_counters
   uint64_t insert_pending_upper = 0;
+  // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
+  // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
+  // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
+  // insertion, and the log grows (one synchronisation) only when it could fill
+  bool raw_on = false;
+  RawPoint* d_raw = nullptr;
+  uint32_t raw_capacity = 0;         // entries
+  uint64_t raw_used_upper = 0;       // entries appended so far, at most
+  size_t raw_hint = 0;               // the last vgicp_map_reset's capacity_hint
+  bool raw_broken = false;           // an append did not fit: the store refuses every call until it is made anew
+  uint32_t* h_raw_ctr = nullptr;     // pinned, 4 words: the log's device words after a synchronous call
   // frame statistics
   uint64_t stat_launches0 = 0, stat_copies0 = 0, stat_syncs0 = 0;
   bool stage_events = false;

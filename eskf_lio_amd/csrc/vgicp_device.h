@@ -226,7 +226,10 @@ hipError_t launch_table_clear(hipStream_t s, VoxelRecord* table, uint64_t slots)
 uint32_t table_dense_blocks(uint64_t slots);
 hipError_t launch_table_dense(hipStream_t s, VoxelRecord* table, uint64_t slots, VoxelRecord* dense, uint64_t dense_capacity,
                               uint32_t* block_counts);
-// claimed: scratch of n words (upsert) / old_slots words (rehash): claim launch -> write launch
+// claimed: scratch of n words (upsert) / old_slots words (rehash): claim launch -> write launch.  A word is the slot
+// claimed with kClaimFresh set when the record is new, or kClaimFailed (probe sequence exhausted; rehash: not FULL).
+constexpr uint32_t kClaimFresh = 0x80000000u;
+constexpr uint32_t kClaimFailed = 0x7FFFFFFFu;
 hipError_t launch_upsert(hipStream_t s, VoxelRecord* table, uint32_t mask, uint32_t n,
                          const int32_t* keys, const double* means, const double* covs,
                          uint32_t* counters /* [0] new inserts, [1] failures */, uint32_t* claimed);
@@ -359,10 +362,41 @@ hipError_t launch_transform_points(hipStream_t s, double* pts, uint32_t n, const
 size_t deskew_scratch_words(uint32_t states);
 hipError_t launch_deskew(hipStream_t s, double* pts, uint32_t n, const double* point_time, const double* state_time,
                          uint32_t states, const double* poses, uint32_t* ends, bool ordered_states);
+// The raw points of the map (VGICP_OPTION_MAP_RAW_POINTS; LocalMap's Voxel::points, include/ESKF_LIO/LocalMap.hpp:63-87):
+// an append log of every point an insertion ACCEPTED (the constructor, or addPoint while count < max), as prepare_point
+// transformed it.  slot: the voxel's table slot (its identity: a tombstone is never claimed again, so the entries of an
+// evicted voxel are dead and stay dead); ordinal: the voxel's count before the point, i.e. its index in Voxel::points.
+struct RawPoint {
+  double xyz[3];
+  uint32_t slot;
+  uint32_t ordinal;
+};
+static_assert(sizeof(RawPoint) == 32, "one raw point = 32 bytes");
+// ctr[0] entries appended so far, ctr[1] != 0 when an append did not fit (nothing is written then), ctr[2] scratch of
+// the compaction.  entries == nullptr: the store is off.
+struct RawLog {
+  RawPoint* entries = nullptr;
+  uint32_t capacity = 0;
+  uint32_t* ctr = nullptr;
+};
 hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, double voxel_size,
                              const double* points_aos, const double* covs_aos, uint32_t n,
                              const double pose12[12], uint64_t max_points, void* scratch,
-                             size_t scratch_bytes, uint32_t* counters, bool short_lists = false);
+                             size_t scratch_bytes, uint32_t* counters, bool short_lists = false,
+                             const RawLog& raw = RawLog());
+// The log's live entries (slot FULL in `table`; with `claimed`, the rehash's old-slot -> new-slot words, those whose
+// old slot was carried over, renamed to the new slot) appended to dst; ctr[2] (zero before) counts them.  The source
+// holds *ctr[0] entries, at most `src_upper`; `slots`: of `table` (or of the old table that `claimed` covers).
+hipError_t launch_raw_compact(hipStream_t s, const RawPoint* src, uint32_t src_upper, const uint32_t* ctr,
+                              const VoxelRecord* table, uint64_t slots, const uint32_t* claimed, RawPoint* dst,
+                              uint32_t dst_capacity, uint32_t* dst_ctr);
+// Output offsets of the export: offsets[slot] = where the voxel's points start (FULL slots, unspecified voxel order,
+// each voxel's `count` points contiguous); *total (zero before) = the sum of count.  offsets may be nullptr (size only).
+hipError_t launch_raw_offsets(hipStream_t s, const VoxelRecord* table, uint64_t slots, uint32_t* offsets, uint32_t* total);
+// Every live entry to keys / points[offsets[slot] + ordinal] (positions at or beyond `capacity` are dropped).
+hipError_t launch_raw_scatter(hipStream_t s, const RawPoint* log, uint32_t upper, const uint32_t* ctr,
+                              const VoxelRecord* table, uint64_t slots, const uint32_t* offsets, uint32_t capacity,
+                              int32_t* keys, double* points);
 // short_lists: no sort — every voxel's points hang on a list (the record's spare word) that the voxel's first point
 // walks in scan order.  For scans that put a handful of points into a voxel at most (a scan the device down-sampled
 // itself); correct for any scan, quadratic in the points of one voxel beyond eight.

@@ -1605,8 +1605,7 @@ __global__ void table_clear_kernel(VoxelRecord* table, uint64_t slots) {
 // per million voxels (profiles/r08_c2_kernel_stats.csv); eight lanes per record in ONE launch needs the key visible
 // before the state inside the launch: write-through key stores + wait cost 1.45 ms, a release fence per wave (it writes
 // the XCD's L2 back) 5.5 ms.
-constexpr uint32_t kClaimFresh = 0x80000000u;   // bit 31 of the scratch word: the record is new
-constexpr uint32_t kClaimFailed = 0x7FFFFFFFu;  // probe sequence exhausted
+// kClaimFresh / kClaimFailed: vgicp_device.h (the raw-point store reads the rehash's scratch words too)
 
 __device__ __forceinline__ uint32_t claim_slot(VoxelRecord* table, uint32_t mask, int32_t kx, int32_t ky, int32_t kz) {
   uint32_t slot = voxel_hash(kx, ky, kz) & mask;

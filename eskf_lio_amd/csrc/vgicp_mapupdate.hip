@@ -24,6 +24,13 @@
 //   2. apply     the leader walks the list, takes the points in ascending index = scan order (a register buffer of
 //                kListChunk indices per walk; longer lists take several walks: correct for any length, quadratic
 //                beyond the buffer, which is why arbitrary scans keep the sort), applies them, empties the list.
+//
+// With the raw-point store on (RawLog, VGICP_OPTION_MAP_RAW_POINTS) both apply kernels also keep the points they accept:
+// a segment head / list leader knows how many that is before it applies them (min(points, max - count)), reserves as
+// many log entries with one add per wave and writes them in its walk — a point's ordinal is the count before it, so the
+// export can place every point without ordering the log.  The log is never written past its capacity: the host keeps
+// an upper bound of what is appended (every point of an insertion may be accepted) and grows the log before it could
+// fill; should an append not fit anyway, ctr[1] is set, nothing is written and the call fails.
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
 #include "vgicp_sort.h"
@@ -167,16 +174,79 @@ __global__ void insert_prepare_kernel(VoxelRecord* table, uint32_t mask, double 
   }
 }
 
+// Raw-point store: base of `k` consecutive log entries for this lane (block_reserve below).
+// Points of `len` that the constructor / addPoint accept into a voxel that holds `count` (max_points >= 1).
+__device__ __forceinline__ uint32_t accepted_points(uint64_t count, uint32_t len, uint64_t max_points) {
+  const uint64_t room = count < max_points ? max_points - count : 0;
+  return (uint64_t)len < room ? len : (uint32_t)room;
+}
+
+// The same for the whole workgroup (kBlock threads, every one of them here): one atomic per workgroup — the
+// insertion's kernels are short, and hundreds of waves adding to one word cost more than the scan.
+constexpr uint32_t kBlock = 256;
+__device__ __forceinline__ uint32_t block_reserve(uint32_t* counter, uint32_t k) {
+  __shared__ uint32_t wave_total[kBlock / 64];
+  __shared__ uint32_t block_base;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t incl = k;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t v = __shfl_up(incl, (unsigned int)d, 64);
+    if ((int)lane >= d) incl += v;
+  }
+  if (lane == 63u) wave_total[wave] = incl;
+  __syncthreads();
+  uint32_t before = 0, total = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kBlock / 64; ++w) {
+    before += w < wave ? wave_total[w] : 0u;
+    total += wave_total[w];
+  }
+  if (threadIdx.x == 0) block_base = total ? atomicAdd(counter, total) : 0u;
+  __syncthreads();
+  return block_base + before + incl - k;
+}
+
+// The log entries of one segment / list: reserved by every lane of the workgroup, `k` of them for this lane; false
+// (and ctr[1] set) when they do not fit.
+__device__ __forceinline__ bool raw_reserve(const RawLog& raw, uint32_t k, uint32_t& at) {
+  at = block_reserve(&raw.ctr[0], k);
+  const bool fits = (uint64_t)at + k <= raw.capacity;
+  if (k != 0u && !fits) atomicOr(&raw.ctr[1], 1u);
+  return fits;
+}
+
+__device__ __forceinline__ void raw_write(const RawLog& raw, uint32_t at, const double* __restrict__ wpts, uint32_t i,
+                                          uint32_t slot, uint64_t ordinal) {
+  RawPoint* e = raw.entries + at;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) e->xyz[k] = wpts[3 * (size_t)i + k];
+  e->slot = slot;
+  e->ordinal = (uint32_t)ordinal;
+}
+
 // Voxel(max, p, C) / Voxel::addPoint applied to the segment that starts at sorted position j.
+template <bool RAW>
 __global__ void insert_apply_kernel(VoxelRecord* table, const uint32_t* __restrict__ slot_sorted,
                                     const uint32_t* __restrict__ idx_sorted, uint32_t n,
                                     const double* __restrict__ wpts, const double* __restrict__ wcovs,
-                                    uint64_t max_points) {
+                                    uint64_t max_points, RawLog raw) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t slot = slot_sorted[j];
-  if (slot == kNoSlot) return;
-  if (j > 0 && slot_sorted[j - 1] == slot) return;  // not the head of its segment
+  uint32_t slot = kNoSlot;
+  bool head = false;
+  if (j < n) {
+    slot = slot_sorted[j];
+    head = slot != kNoSlot && !(j > 0 && slot_sorted[j - 1] == slot);  // the head of its segment
+  }
+  uint32_t at = 0;
+  bool keep = false;
+  if constexpr (RAW) {
+    uint32_t len = 0;
+    if (head)
+      for (uint32_t q = j; q < n && slot_sorted[q] == slot; ++q) ++len;
+    keep = raw_reserve(raw, head ? accepted_points(table[slot].count, len, max_points) : 0u, at);
+  }
+  if (!head) return;
   VoxelRecord* rec = table + slot;
   uint64_t count = rec->count;
   double mean[3], cov[9];
@@ -187,6 +257,7 @@ __global__ void insert_apply_kernel(VoxelRecord* table, const uint32_t* __restri
   for (uint32_t q = j; q < n && slot_sorted[q] == slot; ++q) {
     const uint32_t i = idx_sorted[q];
     if (count == 0) {  // constructor
+      if constexpr (RAW) { if (keep) raw_write(raw, at++, wpts, i, slot, count); }
 #pragma unroll
       for (int k = 0; k < 3; ++k) mean[k] = wpts[3 * (size_t)i + k];
 #pragma unroll
@@ -199,6 +270,7 @@ __global__ void insert_apply_kernel(VoxelRecord* table, const uint32_t* __restri
       for (int k = 0; k < 3; ++k) mean[k] = (nn * mean[k] + wpts[3 * (size_t)i + k]) / n1;
 #pragma unroll
       for (int k = 0; k < 9; ++k) cov[k] = (nn * cov[k] + wcovs[9 * (size_t)i + k]) / n1;
+      if constexpr (RAW) { if (keep) raw_write(raw, at++, wpts, i, slot, count); }
       ++count;
     }
   }
@@ -211,22 +283,32 @@ __global__ void insert_apply_kernel(VoxelRecord* table, const uint32_t* __restri
 
 // The same for a voxel whose points hang on its list (short_lists): run by the voxel's leader.
 constexpr int kListChunk = 8;
+template <bool RAW>
 __global__ void insert_apply_list_kernel(VoxelRecord* table, const uint32_t* __restrict__ slot_of,
                                          const uint32_t* __restrict__ next_of, uint32_t n,
                                          const double* __restrict__ wpts, const double* __restrict__ wcovs,
-                                         uint64_t max_points) {
+                                         uint64_t max_points, RawLog raw) {
   const uint32_t me = blockIdx.x * blockDim.x + threadIdx.x;
-  if (me >= n || next_of[me] != 0u) return;  // on no list (table full), or not the leader
-  VoxelRecord* rec = table + slot_of[me];
-  const uint32_t head = (uint32_t)rec->reserved;  // index + 1 of the point that pushed itself last
-  uint64_t count = rec->count;
+  const bool leader = me < n && next_of[me] == 0u;  // not: on no list (table full), or not the leader
+  if (!RAW && !leader) return;                        // (the store's reservation needs every lane of the workgroup)
+  const uint32_t slot = leader ? slot_of[me] : 0u;
+  VoxelRecord* rec = table + slot;
+  uint32_t head = 0;  // index + 1 of the point that pushed itself last
+  uint64_t count = 0;
   double mean[3], cov[9];
+  if (leader) {
+    head = (uint32_t)rec->reserved;
+    count = rec->count;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) mean[k] = rec->mean[k];
+    for (int k = 0; k < 3; ++k) mean[k] = rec->mean[k];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) cov[k] = rec->cov[k];
+    for (int k = 0; k < 9; ++k) cov[k] = rec->cov[k];
+  }
+  uint32_t at = 0;
+  bool keep = false;
   auto apply = [&](uint32_t i) {
     if (count == 0) {  // constructor
+      if constexpr (RAW) { if (keep) raw_write(raw, at++, wpts, i, slot, count); }
 #pragma unroll
       for (int k = 0; k < 3; ++k) mean[k] = wpts[3 * (size_t)i + k];
 #pragma unroll
@@ -239,36 +321,56 @@ __global__ void insert_apply_list_kernel(VoxelRecord* table, const uint32_t* __r
       for (int k = 0; k < 3; ++k) mean[k] = (nn * mean[k] + wpts[3 * (size_t)i + k]) / n1;
 #pragma unroll
       for (int k = 0; k < 9; ++k) cov[k] = (nn * cov[k] + wcovs[9 * (size_t)i + k]) / n1;
+      if constexpr (RAW) { if (keep) raw_write(raw, at++, wpts, i, slot, count); }
       ++count;
     }
   };
-  if (head == me + 1u) {
-    apply(me);  // the usual case: the voxel received this one point
-  } else {
-    // ascending index, kListChunk at a time: every walk keeps the smallest indices above the last one applied
-    long long done = -1;  // the largest index applied so far
-    for (;;) {
-      uint32_t buf[kListChunk];
+  // ascending index, kListChunk at a time: every walk keeps the smallest indices above the last one applied
+  uint32_t buf[kListChunk];
+  auto gather = [&](long long after) {
 #pragma unroll
-      for (int k = 0; k < kListChunk; ++k) buf[k] = 0xFFFFFFFFu;
-      int held = 0;
-      for (uint32_t cur = head; cur != 0u; cur = next_of[cur - 1u]) {
-        uint32_t x = cur - 1u;
-        if ((long long)x <= done) continue;
-        // insert x into the ascending buffer, dropping the largest when it is full (static indices: registers)
+    for (int k = 0; k < kListChunk; ++k) buf[k] = 0xFFFFFFFFu;
+    int held = 0;
+    for (uint32_t cur = head; cur != 0u; cur = next_of[cur - 1u]) {
+      uint32_t x = cur - 1u;
+      if ((long long)x <= after) continue;
+      // insert x into the ascending buffer, dropping the largest when it is full (static indices: registers)
 #pragma unroll
-        for (int k = 0; k < kListChunk; ++k) {
-          const uint32_t lo = x < buf[k] ? x : buf[k], hi = x < buf[k] ? buf[k] : x;
-          buf[k] = lo;
-          x = hi;
-        }
-        if (held < kListChunk) ++held;
+      for (int k = 0; k < kListChunk; ++k) {
+        const uint32_t lo = x < buf[k] ? x : buf[k], hi = x < buf[k] ? buf[k] : x;
+        buf[k] = lo;
+        x = hi;
       }
-#pragma unroll
-      for (int k = 0; k < kListChunk; ++k)
-        if (k < held) { apply(buf[k]); done = (long long)buf[k]; }
-      if (held < kListChunk) break;
+      if (held < kListChunk) ++held;
     }
+    return held;
+  };
+  int held = 0;
+  if (leader) {
+    if (head == me + 1u) {  // the usual case: the voxel received this one point
+      buf[0] = me;
+      held = 1;
+    } else {
+      held = gather(-1);
+    }
+  }
+  if constexpr (RAW) {
+    // the list's length: the first walk has it unless the list is longer than one chunk
+    uint32_t len = (uint32_t)held;
+    if (held == kListChunk) {
+      len = 0;
+      for (uint32_t cur = head; cur != 0u; cur = next_of[cur - 1u]) ++len;
+    }
+    keep = raw_reserve(raw, leader ? accepted_points(count, len, max_points) : 0u, at);
+    if (!leader) return;
+  }
+  long long done = -1;  // the largest index applied so far
+  for (;;) {
+#pragma unroll
+    for (int k = 0; k < kListChunk; ++k)
+      if (k < held) { apply(buf[k]); done = (long long)buf[k]; }
+    if (held < kListChunk) break;
+    held = gather(done);
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) rec->mean[k] = mean[k];
@@ -317,6 +419,58 @@ __global__ void export_kernel(const VoxelRecord* __restrict__ table, uint64_t sl
   counts[pos] = rec->count;
 }
 
+// ---- the raw-point store (RawLog) ----
+// An entry's slot is checked against the table before it is used: after an append that did not fit (ctr[1]; the call
+// that made it failed) the log may hold entries nobody wrote, and those must not index anything.
+__global__ void raw_compact_kernel(const RawPoint* __restrict__ src, uint32_t src_upper, const uint32_t* ctr,
+                                   const VoxelRecord* __restrict__ table, uint64_t slots,
+                                   const uint32_t* __restrict__ claimed, RawPoint* __restrict__ dst,
+                                   uint32_t dst_capacity, uint32_t* dst_ctr) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t used = ctr[0] < src_upper ? ctr[0] : src_upper;
+  if (e >= used) return;
+  RawPoint p = src[e];
+  if ((uint64_t)p.slot >= slots) return;
+  if (claimed) {
+    const uint32_t c = claimed[p.slot];
+    if (c == kClaimFailed) return;  // the voxel was gone before the rehash
+    p.slot = c & ~kClaimFresh;
+  } else if (table[p.slot].state != SLOT_FULL) {
+    return;
+  }
+  const uint32_t pos = wave_append(dst_ctr);
+  if (pos < dst_capacity) dst[pos] = p;
+}
+
+__global__ void raw_offsets_kernel(const VoxelRecord* __restrict__ table, uint64_t slots, uint32_t* __restrict__ offsets,
+                                   uint32_t* total) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t c = 0;
+  if (i < slots && table[i].state == SLOT_FULL) c = (uint32_t)table[i].count;
+  const uint32_t at = block_reserve(total, c);
+  if (offsets && i < slots) offsets[i] = at;
+}
+
+__global__ void raw_scatter_kernel(const RawPoint* __restrict__ log, uint32_t upper, const uint32_t* ctr,
+                                   const VoxelRecord* __restrict__ table, uint64_t slots,
+                                   const uint32_t* __restrict__ offsets, uint32_t capacity, int32_t* __restrict__ keys,
+                                   double* __restrict__ points) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t used = ctr[0] < upper ? ctr[0] : upper;
+  if (e >= used) return;
+  const RawPoint p = log[e];
+  if ((uint64_t)p.slot >= slots) return;   // see raw_compact_kernel
+  const VoxelRecord* rec = table + p.slot;
+  if (rec->state != SLOT_FULL || p.ordinal >= rec->count) return;  // dead (evicted / erased voxel)
+  const uint64_t pos = (uint64_t)offsets[p.slot] + p.ordinal;
+  if (pos >= capacity) return;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    keys[3 * pos + k] = rec->key[k];
+    points[3 * pos + k] = p.xyz[k];
+  }
+}
+
 inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((work + block - 1) / block); }
 
 }  // namespace
@@ -330,7 +484,7 @@ size_t map_insert_scratch_bytes(uint32_t n) {
 hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, double voxel_size,
                              const double* points_aos, const double* covs_aos, uint32_t n,
                              const double pose12[12], uint64_t max_points, void* scratch,
-                             size_t scratch_bytes, uint32_t* counters, bool short_lists) {
+                             size_t scratch_bytes, uint32_t* counters, bool short_lists, const RawLog& raw) {
   if (n == 0) return hipSuccess;
   if (scratch_bytes < map_insert_scratch_bytes(n)) return hipErrorInvalidValue;
   InsertScratch w = carve(scratch, n);
@@ -341,8 +495,13 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
                        mask, voxel_size, points_aos, covs_aos, n, pose, w.wpts, w.wcovs, w.slot_in, w.idx_in, counters);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_list_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, table,
-                       w.slot_in, w.idx_in, n, w.wpts, w.wcovs, max_points);
+    if (raw.entries) {
+      ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_list_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s,
+                         table, w.slot_in, w.idx_in, n, w.wpts, w.wcovs, max_points, raw);
+    } else {
+      ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_list_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s,
+                         table, w.slot_in, w.idx_in, n, w.wpts, w.wcovs, max_points, raw);
+    }
     return hipGetLastError();
   }
   ++g_kernel_launches; hipLaunchKernelGGL(insert_prepare_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, mask,
@@ -354,8 +513,13 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
   e = sortk::sort_pairs(w.slot_in, w.idx_in, w.slot_out, w.idx_out, w.split, n, s);
   if (e != hipSuccess) return e;
   g_kernel_launches += sortk::launches_for(n);
-  ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, w.slot_out,
-                     w.idx_out, n, w.wpts, w.wcovs, max_points);
+  if (raw.entries) {
+    ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table,
+                       w.slot_out, w.idx_out, n, w.wpts, w.wcovs, max_points, raw);
+  } else {
+    ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table,
+                       w.slot_out, w.idx_out, n, w.wpts, w.wcovs, max_points, raw);
+  }
   return hipGetLastError();
 }
 
@@ -371,6 +535,30 @@ hipError_t launch_map_export(hipStream_t s, const VoxelRecord* table, uint64_t s
                              uint32_t* counters) {
   ++g_kernel_launches; hipLaunchKernelGGL(export_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots,
                      capacity, keys, means, covs, counts, counters);
+  return hipGetLastError();
+}
+
+hipError_t launch_raw_compact(hipStream_t s, const RawPoint* src, uint32_t src_upper, const uint32_t* ctr,
+                              const VoxelRecord* table, uint64_t slots, const uint32_t* claimed, RawPoint* dst,
+                              uint32_t dst_capacity, uint32_t* dst_ctr) {
+  if (src_upper == 0) return hipSuccess;
+  ++g_kernel_launches; hipLaunchKernelGGL(raw_compact_kernel, dim3(blocks_for(src_upper, 256)), dim3(256), 0, s, src,
+                     src_upper, ctr, table, slots, claimed, dst, dst_capacity, dst_ctr);
+  return hipGetLastError();
+}
+
+hipError_t launch_raw_offsets(hipStream_t s, const VoxelRecord* table, uint64_t slots, uint32_t* offsets, uint32_t* total) {
+  ++g_kernel_launches; hipLaunchKernelGGL(raw_offsets_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots,
+                     offsets, total);
+  return hipGetLastError();
+}
+
+hipError_t launch_raw_scatter(hipStream_t s, const RawPoint* log, uint32_t upper, const uint32_t* ctr,
+                              const VoxelRecord* table, uint64_t slots, const uint32_t* offsets, uint32_t capacity,
+                              int32_t* keys, double* points) {
+  if (upper == 0) return hipSuccess;
+  ++g_kernel_launches; hipLaunchKernelGGL(raw_scatter_kernel, dim3(blocks_for(upper, 256)), dim3(256), 0, s, log, upper,
+                     ctr, table, slots, offsets, capacity, keys, points);
   return hipGetLastError();
 }
 

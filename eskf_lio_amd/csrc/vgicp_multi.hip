@@ -510,6 +510,8 @@ int map_reset(vgicp_ctx* ctx, double voxel_size, size_t capacity_hint) {
 }
 int map_upsert(vgicp_ctx* ctx, size_t n, const int32_t* keys, const double* means, const double* covs) {
   vgicp_multi* g = ctx->multi;
+  // refused before any replica takes the batch (only the first keeps raw points: the others would accept it)
+  if (g->subs[0]->raw_on) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the map keeps raw points (VGICP_OPTION_MAP_RAW_POINTS): a mirror batch carries none");
   return run_all(ctx, [&](int r) { return vgicp_map_upsert(g->subs[(size_t)r], n, keys, means, covs); });
 }
 int map_erase(vgicp_ctx* ctx, size_t n, const int32_t* keys) {
@@ -755,6 +757,8 @@ int get_frame_stats(vgicp_ctx* ctx, vgicp_frame_stats* out, int reset) {
 
 int set_option(vgicp_ctx* ctx, int option, int value) {
   vgicp_multi* g = ctx->multi;
+  // the raw points are read from the first device only (vgicp_map_points_export, like vgicp_map_export): only it keeps them
+  if (option == VGICP_OPTION_MAP_RAW_POINTS) return sub_fail(ctx, g->subs[0], vgicp_set_option(g->subs[0], option, value));
   return run_all(ctx, [&](int r) { return vgicp_set_option(g->subs[(size_t)r], option, value); });
 }
 

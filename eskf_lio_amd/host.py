@@ -35,6 +35,11 @@ def load_library() -> C.CDLL:
     lib.host_localmap_create_config.restype = vp
     lib.host_localmap_create_config.argtypes = [C.c_double, sz, C.c_double, C.c_double, C.c_int, C.c_double,
                                                 C.c_double, C.c_int, C.c_int]
+    lib.host_localmap_create_config_raw.restype = vp
+    lib.host_localmap_create_config_raw.argtypes = [C.c_double, sz, C.c_double, C.c_double, C.c_int, C.c_double,
+                                                    C.c_double, C.c_int, C.c_int, C.c_int]
+    lib.host_localmap_saves_raw_points.restype = C.c_int
+    lib.host_localmap_saves_raw_points.argtypes = [vp]
     lib.host_localmap_create.restype = vp
     lib.host_localmap_create.argtypes = [C.c_double, sz]
     lib.host_localmap_destroy.argtypes = [vp]
@@ -103,18 +108,23 @@ def _check(lib, rc):
 
 class LocalMap:
     """ESKF_LIO::LocalMap.  config: the YAML keys + device_resident (default True: the grid the registration reads lives
-    on the device) + keep_raw_points (default True: a host-side shadow grid keeps every raw point for save())."""
+    on the device) + keep_raw_points (default True: a host-side shadow grid keeps every raw point for save()) +
+    raw_points_on_device (default False: with the two above, the device map keeps the raw points instead of the
+    shadow grid, LocalMapConfig::rawPointsOnDevice)."""
 
     def __init__(self, voxelSize: float, maxNumPointsPerVoxel: int, config: Optional[dict] = None):
         self._lib = load_library()
         if config is None:
             self._h = self._lib.host_localmap_create(float(voxelSize), int(maxNumPointsPerVoxel))
         else:
-            self._h = self._lib.host_localmap_create_config(
-                float(voxelSize), int(maxNumPointsPerVoxel), float(config["translation_sq_threshold"]),
-                float(config["cosine_threshold"]), int(bool(config["remove_distant_points"])),
-                float(config["distance_threshold"]), float(config["removing_period"]),
-                int(bool(config.get("device_resident", True))), int(bool(config.get("keep_raw_points", True))))
+            args = (float(voxelSize), int(maxNumPointsPerVoxel), float(config["translation_sq_threshold"]),
+                    float(config["cosine_threshold"]), int(bool(config["remove_distant_points"])),
+                    float(config["distance_threshold"]), float(config["removing_period"]),
+                    int(bool(config.get("device_resident", True))), int(bool(config.get("keep_raw_points", True))))
+            if "raw_points_on_device" in config:
+                self._h = self._lib.host_localmap_create_config_raw(*args, int(bool(config["raw_points_on_device"])))
+            else:
+                self._h = self._lib.host_localmap_create_config(*args)
         if not self._h:
             raise RuntimeError(self._lib.host_last_error().decode())
 
@@ -125,6 +135,10 @@ class LocalMap:
 
     def __len__(self):
         return self._lib.host_localmap_size(self._h)
+
+    def savesRawPoints(self) -> bool:
+        """True while save() writes every stored raw point, as the reference does."""
+        return bool(self._lib.host_localmap_saves_raw_points(self._h))
 
     def drain(self) -> int:
         """Waits for the shadow grid's worker (LocalMap::grid()); the host grid's voxel count."""

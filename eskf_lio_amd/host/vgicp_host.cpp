@@ -54,11 +54,12 @@ extern "C" {
 
 const char * host_last_error(void) {return g_error.c_str();}
 
-// LocalMap(config) — the YAML constructor's keys as plain arguments.
-LocalMap * host_localmap_create_config(
+// LocalMap(config) — the YAML constructor's keys as plain arguments, with LocalMapConfig::rawPointsOnDevice (the device
+// map keeps the raw points save() writes).
+LocalMap * host_localmap_create_config_raw(
   double voxel_size, size_t max_points_per_voxel, double translation_sq_threshold,
   double cosine_threshold, int remove_distant_points, double distance_threshold,
-  double remove_period, int device_resident, int keep_raw_points)
+  double remove_period, int device_resident, int keep_raw_points, int raw_points_on_device)
 {
   LocalMap * out = nullptr;
   guarded(
@@ -73,9 +74,21 @@ LocalMap * host_localmap_create_config(
       c.removePeriod = remove_period;
       c.deviceResident = device_resident != 0;
       c.keepRawPoints = keep_raw_points != 0;
+      c.rawPointsOnDevice = raw_points_on_device != 0;
       out = new LocalMap(c);
     });
   return out;
+}
+
+// The same without rawPointsOnDevice (the signature of the earlier library).
+LocalMap * host_localmap_create_config(
+  double voxel_size, size_t max_points_per_voxel, double translation_sq_threshold,
+  double cosine_threshold, int remove_distant_points, double distance_threshold,
+  double remove_period, int device_resident, int keep_raw_points)
+{
+  return host_localmap_create_config_raw(
+    voxel_size, max_points_per_voxel, translation_sq_threshold, cosine_threshold, remove_distant_points,
+    distance_threshold, remove_period, device_resident, keep_raw_points, 0);
 }
 
 // LocalMap(double voxelSize, size_t maxNumPointsPerVoxel, bool visualize = false)
@@ -90,6 +103,7 @@ void host_localmap_destroy(LocalMap * map) {delete map;}
 // helper threads of the drop-in's full-hash check (CloudPreprocessorConfig::residentCheckThreads; 0 = the caller alone)
 void host_hash_helpers(int n) {ESKF_LIO::shim::HashCrew::instance().setHelpers(n);}
 size_t host_localmap_size(const LocalMap * map) {return map->size();}
+int host_localmap_saves_raw_points(const LocalMap * map) {return map->savesRawPoints() ? 1 : 0;}
 // waits until the shadow grid's worker has filed every cloud handed to it (what LocalMap::grid() / save() do first);
 // returns the host grid's voxel count
 size_t host_localmap_drain(const LocalMap * map) {return map->grid().size();}

@@ -45,6 +45,16 @@
 #include <vector>
 
 #include "../vgicp_hip.h"
+#include "../vgicp_hip_map_points.h"
+
+// The raw-point store's entry points (vgicp_hip_map_points.h, and vgicp_set_option for its option) are referenced
+// weakly, so a program that links a stand-in of the C ABI without them (tests/native/shadow_stress.cpp) still links: a
+// map then skips switching the option, and one that asks for raw points on the device refuses to be built.  Against the
+// module they resolve as usual.  This weakens vgicp_set_option for every translation unit that includes this header
+// (INTEGRATION.md §A).
+#pragma weak vgicp_map_points_size
+#pragma weak vgicp_map_points_export
+#pragma weak vgicp_set_option
 #include "ShimTypes.hpp"
 
 #if defined(ESKF_LIO_SHIM_NATIVE_TYPES) && __has_include(<yaml-cpp/yaml.h>)
@@ -79,6 +89,11 @@ struct LocalMapConfig
   // ones (0.5 - 0.6 ms per 60 000-point frame instead of 3.6 - 4.5), and save() still writes the reference's content.
   bool deviceResident = true;
   bool keepRawPoints = true;
+  // With deviceResident and keepRawPoints: the raw points are kept by the device map itself
+  // (VGICP_OPTION_MAP_RAW_POINTS, include/vgicp_hip_map_points.h; 32 bytes per kept point on the device) instead of the
+  // shadow grid — no worker thread, no host copy of the prepared scan needed, and save() writes every raw point
+  // whatever the host-copy mode.  YAML: local_map.raw_points_on_device (optional, default false).
+  bool rawPointsOnDevice = false;
 };
 
 namespace shim
@@ -733,10 +748,12 @@ public:
     , removePeriod_(config.removePeriod)
     , deviceResident_(config.deviceResident)
     , keepRawPoints_(config.keepRawPoints)
+    , rawOnDevice_(config.deviceResident && config.keepRawPoints && config.rawPointsOnDevice)
     , visualize_(visualize)
     , ctx_(ctx ? ctx : shim::defaultContext())
   {
     shim::check(ctx_, vgicp_map_reset(ctx_, voxelSize_, 0), "vgicp_map_reset");
+    storeRawPointsOnDevice();
   }
 
   ~LocalMap() {shadowStop();}
@@ -759,6 +776,7 @@ public:
     , ctx_(ctx ? ctx : shim::defaultContext())
   {
     shim::check(ctx_, vgicp_map_reset(ctx_, voxelSize_, 0), "vgicp_map_reset");
+    storeRawPointsOnDevice();
   }
 
 #if defined(ESKF_LIO_SHIM_HAVE_YAML)
@@ -779,6 +797,7 @@ public:
     c.removeDistantPoints = m["remove_distant_points"]["enabled"].as<bool>();
     c.distanceThreshold = m["remove_distant_points"]["distance_threshold"].as<double>();
     c.removePeriod = m["remove_distant_points"]["removing_period"].as<double>();
+    if (m["raw_points_on_device"].IsDefined()) {c.rawPointsOnDevice = m["raw_points_on_device"].as<bool>();}
     return c;
   }
 #endif
@@ -830,7 +849,7 @@ public:
       // The host side of the same update, for save(): the cloud moved into the world frame in place (src/LocalMap.cpp:15)
       // and, when it was inserted, the reference's insertion loop on the shadow grid -- on the worker thread when nobody
       // else can see the cloud (the caller moved its pointer in, src/Odometry.cpp:86), else the transform at least here.
-      if (hostIsCurrent && keepRawPoints_ && shadowComplete_) {
+      if (hostIsCurrent && keepRawPoints_ && shadowComplete_ && !rawOnDevice_) {
         const bool mine = cloud.use_count() == 1;
         ShadowOp op;
         if (mine) {
@@ -883,7 +902,7 @@ public:
         evicted = true;
         std::cout << "removed " << numRemovedVoxels << " voxels\n";
       }
-      if (keepRawPoints_ && shadowComplete_) {
+      if (keepRawPoints_ && shadowComplete_ && !rawOnDevice_) {
         ShadowOp op;
         // the worker thread reads the cloud later: it gets the caller's object only when nobody else can reach it
         // (src/Odometry.cpp:86 moves its pointer in), else a copy — a caller that keeps its pointer may edit or resize
@@ -976,14 +995,26 @@ public:
 
   // reference: src/LocalMap.cpp:156-167 writes a .pcd through Open3D and a PinholeCameraTrajectory
   // JSON. Written here without Open3D: ASCII PCD v0.7 — of every stored point when the host map is
-  // authoritative (as the reference writes), of ONE point per voxel (its mean, read back with
-  // vgicp_map_export) in deviceResident mode, where the raw points are not kept — and the 4x4 poses as a
-  // JSON array of column-major "extrinsic" arrays (the field Open3D's trajectory reader uses).
+  // authoritative (as the reference writes) or the raw points are kept (by the device map, read back with
+  // vgicp_map_points_export, or by the shadow grid), else of ONE point per voxel (its mean, read back with
+  // vgicp_map_export) in deviceResident mode — and the 4x4 poses as a JSON array of column-major
+  // "extrinsic" arrays (the field Open3D's trajectory reader uses).
   void save(const std::string & cloud_path, const std::string & trajectory_path) const
   {
     shadowDrain();
-    std::vector<double> deviceMeans;
-    if (deviceResident_ && !(keepRawPoints_ && shadowComplete_)) {
+    std::vector<double> deviceMeans;   // or the device map's raw points
+    if (rawOnDevice_) {
+      size_t n = 0, written = 0;
+      shim::check(ctx_, vgicp_map_points_size(ctx_, &n, nullptr), "vgicp_map_points_size");
+      std::vector<int32_t> keys(3 * n);
+      deviceMeans.resize(3 * n);
+      if (n) {
+        shim::check(
+          ctx_, vgicp_map_points_export(ctx_, n, keys.data(), deviceMeans.data(), &written),
+          "vgicp_map_points_export");
+      }
+      deviceMeans.resize(3 * written);
+    } else if (deviceResident_ && !(keepRawPoints_ && shadowComplete_)) {
       const size_t n = size();
       std::vector<int32_t> keys(3 * n);
       std::vector<double> covs(9 * n);
@@ -1042,10 +1073,28 @@ public:
   }
   // true while save() will write every stored raw point, as the reference does (false once a frame was inserted on the
   // device whose prepared scan never reached the host)
-  bool savesRawPoints() const {return !deviceResident_ || (keepRawPoints_ && shadowComplete_);}
+  bool savesRawPoints() const {return !deviceResident_ || rawOnDevice_ || (keepRawPoints_ && shadowComplete_);}
+  // the device map keeps the raw points (LocalMapConfig::rawPointsOnDevice)
+  bool rawPointsOnDevice() const {return rawOnDevice_;}
 
 private:
   static Key toKey(const Vector3i & v) {return Key{v(0), v(1), v(2)};}
+  // the context may have served another map before (shim::defaultContext is shared, and a caller may switch the option
+  // through the C ABI): the option is set to THIS map's config every time.  The map is empty here (just reset), which is
+  // when the option is accepted; switching it off costs no launch.
+  void storeRawPointsOnDevice()
+  {
+    const bool available = vgicp_set_option && vgicp_map_points_size && vgicp_map_points_export;
+    if (!available) {
+      if (rawOnDevice_) {
+        throw std::runtime_error("LocalMapConfig::rawPointsOnDevice: the linked vgicp module has no raw-point store");
+      }
+      return;   // a stand-in of the C ABI without the store: nothing to switch off
+    }
+    shim::check(
+      ctx_, vgicp_set_option(ctx_, VGICP_OPTION_MAP_RAW_POINTS, rawOnDevice_ ? 1 : 0),
+      "vgicp_set_option(VGICP_OPTION_MAP_RAW_POINTS)");
+  }
   static double now()
   {
     return std::chrono::duration<double>(
@@ -1197,6 +1246,7 @@ private:
   double removePeriod_;
   bool deviceResident_ = false;
   bool keepRawPoints_ = false;
+  bool rawOnDevice_ = false;         // the device map keeps the raw points: no shadow grid
   bool shadowComplete_ = true;       // every frame inserted on the device so far has also reached the shadow grid
   std::thread shadowThread_;
   mutable std::mutex shadowMutex_;

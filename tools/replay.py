@@ -6,16 +6,19 @@ usage: python tools/replay.py --bag run_0.db3 [--imu-topic /alphasense/imu] [--l
        python tools/replay.py --synthetic 20 --points 60000          (GPU box; no recording needed)
 options: --out traj.tum   --device-map (keep the voxel grid on the GPU only)   --write-bag file.db3
          --resident (the scan never leaves the GPU between the raw sweep and the pose)
+         --raw-points-on-device (with --resident: the map keeps its raw points, VGICP_OPTION_MAP_RAW_POINTS; their
+         export is timed at the end)
 The configuration is the reference's config/hilti_config.yaml as a dict (eskf_lio_amd/replay.py:DEFAULT_CONFIG);
 --config file.yaml overrides it with a file of the reference's own layout."""
 import argparse
 import os
 import sys
+import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from eskf_lio_amd import replay, synth  # noqa: E402
+from eskf_lio_amd import capi, replay, synth  # noqa: E402
 
 
 def config_from_yaml(path):
@@ -58,7 +61,11 @@ def main():
     ap.add_argument("--device-map", action="store_true")
     ap.add_argument("--resident", action="store_true",
                     help="scan stays on the GPU from the raw sweep to the pose (vgicp_scan_prepare chain)")
+    ap.add_argument("--raw-points-on-device", action="store_true",
+                    help="with --resident: the device map keeps every voxel's raw points (VGICP_OPTION_MAP_RAW_POINTS)")
     args = ap.parse_args()
+    if args.raw_points_on_device and not args.resident:
+        ap.error("--raw-points-on-device needs --resident")
     cfg, imu_topic, lidar_topic = replay.DEFAULT_CONFIG, replay.IMU_TOPIC, replay.LIDAR_TOPIC
     if args.config:
         cfg, imu_topic, lidar_topic = config_from_yaml(args.config)
@@ -76,11 +83,18 @@ def main():
     else:
         ap.error("one of --bag / --synthetic is required")
     backend = replay.DeviceBackend(cfg) if args.resident else replay.GpuBackend(cfg, device_resident_map=args.device_map)
+    if args.raw_points_on_device:
+        backend.ctx.set_option(capi.OPTION_MAP_RAW_POINTS, 1)   # the map is empty here, as the option wants
     odo = replay.Odometry(cfg, backend)
     traj = odo.run(events)
     replay.write_tum(args.out, traj)
     print(f"{len(traj)} poses -> {args.out}; Gauss-Newton rounds per frame: {odo.backend.iterations}")
     print(odo.report())
+    if args.raw_points_on_device:
+        t0 = time.perf_counter()
+        keys, _ = backend.ctx.map_points_export()
+        print(f"raw points kept on the device: {len(keys)} in {backend.ctx.map_size()[0]} voxels; "
+              f"map_points_export (size query + export) {1e3 * (time.perf_counter() - t0):.2f} ms")
     if truth is not None:
         err = [np.linalg.norm(T[:3, 3] - G[:3, 3]) for (_, T), (_, G) in zip(traj, truth)]
         print(f"synthetic stream: position error against the generating motion, max {max(err):.4f} m")
