@@ -42,6 +42,10 @@ EXPORTS = (
 # every symbol include/vgicp_hip_map_points.h declares (an extension header: EXPORTS stays the main header's list)
 MAP_POINTS_EXPORTS = ("vgicp_map_points_size", "vgicp_map_points_export")
 
+# every symbol include/vgicp_hip_batch.h declares (likewise an extension header)
+BATCH_EXPORTS = ("vgicp_align_resident_batch", "vgicp_align_batch_width")
+BATCH_MAX = 64
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -73,6 +77,14 @@ class Stats(C.Structure):
                 ("launches", C.c_int32), ("seconds", C.c_double), ("device_seconds", C.c_double),
                 ("corr_count", C.POINTER(C.c_uint64)), ("normal_eq", C.POINTER(C.c_double)),
                 ("kernel_ms", C.POINTER(C.c_float))]
+
+
+class BatchStats(C.Structure):
+    _fields_ = [("hypotheses_per_launch", C.c_int32), ("launches", C.c_int32), ("seconds", C.c_double),
+                ("device_seconds", C.c_double),
+                ("status", C.POINTER(C.c_int32)), ("iterations", C.POINTER(C.c_int32)),
+                ("converged", C.POINTER(C.c_int32)), ("corr_count", C.POINTER(C.c_uint64)),
+                ("normal_eq", C.POINTER(C.c_double))]
 
 
 _lib: Optional[C.CDLL] = None
@@ -144,7 +156,9 @@ def load_library() -> C.CDLL:
     lib.vgicp_peer_disconnect.argtypes = [vp]
     lib.vgicp_map_points_size.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
     lib.vgicp_map_points_export.argtypes = [vp, sz, ip, dp, C.POINTER(sz)]
-    for name in EXPORTS + MAP_POINTS_EXPORTS:
+    lib.vgicp_align_resident_batch.argtypes = [vp, sz, dp, C.POINTER(Params), dp, C.POINTER(BatchStats)]
+    lib.vgicp_align_batch_width.argtypes = [vp, C.POINTER(sz)]
+    for name in EXPORTS + MAP_POINTS_EXPORTS + BATCH_EXPORTS:
         fn = getattr(lib, name)
         if name not in ("vgicp_last_error", "vgicp_peer_status"):
             fn.restype = C.c_int
@@ -170,6 +184,18 @@ def pose_to_abi(T: np.ndarray) -> np.ndarray:
 
 def pose_from_abi(v: np.ndarray) -> np.ndarray:
     return np.asarray(v, dtype=np.float64).reshape(4, 4).T.copy()
+
+
+class BatchResult(list):
+    """What align_resident_batch returns: one AlignResult per guess, and how the batch ran."""
+
+    def __init__(self, hypotheses_per_launch: int = 1, launches: int = 0, seconds: float = 0.0,
+                 device_seconds: float = 0.0):
+        super().__init__()
+        self.hypotheses_per_launch = hypotheses_per_launch
+        self.launches = launches
+        self.seconds = seconds
+        self.device_seconds = device_seconds
 
 
 @dataclass
@@ -411,6 +437,47 @@ class Context:
             self._h, _dp(g), C.byref(p), out, C.byref(st)),
             max_iteration, translation_sq_threshold, cosine_threshold, chunk_iterations, flags,
             allow_degenerate)
+
+    def align_resident_batch(self, guesses, max_iteration, translation_sq_threshold, cosine_threshold,
+                             flags: int = 0) -> "BatchResult":
+        """vgicp_align_resident_batch (vgicp_hip_batch.h): the resident scan from every guess of `guesses` (k 4x4
+        poses).  A list of the AlignResults align_resident would return, one per guess (status / message say when a
+        hypothesis is degenerate; nothing is raised for that), with hypotheses_per_launch and launches."""
+        gs = [pose_to_abi(g) for g in guesses]
+        k = len(gs)
+        g = np.ascontiguousarray(np.stack(gs).reshape(k, 16)) if k else np.zeros((0, 16))
+        cap = max(int(max_iteration), 0)
+        p = Params(int(max_iteration), 0, float(translation_sq_threshold), float(cosine_threshold), int(flags), 0)
+        out = np.zeros((max(k, 1), 16))
+        status = np.zeros(max(k, 1), dtype=np.int32)
+        its = np.zeros(max(k, 1), dtype=np.int32)
+        conv = np.zeros(max(k, 1), dtype=np.int32)
+        counts = np.zeros((max(k, 1), max(cap, 1)), dtype=np.uint64)
+        neq = np.zeros((max(k, 1), max(cap, 1), 27))
+        i32p = C.POINTER(C.c_int32)
+        st = BatchStats()
+        st.status, st.iterations, st.converged = (status.ctypes.data_as(i32p), its.ctypes.data_as(i32p),
+                                                  conv.ctypes.data_as(i32p))
+        # the ABI's layout is k x max_iteration (x 27): the arrays above have exactly that stride when cap >= 1
+        st.corr_count = counts.ctypes.data_as(C.POINTER(C.c_uint64))
+        st.normal_eq = _dp(neq)
+        self._check(self._lib.vgicp_align_resident_batch(self._h, k, _dp(g), C.byref(p), _dp(out), C.byref(st)))
+        res = BatchResult(hypotheses_per_launch=st.hypotheses_per_launch, launches=st.launches, seconds=st.seconds,
+                          device_seconds=st.device_seconds)
+        for h in range(k):
+            it = int(its[h])
+            res.append(AlignResult(pose=pose_from_abi(out[h]), iterations=it, converged=bool(conv[h]),
+                                   world_size=1, launches=st.launches, seconds=st.seconds,
+                                   device_seconds=st.device_seconds, corr_count=counts[h, :it].copy(),
+                                   normal_eq=neq[h, :it].copy(), kernel_ms=None, status=int(status[h]),
+                                   message="solved pose is not finite" if status[h] else ""))
+        return res
+
+    def align_batch_width(self) -> int:
+        """vgicp_align_batch_width: hypotheses one launch takes for the scan that is resident now."""
+        w = C.c_size_t(0)
+        self._check(self._lib.vgicp_align_batch_width(self._h, C.byref(w)))
+        return int(w.value)
 
     # -- hooks --
     def accumulate(self, points, covs, pose):

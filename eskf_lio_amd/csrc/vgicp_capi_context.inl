@@ -97,6 +97,16 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
   VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_rows_persist), persistent_rows_words() * 8));
   VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_parts_persist), persistent_parts_words() * 8));
   VG_CREATE(hipHostMalloc(&ctx->h_exchange_image, (persistent_rows_words() + persistent_parts_words()) * 8, 0));
+  {
+    // the batched align's storage: nothing is allocated inside vgicp_align_resident_batch
+    const size_t batch_bytes = ((size_t)VGICP_BATCH_MAX * kBatchSlotRows + 1) * kSlots * sizeof(double);
+    VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_batch_exchange), (team_rows_words() + team_parts_words()) * 8));
+    VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_batch), batch_bytes, 0));
+    std::memset(ctx->h_batch, 0, batch_bytes);
+    void* dev = nullptr;
+    VG_CREATE(hipHostGetDevicePointer(&dev, ctx->h_batch, 0));
+    ctx->h_batch_dev = static_cast<double*>(dev);
+  }
   ctx->persist_grid = (uint32_t)std::min<int>(ctx->cu_count, kExchangeRows);
   if (max_persist_grid >= 1 && max_persist_grid < ctx->persist_grid) ctx->persist_grid = max_persist_grid;
   if (const char* pg = std::getenv("VGICP_PERSIST_GRID")) {  // fewer workgroups: several contexts sharing one device
@@ -262,6 +272,8 @@ int vgicp_destroy(vgicp_ctx* ctx) {
   (void)hipFree(ctx->d_rows_persist);
   (void)hipFree(ctx->d_parts_persist);
   (void)hipHostFree(ctx->h_exchange_image);
+  (void)hipFree(ctx->d_batch_exchange);
+  if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
   (void)hipFree(ctx->d_rows[0]);
   (void)hipFree(ctx->d_rows[1]);
   (void)hipFree(ctx->d_sums);

@@ -23,6 +23,7 @@
 
 #include "../../include/vgicp_hip.h"
 #include "../../include/vgicp_hip_map_points.h"
+#include "../../include/vgicp_hip_batch.h"
 #include "vgicp_device.h"
 
 using namespace vgicp;
@@ -81,6 +82,7 @@ constexpr uint64_t kRawMinEntries = 4096;
 constexpr uint64_t kRawMaxEntries = 1ull << 31;   // 64 GiB of raw points; ordinals and offsets stay 32-bit
 constexpr int kDefaultChunk = 4;
 constexpr int kMaxChunksInFlight = 2;
+constexpr int kBatchSlotRows = 64;   // rows of kSlots doubles per hypothesis of a batch: the final state, then up to 63 rounds of log
 constexpr int kPersistentCooldownAligns = 8;  // aligns on the per-launch loop after the single launch gave up
 
 }  // namespace vgicp
@@ -301,6 +303,10 @@ struct vgicp_ctx {
   double* d_rows_persist = nullptr;  // [3][kExchangeRows][kSlots] (vgicp_device.h, PersistArgs)
   double* d_parts_persist = nullptr; // [3][kFolders][kSlots]
   void* h_exchange_image = nullptr;  // pinned: what the two buffers hold between launches
+  // the batched align (vgicp_hip_batch.h): storage of its own, made with the context
+  double* d_batch_exchange = nullptr;  // team rows, then team parts (team_rows_words() + team_parts_words()); all unset before a launch
+  double* h_batch = nullptr;           // pinned: VGICP_BATCH_MAX blocks of kBatchSlotRows rows (state, then log), then the abort word's row
+  double* h_batch_dev = nullptr;       // the same memory as the device addresses it
   bool persistent_enabled = true;    // cleared by VGICP_PERSISTENT=0 or when a workgroup does not fit a CU
   double prefetch_margin = 0.015;    // see PersistArgs::prefetch_margin; VGICP_PREFETCH_MARGIN overrides (0 = off).  Round 6: 0.03 -> 0.015
                                      // once the workgroups that are no folders stopped polling early (C2: 0 7.18, 0.01 6.41, 0.015 6.34, 0.02 6.35, 0.03 6.52, 0.04 6.66 us per round)
@@ -503,6 +509,10 @@ int adopt_device_scan(vgicp_ctx* ctx, int src_device, const double* d_points, co
 int map_insert_device(vgicp_ctx* ctx, const double* d_points, const double* d_covs, size_t n, const double transform[16],
                       size_t max_points_per_voxel, bool short_lists, bool deferred, size_t* new_voxels);
 int settle_context(vgicp_ctx* ctx);
+// vgicp_align_resident_batch as k single aligns in a row (vgicp_capi_batch.inl); *first_bad: the first hypothesis status
+// that is not VGICP_OK
+int align_batch_sequential(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp_params* params, double* out_poses,
+                           vgicp_batch_stats* stats, bool loop_only, int* first_bad);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 bool insertion_lists_stay_short_for(const vgicp_ctx* ctx, double prep_voxel);
@@ -529,6 +539,9 @@ int align(vgicp_ctx* ctx, size_t n, const double* points, const double* covs, co
 int scan_upload(vgicp_ctx* ctx, size_t n, const double* points, const double* covs);
 int align_resident(vgicp_ctx* ctx, const double guess[16], const vgicp_params* params, double out_pose[16],
                    vgicp_stats* stats);
+int align_resident_batch(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp_params* params, double* out_poses,
+                         vgicp_batch_stats* stats, int* first_bad);
+int align_batch_width(vgicp_ctx* ctx, size_t* hypotheses_per_launch);
 int scan_prepare(vgicp_ctx* ctx, size_t n, const double* points, const double* point_time, size_t num_states,
                  const double* states, const double extrinsic[16], double voxel_size, int knn, size_t* kept,
                  int64_t* deskewed, bool deferred, uint64_t ticket = 0);

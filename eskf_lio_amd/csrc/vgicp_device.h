@@ -175,9 +175,35 @@ struct FusedUpload {
   unsigned long long* unit_clock;  // device word: the latest s_memrealtime at which a workgroup had its points in LDS
 };
 
+// The batched align (vgicp_align_resident_batch): several hypotheses, one resident scan, ONE persistent launch.  With one
+// point per thread a scan of n points occupies T = ceil(n / 448) workgroups; the launch's workgroups [h T, (h + 1) T)
+// are TEAM h and run hypothesis h exactly as the single launch runs it on its first T workgroups, with the team-local
+// index vb = blockIdx.x - h T in the place of blockIdx.x.  Workgroups beyond teams x T leave at once.  A team has exchange
+// words of its own (PersistArgs::rows / parts point at team 0's):
+//   rows   [3][16 U][kSlots], U = ceil(T / 16)   workgroup vb's row at (vb % 16) * U + vb / 16
+//   parts  [3][kFolders][kSlots]                 folder g is the team's workgroup vb = g < 16
+// The single launch's folders add 16 rows and its workgroups 16 parts, of which those that belong to workgroups without
+// points are +0.0; a team has no such workgroups and puts a literal +0.0 into the same positions of the same pairwise
+// tree (poll_and_sum's `live`), so every sum has the single launch's bits.  Every word is kRowUnset when a launch starts
+// (the host's memset in front of it) and PersistArgs::round0 is 0: the owner of a word changes with T from call to call.
+constexpr int kTeamsMax = 16;          // hypotheses per launch
+constexpr int kTeamRowsMax = 512;      // rows per buffer over all teams: teams x 16 U <= 480 for every T at a grid of 256
+struct TeamArgs {
+  uint32_t teams;         // hypotheses of this launch
+  uint32_t team_wgs;      // T
+  uint32_t folder_rows;   // U
+  uint32_t slot_words;    // doubles between the state + log blocks of two hypotheses (PersistArgs::state / log: team 0's)
+  uint32_t* abort_word;   // ONE word for the whole launch: = PersistArgs::seq when any workgroup of any team gave up
+  double pose0[kTeamsMax][12];
+};
+constexpr size_t team_rows_words() { return 3 * (size_t)kTeamRowsMax * kSlots; }
+constexpr size_t team_parts_words() { return 3 * (size_t)kTeamsMax * kFolders * kSlots; }
+
 // ---- launchers (defined in vgicp_kernels.hip) ----
 // The whole ICP::align loop in one launch (512-thread workgroups, at most one per CU).
 hipError_t launch_persistent(hipStream_t s, const PersistArgs& args, uint32_t grid);
+// The same loop for args.teams hypotheses side by side (single device, one point per thread, no stamps, settled scan).
+hipError_t launch_persistent_teams(hipStream_t s, const PersistArgs& args, const TeamArgs& teams, uint32_t grid);
 // The same launch with the scan's upload fused into round 0 (single device, args.n <= grid x 448, no stamps).
 hipError_t launch_persistent_fused(hipStream_t s, const PersistArgs& args, const FusedUpload& up, uint32_t grid);
 // How launch_persistent splits the CU's LDS for a scan of n points on `grid` workgroups: points per

@@ -796,16 +796,25 @@ constexpr int kL2Delay = 64;   // s_sleep units (64 clocks each) a workgroup tha
 // fraction of a memory round trip apart so that a word which lands just after a poll has passed need not wait a whole
 // round trip for the next, made every round SLOWER (C2 +0.3 / +0.9 / +1.5 us: the polls of 256 workgroups queue at the
 // memory side, profiles/NOTES_dropped_experiments.md) — which is what led to kL2Delay: poll LESS.
-template <bool SYSTEM>
-__device__ __forceinline__ bool poll_and_sum(const double* src, uint32_t lane, uint32_t spin_limit, double& sum) {
+// LIVE (the team launch): only the first `live` of the 16 rows belong to a workgroup; the others are taken as +0.0
+// without a load — the value the single launch finds there — and are added in their place of the tree all the same.
+template <bool SYSTEM, bool LIVE = false>
+__device__ __forceinline__ bool poll_and_sum(const double* src, uint32_t lane, uint32_t spin_limit, double& sum,
+                                             uint32_t live = (uint32_t)kFolders) {
   constexpr int H = kFolders / 2;
   const uint32_t slot = lane & 31u, half = lane >> 5;
   const bool active = slot <= (uint32_t)kCountSlot;
   const double* mine = src + (size_t)half * H * kSlots + (active ? slot : 0u);
   unsigned long long w[H];
+  if constexpr (LIVE) {
 #pragma unroll
-  for (int k = 0; k < H; ++k)
-    w[k] = active ? (SYSTEM ? load_system_bits(mine + k * kSlots) : load_through_bits(mine + k * kSlots)) : 0ull;
+    for (int k = 0; k < H; ++k)   // a word that is not live is never kRowUnset, so the loop below leaves it alone
+      w[k] = (active && half * H + (uint32_t)k < live) ? load_through_bits(mine + k * kSlots) : 0ull;
+  } else {
+#pragma unroll
+    for (int k = 0; k < H; ++k)
+      w[k] = active ? (SYSTEM ? load_system_bits(mine + k * kSlots) : load_through_bits(mine + k * kSlots)) : 0ull;
+  }
   for (uint32_t spins = 0;; ++spins) {
     bool missing = false;
 #pragma unroll
@@ -943,9 +952,18 @@ __device__ __forceinline__ bool fused_round0_load(const FusedUpload& f, uint64_t
 // per thread (waves 1..7), kept in registers together with the
 // voxel record it used, plus the neighbour prefetch.  Separate instantiations keep both within 256 VGPRs.
 // FUSED: round 0's points arrive through the staging memory of the upload (fused_round0_load), !MANY, !MULTI, !STAMPS.
-template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool FUSED = false>
-__device__ __forceinline__ void persistent_body(const PersistArgs& a, const FusedUpload& up) {
+// TEAM: one of several hypotheses that share a launch (TeamArgs in vgicp_device.h): the workgroup's index inside its team
+// stands where blockIdx.x stands otherwise, the exchange words are the team's own, !MANY, !MULTI, !STAMPS, !FUSED.
+struct TeamView {
+  uint32_t vb = 0;           // index of the workgroup inside its team
+  uint32_t team_wgs = 0;     // T
+  uint32_t folder_rows = 0;  // U
+  uint32_t* abort_word = nullptr;
+};
+template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool FUSED = false, bool TEAM = false>
+__device__ __forceinline__ void persistent_body(const PersistArgs& a, const FusedUpload& up, const TeamView& tv = TeamView()) {
   static_assert(!FUSED || (!MULTI && !STAMPS && !MANY), "the fused upload serves the single-device one-point-per-thread body");
+  static_assert(!TEAM || (!MULTI && !STAMPS && !MANY && !FUSED), "teams run the single-device one-point-per-thread body");
   static_assert(BLOCK / kSlots == kFolders, "the exchange reproduces the fold order of iterate_kernel<512>");
   constexpr int kWaves = BLOCK / 64;
   constexpr int kWorkers = BLOCK - 64;
@@ -970,7 +988,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
   // a.n bounds the count the device holds (a scan preparation that gave up must not send this launch out of range)
   const uint32_t n_pts = a.n_dev ? (*a.n_dev < a.n ? *a.n_dev : a.n) : a.n;  // uniform
   const bool cov_sym = MANY && a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
-  const uint32_t grid = gridDim.x, blk = blockIdx.x;
+  const uint32_t grid = gridDim.x, blk = TEAM ? tv.vb : blockIdx.x;
   // MANY (the scan, or the upper bound the launch plan was made from, has more points than grid x 448): a thread owns
   // several points anyway, so wave 0 owns points as well and turns solver after the accumulate phase — 512 points
   // per workgroup pass instead of 448, two point-carrying waves on every SIMD instead of 2/2/2/1.
@@ -1000,7 +1018,11 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
   const uint32_t parked = MANY ? (fit < a.stash_points ? fit : a.stash_points) : 0u;  // uniform
   const bool folder = blk < (uint32_t)kFolders;  // folder g adds the rows of workgroups g, g + 16, g + 32 ...
   // row of workgroup b inside a buffer: the 16 rows of a folder are consecutive
-  const uint32_t my_row = (blk % kFolders) * kFolders + blk / kFolders;
+  const uint32_t my_row = TEAM ? (blk % kFolders) * tv.folder_rows + blk / kFolders : (blk % kFolders) * kFolders + blk / kFolders;
+  // rows of one buffer; TEAM: how many of a folder's 16 rows and of the 16 parts belong to a workgroup of the team
+  const uint32_t buf_rows = TEAM ? (uint32_t)kFolders * tv.folder_rows : (uint32_t)kExchangeRows;
+  const uint32_t live_rows = TEAM ? (tv.team_wgs - blk + (uint32_t)kFolders - 1u) / (uint32_t)kFolders : (uint32_t)kFolders;  // folders only
+  const uint32_t live_parts = TEAM ? (tv.team_wgs < (uint32_t)kFolders ? tv.team_wgs : (uint32_t)kFolders) : (uint32_t)kFolders;
 
   Pose total;
 #pragma unroll
@@ -1212,7 +1234,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
       // the buffers rotate with a round number that runs on from launch to launch (a.round0: rounds executed on
       // this context before): nothing has to be tidied up when a launch ends
       const uint32_t buf = (a.round0 + (uint32_t)it) % 3u;
-      double* rows = a.rows + (size_t)buf * kExchangeRows * kSlots;
+      double* rows = a.rows + (size_t)buf * buf_rows * kSlots;
       double* parts = a.parts + (size_t)buf * kFolders * kSlots;
       // ---- level 1: publish this workgroup's row (every re-arming store of mine has completed) ----
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1229,7 +1251,8 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
       const uint32_t spin_limit = (FUSED && it == 0 && up.spin_limit > a.spin_limit) ? up.spin_limit : a.spin_limit;
       if (folder) {  // uniform
         double part = 0.0;
-        ok = poll_and_sum<false>(rows + (size_t)blk * kFolders * kSlots, lane, spin_limit, part);
+        if constexpr (TEAM) ok = poll_and_sum<false, true>(rows + (size_t)blk * tv.folder_rows * kSlots, lane, spin_limit, part, live_rows);
+        else ok = poll_and_sum<false>(rows + (size_t)blk * kFolders * kSlots, lane, spin_limit, part);
         if (ok && lane <= (uint32_t)kCountSlot) store_through_bits(parts + (size_t)blk * kSlots + lane, publishable(part));
       }
       if (STAMPS) { const uint64_t n = wall_clock64(); acc_l1 += n - t_mark; t_mark = n; }
@@ -1241,7 +1264,8 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
         // polls and stores go through.  One point per thread (C2): 6.82 -> 6.55 us per round with 64 units (50: 6.63,
         // 60 - 70: 6.55, 85: 6.9, 100: 7.1); several points per thread (C5): no gain, not delayed.
         if (!MANY && !folder) __builtin_amdgcn_s_sleep(kL2Delay);
-        if (ok) ok = poll_and_sum<false>(parts, lane, spin_limit, tot);
+        if constexpr (TEAM) { if (ok) ok = poll_and_sum<false, true>(parts, lane, spin_limit, tot, live_parts); }
+        else if (ok) ok = poll_and_sum<false>(parts, lane, spin_limit, tot);
       } else {
         // ---- several GPUs: workgroup 0 adds the parts to this rank's total and stores it into the mailbox
         // of every rank (its own included); every workgroup then adds the ranks' totals in rank order ----
@@ -1308,7 +1332,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
       asm volatile("" : "+v"(lane_here));
       const uint32_t rearm = (a.round0 + (uint32_t)it + 2u) % 3u;
       if (lane_here <= (uint32_t)kCountSlot) {
-        store_through_bits(a.rows + ((size_t)rearm * kExchangeRows + my_row) * kSlots + lane_here, kRowUnset);
+        store_through_bits(a.rows + ((size_t)rearm * buf_rows + my_row) * kSlots + lane_here, kRowUnset);
         if (folder) store_through_bits(a.parts + ((size_t)rearm * kFolders + blk) * kSlots + lane_here, kRowUnset);
       }
       if (MULTI && blk == 0 && lane_here <= (uint32_t)kCountSlot) {
@@ -1332,7 +1356,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
   if (gave_up) {
     // The host sees state->seq != seq (workgroup 0) or state->abort_seq == seq (any other workgroup: it may have
     // timed out although workgroup 0 found everything in place), resets the exchange buffers and uses launches.
-    if (tid == 0) a.state->abort_seq = a.seq;
+    if (tid == 0) { if constexpr (TEAM) *tv.abort_word = a.seq; else a.state->abort_seq = a.seq; }
     if (MULTI && blk == 0 && tid < a.world)   // the peers learn it from the verdict word, at the latest at their end
       store_system_bits(a.mail[tid] + kMailRowWords + a.rank, (unsigned long long)a.mail_seq << 1);
     return;
@@ -1414,6 +1438,27 @@ __global__ __launch_bounds__(BLOCK) void persistent_kernel(PersistArgs a) {
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void persistent_fused_kernel(PersistArgs a, FusedUpload up) {
   persistent_body<BLOCK, false, false, false, true>(a, up);
+}
+
+// The batched align: team h = workgroups [h T, (h + 1) T) runs hypothesis h (TeamArgs in vgicp_device.h).  A kernel of
+// its own, so that the instantiations above keep their code and their registers.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void persistent_team_kernel(PersistArgs a, TeamArgs t) {
+  const uint32_t h = blockIdx.x / t.team_wgs;  // uniform
+  if (h >= t.teams) return;
+  const FusedUpload none{};
+  TeamView tv;
+  tv.vb = blockIdx.x - h * t.team_wgs;
+  tv.team_wgs = t.team_wgs;
+  tv.folder_rows = t.folder_rows;
+  tv.abort_word = t.abort_word;
+  a.rows += (size_t)h * 3 * kFolders * t.folder_rows * kSlots;
+  a.parts += (size_t)h * 3 * kFolders * kSlots;
+  a.state = reinterpret_cast<AlignState*>(reinterpret_cast<double*>(a.state) + (size_t)h * t.slot_words);
+  a.log += (size_t)h * t.slot_words;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) a.pose0[k] = t.pose0[h][k];
+  persistent_body<BLOCK, false, false, false, false, true>(a, none, tv);
 }
 
 // Multi-GPU only: fold this rank's rows into one row (fixed order) so the all-reduce moves 256 B.
@@ -1990,6 +2035,19 @@ hipError_t launch_persistent_fused(hipStream_t s, const PersistArgs& args, const
     return hipErrorInvalidValue;
   const size_t dyn = std::max<size_t>(args.prefetch_margin > 0.0 ? kPrefetchBytes : 0u, kFusedLoadBytes);
   ++g_kernel_launches; hipLaunchKernelGGL(persistent_fused_kernel<512>, dim3(grid), dim3(512), dyn, s, args, up);
+  return hipGetLastError();
+}
+
+hipError_t launch_persistent_teams(hipStream_t s, const PersistArgs& args, const TeamArgs& teams, uint32_t grid) {
+  // one point per thread, a settled scan, every team inside the grid and inside the exchange storage
+  if (args.memo_points != 0 || args.stash_bytes != 0 || args.world > 1 || args.stamps != nullptr || args.n_dev != nullptr ||
+      args.round0 != 0 || teams.teams < 1 || teams.teams > (uint32_t)kTeamsMax || teams.team_wgs < 1 ||
+      (uint64_t)teams.teams * teams.team_wgs > grid || (uint64_t)args.n > (uint64_t)teams.team_wgs * kPersistWorkers ||
+      teams.folder_rows != (teams.team_wgs + kFolders - 1) / kFolders ||
+      (uint64_t)teams.teams * kFolders * teams.folder_rows > (uint64_t)kTeamRowsMax || teams.abort_word == nullptr)
+    return hipErrorInvalidValue;
+  const size_t dyn = args.prefetch_margin > 0.0 ? kPrefetchBytes : 0u;
+  ++g_kernel_launches; hipLaunchKernelGGL(persistent_team_kernel<512>, dim3(grid), dim3(512), dyn, s, args, teams);
   return hipGetLastError();
 }
 

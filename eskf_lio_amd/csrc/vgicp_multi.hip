@@ -653,6 +653,18 @@ int align_resident(vgicp_ctx* ctx, const double guess[16], const vgicp_params* p
   return align_shards(ctx, nullptr, nullptr, guess, params, out_pose, stats);
 }
 
+// vgicp_hip_batch.h on a multi-device context: every hypothesis is one point-sharded align over all devices, one after
+// another (teams of one device's launch would have to share the mailboxes; not built)
+int align_resident_batch(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp_params* params, double* out_poses,
+                         vgicp_batch_stats* stats, int* first_bad) {
+  return vgicp_internal::align_batch_sequential(ctx, k, guesses, params, out_poses, stats, /*loop_only=*/false, first_bad);
+}
+int align_batch_width(vgicp_ctx* ctx, size_t* hypotheses_per_launch) {
+  if (ctx->multi->resident == Resident::None) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
+  *hypotheses_per_launch = 1;
+  return VGICP_OK;
+}
+
 // CloudPreprocessor::process on device 0 (one sweep is one device's work: sort, octree, 30-NN), the result dealt out
 // to the other devices right before the align.
 int scan_prepare(vgicp_ctx* ctx, size_t n, const double* points, const double* point_time, size_t num_states,

@@ -54,11 +54,16 @@ def load_library() -> C.CDLL:
     lib.host_localmap_export.restype = sz
     lib.host_localmap_export.argtypes = [vp, sz, C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_uint64)]
     lib.host_localmap_save.argtypes = [vp, C.c_char_p, C.c_char_p]
+    lib.host_localmap_counter.restype = C.c_uint64
+    lib.host_localmap_counter.argtypes = [vp, C.c_int]
     lib.host_icp_create.restype = vp
     lib.host_icp_create.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int]
     lib.host_icp_destroy.argtypes = [vp]
     lib.host_icp_align.argtypes = [vp, sz, dp, dp, vp, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_uint64), sz]
+    i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    lib.host_icp_align_hypotheses.argtypes = [vp, sz, dp, dp, vp, sz, dp, dp, i32p, i32p, u64p, i32p, dp, i32p]
+    lib.host_frame_hypotheses.argtypes = [vp, vp, vp, vp, sz, dp, dp, i32p, i32p, u64p, i32p, i32p]
     lib.host_preprocessor_create.restype = vp
     lib.host_preprocessor_create.argtypes = [C.c_double, dp, C.c_int, C.c_int]
     lib.host_frame_begin.restype = vp
@@ -174,6 +179,10 @@ class LocalMap:
         assert w == n
         return keys, means, covs, counts
 
+    def counter(self, which: int) -> int:
+        """vgicp_get_counter of the map's device context (capi.Context.counter)."""
+        return int(self._lib.host_localmap_counter(self._h, int(which)))
+
     def save(self, cloud_path: str, trajectory_path: str):
         _check(self._lib, self._lib.host_localmap_save(self._h, cloud_path.encode(), trajectory_path.encode()))
 
@@ -210,6 +219,48 @@ class ICP:
         self.iterations, self.converged = it.value, bool(conv.value)
         self.correspondence_counts = counts[:it.value].copy()
         return capi.pose_from_abi(out)
+
+
+    def alignHypotheses(self, points, covs, localMap: LocalMap, guesses):
+        """ICP::alignHypotheses on a cloud made from the arrays (one upload) -> [dict(pose, converged, iterations,
+        finalCorrespondences)], one per guess."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        cvs = np.ascontiguousarray(covs, dtype=np.float64).reshape(-1, 9)
+        g, out, it, conv, fin = _fan_buffers(guesses)
+        res = C.c_int32()
+        _check(self._lib, self._lib.host_icp_align_hypotheses(
+            self._h, pts.shape[0], _dp(pts), _dp(cvs), localMap._h, g.shape[0], _dp(g), _dp(out), _i32(it), _i32(conv),
+            fin.ctypes.data_as(C.POINTER(C.c_uint64)), None, None, C.byref(res)))
+        self.used_resident = bool(res.value)
+        return _fan_results(out, it, conv, fin)
+
+    def alignBest(self, points, covs, localMap: LocalMap, guesses) -> np.ndarray:
+        """ICP::alignBest -> the chosen pose; self.best is the chosen index, self.iterations / self.converged describe
+        that hypothesis."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        cvs = np.ascontiguousarray(covs, dtype=np.float64).reshape(-1, 9)
+        g, _, it, conv, _ = _fan_buffers(guesses)
+        best, pose = C.c_int32(-1), np.zeros(16)
+        _check(self._lib, self._lib.host_icp_align_hypotheses(
+            self._h, pts.shape[0], _dp(pts), _dp(cvs), localMap._h, g.shape[0], _dp(g), None, _i32(it), _i32(conv), None,
+            C.byref(best), _dp(pose), None))
+        self.best, self.iterations, self.converged = int(best.value), int(it[0]), bool(conv[0])
+        return capi.pose_from_abi(pose)
+
+
+def _i32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _fan_buffers(guesses):
+    g = np.ascontiguousarray(np.stack([capi.pose_to_abi(T) for T in guesses]).reshape(-1, 16))
+    k = g.shape[0]
+    return g, np.zeros((k, 16)), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.uint64)
+
+
+def _fan_results(out, it, conv, fin):
+    return [dict(pose=capi.pose_from_abi(out[h]), converged=bool(conv[h]), iterations=int(it[h]),
+                 finalCorrespondences=int(fin[h])) for h in range(out.shape[0])]
 
 
 class CloudPreprocessor:
@@ -285,6 +336,16 @@ class Frame:
         _check(self._lib, self._lib.host_frame_run(self._h, preprocessor._h, icp._h, localMap._h, _dp(g),
                                                    1 if first_frame else 0, int(mutate),
                                                    stage_next._h if stage_next is not None else None, int(bool(move_cloud))))
+
+    def hypotheses(self, preprocessor: "CloudPreprocessor", icp: "ICP", localMap: "LocalMap", guesses):
+        """process(states, meas), then ICP::alignHypotheses on the cloud it left resident (no map update) ->
+        (results as ICP.alignHypotheses, used_resident, hypotheses per launch)."""
+        g, out, it, conv, fin = _fan_buffers(guesses)
+        res, per = C.c_int32(), C.c_int32()
+        _check(self._lib, self._lib.host_frame_hypotheses(
+            self._h, preprocessor._h, icp._h, localMap._h, g.shape[0], _dp(g), _dp(out), _i32(it), _i32(conv),
+            fin.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(res), C.byref(per)))
+        return _fan_results(out, it, conv, fin), bool(res.value), int(per.value)
 
     def end(self, want_cloud: bool = False):
         """-> dict(pose, iterations, used_resident, corr0, host_points[, points, covs])."""

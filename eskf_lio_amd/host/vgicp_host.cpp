@@ -172,6 +172,14 @@ int host_localmap_save(const LocalMap * map, const char * cloud_path, const char
   return guarded([&] {map->save(cloud_path, trajectory_path);});
 }
 
+// vgicp_get_counter of the map's device context (0 where the map has none)
+uint64_t host_localmap_counter(const LocalMap * map, int which)
+{
+  uint64_t v = 0;
+  guarded([&] {if (map->context()) {vgicp_get_counter(map->context(), which, &v);}});
+  return v;
+}
+
 // ICP(config) — registration.max_iteration / translation_sq_threshold / cosine_threshold
 ICP * host_icp_create(
   int max_iteration, double translation_sq_threshold, double cosine_threshold, int chunk_iterations)
@@ -202,6 +210,38 @@ int host_icp_align(
       for (size_t k = 0; k < st.correspondenceCounts.size() && k < corr_capacity; ++k) {
         corr_count[k] = st.correspondenceCounts[k];
       }
+    });
+}
+
+// icp->alignHypotheses(cloud, localMap, guesses) / icp->alignBest(...) on a cloud built from the arrays (not resident:
+// one upload).  out_poses k x 16, iterations / converged / final_corr k entries (each optional); with best != NULL the
+// call is alignBest: *best receives the chosen index and best_pose its pose.
+int host_icp_align_hypotheses(
+  ICP * icp, size_t n, const double * points, const double * covs, const LocalMap * map, size_t k,
+  const double * guesses, double * out_poses, int32_t * iterations, int32_t * converged, uint64_t * final_corr,
+  int32_t * best, double best_pose[16], int32_t * used_resident)
+{
+  return guarded(
+    [&] {
+      const PointCloud cloud = makeCloud(n, points, covs);
+      std::vector<Isometry3d> g(k);
+      for (size_t h = 0; h < k; ++h) {g[h] = ESKF_LIO::shim::poseFromData(guesses + 16 * h);}
+      if (best) {
+        const Isometry3d T = icp->alignBest(cloud, *map, g);
+        *best = static_cast<int32_t>(icp->lastBestHypothesis());
+        if (best_pose) {std::memcpy(best_pose, ESKF_LIO::shim::poseData(T), 16 * sizeof(double));}
+        if (iterations) {iterations[0] = icp->lastStats().iterations;}
+        if (converged) {converged[0] = icp->lastStats().converged ? 1 : 0;}
+      } else {
+        const auto all = icp->alignHypotheses(cloud, *map, g);
+        for (size_t h = 0; h < all.size(); ++h) {
+          if (out_poses) {std::memcpy(out_poses + 16 * h, ESKF_LIO::shim::poseData(all[h].pose), 16 * sizeof(double));}
+          if (iterations) {iterations[h] = all[h].iterations;}
+          if (converged) {converged[h] = all[h].converged ? 1 : 0;}
+          if (final_corr) {final_corr[h] = all[h].finalCorrespondences;}
+        }
+      }
+      if (used_resident) {*used_resident = icp->lastUsedResidentScan() ? 1 : 0;}
     });
 }
 
@@ -317,6 +357,30 @@ int host_frame_run(
       // move_cloud: as src/Odometry.cpp:86 hands it over (std::move: the map becomes the cloud's only owner);
       // else a copy of the pointer stays with the frame so that host_frame_end can return the cloud
       if (move_cloud) {map->updateLocalMap(std::move(f->meas->cloud), f->pose);} else {map->updateLocalMap(f->meas->cloud, f->pose);}
+    });
+}
+
+// process(states, meas) as host_frame_run does it, then icp->alignHypotheses(*meas.cloud, localMap, guesses) on the
+// cloud process() just stamped (no updateLocalMap): the fan on the resident scan.  Outputs as host_icp_align_hypotheses.
+int host_frame_hypotheses(
+  HostFrame * f, const CloudPreprocessor * p, ICP * icp, LocalMap * map, size_t k, const double * guesses,
+  double * out_poses, int32_t * iterations, int32_t * converged, uint64_t * final_corr, int32_t * used_resident,
+  int32_t * per_launch)
+{
+  return guarded(
+    [&] {
+      p->process(f->states, f->meas);
+      std::vector<Isometry3d> g(k);
+      for (size_t h = 0; h < k; ++h) {g[h] = ESKF_LIO::shim::poseFromData(guesses + 16 * h);}
+      const auto all = icp->alignHypotheses(*f->meas->cloud, *map, g);
+      for (size_t h = 0; h < all.size(); ++h) {
+        if (out_poses) {std::memcpy(out_poses + 16 * h, ESKF_LIO::shim::poseData(all[h].pose), 16 * sizeof(double));}
+        if (iterations) {iterations[h] = all[h].iterations;}
+        if (converged) {converged[h] = all[h].converged ? 1 : 0;}
+        if (final_corr) {final_corr[h] = all[h].finalCorrespondences;}
+      }
+      if (used_resident) {*used_resident = icp->lastUsedResidentScan() ? 1 : 0;}
+      if (per_launch) {*per_launch = icp->lastHypothesesPerLaunch();}
     });
 }
 

@@ -11,6 +11,8 @@
 // Registration.cpp:23 and never reset), so after the first converged frame its message can never
 // print again; here convergence is per call and readable through lastStats().  A HIP / argument
 // error throws std::runtime_error (the reference has no error path at all).
+// Added (no counterpart in the reference): alignHypotheses / alignBest register the cloud from a fan of guesses in one
+// call (vgicp_hip_batch.h) — for an integrator without a prior, after a stall, or on re-entry into an earlier map.
 #ifndef ESKF_LIO_SHIM_REGISTRATION_HPP_
 #define ESKF_LIO_SHIM_REGISTRATION_HPP_
 
@@ -21,6 +23,7 @@
 #include <vector>
 
 #include "LocalMap.hpp"
+#include "../vgicp_hip_batch.h"
 
 namespace ESKF_LIO
 {
@@ -148,7 +151,124 @@ public:
     return shim::poseFromData(pose);
   }
 
+  // One registration of a fan: what align() would have returned and reported for that guess.
+  struct Hypothesis
+  {
+    Isometry3d pose;
+    bool converged = false;
+    int iterations = 0;
+    uint64_t finalCorrespondences = 0;   // correspondences of the last round
+  };
+
+  // Registers `cloud` from every guess (at most VGICP_BATCH_MAX) in one call of vgicp_align_resident_batch: the resident
+  // scan when the cloud still is what CloudPreprocessor::process left on the device (the stamp and the hash of the host
+  // data say so, as in align()), else ONE upload of the cloud.  Each result is bit for bit align()'s for that guess.
+  std::vector<Hypothesis> alignHypotheses(
+    const PointCloud & cloud, const LocalMap & localMap, const std::vector<Isometry3d> & guesses)
+  {
+    std::vector<Hypothesis> out;
+    const size_t k = guesses.size();
+    if (k == 0) {return out;}
+    if (k > static_cast<size_t>(VGICP_BATCH_MAX)) {
+      throw std::runtime_error("ICP::alignHypotheses: more than VGICP_BATCH_MAX guesses");
+    }
+    vgicp_ctx * ctx = localMap.context();
+    vgicp_params params{};
+    params.max_iteration = maxIteration_;
+    params.chunk_iterations = chunkIterations_;
+    params.translation_sq_threshold = translationSquaredThreshold_;
+    params.cosine_threshold = cosineThreshold_;
+    bool resident = false;
+    {
+      shim::TraceScope ts(shim::Trace::AlignVerify);
+      resident = shim::residentStampOf(ctx, cloud) != nullptr;
+    }
+    shim::TraceScope tsCall(shim::Trace::AlignCall);
+    if (!resident) {
+      const size_t n = cloud.points_.size();
+      if (cloud.covariances_.size() != n) {
+        throw std::runtime_error(
+                "ICP::alignHypotheses: the cloud has " + std::to_string(n) + " points but " +
+                std::to_string(cloud.covariances_.size()) + " covariances (a cloud prepared with a deferred host "
+                "copy and changed since? call shim::materialize first)");
+      }
+      const double * pts = n ? cloud.points_.data()->data() : nullptr;
+      const double * covs = n ? cloud.covariances_.data()->data() : nullptr;
+      shim::check(ctx, vgicp_scan_upload(ctx, n, pts, covs), "vgicp_scan_upload");
+    }
+    lastUsedResidentScan_ = resident;
+    const size_t rounds = static_cast<size_t>(maxIteration_ > 0 ? maxIteration_ : 0);
+    std::vector<double> in(16 * k), poses(16 * k);
+    for (size_t h = 0; h < k; ++h) {
+      const double * g = shim::poseData(guesses[h]);
+      for (int e = 0; e < 16; ++e) {in[16 * h + e] = g[e];}
+    }
+    std::vector<int32_t> status(k, 0), iterations(k, 0), converged(k, 0);
+    fanCounts_.assign(k * rounds + 1, 0);
+    fanRounds_ = rounds;
+    vgicp_batch_stats stats{};
+    stats.status = status.data();
+    stats.iterations = iterations.data();
+    stats.converged = converged.data();
+    stats.corr_count = fanCounts_.data();
+    // (a hypothesis whose pose is not finite comes back in status[], as align() returns such a pose: no throw)
+    shim::check(ctx, vgicp_align_resident_batch(ctx, k, in.data(), &params, poses.data(), &stats),
+      "vgicp_align_resident_batch");
+    fanSeconds_ = stats.seconds;
+    fanDeviceSeconds_ = stats.device_seconds;
+    lastHypothesesPerLaunch_ = stats.hypotheses_per_launch;
+    out.resize(k);
+    for (size_t h = 0; h < k; ++h) {
+      out[h].pose = shim::poseFromData(poses.data() + 16 * h);
+      out[h].converged = converged[h] != 0;
+      out[h].iterations = iterations[h];
+      out[h].finalCorrespondences = iterations[h] > 0 ? fanCounts_[h * rounds + static_cast<size_t>(iterations[h]) - 1] : 0;
+    }
+    return out;
+  }
+
+  // Which hypothesis of a fan to keep: the one with the most correspondences in its last round; a converged one goes
+  // before one that is not, ties go to the lower index.  (A fan that straddles two basins is told apart by that count
+  // alone: the wrong basin matches far fewer points.)  hypotheses must not be empty.
+  static size_t selectBest(const std::vector<Hypothesis> & hypotheses)
+  {
+    size_t best = 0;
+    for (size_t h = 1; h < hypotheses.size(); ++h) {
+      const Hypothesis & a = hypotheses[h];
+      const Hypothesis & b = hypotheses[best];
+      if ((a.converged && !b.converged) ||
+        (a.converged == b.converged && a.finalCorrespondences > b.finalCorrespondences))
+      {
+        best = h;
+      }
+    }
+    return best;
+  }
+
+  // alignHypotheses, then the pose of selectBest's choice; lastStats() describes that hypothesis, as after align().
+  Isometry3d alignBest(
+    const PointCloud & cloud, const LocalMap & localMap, const std::vector<Isometry3d> & guesses)
+  {
+    if (guesses.empty()) {throw std::runtime_error("ICP::alignBest: no guess");}
+    const std::vector<Hypothesis> all = alignHypotheses(cloud, localMap, guesses);
+    const size_t best = selectBest(all);
+    lastBest_ = best;
+    lastStats_.iterations = all[best].iterations;
+    lastStats_.converged = all[best].converged;
+    lastStats_.seconds = fanSeconds_;
+    lastStats_.deviceSeconds = fanDeviceSeconds_;
+    lastStats_.correspondenceCounts.assign(
+      fanCounts_.begin() + static_cast<std::ptrdiff_t>(best * fanRounds_),
+      fanCounts_.begin() + static_cast<std::ptrdiff_t>(best * fanRounds_ + static_cast<size_t>(all[best].iterations)));
+    if (!lastStats_.converged) {
+      std::cout << "ICP not converged!\n";
+    }
+    return all[best].pose;
+  }
+
   const Stats & lastStats() const {return lastStats_;}
+  size_t lastBestHypothesis() const {return lastBest_;}                   // of the last alignBest()
+  int lastHypothesesPerLaunch() const {return lastHypothesesPerLaunch_;}  // of the last alignHypotheses(): 1 = one by one
   // whether the last align() found its cloud resident on the device (prepared there by CloudPreprocessor::process)
   bool lastUsedResidentScan() const {return lastUsedResidentScan_;}
 
@@ -161,6 +281,11 @@ private:
   int chunkIterations_ = 0;
   Stats lastStats_;
   bool lastUsedResidentScan_ = false;
+  std::vector<uint64_t> fanCounts_;   // the last fan's per-round counts, hypothesis-major
+  size_t fanRounds_ = 0;
+  double fanSeconds_ = 0.0, fanDeviceSeconds_ = 0.0;
+  size_t lastBest_ = 0;
+  int lastHypothesesPerLaunch_ = 0;
 };
 
 }  // namespace ESKF_LIO
