@@ -1,7 +1,8 @@
 // vgicp_capi_align.inl — part of vgicp_capi.hip.
-// ICP::align's launch schedule (reference src/Registration.cpp:15-28): the single persistent launch, the
-// launch-per-round loop (RCCL all-reduce between launches with a communicator), the dense record copy, give-up and
-// fallback handling.
+// ICP::align's launch schedule (reference src/Registration.cpp:15-28).  One place each for: the verdict on a persistent
+// launch (launch_committed), what a give-up costs (count_fallback), the exchange's rotation (advance_exchange,
+// settle_after_launch), the report (report_align); then the two paths of a resident scan, align_persistent and
+// align_on_loop (RCCL all-reduce between launches with a communicator), behind run_align, which asks plan_align.
 namespace {
 uint32_t iterate_grid(const vgicp_ctx* ctx) {
   const uint32_t block = (uint32_t)ctx->iter_block - 64;  // wave 0 of a workgroup solves, the rest own points
@@ -59,36 +60,31 @@ int fail_rccl(const vgicp_ctx* ctx, int code, const char* what) {
   return fail(ctx, VGICP_ERR_RCCL, std::string(what) + ": " + txt);
 }
 
-bool finite16(const double* m) {
-  for (int i = 0; i < 16; ++i)
-    if (!std::isfinite(m[i])) return false;
-  return true;
+// IterArgs of launch j of an align: state and rows ping-pong, launch 0 writes every point's memo.  The prologue reads
+// round j-1's rows: `summed` = the ONE row in d_sums (RCCL's all-reduce, the group's host sum), else the body_grid rows
+// launch j-1 wrote.
+IterArgs launch_args(const vgicp_ctx* ctx, const IterArgs& base, int j, uint32_t body_grid, bool summed) {
+  IterArgs a = base;
+  a.state_in = ctx->d_state + (j & 1);
+  a.state_out = ctx->d_state + ((j + 1) & 1);
+  a.rows = ctx->d_rows[j & 1];
+  a.memo_valid = j > 0 ? 1u : 0u;
+  a.prev = summed ? ctx->d_sums : ctx->d_rows[(j + 1) & 1];
+  a.prev_rows = j > 0 ? (summed ? 1u : body_grid) : 0u;
+  return a;
 }
 
 // Enqueue launch j of an align on the context's stream.  Launch j's prologue closes round j-1 (fold
 // its rows, solve, advance the pose) and its body accumulates round j; the launch after the last
 // round is prologue-only and runs as a single workgroup (`closing`).  With a communicator each body
 // launch is followed by this rank's row fold and the 256-byte all-reduce the next prologue reads.
-int enqueue_launch(vgicp_ctx* ctx, const IterArgs& base, int j, uint32_t body_grid, bool closing,
-                   bool use_comm) {
-  IterArgs a = base;
-  a.state_in = ctx->d_state + (j & 1);
-  a.state_out = ctx->d_state + ((j + 1) & 1);
-  a.rows = ctx->d_rows[j & 1];
-  a.memo_valid = j > 0 ? 1u : 0u;   // launch 0 of an align writes every point's memo
-  if (use_comm) {
-    a.prev = ctx->d_sums;
-    a.prev_rows = j > 0 ? 1u : 0u;
-  } else {
-    a.prev = ctx->d_rows[(j + 1) & 1];
-    a.prev_rows = j > 0 ? body_grid : 0u;
-  }
+int enqueue_launch(vgicp_ctx* ctx, const IterArgs& base, int j, uint32_t body_grid, bool closing, bool use_comm) {
+  const IterArgs a = launch_args(ctx, base, j, body_grid, use_comm);
   if (closing) VG_HIP(ctx, launch_close(ctx->stream, a, ctx->iter_block));
   else VG_HIP(ctx, launch_iterate(ctx->stream, a, body_grid, ctx->iter_block));
   if (use_comm && !closing) {
     VG_HIP(ctx, launch_fold_rows(ctx->stream, a.rows, body_grid, a.state_out, ctx->d_sums));
-    const int rc = ctx->rccl.AllReduce(ctx->d_sums, ctx->d_sums, kSlots, kNcclDouble, kNcclSum,
-                                       ctx->comm, ctx->stream);
+    const int rc = ctx->rccl.AllReduce(ctx->d_sums, ctx->d_sums, kSlots, kNcclDouble, kNcclSum, ctx->comm, ctx->stream);
     if (rc != 0) return fail_rccl(ctx, rc, "ncclAllReduce");
   }
   return VGICP_OK;
@@ -130,10 +126,10 @@ int reset_persistent_exchange(vgicp_ctx* ctx) {
 // 8.6 GB) gets a dense copy of its FULL records for the several-points-per-thread launch: tools/micro/gather_pieces
 // measured 6.7 ns per random 128-byte line and CU out of a 5-10 GB table against 5.4 ns out of 2.5 GB, and a cliff for
 // more lines in flight above 4 GB.  Smaller tables (C2: 512 MB) never use it.  VGICP_DENSE_SLOTS (read when the context is created) overrides the threshold, 0 = never.
-bool wants_dense(const vgicp_ctx* ctx, uint32_t n_upper) {
-  return ctx->table && ctx->dense_slots_threshold != 0 && ctx->slots >= ctx->dense_slots_threshold && ctx->voxels > 0 &&
-         (uint64_t)n_upper > (uint64_t)ctx->persist_grid * 448u;
+bool large_table(const vgicp_ctx* ctx) {
+  return ctx->table && ctx->dense_slots_threshold != 0 && ctx->slots >= ctx->dense_slots_threshold && ctx->voxels > 0;
 }
+bool wants_dense(const vgicp_ctx* ctx, uint32_t n_upper) { return large_table(ctx) && !one_point_per_thread(n_upper, ctx->persist_grid); }
 // Storage of the dense copy: sized when the TABLE is (re)allocated (vgicp_map_reset, a growing upsert / insertion) —
 // never inside an align.  The table keeps FULL + tombstones + incoming <= slots / 2, so slots / 2 records always suffice.
 int reserve_dense(vgicp_ctx* ctx) {
@@ -171,30 +167,108 @@ int ensure_dense(vgicp_ctx* ctx, bool* usable) {
   return VGICP_OK;
 }
 
+// ---- one place each: verdict, fallback account, rotation, report ------------------------------------------------------
+// Whether a persistent launch's result may be used: the echo of its sequence number is there, workgroup 0's loop ran to
+// its end, and NOBODY gave up — `abort_word` is the header's abort_seq for the single and the fused launch, the ONE shared
+// word of a team launch.  (Echo and commit WITH the abort word: workgroup 0 arrived late, found every row in place and
+// finished while another workgroup had already stopped waiting — its rows of the later rounds are missing.)
+bool launch_committed(const AlignState& st, uint32_t seq, uint32_t abort_word) {
+  return st.seq == seq && st.outcome == kOutcomeCommitted && abort_word != seq;
+}
+
+// What a give-up costs a context that runs alone: counted, the next aligns stay on the loop, one line (the first time, or
+// VGICP_VERBOSE).  Not for: a fused launch whose copy threads were slow, a sub-context of a group, the peer verdict.
+void count_fallback(vgicp_ctx* ctx, const char* what, const char* also) {
+  ++ctx->persistent_fallbacks;
+  ctx->persistent_cooldown = kPersistentCooldownAligns;
+  if (ctx->persistent_fallbacks == 1 || ctx->dev.verbose)
+    std::fprintf(stderr, "[vgicp] %s (fallback #%llu): using one launch per iteration for %sthe next %d aligns\n", what,
+                 (unsigned long long)ctx->persistent_fallbacks, also, kPersistentCooldownAligns);
+}
+
+// The exchange buffers rotate by round % 3 and the round number runs on from launch to launch: a committed launch's rounds.
+void advance_exchange(vgicp_ctx* ctx, const AlignState& st, bool multi) {
+  ctx->persist_round0 = (ctx->persist_round0 + (uint32_t)st.iteration) % 3u;
+  if (multi) ctx->mail_round0 += (uint32_t)st.iteration;
+}
+
+// The frame's ONE synchronisation has happened: what was deferred is known now (a pending scan's size and verdict, the
+// counts of the previous frame's map insertion).  When that fails the launch itself may well have completed: the
+// exchange's rotation is kept in step before the failure is reported.
+int settle_after_launch(vgicp_ctx* ctx, const AlignState& st, uint32_t seq, bool multi) {
+  const int rc_scan = settle_scan(ctx);
+  const int rc_ins = settle_insert(ctx);
+  if (rc_scan == VGICP_OK && rc_ins == VGICP_OK) return VGICP_OK;
+  if (launch_committed(st, seq, st.abort_seq)) advance_exchange(ctx, st, multi);
+  else (void)reset_persistent_exchange(ctx);
+  return rc_scan != VGICP_OK ? rc_scan : rc_ins;
+}
+
+// The per-round rows of a log as the caller gets them.
+void report_rows(int rounds, const double* log, uint64_t* corr_count, double* normal_eq) {
+  for (int it = 0; it < rounds; ++it) {
+    const double* row = log + (size_t)it * kSlots;
+    if (corr_count) corr_count[it] = (uint64_t)row[kCountSlot];
+    if (normal_eq) std::memcpy(normal_eq + (size_t)it * kNormalEq, row, kNormalEq * sizeof(double));
+  }
+}
+int report_pose(const vgicp_ctx* ctx, const AlignState& st, double* out_pose) {
+  state_to_pose(st.pose, out_pose);
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(out_pose[i])) return fail(ctx, VGICP_ERR_DEGENERATE, "solved pose is not finite (singular normal equations)");
+  return VGICP_OK;
+}
+// An align's final state and log as out_pose, vgicp_stats and the status.
+int report_align(const vgicp_ctx* ctx, const AlignState& st, const double* log, int world, int launches, double device_seconds,
+                 double t0, double* out_pose, vgicp_stats* stats) {
+  if (stats) {
+    stats->iterations = st.iteration;
+    stats->converged = st.converged;
+    stats->world_size = world;
+    stats->launches = launches;
+    stats->device_seconds = device_seconds;
+    report_rows(st.iteration, log, stats->corr_count, stats->normal_eq);
+    stats->seconds = now_seconds() - t0;
+  }
+  return report_pose(ctx, st, out_pose);
+}
+
+// developer aid: where the host time of an align goes (read once per process, by the first align that gets here)
+bool trace_align() { static const bool on = std::getenv("VGICP_TRACE_ALIGN") != nullptr; return on; }
+
+// ---- the persistent launch --------------------------------------------------------------------------------------------
+// What EVERY persistent launch is told (single, fused, teams): the scan, the table, the thresholds, a sequence number.
+void persistent_args_common(vgicp_ctx* ctx, const vgicp_params* params, PersistArgs* out) {
+  PersistArgs& a = *out;
+  std::memset(&a, 0, sizeof a);
+  a.scan = ctx->d_scan;
+  a.stride = ctx->stride;
+  a.n = ctx->n;                                        // a pending scan: the raw count, an upper bound
+  a.mask = (uint32_t)(ctx->slots - 1);
+  a.table = ctx->table;
+  a.voxel_size = ctx->voxel_size;
+  a.seq = ++ctx->persist_seq == 0 ? ++ctx->persist_seq : ctx->persist_seq;  // never 0
+  a.cosine_threshold = params->cosine_threshold;
+  a.translation_sq_threshold = params->translation_sq_threshold;
+  a.max_iteration = params->max_iteration;
+}
+
 // The arguments of the single persistent launch, and the header row of the pinned log reset for it: everything the
 // host does before the launch (never allocates; the dense copy is rebuilt only when the map changed).
 int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, PersistArgs* out) {
   static_assert(sizeof(AlignState) <= kSlots * sizeof(double), "the state must fit the log's header row");
   const uint32_t grid = ctx->persist_grid;  // always the same, all resident: the exchange buffers rely on it
-  const int max_it = params->max_iteration;
   PersistArgs& a = *out;
-  std::memset(&a, 0, sizeof a);
-  a.scan = ctx->d_scan;
-  a.stride = ctx->stride;
-  a.n = ctx->n;                                        // a pending scan: the raw count, an upper bound ...
-  a.n_dev = ctx->scan_pending ? ctx->d_counters : nullptr;  // ... and the kept count is read from the device
-  a.asym_dev = ctx->scan_sym_known ? ctx->d_ins_counters + 2 : nullptr;  // word 2 of that block: the symmetry verdict
+  persistent_args_common(ctx, params, &a);
+  a.n_dev = ctx->scan_pending ? ctx->d_counters : nullptr;  // a pending scan's kept count is read from the device
+  // word 2 of that block: the symmetry verdict (developer A/B no_sym: always read all twelve planes)
+  a.asym_dev = (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
   a.scan_seq = ctx->scan_seq;
-  if (ctx->dev.no_sym) a.asym_dev = nullptr;  // developer A/B: always read all twelve planes
-  a.mask = (uint32_t)(ctx->slots - 1);
-  a.table = ctx->table;
   if (wants_dense(ctx, ctx->n)) {
     bool usable = false;
-    const int rc_dense = ensure_dense(ctx, &usable);   // a no-op unless the map changed since the last align; never allocates
-    if (rc_dense != VGICP_OK) return rc_dense;
+    VG_RC(ensure_dense(ctx, &usable));   // a no-op unless the map changed since the last align; never allocates
     if (usable) a.dense = ctx->d_dense;
   }
-  a.voxel_size = ctx->voxel_size;
   a.rows = ctx->d_rows_persist;
   a.parts = ctx->d_parts_persist;
   a.round0 = ctx->persist_round0;
@@ -204,18 +278,14 @@ int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* par
   a.log = ctx->h_log_dev;
   // between GPUs the ranks' host threads reach the launch at slightly different times: a rank waits much longer
   // for a peer (~1 s) than for a workgroup of its own device (~50 ms) before it gives up
-  a.spin_limit = (ctx->peers_connected && ctx->peer_world > 1) ? ctx->persist_spin_limit * 20u : ctx->persist_spin_limit;
-  a.seq = ++ctx->persist_seq == 0 ? ++ctx->persist_seq : ctx->persist_seq;  // never 0
+  const bool multi = ctx->peers_connected && ctx->peer_world > 1;
+  a.spin_limit = multi ? ctx->persist_spin_limit * 20u : ctx->persist_spin_limit;
   pose_to_state(guess, a.pose0);
-  a.cosine_threshold = params->cosine_threshold;
-  a.translation_sq_threshold = params->translation_sq_threshold;
-  a.max_iteration = max_it;
   persistent_lds_plan(ctx->n, grid, &a.memo_points, &a.stash_points, &a.stash_bytes, ctx->persist_lds_budget);
   if (ctx->dev.no_stash) a.stash_points = a.stash_bytes = 0;
   if (ctx->dev.no_memo) a.memo_points = 0;
-  a.prefetch_margin = (a.memo_points == 0 && a.stash_points == 0 && ctx->n <= grid * 448u) ? ctx->prefetch_margin : 0.0;
+  a.prefetch_margin = (a.memo_points == 0 && a.stash_points == 0 && one_point_per_thread(ctx->n, grid)) ? ctx->prefetch_margin : 0.0;
   a.stamps = ctx->d_stamps;
-  const bool multi = ctx->peers_connected && ctx->peer_world > 1;
   a.world = multi ? (uint32_t)ctx->peer_world : 1u;
   a.rank = multi ? (uint32_t)ctx->peer_rank : 0u;
   a.mail = ctx->d_mail_table;
@@ -228,183 +298,155 @@ int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* par
   return fetch_insert_totals(ctx);   // normally carried by the preparation's copy
 }
 
-// The whole align in one launch (single GPU). Returns VGICP_OK and *ran = true when the kernel
-// completed; *ran = false when it gave up (the caller then uses launches).
-int run_align_persistent(vgicp_ctx* ctx, const double* guess, const vgicp_params* params,
-                         AlignState* result, bool* ran, float* device_ms) {
+// The whole align in one launch, one synchronisation.  *ran = true: the launch committed and is reported; false with
+// VGICP_OK: it gave up, is accounted for, and the caller runs the align on the loop.
+int align_persistent(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, const AlignPlan& plan, double t0,
+                     double* out_pose, vgicp_stats* stats, bool* ran) {
   *ran = false;
-  const uint32_t grid = ctx->persist_grid;
+  if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[2], ctx->stream)); ctx->ev_stage_set[2] = true; }
   PersistArgs a;
-  { const int rc_args = persistent_args(ctx, guess, params, &a); if (rc_args != VGICP_OK) return rc_args; }
+  VG_RC(persistent_args(ctx, guess, params, &a));
   const bool multi = a.world > 1;
-  AlignState* header = reinterpret_cast<AlignState*>(ctx->h_log - kSlots);
-  // one launch, one synchronisation
-  static const bool trace_align = std::getenv("VGICP_TRACE_ALIGN") != nullptr;   // developer aid: where the host time of an align goes
-  const double ta0 = trace_align ? now_seconds() : 0.0;
+  const bool trace = trace_align();
+  const double ta0 = trace ? now_seconds() : 0.0;
   VG_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
-  VG_HIP(ctx, launch_persistent(ctx->stream, a, grid));
+  VG_HIP(ctx, launch_persistent(ctx->stream, a, ctx->persist_grid));
   VG_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
   if (ctx->stage_events) VG_HIP(ctx, hipEventRecord(ctx->ev_stage[3], ctx->stream));
-  const double ta1 = trace_align ? now_seconds() : 0.0;
+  const double ta1 = trace ? now_seconds() : 0.0;
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const double ta2 = trace_align ? now_seconds() : 0.0;
-  VG_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_begin, ctx->ev_end));
-  if (trace_align && ta2 - ta0 > 2e-3)
+  const double ta2 = trace ? now_seconds() : 0.0;
+  float ms = 0.f;
+  VG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+  if (trace && ta2 - ta0 > 2e-3)
     std::fprintf(stderr, "[vgicp trace] align: enqueue %.3f ms, hipStreamSynchronize %.3f ms, the launch itself %.3f ms (events)\n",
-                 (ta1 - ta0) * 1e3, (ta2 - ta1) * 1e3, (double)*device_ms);
-  std::memcpy(result, header, sizeof(AlignState));
+                 (ta1 - ta0) * 1e3, (ta2 - ta1) * 1e3, (double)ms);
+  AlignState* result = &ctx->h_state[0];
+  std::memcpy(result, ctx->h_log - kSlots, sizeof(AlignState));
   ++ctx->persistent_launches;
-  {
-    // the frame's ONE synchronisation has happened: what was deferred is known now (a pending scan's size and
-    // verdict, the counts of the previous frame's map insertion)
-    const int rc_scan = settle_scan(ctx);
-    const int rc_ins = settle_insert(ctx);
-    if (rc_scan != VGICP_OK || rc_ins != VGICP_OK) {
-      // the launch itself may well have completed: keep the exchange buffers' rotation in step before reporting
-      if (result->seq == a.seq && result->outcome == kOutcomeCommitted && result->abort_seq != a.seq) {
-        ctx->persist_round0 = (ctx->persist_round0 + (uint32_t)result->iteration) % 3u;
-        if (multi) ctx->mail_round0 += (uint32_t)result->iteration;
-      } else {
-        (void)reset_persistent_exchange(ctx);
-      }
-      return rc_scan != VGICP_OK ? rc_scan : rc_ins;
-    }
+  VG_RC(settle_after_launch(ctx, *result, a.seq, multi));
+  if (launch_committed(*result, a.seq, result->abort_seq)) {
+    advance_exchange(ctx, *result, multi);
+    if (ctx->stage_events) ctx->ev_stage_set[3] = true;
+    *ran = true;
+    return report_align(ctx, *result, ctx->h_log, plan.peer_path ? ctx->peer_world : 1, 1, ms * 1e-3, t0, out_pose, stats);
   }
-  const bool committed = result->seq == a.seq && result->outcome == kOutcomeCommitted;
-  const bool someone_gave_up = result->abort_seq == a.seq;
-  if (!committed || someone_gave_up) {
-    // An in-kernel wait timed out (a workgroup was not resident: something else holds CUs of this device; or a
-    // peer GPU did not deliver).  `someone_gave_up` with `committed`: workgroup 0 arrived late, found every row in
-    // place and finished while another workgroup had already stopped waiting — its rows of the later rounds are
-    // missing, the result must not be used.  Put the exchange back into its initial state, use the per-launch
-    // loop for this align and the next few, then try the single launch again.
+  // An in-kernel wait timed out (a workgroup was not resident: something else holds CUs of this device; or a peer GPU
+  // did not deliver).  Put the exchange back into its initial state, use the per-launch loop for this align and the
+  // next few, then try the single launch again.
+  const bool wg0_committed = launch_committed(*result, a.seq, 0u);   // workgroup 0's own verdict, whoever else gave up
+  if (ctx->owner && multi) {
+    // a sub-context of an in-process multi-device context: every sub-context's launch has ended when its thread
+    // returns, so the group itself counts and cools down (note_fallback), re-arms all mailboxes and runs this align
+    // with the rows added on the host
     ++ctx->persistent_fallbacks;
-    if (ctx->owner && multi) {
-      if (ctx->dev.verbose)
-        std::fprintf(stderr, "[vgicp] rank %d of %d: persistent launch did not commit (echo %s, outcome %u, a workgroup gave up: %s, "
-                     "rounds reported %d, %u points)\n", ctx->peer_rank, ctx->peer_world, result->seq == a.seq ? "yes" : "no",
-                     result->outcome, someone_gave_up ? "yes" : "no", result->iteration, ctx->n);
-      // a sub-context of an in-process multi-device context: every sub-context's launch has ended when its thread
-      // returns, so the group itself re-arms all mailboxes and runs this align with the rows added on the host
-      const int rc_reset = reset_persistent_exchange(ctx);
-      return rc_reset != VGICP_OK ? rc_reset : vgicp_internal::kNeedGroupLoop;
-    }
-    ctx->persistent_cooldown = kPersistentCooldownAligns;
-    if (ctx->persistent_fallbacks == 1 || ctx->dev.verbose)
-      std::fprintf(stderr, "[vgicp] persistent align launch gave up waiting for a workgroup%s (fallback #%llu): using one "
-                   "launch per iteration for the next %d aligns\n", multi ? " or a peer GPU" : "",
-                   (unsigned long long)ctx->persistent_fallbacks, kPersistentCooldownAligns);
-    int rc = reset_persistent_exchange(ctx);
-    if (multi) {
-      // Between GPUs the outcome is collective (the verdict words at the end of the launch): every rank leaves the
-      // mailboxes for good in the SAME align and re-runs it through the host collective, so the all-reduces pair up.
-      // A peer's kernel may still be writing into a mailbox, so they are not touched again.
-      ctx->peer_enabled = false;
-      const bool agreed = result->outcome == kOutcomeAgreedAbort || (result->outcome == kOutcomeNone && !committed);
-      std::fprintf(stderr, "[vgicp] rank %d: the in-kernel exchange between GPUs gave up (%s); this communicator "
-                   "continues with one launch + one RCCL all-reduce per iteration\n", ctx->peer_rank,
-                   result->outcome == kOutcomeAgreedAbort ? "a peer reported it" :
-                   result->outcome == kOutcomeNoAgreement ? "a peer's verdict never arrived" :
-                   committed ? "a workgroup of this rank, after the verdict was sent" : "this rank timed out");
-      if (rc == VGICP_OK && !agreed)
-        return fail(ctx, VGICP_ERR_RCCL, "the ranks could not agree on the outcome of this align (a peer's verdict is missing "
-                    "or this rank's verdict was sent before one of its workgroups gave up): not re-running it alone");
-    }
-    return rc;
+    if (ctx->dev.verbose)
+      std::fprintf(stderr, "[vgicp] rank %d of %d: persistent launch did not commit (echo %s, outcome %u, a workgroup gave up: %s, "
+                   "rounds reported %d, %u points)\n", ctx->peer_rank, ctx->peer_world, result->seq == a.seq ? "yes" : "no",
+                   result->outcome, result->abort_seq == a.seq ? "yes" : "no", result->iteration, ctx->n);
+    const int rc_reset = reset_persistent_exchange(ctx);
+    return rc_reset != VGICP_OK ? rc_reset : vgicp_internal::kNeedGroupLoop;
   }
-  ctx->persist_round0 = (ctx->persist_round0 + (uint32_t)result->iteration) % 3u;
-  if (multi) ctx->mail_round0 += (uint32_t)result->iteration;
-  *ran = true;
-  return VGICP_OK;
+  count_fallback(ctx, multi ? "persistent align launch gave up waiting for a workgroup or a peer GPU"
+                            : "persistent align launch gave up waiting for a workgroup", "");
+  const int rc = reset_persistent_exchange(ctx);
+  if (multi) {
+    // Between GPUs the outcome is collective (the verdict words at the end of the launch): every rank leaves the
+    // mailboxes for good in the SAME align and re-runs it through the host collective, so the all-reduces pair up.
+    // A peer's kernel may still be writing into a mailbox, so they are not touched again.
+    ctx->peer_enabled = false;
+    const bool agreed = result->outcome == kOutcomeAgreedAbort || (result->outcome == kOutcomeNone && !wg0_committed);
+    std::fprintf(stderr, "[vgicp] rank %d: the in-kernel exchange between GPUs gave up (%s); this communicator "
+                 "continues with one launch + one RCCL all-reduce per iteration\n", ctx->peer_rank,
+                 result->outcome == kOutcomeAgreedAbort ? "a peer reported it" :
+                 result->outcome == kOutcomeNoAgreement ? "a peer's verdict never arrived" :
+                 wg0_committed ? "a workgroup of this rank, after the verdict was sent" : "this rank timed out");
+    if (rc == VGICP_OK && !agreed)
+      return fail(ctx, VGICP_ERR_RCCL, "the ranks could not agree on the outcome of this align (a peer's verdict is missing "
+                  "or this rank's verdict was sent before one of its workgroups gave up): not re-running it alone");
+  }
+  return rc;
 }
 
-// loop_only: the fused align's launch has just given up and been counted (fallback and cooldown are set): this align
-// goes to the launch-per-round loop without touching the cooldown.
-int run_align(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, double* out_pose,
-              vgicp_stats* stats, bool loop_only = false) {
-  const double t0 = now_seconds();
+// ---- the launch-per-round loop ----------------------------------------------------------------------------------------
+// What every align needs before anything is enqueued for it.
+int align_ready(vgicp_ctx* ctx, const vgicp_params* params) {
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
-  int rc = check_params(ctx, params);
-  if (rc != VGICP_OK) return rc;
-  const int max_it = params->max_iteration;
-  rc = ensure_log(ctx, max_it);
-  if (rc != VGICP_OK) return rc;
-  const bool profile = (params->flags & VGICP_FLAG_PROFILE) != 0;
-  int chunk = params->chunk_iterations > 0 ? params->chunk_iterations : kDefaultChunk;
-  if (profile) chunk = 1;
+  VG_RC(check_params(ctx, params));
+  return ensure_log(ctx, params->max_iteration);
+}
 
-  const bool peer_path = ctx->peers_connected && ctx->peer_enabled && ctx->peer_world > 1;
-  const bool alone = ctx->world_size == 1;  // also a communicator of one rank: nothing to exchange
-  const bool single_launch = !loop_only && !(ctx->persistent_cooldown > 0 && !peer_path) && ctx->persistent_enabled &&
-                             (alone || peer_path) && !profile && max_it > 0 &&
-                             (params->flags & VGICP_FLAG_NO_PERSISTENT) == 0;
-  if (ctx->owner && ctx->peer_world > 1 && !single_launch) return vgicp_internal::kNeedGroupLoop;  // the group's host-summed loop
-  if (!single_launch) {
-    // the launch-per-round loop sizes its grid from the scan: a pending scan has to be settled first
-    rc = settle(ctx);
-    if (rc != VGICP_OK) return rc;
-    if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
-  }
-  if (loop_only) {
-  } else if (ctx->persistent_cooldown > 0 && !peer_path) --ctx->persistent_cooldown;
-  else if (single_launch) {
-    bool ran = false;
-    float ms = 0.f;
-    AlignState* hf = &ctx->h_state[0];
-    if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[2], ctx->stream)); ctx->ev_stage_set[2] = true; }
-    rc = run_align_persistent(ctx, guess, params, &ctx->h_state[1], &ran, &ms);
-    if (rc != VGICP_OK) return rc;
-    if (ran) {
-      if (ctx->stage_events) ctx->ev_stage_set[3] = true;
-      *hf = ctx->h_state[1];
-      state_to_pose(hf->pose, out_pose);
-      if (stats) {
-        stats->iterations = hf->iteration;
-        stats->converged = hf->converged;
-        stats->world_size = peer_path ? ctx->peer_world : 1;
-        stats->launches = 1;
-        stats->device_seconds = ms * 1e-3;
-        for (int it = 0; it < hf->iteration; ++it) {
-          const double* row = ctx->h_log + (size_t)it * kSlots;
-          if (stats->corr_count) stats->corr_count[it] = (uint64_t)row[kCountSlot];
-          if (stats->normal_eq) std::memcpy(stats->normal_eq + (size_t)it * kNormalEq, row, kNormalEq * sizeof(double));
-        }
-        stats->seconds = now_seconds() - t0;
-      }
-      if (!finite16(out_pose)) return fail(ctx, VGICP_ERR_DEGENERATE, "solved pose is not finite (singular normal equations)");
-      return VGICP_OK;
-    }
-  }
-
-  if (ctx->peers_connected && ctx->peer_world > 1 && ctx->comm == nullptr)
-    return fail(ctx, VGICP_ERR_RCCL, "the in-kernel exchange between GPUs is not available for this align (gave up earlier, "
-                "profiling or VGICP_FLAG_NO_PERSISTENT) and there is no RCCL communicator to fall back to");
+// The loop's start on one device: the initial AlignState, uploaded.
+int upload_initial_state(vgicp_ctx* ctx, const double* guess, const vgicp_params* params) {
   AlignState* h0 = &ctx->h_state[0];
   std::memset(h0, 0, sizeof(AlignState));
   pose_to_state(guess, h0->pose);
   h0->cosine_threshold = params->cosine_threshold;
   h0->translation_sq_threshold = params->translation_sq_threshold;
-  h0->max_iteration = max_it;
-  h0->done = (max_it == 0) ? 1 : 0;
+  h0->max_iteration = params->max_iteration;
+  h0->done = (params->max_iteration == 0) ? 1 : 0;
   VG_HIP(ctx, hipMemcpyAsync(ctx->d_state, h0, sizeof(AlignState), hipMemcpyHostToDevice, ctx->stream));
+  return VGICP_OK;
+}
 
+// max_it bodies + the closing prologue; with VGICP_FLAG_PROFILE an event pair per launch (made once, kept).
+int loop_launches(vgicp_ctx* ctx, const vgicp_params* params, int* total_launches) {
+  *total_launches = params->max_iteration > 0 ? params->max_iteration + 1 : 0;
+  if ((params->flags & VGICP_FLAG_PROFILE) == 0) return VGICP_OK;
+  for (size_t k = ctx->ev_prof.size(); k < 2 * (size_t)*total_launches; ++k) {
+    ctx->ev_prof.push_back(nullptr);
+    VG_HIP(ctx, hipEventCreate(&ctx->ev_prof.back()));
+  }
+  return VGICP_OK;
+}
+
+// The loop's end on the device that reports (ev_begin was recorded in front of launch 0): final state and log come
+// back, one synchronisation, the report.
+int report_loop(vgicp_ctx* ctx, const vgicp_params* params, int launched, int world, double t0, double* out_pose,
+                vgicp_stats* stats) {
+  const int max_it = params->max_iteration;
+  VG_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
+  AlignState* hf = &ctx->h_state[0];
+  VG_HIP(ctx, hipMemcpyAsync(hf, ctx->d_state + (launched & 1), sizeof(AlignState), hipMemcpyDeviceToHost, ctx->stream));
+  const bool want_log = stats && (stats->corr_count || stats->normal_eq);
+  if (want_log && max_it > 0)
+    VG_HIP(ctx, hipMemcpyAsync(ctx->h_log, ctx->d_log, (size_t)max_it * kSlots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  if (stats) VG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+  if (stats && stats->kernel_ms && (params->flags & VGICP_FLAG_PROFILE) != 0) {
+    // one entry per body launch (the closing single-workgroup launch is not a round)
+    for (int it = 0; it < std::min(launched, max_it); ++it) {
+      float k = 0.f;
+      VG_HIP(ctx, hipEventElapsedTime(&k, ctx->ev_prof[2 * it], ctx->ev_prof[2 * it + 1]));
+      stats->kernel_ms[it] = k;
+    }
+  }
+  return report_align(ctx, *hf, ctx->h_log, world, launched, ms * 1e-3, t0, out_pose, stats);
+}
+
+// One launch per round for the resident scan, which must be settled (RCCL, VGICP_FLAG_NO_PERSISTENT / _PROFILE, a
+// cool-down, a launch that has just given up): touches neither the cool-down nor the counters.
+int align_on_loop(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, double* out_pose, vgicp_stats* stats,
+                  double t0) {
+  VG_RC(align_ready(ctx, params));
+  const int max_it = params->max_iteration;
+  const bool profile = (params->flags & VGICP_FLAG_PROFILE) != 0;
+  const int chunk = profile ? 1 : params->chunk_iterations > 0 ? params->chunk_iterations : kDefaultChunk;
+  if (ctx->peers_connected && ctx->peer_world > 1 && ctx->comm == nullptr)
+    return fail(ctx, VGICP_ERR_RCCL, "the in-kernel exchange between GPUs is not available for this align (gave up earlier, "
+                "profiling or VGICP_FLAG_NO_PERSISTENT) and there is no RCCL communicator to fall back to");
+  VG_RC(upload_initial_state(ctx, guess, params));
   // a table far beyond the caches' reach: the loop reads remembered records from the dense copy too (rebuilt here
   // when the map changed since; storage was made with the table, nothing is allocated)
-  if (ctx->table && ctx->dense_slots_threshold != 0 && ctx->slots >= ctx->dense_slots_threshold && ctx->voxels > 0) {
-    bool usable = false;
-    rc = ensure_dense(ctx, &usable);
-    if (rc != VGICP_OK) return rc;
-  }
+  bool usable = false;
+  if (large_table(ctx)) VG_RC(ensure_dense(ctx, &usable));
   const IterArgs base = base_args(ctx);
   const uint32_t grid = iterate_grid(ctx);
   const bool use_comm = ctx->comm != nullptr;
-  const int total_launches = max_it > 0 ? max_it + 1 : 0;  // max_it bodies + the closing prologue
-  if (profile && (int)ctx->ev_prof.size() < 2 * total_launches) {
-    const size_t old = ctx->ev_prof.size();
-    ctx->ev_prof.resize(2 * (size_t)total_launches, nullptr);
-    for (size_t k = old; k < ctx->ev_prof.size(); ++k) VG_HIP(ctx, hipEventCreate(&ctx->ev_prof[k]));
-  }
+  int total_launches = 0;
+  VG_RC(loop_launches(ctx, params, &total_launches));
 
   VG_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
   int launched = 0;
@@ -419,14 +461,12 @@ int run_align(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, d
       for (int k = 0; k < todo; ++k) {
         const int j = launched + k;
         if (profile) VG_HIP(ctx, hipEventRecord(ctx->ev_prof[2 * j], ctx->stream));
-        rc = enqueue_launch(ctx, base, j, grid, /*closing=*/j == max_it, use_comm);
-        if (rc != VGICP_OK) return rc;
+        VG_RC(enqueue_launch(ctx, base, j, grid, /*closing=*/j == max_it, use_comm));
         if (profile) VG_HIP(ctx, hipEventRecord(ctx->ev_prof[2 * j + 1], ctx->stream));
       }
       launched += todo;
       const int slot = chunks_enqueued % kMaxChunksInFlight;
-      VG_HIP(ctx, hipMemcpyAsync(&ctx->h_state[1 + slot], ctx->d_state + (launched & 1),
-                                 sizeof(AlignState), hipMemcpyDeviceToHost, ctx->stream));
+      VG_HIP(ctx, hipMemcpyAsync(&ctx->h_state[1 + slot], ctx->d_state + (launched & 1), sizeof(AlignState), hipMemcpyDeviceToHost, ctx->stream));
       VG_HIP(ctx, hipEventRecord(ctx->ev_chunk[slot], ctx->stream));
       ++chunks_enqueued;
     }
@@ -436,42 +476,27 @@ int run_align(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, d
     if (ctx->h_state[1 + slot].done || (launched >= total_launches && chunks_checked == chunks_enqueued))
       finished = true;
   }
-  VG_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
-  AlignState* hf = &ctx->h_state[0];
-  VG_HIP(ctx, hipMemcpyAsync(hf, ctx->d_state + (launched & 1), sizeof(AlignState),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  const bool want_log = stats && (stats->corr_count || stats->normal_eq);
-  if (want_log && max_it > 0)
-    VG_HIP(ctx, hipMemcpyAsync(ctx->h_log, ctx->d_log, (size_t)max_it * kSlots * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream));
-  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return report_loop(ctx, params, launched, ctx->world_size, t0, out_pose, stats);
+}
 
-  state_to_pose(hf->pose, out_pose);
-  if (stats) {
-    stats->iterations = hf->iteration;
-    stats->converged = hf->converged;
-    stats->world_size = ctx->world_size;
-    stats->launches = launched;
-    float ms = 0.f;
-    VG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
-    stats->device_seconds = ms * 1e-3;
-    for (int it = 0; it < hf->iteration; ++it) {
-      const double* row = ctx->h_log + (size_t)it * kSlots;
-      if (stats->corr_count) stats->corr_count[it] = (uint64_t)row[kCountSlot];
-      if (stats->normal_eq) std::memcpy(stats->normal_eq + (size_t)it * kNormalEq, row, kNormalEq * sizeof(double));
-    }
-    if (profile && stats->kernel_ms) {
-      // one entry per body launch (the closing single-workgroup launch is not a round)
-      for (int it = 0; it < std::min(launched, max_it); ++it) {
-        float k = 0.f;
-        VG_HIP(ctx, hipEventElapsedTime(&k, ctx->ev_prof[2 * it], ctx->ev_prof[2 * it + 1]));
-        stats->kernel_ms[it] = k;
-      }
-    }
-    stats->seconds = now_seconds() - t0;
+// vgicp_align_resident on one context: plan, then the persistent launch or the loop (or both, when the launch gives up).
+int run_align(vgicp_ctx* ctx, const double* guess, const vgicp_params* params, double* out_pose, vgicp_stats* stats) {
+  const double t0 = now_seconds();
+  VG_RC(align_ready(ctx, params));
+  const AlignPlan plan = plan_align(align_facts(ctx, params, AlignCall::Resident, ctx->n));
+  if (plan.path == AlignPath::GroupLoop) return vgicp_internal::kNeedGroupLoop;  // the group's host-summed loop
+  if (plan.path == AlignPath::Loop) {
+    // the launch-per-round loop sizes its grid from the scan: a pending scan has to be settled first
+    VG_RC(settle(ctx));
+    if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
   }
-  if (!finite16(out_pose)) return fail(ctx, VGICP_ERR_DEGENERATE, "solved pose is not finite (singular normal equations)");
-  return VGICP_OK;
+  ctx->persistent_cooldown -= plan.cooldown_drop;
+  if (plan.path == AlignPath::Persistent) {
+    bool ran = false;
+    const int rc = align_persistent(ctx, guess, params, plan, t0, out_pose, stats, &ran);
+    if (rc != VGICP_OK || ran) return rc;
+  }
+  return align_on_loop(ctx, guess, params, out_pose, stats, t0);
 }
 
 }  // namespace

@@ -1,22 +1,8 @@
 // vgicp_capi_batch.inl — part of vgicp_capi.hip.
-// vgicp_align_resident_batch / vgicp_align_batch_width (include/vgicp_hip_batch.h): argument checks, settling, the team
-// plan, the launches with their one synchronisation, the acceptance rule and the sequential paths through run_align.
+// vgicp_align_resident_batch / vgicp_align_batch_width (include/vgicp_hip_batch.h): argument checks, settling, the
+// launches with their one synchronisation, and the k single aligns in a row.  Whether a batch runs as teams, and how
+// wide: plan_align / team_width (vgicp_align_plan.h).
 namespace {
-// How many hypotheses one team launch takes for the resident (settled) scan; 1 = a batch runs its aligns one by one.
-// T = ceil(n / 448) workgroups per team, as many teams as fit the grid vgicp_create verified to be resident.
-uint32_t batch_width(const vgicp_ctx* ctx, uint32_t* team_wgs) {
-  *team_wgs = 0;
-  const bool one_device = ctx->world_size == 1 && ctx->owner == nullptr && ctx->comm == nullptr && !ctx->peers_connected;
-  if (!one_device || !ctx->persistent_enabled || ctx->d_stamps != nullptr || ctx->n == 0 ||
-      (uint64_t)ctx->n > (uint64_t)ctx->persist_grid * 448u)
-    return 1;
-  const uint32_t T = (ctx->n + 447u) / 448u;
-  const uint32_t width = std::min<uint32_t>((uint32_t)kTeamsMax, ctx->persist_grid / T);
-  if (width < 2) return 1;
-  *team_wgs = T;
-  return width;
-}
-
 AlignState* batch_state(const vgicp_ctx* ctx, size_t h) {
   return reinterpret_cast<AlignState*>(ctx->h_batch + h * (size_t)kBatchSlotRows * kSlots);
 }
@@ -25,12 +11,8 @@ void batch_report(size_t h, int max_it, const AlignState* st, const double* log,
   if (!stats) return;
   if (stats->iterations) stats->iterations[h] = st->iteration;
   if (stats->converged) stats->converged[h] = st->converged;
-  for (int it = 0; it < st->iteration; ++it) {
-    const double* row = log + (size_t)it * kSlots;
-    if (stats->corr_count) stats->corr_count[h * (size_t)max_it + it] = (uint64_t)row[kCountSlot];
-    if (stats->normal_eq)
-      std::memcpy(stats->normal_eq + (h * (size_t)max_it + it) * kNormalEq, row, kNormalEq * sizeof(double));
-  }
+  report_rows(st->iteration, log, stats->corr_count ? stats->corr_count + h * (size_t)max_it : nullptr,
+              stats->normal_eq ? stats->normal_eq + h * (size_t)max_it * kNormalEq : nullptr);
 }
 
 // The k hypotheses as teams of persistent launches: ceil(k / width) launches back to back, ONE synchronisation.
@@ -43,20 +25,10 @@ int run_batch_teams(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp
   const size_t slot_words = (size_t)kBatchSlotRows * kSlots;
   uint32_t* abort_host = reinterpret_cast<uint32_t*>(ctx->h_batch + (size_t)VGICP_BATCH_MAX * slot_words);
   PersistArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.scan = ctx->d_scan;
-  a.stride = ctx->stride;
-  a.n = ctx->n;   // settled: the kept count
-  a.mask = (uint32_t)(ctx->slots - 1);
-  a.table = ctx->table;
-  a.voxel_size = ctx->voxel_size;
+  persistent_args_common(ctx, params, &a);   // n is settled: the kept count; one sequence number for the whole call
   a.rows = ctx->d_batch_exchange;
   a.parts = ctx->d_batch_exchange + team_rows_words();
   a.spin_limit = ctx->persist_spin_limit;
-  a.seq = ++ctx->persist_seq == 0 ? ++ctx->persist_seq : ctx->persist_seq;  // never 0; one number for the whole call
-  a.cosine_threshold = params->cosine_threshold;
-  a.translation_sq_threshold = params->translation_sq_threshold;
-  a.max_iteration = max_it;
   a.round0 = 0;   // every launch starts from unset words
   a.world = 1;
   a.prefetch_margin = ctx->prefetch_margin;   // one point per thread, no memo, no stash: as the single launch has it
@@ -90,29 +62,18 @@ int run_batch_teams(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp
   float ms = 0.f;
   VG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
   ctx->persistent_launches += (uint64_t)launches;
-  // accepted only if every team's echo is there and nobody gave up (run_align_persistent's rule, k-wide)
-  bool committed = *abort_host != a.seq;
-  for (size_t h = 0; h < k && committed; ++h) {
-    const AlignState* st = batch_state(ctx, h);
-    committed = st->seq == a.seq && st->outcome == kOutcomeCommitted;
-  }
+  // accepted only if every team's echo is there and nobody gave up: the ONE abort word speaks for every hypothesis
+  bool committed = true;
+  for (size_t h = 0; h < k && committed; ++h) committed = launch_committed(*batch_state(ctx, h), a.seq, *abort_host);
   if (!committed) {
-    ++ctx->persistent_fallbacks;
-    ctx->persistent_cooldown = kPersistentCooldownAligns;
-    if (ctx->persistent_fallbacks == 1 || ctx->dev.verbose)
-      std::fprintf(stderr, "[vgicp] batched align launch gave up waiting for a workgroup (fallback #%llu): using one launch "
-                   "per iteration for this batch and the next %d aligns\n", (unsigned long long)ctx->persistent_fallbacks,
-                   kPersistentCooldownAligns);
+    count_fallback(ctx, "batched align launch gave up waiting for a workgroup", "this batch and ");
     return VGICP_OK;
   }
   *ran = true;
   for (size_t h = 0; h < k; ++h) {
     const AlignState* st = batch_state(ctx, h);
-    double* pose = out_poses + 16 * h;
-    state_to_pose(st->pose, pose);
     batch_report(h, max_it, st, ctx->h_batch + h * slot_words + kSlots, stats);
-    int status = VGICP_OK;
-    if (!finite16(pose)) status = fail(ctx, VGICP_ERR_DEGENERATE, "solved pose is not finite (singular normal equations)");
+    const int status = report_pose(ctx, *st, out_poses + 16 * h);
     if (stats && stats->status) stats->status[h] = status;
     if (status != VGICP_OK && *first_bad == VGICP_OK) *first_bad = status;
   }
@@ -126,7 +87,8 @@ int run_batch_teams(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp
 }  // namespace
 
 // The k aligns one after another through the single call's own paths (also the multi-device forward); loop_only: on the
-// launch-per-round loop without touching the cool-down.  Any status but VGICP_OK / VGICP_ERR_DEGENERATE ends the batch.
+// launch-per-round loop (align_on_loop), which touches neither cool-down nor counters.  Any status but VGICP_OK /
+// VGICP_ERR_DEGENERATE ends the batch.
 int vgicp_internal::align_batch_sequential(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp_params* params,
                                            double* out_poses, vgicp_batch_stats* stats, bool loop_only, int* first_bad) {
   const size_t max_it = (size_t)std::max(params->max_iteration, 0);
@@ -137,7 +99,7 @@ int vgicp_internal::align_batch_sequential(vgicp_ctx* ctx, size_t k, const doubl
     std::memset(&st, 0, sizeof st);
     if (stats && stats->corr_count) st.corr_count = stats->corr_count + h * max_it;
     if (stats && stats->normal_eq) st.normal_eq = stats->normal_eq + h * max_it * kNormalEq;
-    const int rc = loop_only ? run_align(ctx, guesses + 16 * h, params, out_poses + 16 * h, &st, /*loop_only=*/true)
+    const int rc = loop_only ? align_on_loop(ctx, guesses + 16 * h, params, out_poses + 16 * h, &st, now_seconds())
                              : vgicp_align_resident(ctx, guesses + 16 * h, params, out_poses + 16 * h, &st);
     if (rc != VGICP_OK && rc != VGICP_ERR_DEGENERATE) return rc;
     if (stats && stats->status) stats->status[h] = rc;
@@ -179,20 +141,15 @@ int vgicp_align_resident_batch(vgicp_ctx* ctx, size_t k, const double* guesses, 
   rc = settle(ctx);
   if (rc != VGICP_OK) return rc;
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
-  const int max_it = params->max_iteration;
-  uint32_t team_wgs = 0;
-  const uint32_t width = batch_width(ctx, &team_wgs);
-  const bool wide = k >= 2 && width >= 2 && max_it > 0 && max_it < kBatchSlotRows &&
-                    (params->flags & (VGICP_FLAG_PROFILE | VGICP_FLAG_NO_PERSISTENT)) == 0;
-  if (!wide) {
+  const AlignPlan plan = plan_align(align_facts(ctx, params, AlignCall::Batch, ctx->n, k));
+  bool ran = false;
+  if (plan.width < 2) {
     rc = vgicp_internal::align_batch_sequential(ctx, k, guesses, params, out_poses, stats, /*loop_only=*/false, &first_bad);
-  } else if (ctx->persistent_cooldown > 0) {
-    // inside the cool-down no launch is attempted and nothing is counted: k aligns on the loop, k aligns of cool-down
-    ctx->persistent_cooldown = std::max(0, ctx->persistent_cooldown - (int)k);
-    rc = vgicp_internal::align_batch_sequential(ctx, k, guesses, params, out_poses, stats, /*loop_only=*/true, &first_bad);
   } else {
-    bool ran = false;
-    rc = run_batch_teams(ctx, k, guesses, params, width, team_wgs, out_poses, stats, &first_bad, &ran);
+    // inside the cool-down no launch is attempted and nothing is counted: k aligns on the loop, k aligns of cool-down
+    ctx->persistent_cooldown -= plan.cooldown_drop;
+    if (plan.path == AlignPath::Teams)
+      rc = run_batch_teams(ctx, k, guesses, params, plan.width, plan.team_wgs, out_poses, stats, &first_bad, &ran);
     if (rc == VGICP_OK && !ran)
       rc = vgicp_internal::align_batch_sequential(ctx, k, guesses, params, out_poses, stats, /*loop_only=*/true, &first_bad);
   }
@@ -209,7 +166,7 @@ int vgicp_align_batch_width(vgicp_ctx* ctx, size_t* hypotheses_per_launch) {
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
   uint32_t team_wgs = 0;
-  *hypotheses_per_launch = batch_width(ctx, &team_wgs);
+  *hypotheses_per_launch = team_width(align_facts(ctx, nullptr, AlignCall::Batch, ctx->n), &team_wgs);
   return VGICP_OK;
 }
 }  // extern "C"

@@ -88,41 +88,27 @@ double tree_sum_host(const double* v, int count) {
 }
 }  // namespace
 
+// The group's form of align_on_loop: the same launches on every device, `prev` is the row the HOST summed over the ranks
+// between the launches (one synchronisation per round); the lead device's events and log make the report.
 int align_host_summed(vgicp_ctx* const* subs, int n, const double guess[16], const vgicp_params* params,
                       double out_pose[16], vgicp_stats* stats) {
   const double t0 = now_seconds();
   vgicp_ctx* lead = subs[0];
-  int rc = check_params(lead, params);
-  if (rc != VGICP_OK) return rc;
+  VG_RC(check_params(lead, params));
   const int max_it = params->max_iteration;
   const bool profile = (params->flags & VGICP_FLAG_PROFILE) != 0;
   std::vector<uint32_t> grid((size_t)n);
   for (int r = 0; r < n; ++r) {
     vgicp_ctx* ctx = subs[r];
     VG_HIP(ctx, hipSetDevice(ctx->device));
-    rc = settle(ctx);
-    if (rc != VGICP_OK) return rc;
-    if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
-    if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
-    rc = ensure_log(ctx, max_it);
-    if (rc != VGICP_OK) return rc;
-    AlignState* h0 = &ctx->h_state[0];
-    std::memset(h0, 0, sizeof(AlignState));
-    pose_to_state(guess, h0->pose);
-    h0->cosine_threshold = params->cosine_threshold;
-    h0->translation_sq_threshold = params->translation_sq_threshold;
-    h0->max_iteration = max_it;
-    h0->done = (max_it == 0) ? 1 : 0;
-    VG_HIP(ctx, hipMemcpyAsync(ctx->d_state, h0, sizeof(AlignState), hipMemcpyHostToDevice, ctx->stream));
+    VG_RC(settle(ctx));
+    VG_RC(align_ready(ctx, params));
+    VG_RC(upload_initial_state(ctx, guess, params));
     grid[(size_t)r] = iterate_grid(ctx);
   }
-  const int total_launches = max_it > 0 ? max_it + 1 : 0;  // max_it bodies + the closing prologue
   VG_HIP(lead, hipSetDevice(lead->device));
-  if (profile && (int)lead->ev_prof.size() < 2 * total_launches) {
-    const size_t old = lead->ev_prof.size();
-    lead->ev_prof.resize(2 * (size_t)total_launches, nullptr);
-    for (size_t k = old; k < lead->ev_prof.size(); ++k) VG_HIP(lead, hipEventCreate(&lead->ev_prof[k]));
-  }
+  int total_launches = 0;
+  VG_RC(loop_launches(lead, params, &total_launches));
   VG_HIP(lead, hipEventRecord(lead->ev_begin, lead->stream));
   int launched = 0;
   for (int j = 0; j < total_launches; ++j) {
@@ -130,13 +116,7 @@ int align_host_summed(vgicp_ctx* const* subs, int n, const double guess[16], con
     for (int r = 0; r < n; ++r) {
       vgicp_ctx* ctx = subs[r];
       VG_HIP(ctx, hipSetDevice(ctx->device));
-      IterArgs a = base_args(ctx);
-      a.state_in = ctx->d_state + (j & 1);
-      a.state_out = ctx->d_state + ((j + 1) & 1);
-      a.rows = ctx->d_rows[j & 1];
-      a.prev = ctx->d_sums;           // the row the host summed over the ranks
-      a.prev_rows = j > 0 ? 1u : 0u;
-      a.memo_valid = j > 0 ? 1u : 0u;
+      const IterArgs a = launch_args(ctx, base_args(ctx), j, grid[(size_t)r], /*summed=*/true);
       if (profile && r == 0) VG_HIP(ctx, hipEventRecord(ctx->ev_prof[2 * j], ctx->stream));
       if (closing) VG_HIP(ctx, launch_close(ctx->stream, a, ctx->iter_block));
       else {
@@ -169,38 +149,7 @@ int align_host_summed(vgicp_ctx* const* subs, int n, const double guess[16], con
     }
   }
   VG_HIP(lead, hipSetDevice(lead->device));
-  VG_HIP(lead, hipEventRecord(lead->ev_end, lead->stream));
-  AlignState* hf = &lead->h_state[0];
-  VG_HIP(lead, hipMemcpyAsync(hf, lead->d_state + (launched & 1), sizeof(AlignState), hipMemcpyDeviceToHost, lead->stream));
-  const bool want_log = stats && (stats->corr_count || stats->normal_eq);
-  if (want_log && max_it > 0)
-    VG_HIP(lead, hipMemcpyAsync(lead->h_log, lead->d_log, (size_t)max_it * kSlots * sizeof(double), hipMemcpyDeviceToHost, lead->stream));
-  VG_HIP(lead, hipStreamSynchronize(lead->stream));
-  state_to_pose(hf->pose, out_pose);
-  if (stats) {
-    stats->iterations = hf->iteration;
-    stats->converged = hf->converged;
-    stats->world_size = n;
-    stats->launches = launched;
-    float ms = 0.f;
-    VG_HIP(lead, hipEventElapsedTime(&ms, lead->ev_begin, lead->ev_end));
-    stats->device_seconds = ms * 1e-3;
-    for (int it = 0; it < hf->iteration; ++it) {
-      const double* row = lead->h_log + (size_t)it * kSlots;
-      if (stats->corr_count) stats->corr_count[it] = (uint64_t)row[kCountSlot];
-      if (stats->normal_eq) std::memcpy(stats->normal_eq + (size_t)it * kNormalEq, row, kNormalEq * sizeof(double));
-    }
-    if (profile && stats->kernel_ms) {
-      for (int it = 0; it < std::min(launched, max_it); ++it) {
-        float k = 0.f;
-        VG_HIP(lead, hipEventElapsedTime(&k, lead->ev_prof[2 * it], lead->ev_prof[2 * it + 1]));
-        stats->kernel_ms[it] = k;
-      }
-    }
-    stats->seconds = now_seconds() - t0;
-  }
-  if (!finite16(out_pose)) return fail(lead, VGICP_ERR_DEGENERATE, "solved pose is not finite (singular normal equations)");
-  return VGICP_OK;
+  return report_loop(lead, params, launched, n, t0, out_pose, stats);
 }
 
 int adopt_device_scan(vgicp_ctx* ctx, int src_device, const double* d_points, const double* d_covs, size_t n,

@@ -4,29 +4,17 @@ namespace {
 // ---- the fused align: vgicp_align of a staged scan in ONE launch ----------------------------------------------------
 // The persistent launch is enqueued before the copy threads start; each workgroup waits for the staged unit(s) that hold
 // its 448 points and reads them over PCIe itself (fused_round0_load), so neither pack_arena_kernel, nor the kernel
-// boundary, nor the re-read of the planes stand between the last unit and round 0.  Taken only where the single launch
-// would run the one-point-per-thread body on one device; everything else keeps the pack launch in front.
-bool fused_align_fits(const vgicp_ctx* ctx, size_t n, const double* points, const double* covs, const vgicp_params* params) {
-  return params && params->max_iteration > 0 && (params->flags & (VGICP_FLAG_PROFILE | VGICP_FLAG_NO_PERSISTENT)) == 0 &&
-         !ctx->dev.no_fused && ctx->d_stamps == nullptr && !ctx->stage_events && ctx->owner == nullptr &&
-         ctx->world_size == 1 && !(ctx->peers_connected && ctx->peer_world > 1) && ctx->persistent_enabled &&
-         ctx->persistent_cooldown == 0 && n > 0 && n <= (size_t)ctx->persist_grid * 448u && points && covs &&
-         upload_is_staged(ctx, n, points, covs);
-}
-
+// boundary, nor the re-read of the planes stand between the last unit and round 0.  Where it is taken: plan_align
+// (AlignPath::Fused); everything else keeps the pack launch in front.
 int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* covs, const double* guess,
                 const vgicp_params* params, double* out_pose, vgicp_stats* stats) {
   const double t0 = now_seconds();
-  int rc = check_params(ctx, params);
-  if (rc != VGICP_OK) return rc;
-  rc = ensure_log(ctx, params->max_iteration);
-  if (rc != VGICP_OK) return rc;
+  VG_RC(check_params(ctx, params));
+  VG_RC(ensure_log(ctx, params->max_iteration));
   UploadJob up;
-  rc = scan_upload_stage(ctx, n, points, covs, &up);
-  if (rc != VGICP_OK) return rc;
+  VG_RC(scan_upload_stage(ctx, n, points, covs, &up));
   PersistArgs a;
-  rc = persistent_args(ctx, guess, params, &a);
-  if (rc != VGICP_OK) return rc;
+  VG_RC(persistent_args(ctx, guess, params, &a));
   FusedUpload f;
   std::memset(&f, 0, sizeof f);
   CopyCrew* crew = ctx->crew;
@@ -41,78 +29,50 @@ int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   f.aos_cov = ctx->d_scan_aos + 3 * ctx->scan_capacity;
   f.asym = ctx->d_ins_counters + 2;
   f.unit_clock = ctx->d_unit_clock;
-  static const bool trace_align = std::getenv("VGICP_TRACE_ALIGN") != nullptr;   // developer aid: where the host time goes
+  const bool trace = trace_align();   // where the host time goes
   scan_upload_post(ctx, &up);
-  const double ta0 = trace_align ? now_seconds() : 0.0;
+  const double ta0 = trace ? now_seconds() : 0.0;
   const hipError_t e_launch = launch_persistent_fused(ctx->stream, a, f, ctx->persist_grid);
-  const double ta1 = trace_align ? now_seconds() : 0.0;
+  const double ta1 = trace ? now_seconds() : 0.0;
   bool slow = false;
-  rc = scan_upload_copy(ctx, up, &slow);
+  const int rc = scan_upload_copy(ctx, up, &slow);
   if (rc != VGICP_OK) {
     // a copy thread never delivered: the launch has given up waiting for its unit by now (crew_gave_up synchronised)
     (void)reset_persistent_exchange(ctx);
     return rc;
   }
   if (e_launch != hipSuccess) return fail_hip(ctx, e_launch, "launch_persistent_fused");
-  const double ta2 = trace_align ? now_seconds() : 0.0;
+  const double ta2 = trace ? now_seconds() : 0.0;
   VG_HIP(ctx, hipEventRecord(ctx->ev_upload, ctx->stream));
   ctx->upload_in_flight = true;
   ctx->upload_bytes += n * kScanPlanes * sizeof(double);
   ctx->upload_seconds += now_seconds() - up.t0;  // host side: the staging copy + the enqueue of the launch
   ctx->scan_ready = true;
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const double ta3 = trace_align ? now_seconds() : 0.0;
-  if (trace_align && ta3 - ta0 > 2e-3)
+  const double ta3 = trace ? now_seconds() : 0.0;
+  if (trace && ta3 - ta0 > 2e-3)
     std::fprintf(stderr, "[vgicp trace] fused align: enqueue %.3f ms, copy %.3f ms, hipStreamSynchronize %.3f ms\n",
                  (ta1 - ta0) * 1e3, (ta2 - ta1) * 1e3, (ta3 - ta2) * 1e3);
   ++ctx->persistent_launches;
   AlignState* hf = &ctx->h_state[0];
   std::memcpy(hf, reinterpret_cast<const AlignState*>(ctx->h_log - kSlots), sizeof(AlignState));
-  {
-    const int rc_scan = settle_scan(ctx);
-    const int rc_ins = settle_insert(ctx);
-    if (rc_scan != VGICP_OK || rc_ins != VGICP_OK) {
-      (void)reset_persistent_exchange(ctx);
-      return rc_scan != VGICP_OK ? rc_scan : rc_ins;
-    }
-  }
-  if (hf->seq != a.seq || hf->outcome != kOutcomeCommitted || hf->abort_seq == a.seq) {
+  VG_RC(settle_after_launch(ctx, *hf, a.seq, /*multi=*/false));
+  if (!launch_committed(*hf, a.seq, hf->abort_seq)) {
     // A wait inside the launch ran out.  The copy threads have delivered everything by now: pack the scan behind the
     // launch (no flags to wait for), put the exchange back into its initial state and run the align again.  Copy threads
     // that were held up (counted once, as slow) explain it: the single launch is simply repeated.  Otherwise the device
-    // did not have every workgroup resident: a persistent fallback, handled as run_align_persistent handles one.
+    // did not have every workgroup resident: a persistent fallback, this align goes to the loop.
     VG_HIP(ctx, launch_pack_staged(ctx, false));
-    rc = reset_persistent_exchange(ctx);
-    if (rc != VGICP_OK) return rc;
-    if (!slow) {
-      ++ctx->persistent_fallbacks;
-      ctx->persistent_cooldown = kPersistentCooldownAligns;
-      if (ctx->persistent_fallbacks == 1 || ctx->dev.verbose)
-        std::fprintf(stderr, "[vgicp] persistent align launch gave up waiting for a workgroup (fallback #%llu): using one "
-                     "launch per iteration for the next %d aligns\n", (unsigned long long)ctx->persistent_fallbacks,
-                     kPersistentCooldownAligns);
-    }
-    return run_align(ctx, guess, params, out_pose, stats, /*loop_only=*/!slow);
+    VG_RC(reset_persistent_exchange(ctx));
+    if (slow) return run_align(ctx, guess, params, out_pose, stats);
+    count_fallback(ctx, "persistent align launch gave up waiting for a workgroup", "");
+    return align_on_loop(ctx, guess, params, out_pose, stats, now_seconds());
   }
-  ctx->persist_round0 = (ctx->persist_round0 + (uint32_t)hf->iteration) % 3u;
-  state_to_pose(hf->pose, out_pose);
-  if (stats) {
-    stats->iterations = hf->iteration;
-    stats->converged = hf->converged;
-    stats->world_size = 1;
-    stats->launches = 1;
-    // the registration's device time, the upload excluded: from the moment the last workgroup found its units to the
-    // end of the launch, on the device's constant clock
-    stats->device_seconds = ctx->wall_clock_hz > 0.0 ? (double)hf->unit_to_end_ticks / ctx->wall_clock_hz : 0.0;
-    for (int it = 0; it < hf->iteration; ++it) {
-      const double* row = ctx->h_log + (size_t)it * kSlots;
-      if (stats->corr_count) stats->corr_count[it] = (uint64_t)row[kCountSlot];
-      if (stats->normal_eq) std::memcpy(stats->normal_eq + (size_t)it * kNormalEq, row, kNormalEq * sizeof(double));
-    }
-    stats->seconds = now_seconds() - t0;
-  }
-  if (!finite16(out_pose)) return fail(ctx, VGICP_ERR_DEGENERATE, "solved pose is not finite (singular normal equations)");
-  return VGICP_OK;
+  advance_exchange(ctx, *hf, /*multi=*/false);
+  // the registration's device time, the upload excluded: from the moment the last workgroup found its units to the
+  // end of the launch, on the device's constant clock
+  const double device_seconds = ctx->wall_clock_hz > 0.0 ? (double)hf->unit_to_end_ticks / ctx->wall_clock_hz : 0.0;
+  return report_align(ctx, *hf, ctx->h_log, 1, 1, device_seconds, t0, out_pose, stats);
 }
 }  // namespace
 
@@ -138,7 +98,10 @@ int vgicp_align(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
   const double t0 = now_seconds();
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
-  if (guess && out_pose && fused_align_fits(ctx, n, points, covs, params)) {
+  AlignFacts facts = align_facts(ctx, params, AlignCall::Upload, n);
+  facts.buffers = params && points && covs && guess && out_pose;
+  facts.upload_staged = true;   // asked last, and only when everything else says Fused: it looks the caller's pointers up
+  if (plan_align(facts).path == AlignPath::Fused && upload_is_staged(ctx, n, points, covs)) {
     VG_HIP(ctx, hipSetDevice(ctx->device));
     const int rc = align_fused(ctx, n, points, covs, guess, params, out_pose, stats);   // one launch
     if (stats) stats->seconds = now_seconds() - t0;

@@ -25,6 +25,7 @@
 #include "../../include/vgicp_hip_map_points.h"
 #include "../../include/vgicp_hip_batch.h"
 #include "vgicp_device.h"
+#include "vgicp_align_plan.h"
 
 using namespace vgicp;
 
@@ -82,7 +83,7 @@ constexpr uint64_t kRawMinEntries = 4096;
 constexpr uint64_t kRawMaxEntries = 1ull << 31;   // 64 GiB of raw points; ordinals and offsets stay 32-bit
 constexpr int kDefaultChunk = 4;
 constexpr int kMaxChunksInFlight = 2;
-constexpr int kBatchSlotRows = 64;   // rows of kSlots doubles per hypothesis of a batch: the final state, then up to 63 rounds of log
+static_assert(kPlanTeamsMax == (uint32_t)kTeamsMax, "vgicp_align_plan.h plans with the team kernel's width");
 constexpr int kPersistentCooldownAligns = 8;  // aligns on the per-launch loop after the single launch gave up
 
 }  // namespace vgicp
@@ -456,6 +457,35 @@ struct vgicp_ctx {
   int rank = 0;
 };
 
+// The facts plan_align (vgicp_align_plan.h) decides by, as this context and this call have them: the ONE place where a
+// single-device align's plan meets the context (a multi-device context fills its own: group_facts, vgicp_multi.hip).
+// n: the caller's count (AlignCall::Upload), else the resident scan's.
+inline AlignFacts call_facts(AlignCall call, uint32_t flags, int max_iteration) {
+  AlignFacts f;
+  f.call = call;
+  f.max_iteration = max_iteration;
+  f.profile = (flags & VGICP_FLAG_PROFILE) != 0;
+  f.no_persistent = (flags & VGICP_FLAG_NO_PERSISTENT) != 0;
+  return f;
+}
+inline AlignFacts align_facts(const vgicp_ctx* ctx, const vgicp_params* params, AlignCall call, uint64_t n, size_t k = 1) {
+  AlignFacts f = call_facts(call, params ? params->flags : 0u, params ? params->max_iteration : 0);
+  f.n = n;
+  f.k = k;
+  f.persistent_enabled = ctx->persistent_enabled;
+  f.owner = ctx->owner != nullptr;
+  f.comm = ctx->comm != nullptr;
+  f.peers_connected = ctx->peers_connected;
+  f.peer_enabled = ctx->peer_enabled;
+  f.stamps = ctx->d_stamps != nullptr;
+  f.stage_events = ctx->stage_events;
+  f.no_fused = ctx->dev.no_fused;
+  f.world_size = ctx->world_size;
+  f.peer_world = ctx->peer_world;
+  f.cooldown = ctx->persistent_cooldown;
+  f.grid = ctx->persist_grid;
+  return f;
+}
 
 // ---- helpers shared by the two translation units ----
 namespace vgicp {

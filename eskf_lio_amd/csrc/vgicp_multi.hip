@@ -205,6 +205,19 @@ int deal_prepared(vgicp_ctx* parent) {
   return VGICP_OK;
 }
 
+// The facts plan_align decides a GROUP's align by (vgicp_peer_status: with no flags, one round — the next plain align).
+AlignFacts group_facts(const vgicp_multi* g, uint32_t flags, int max_iteration) {
+  AlignFacts f = call_facts(AlignCall::Group, flags, max_iteration);
+  f.mailboxes = g->mailboxes;
+  // the single launch needs the persistent kernel on EVERY device (VGICP_PERSISTENT=0, or a workgroup that does not fit a
+  // compute unit, leaves a sub-context on the launch-per-round loop)
+  f.persistent_enabled = true;
+  for (const vgicp_ctx* sub : g->subs) f.persistent_enabled = f.persistent_enabled && sub->persistent_enabled;
+  f.cooldown = g->cooldown;
+  return f;
+}
+
+// What a give-up costs the group (its sub-contexts neither cool down nor announce anything: align_persistent).
 void note_fallback(vgicp_ctx* parent, const char* why) {
   vgicp_multi* g = parent->multi;
   ++g->fallbacks;
@@ -235,35 +248,20 @@ int align_shards(vgicp_ctx* parent, const double* points, const double* covs, co
   vgicp_multi* g = parent->multi;
   const double t0 = now_seconds();
   if (!params) return fail(parent, VGICP_ERR_BAD_ARGUMENT, "params is NULL");
-  const bool host_loop_asked = (params->flags & (VGICP_FLAG_PROFILE | VGICP_FLAG_NO_PERSISTENT)) != 0 || params->max_iteration <= 0;
-  // the single launch needs the persistent kernel on EVERY device (VGICP_PERSISTENT=0, or a workgroup that does not fit a
-  // compute unit, leaves a sub-context on the launch-per-round loop): without it the host-summed loop is the path, not a
-  // fallback — nothing is counted, announced or re-wired, and no device waits for a peer that will never publish
-  bool all_persistent = true;
-  for (int r = 0; r < g->n; ++r) all_persistent = all_persistent && g->subs[(size_t)r]->persistent_enabled;
-  bool single = g->mailboxes && all_persistent && !host_loop_asked && g->cooldown == 0;
-  if (g->cooldown > 0 && !host_loop_asked) --g->cooldown;
-  if (single && points) {
-    // no allocation between the launches: a sub-context that has to grow its scan buffers does so now, while nobody's
-    // persistent kernel is running (hipFree waits for the whole device; on a shared device that would be a neighbour's
-    // launch, which in turn waits for this sub-context's)
+  // without the persistent kernel everywhere the host-summed loop is the path, not a fallback — nothing is counted,
+  // announced or re-wired, and no device waits for a peer that will never publish
+  const AlignPlan plan = plan_align(group_facts(g, params->flags, params->max_iteration));
+  const bool single = plan.path == AlignPath::Persistent;
+  g->cooldown -= plan.cooldown_drop;
+  if (single) {
+    // no allocation between the launches: a sub-context that has to grow its buffers (the scan's for a shard that comes
+    // up with this call, the log) does so now, while nobody's persistent kernel is running (hipFree waits for the whole
+    // device; on a shared device that would be a neighbour's launch, which in turn waits for this sub-context's)
+    auto shard = [&](int r) { return points ? g->hi[(size_t)r] - g->lo[(size_t)r] : (size_t)g->subs[(size_t)r]->n; };
     bool grow = false;
-    for (int r = 0; r < g->n; ++r)
-      grow = grow || vgicp_internal::align_needs_allocation(g->subs[(size_t)r], g->hi[(size_t)r] - g->lo[(size_t)r], params->max_iteration);
+    for (int r = 0; r < g->n; ++r) grow = grow || vgicp_internal::align_needs_allocation(g->subs[(size_t)r], shard(r), params->max_iteration);
     if (grow) {
-      const int rc = run_all(parent, [&](int r) {
-        return vgicp_internal::reserve_for_align(g->subs[(size_t)r], g->hi[(size_t)r] - g->lo[(size_t)r], params->max_iteration);
-      });
-      if (rc != VGICP_OK) return rc;
-    }
-  } else if (single) {
-    bool grow = false;
-    for (int r = 0; r < g->n; ++r) grow = grow || vgicp_internal::align_needs_allocation(g->subs[(size_t)r], g->subs[(size_t)r]->n, params->max_iteration);
-    if (grow) {   // the log, or the dense record copy of a large table (the resident shards themselves stay where they are)
-      const int rc = run_all(parent, [&](int r) {
-        vgicp_ctx* sub = g->subs[(size_t)r];
-        return vgicp_internal::reserve_for_align(sub, sub->n, params->max_iteration);
-      });
+      const int rc = run_all(parent, [&](int r) { return vgicp_internal::reserve_for_align(g->subs[(size_t)r], shard(r), params->max_iteration); });
       if (rc != VGICP_OK) return rc;
     }
   }
@@ -421,10 +419,11 @@ namespace vgicp_multi_api {
 
 vgicp_ctx* first(const vgicp_ctx* ctx) { return ctx->multi->subs[0]; }
 
-// What carries the per-round merge of the NEXT align, derived from the same three facts align_shards decides by: "" only
+// What carries the per-round merge of the NEXT align, derived from the facts align_shards plans by (group_facts): "" only
 // while the kernels' own mailboxes do.
 const char* peer_status(const vgicp_ctx* ctx) {
   const vgicp_multi* g = ctx->multi;
+  if (plan_align(group_facts(g, 0, 1)).path == AlignPath::Persistent) return "";
   if (!g->mailboxes) return ctx->peer_status.c_str();
   for (int r = 0; r < g->n; ++r)
     if (!g->subs[(size_t)r]->persistent_enabled) {
@@ -432,12 +431,9 @@ const char* peer_status(const vgicp_ctx* ctx) {
                        "(VGICP_PERSISTENT=0 or its workgroup does not fit a compute unit): one launch per round, the devices' rows added on the host";
       return g->status_text.c_str();
     }
-  if (g->cooldown > 0) {
-    g->status_text = "mailboxes wired, but " + g->last_fallback + " (fallback #" + std::to_string(g->fallbacks) + "): the next " +
-                     std::to_string(g->cooldown) + " aligns run one launch per round with the devices' rows added on the host";
-    return g->status_text.c_str();
-  }
-  return "";
+  g->status_text = "mailboxes wired, but " + g->last_fallback + " (fallback #" + std::to_string(g->fallbacks) + "): the next " +
+                   std::to_string(g->cooldown) + " aligns run one launch per round with the devices' rows added on the host";
+  return g->status_text.c_str();
 }
 
 void scan_replaced(vgicp_ctx* ctx) {   // a hook put its own scan on device 0: nothing is resident as far as the caller goes
