@@ -46,6 +46,10 @@ MAP_POINTS_EXPORTS = ("vgicp_map_points_size", "vgicp_map_points_export")
 BATCH_EXPORTS = ("vgicp_align_resident_batch", "vgicp_align_batch_width")
 BATCH_MAX = 64
 
+# every symbol include/vgicp_hip_evaluate.h declares (likewise an extension header)
+EVALUATE_EXPORTS = ("vgicp_evaluate_resident",)
+EVAL_MAX = 64
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -85,6 +89,17 @@ class BatchStats(C.Structure):
                 ("status", C.POINTER(C.c_int32)), ("iterations", C.POINTER(C.c_int32)),
                 ("converged", C.POINTER(C.c_int32)), ("corr_count", C.POINTER(C.c_uint64)),
                 ("normal_eq", C.POINTER(C.c_double))]
+
+
+class Evaluation(C.Structure):
+    """vgicp_evaluation (vgicp_hip_evaluate.h), 248 bytes."""
+    _fields_ = [("points", C.c_uint64), ("correspondences", C.c_uint64), ("cost", C.c_double),
+                ("sq_error", C.c_double), ("normal_eq", C.c_double * 27)]
+
+
+class EvalStats(C.Structure):
+    _fields_ = [("launches", C.c_int32), ("poses_per_launch", C.c_int32), ("seconds", C.c_double),
+                ("device_seconds", C.c_double)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -158,7 +173,8 @@ def load_library() -> C.CDLL:
     lib.vgicp_map_points_export.argtypes = [vp, sz, ip, dp, C.POINTER(sz)]
     lib.vgicp_align_resident_batch.argtypes = [vp, sz, dp, C.POINTER(Params), dp, C.POINTER(BatchStats)]
     lib.vgicp_align_batch_width.argtypes = [vp, C.POINTER(sz)]
-    for name in EXPORTS + MAP_POINTS_EXPORTS + BATCH_EXPORTS:
+    lib.vgicp_evaluate_resident.argtypes = [vp, sz, dp, C.POINTER(Evaluation), C.POINTER(EvalStats)]
+    for name in EXPORTS + MAP_POINTS_EXPORTS + BATCH_EXPORTS + EVALUATE_EXPORTS:
         fn = getattr(lib, name)
         if name not in ("vgicp_last_error", "vgicp_peer_status"):
             fn.restype = C.c_int
@@ -196,6 +212,44 @@ class BatchResult(list):
         self.launches = launches
         self.seconds = seconds
         self.device_seconds = device_seconds
+
+
+class EvaluationList(list):
+    """What evaluate_resident returns: one PoseEvaluation per pose, and how the call ran."""
+
+    def __init__(self, launches: int = 0, poses_per_launch: int = 0, seconds: float = 0.0, device_seconds: float = 0.0):
+        super().__init__()
+        self.launches = launches
+        self.poses_per_launch = poses_per_launch
+        self.seconds = seconds
+        self.device_seconds = device_seconds
+
+
+@dataclass
+class PoseEvaluation:
+    """One vgicp_evaluation, with the figures an Open3D-style RegistrationResult derives from it."""
+    points: int
+    correspondences: int
+    cost: float          # sum of e^T (R C R^T + C_voxel)^-1 e over the correspondences
+    sq_error: float      # sum of |e|^2 over the correspondences
+    normal_eq: np.ndarray  # 27, packed as a row of AlignResult.normal_eq
+
+    @property
+    def fitness(self) -> float:
+        return self.correspondences / self.points if self.points else 0.0
+
+    @property
+    def inlier_rmse(self) -> float:
+        return float(np.sqrt(self.sq_error / self.correspondences)) if self.correspondences else 0.0
+
+    @property
+    def JTJ(self) -> np.ndarray:
+        """6 x 6: the information matrix of the pose."""
+        return expand_normal_eq(self.normal_eq)[0][0]
+
+    @property
+    def JTr(self) -> np.ndarray:
+        return expand_normal_eq(self.normal_eq)[1][0]
 
 
 @dataclass
@@ -471,6 +525,22 @@ class Context:
                                    device_seconds=st.device_seconds, corr_count=counts[h, :it].copy(),
                                    normal_eq=neq[h, :it].copy(), kernel_ms=None, status=int(status[h]),
                                    message="solved pose is not finite" if status[h] else ""))
+        return res
+
+    def evaluate_resident(self, poses) -> "EvaluationList":
+        """vgicp_evaluate_resident (vgicp_hip_evaluate.h): the resident scan scored at every pose of `poses` (k 4x4
+        poses): a list of PoseEvaluation, with launches and poses_per_launch."""
+        gs = [pose_to_abi(g) for g in poses]
+        k = len(gs)
+        g = np.ascontiguousarray(np.stack(gs).reshape(k, 16)) if k else np.zeros((0, 16))
+        out = (Evaluation * max(k, 1))()
+        st = EvalStats()
+        self._check(self._lib.vgicp_evaluate_resident(self._h, k, _dp(g), out, C.byref(st)))
+        res = EvaluationList(st.launches, st.poses_per_launch, st.seconds, st.device_seconds)
+        for h in range(k):
+            res.append(PoseEvaluation(points=int(out[h].points), correspondences=int(out[h].correspondences),
+                                      cost=float(out[h].cost), sq_error=float(out[h].sq_error),
+                                      normal_eq=np.array(out[h].normal_eq[:], dtype=np.float64)))
         return res
 
     def align_batch_width(self) -> int:

@@ -107,6 +107,16 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
     VG_CREATE(hipHostGetDevicePointer(&dev, ctx->h_batch, 0));
     ctx->h_batch_dev = static_cast<double*>(dev);
   }
+  {
+    // ... and vgicp_evaluate_resident's: the rows of one launch pair, results and poses page-locked
+    const size_t eval_bytes = (size_t)VGICP_EVAL_MAX * (kSlots + 12) * sizeof(double);
+    VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_eval_rows), (size_t)kEvalRowBudget * kSlots * sizeof(double)));
+    VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_eval), eval_bytes, 0));
+    std::memset(ctx->h_eval, 0, eval_bytes);
+    void* dev = nullptr;
+    VG_CREATE(hipHostGetDevicePointer(&dev, ctx->h_eval, 0));
+    ctx->h_eval_dev = static_cast<double*>(dev);
+  }
   ctx->persist_grid = (uint32_t)std::min<int>(ctx->cu_count, kExchangeRows);
   if (max_persist_grid >= 1 && max_persist_grid < ctx->persist_grid) ctx->persist_grid = max_persist_grid;
   if (const char* pg = std::getenv("VGICP_PERSIST_GRID")) {  // fewer workgroups: several contexts sharing one device
@@ -274,6 +284,8 @@ int vgicp_destroy(vgicp_ctx* ctx) {
   (void)hipHostFree(ctx->h_exchange_image);
   (void)hipFree(ctx->d_batch_exchange);
   if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+  (void)hipFree(ctx->d_eval_rows);
+  if (ctx->h_eval) (void)hipHostFree(ctx->h_eval);
   (void)hipFree(ctx->d_rows[0]);
   (void)hipFree(ctx->d_rows[1]);
   (void)hipFree(ctx->d_sums);

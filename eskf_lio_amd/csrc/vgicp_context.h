@@ -24,6 +24,7 @@
 #include "../../include/vgicp_hip.h"
 #include "../../include/vgicp_hip_map_points.h"
 #include "../../include/vgicp_hip_batch.h"
+#include "../../include/vgicp_hip_evaluate.h"
 #include "vgicp_device.h"
 #include "vgicp_align_plan.h"
 
@@ -308,6 +309,10 @@ struct vgicp_ctx {
   double* d_batch_exchange = nullptr;  // team rows, then team parts (team_rows_words() + team_parts_words()); all unset before a launch
   double* h_batch = nullptr;           // pinned: VGICP_BATCH_MAX blocks of kBatchSlotRows rows (state, then log), then the abort word's row
   double* h_batch_dev = nullptr;       // the same memory as the device addresses it
+  // scoring poses (vgicp_hip_evaluate.h): storage of its own, made with the context
+  double* d_eval_rows = nullptr;       // kEvalRowBudget rows: [poses of a launch][rows per pose][kSlots]
+  double* h_eval = nullptr;            // pinned: VGICP_EVAL_MAX result rows of kSlots doubles, then VGICP_EVAL_MAX poses of 12
+  double* h_eval_dev = nullptr;        // the same memory as the device addresses it
   bool persistent_enabled = true;    // cleared by VGICP_PERSISTENT=0 or when a workgroup does not fit a CU
   double prefetch_margin = 0.015;    // see PersistArgs::prefetch_margin; VGICP_PREFETCH_MARGIN overrides (0 = off).  Round 6: 0.03 -> 0.015
                                      // once the workgroups that are no folders stopped polling early (C2: 0 7.18, 0.01 6.41, 0.015 6.34, 0.02 6.35, 0.03 6.52, 0.04 6.66 us per round)

@@ -22,6 +22,8 @@ namespace vgicp {
 constexpr int kSlots = 32;      // doubles per partial row
 constexpr int kNormalEq = 27;   // 21 lower-triangle JTJ entries + 6 JTr entries
 constexpr int kCountSlot = 27;  // match count travels as an exact double
+constexpr int kCostSlot = 28;     // evaluate_kernel only: sum of e^T (R C R^T + C_voxel)^-1 e
+constexpr int kSqErrorSlot = 29;  // evaluate_kernel only: sum of |e|^2
 constexpr int kScanPlanes = 12;
 constexpr int kMaxIterBlocks = 512;  // grid cap (every workgroup folds all rows: keep them few); larger scans grid-stride
 
@@ -199,7 +201,28 @@ struct TeamArgs {
 constexpr size_t team_rows_words() { return 3 * (size_t)kTeamRowsMax * kSlots; }
 constexpr size_t team_parts_words() { return 3 * (size_t)kTeamsMax * kFolders * kSlots; }
 
+// Scoring poses of the resident scan (vgicp_evaluate_resident): launch (rows per pose) x (poses) workgroups write one
+// row each, a second launch folds every pose's rows into 32 doubles.  Row budget of one launch pair: kEvalRowBudget.
+constexpr int kEvalRowBudget = 4096;   // 1 MiB of rows: 16 poses of the largest geometry below 256 x 448 points, 8 of kMaxIterBlocks rows
+struct EvalArgs {
+  const double* scan;  // SoA planes
+  uint64_t stride;
+  uint32_t n;
+  uint32_t mask;
+  const VoxelRecord* table;
+  double voxel_size;
+  const double* poses;       // [poses][12], page-locked host memory as the device addresses it: R column-major (9), t (3)
+  double* rows;              // [poses][rows per pose][kSlots]
+  const uint32_t* asym_dev;  // as IterArgs
+  uint32_t scan_seq;
+  uint32_t pad;
+};
+
 // ---- launchers (defined in vgicp_kernels.hip) ----
+// Rows of `poses` poses (grid: rows_per_pose x poses workgroups of 512 threads), and their fold into out[poses][kSlots]:
+// slots 0-26 the normal equations, 27 the count, 28 the cost, 29 the squared error.
+hipError_t launch_evaluate(hipStream_t s, const EvalArgs& args, uint32_t rows_per_pose, uint32_t poses);
+hipError_t launch_evaluate_fold(hipStream_t s, const double* rows, uint32_t rows_per_pose, uint32_t poses, double* out);
 // The whole ICP::align loop in one launch (512-thread workgroups, at most one per CU).
 hipError_t launch_persistent(hipStream_t s, const PersistArgs& args, uint32_t grid);
 // The same loop for args.teams hypotheses side by side (single device, one point per thread, no stamps, settled scan).

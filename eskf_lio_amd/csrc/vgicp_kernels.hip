@@ -8,6 +8,8 @@
 //                   LocalMap::getVoxelIndex + voxelGrid_.find (src/LocalMap.cpp:94-100,114-118),
 //                   ICP::computeJTJAndJTr (src/Registration.cpp:83-102) and the accumulation of
 //                   ICP::computeTransform (:60-70)
+//   evaluate_kernel that round's body at several given poses at once, plus the objective and the squared error
+//                   (no counterpart in the reference: what Open3D's EvaluateRegistration is to its ICP)
 //   upsert/erase    the effect of LocalMap::updateLocalMap's insert and evict loops on the data the
 //                   path reads (src/LocalMap.cpp:47-72), mirrored from host-computed voxel values
 //   match kernels   LocalMap::correspondenceMatching with materialised output (src/LocalMap.cpp:78-112)
@@ -437,6 +439,19 @@ __device__ __forceinline__ void load_point_sym(const double* scan, uint64_t stri
 template <bool B>
 struct Flag { static constexpr bool value = B; };
 
+// W = S^-1 by cofactors as Eigen's fixed-size inverse (vgicp_math.h inv3), the one division replaced by
+// v_rcp_f64 + one third-order step (rcp_newton: ~1 ulp; a third of the dependent instructions)
+__device__ __forceinline__ void inverse3_cofactor(const double (&S)[9], double (&W)[9]) {
+  const double c00 = S[4] * S[8] - S[7] * S[5], c10 = S[5] * S[6] - S[8] * S[3], c20 = S[3] * S[7] - S[6] * S[4];
+  const double det = c00 * S[0] + c10 * S[1] + c20 * S[2];
+  const double id = rcp_newton(det);
+  const double c01 = S[7] * S[2] - S[1] * S[8], c11 = S[8] * S[0] - S[2] * S[6], c21 = S[6] * S[1] - S[0] * S[7];
+  const double c02 = S[1] * S[5] - S[4] * S[2], c12 = S[2] * S[3] - S[5] * S[0], c22 = S[0] * S[4] - S[3] * S[1];
+  W[0] = c00 * id; W[3] = c10 * id; W[6] = c20 * id;
+  W[1] = c01 * id; W[4] = c11 * id; W[7] = c21 * id;
+  W[2] = c02 * id; W[5] = c12 * id; W[8] = c22 * id;
+}
+
 // FIRST: v holds nothing yet (the thread's first match of the round): the 28 values are stored, not added to
 // zeros — 28 dependent-latency adds less per round in the one-point-per-thread case.  Both loop variants make the
 // same choice for the same point, so they still agree bit for bit.
@@ -457,19 +472,8 @@ __device__ __forceinline__ void accumulate_match(const double* R, const double (
     for (int r = 0; r < 3; ++r)
       S[r + 3 * c] += RC[r] * R[c] + RC[r + 3] * R[c + 3] + RC[r + 6] * R[c + 6];
 
-  // W = S^-1 by cofactors as Eigen's fixed-size inverse (vgicp_math.h inv3), the one division replaced by
-  // v_rcp_f64 + two Newton steps (~1 ulp; a third of the dependent instructions)
   double W[9];
-  {
-    const double c00 = S[4] * S[8] - S[7] * S[5], c10 = S[5] * S[6] - S[8] * S[3], c20 = S[3] * S[7] - S[6] * S[4];
-    const double det = c00 * S[0] + c10 * S[1] + c20 * S[2];
-    const double id = rcp_newton(det);
-    const double c01 = S[7] * S[2] - S[1] * S[8], c11 = S[8] * S[0] - S[2] * S[6], c21 = S[6] * S[1] - S[0] * S[7];
-    const double c02 = S[1] * S[5] - S[4] * S[2], c12 = S[2] * S[3] - S[5] * S[0], c22 = S[0] * S[4] - S[3] * S[1];
-    W[0] = c00 * id; W[3] = c10 * id; W[6] = c20 * id;
-    W[1] = c01 * id; W[4] = c11 * id; W[7] = c21 * id;
-    W[2] = c02 * id; W[5] = c12 * id; W[8] = c22 * id;
-  }
+  inverse3_cofactor(S, W);
   auto acc = [](double& dst, double x) { if (FIRST) dst = x; else dst += x; };
   const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
   // Q = [p]x W  (rows 3..5, columns 0..2 of J^T Sigma^-1 J)
@@ -690,6 +694,130 @@ __global__ __launch_bounds__(BLOCK) void close_kernel(IterArgs a) {
   if (head.stop || a.prev_rows == 0) return;
   __syncthreads();
   if (threadIdx.x < 64) prologue_solve<BLOCK>(a, sh, head.total, threadIdx.x, it, max_it, cos_thr, tsq_thr);
+}
+
+// Scoring poses of the resident scan (vgicp_evaluate_resident, include/vgicp_hip_evaluate.h): what round 0 of the loop
+// accumulates at a pose, for several poses in one launch, plus the objective and the squared error in two spare slots.
+// Grid: (rows per pose) x (poses), the pose index the SLOW dimension, so that workgroups of different poses that run
+// side by side read the same scan lines and table records.  Workgroup (vb, h) is workgroup vb of iterate_kernel<BLOCK>'s
+// first launch from pose h on a grid of gridDim.x: waves 1.. own points, grid-stride, the same `first` rule, the same
+// butterfly, LDS step and tree_sum — so its row's slots 0-27 are that launch's row vb, bit for bit.  No memo, no dense
+// copy, no state: nothing is written but the rows, nothing waits for another workgroup.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void evaluate_kernel(EvalArgs a) {
+  constexpr int kWaves = BLOCK / 64;
+  constexpr int kWorkers = BLOCK - 64;
+  __shared__ double red[kWaves][kSlots];
+
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool worker = wave != 0;
+  const uint32_t stride_pts = gridDim.x * kWorkers;
+  const double inv_voxel = 1.0 / a.voxel_size;
+  const bool cov_sym = a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
+  uint32_t i = worker ? blockIdx.x * kWorkers + (tid - 64) : a.n;
+
+  double q[kScanPlanes];
+#pragma unroll
+  for (int k = 0; k < kScanPlanes; ++k) q[k] = 0.0;
+  if (i < a.n) load_point_sym(a.scan, a.stride, i, q, cov_sym);
+
+  const double* pose = a.poses + (size_t)blockIdx.y * 12;  // uniform: R column-major (9) then t (3)
+  double R[9], t[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = pose[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) t[k] = pose[9 + k];
+
+  double v[kSlots];
+#pragma unroll
+  for (int k = 0; k < kSlots; ++k) v[k] = 0.0;
+
+  bool first = true;
+  while (i < a.n) {
+    const double x = q[0], y = q[1], z = q[2];
+    double C[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) C[k] = q[3 + k];
+    const uint32_t inext = i + stride_pts;
+    if (inext < a.n) load_point_sym(a.scan, a.stride, inext, q, cov_sym);  // the next point under this one's gather
+    i = inext;
+
+    double p[3];
+    transform_point(R, t, x, y, z, p);
+    const int32_t kx = voxel_coord_fast(p[0], a.voxel_size, inv_voxel);
+    const int32_t ky = voxel_coord_fast(p[1], a.voxel_size, inv_voxel);
+    const int32_t kz = voxel_coord_fast(p[2], a.voxel_size, inv_voxel);
+    const VoxelRecord* rec = find_voxel(a.table, a.mask, kx, ky, kz);
+    if (rec != nullptr) {
+      double mu[3], S[9];
+      load_payload(rec, mu, S);
+      if (first) accumulate_match<true>(R, p, C, mu, S, v);
+      else accumulate_match<false>(R, p, C, mu, S, v);
+      // S now holds R C R^T + C_voxel; the same W beside the normal equations (the compiler keeps one copy)
+      double W[9];
+      inverse3_cofactor(S, W);
+      const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
+      const double w0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
+      const double w1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
+      const double w2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
+      v[kCostSlot] += e0 * w0 + e1 * w1 + e2 * w2;
+      v[kSqErrorSlot] += e0 * e0 + e1 * e1 + e2 * e2;
+    }
+    first = false;
+  }
+
+  if (worker) {
+    fold_swap<32, false>(v);
+    fold_swap<16, true>(v);
+    fold<8, 8>(v, (lane & 8) != 0);
+    fold<4, 4>(v, (lane & 4) != 0);
+    fold<2, 2>(v, (lane & 2) != 0);
+    const double wsum = v[0] + xor_lane_f64<1>(v[0]);
+    if ((lane & 1) == 0) red[wave][lane >> 1] = wsum;
+  }
+  __syncthreads();
+  if (tid < kSlots) {
+    double w_sum[kWaves - 1];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) w_sum[w - 1] = red[w][tid];
+    a.rows[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kSlots + tid] = tree_sum<kWaves - 1>(w_sum);
+  }
+}
+
+// The fold of iterate_kernel<512>'s prologue (prologue_fold + the first lines of prologue_solve) over the rows of one
+// pose per workgroup: 16 groups of threads add the rows group, group + 16, ... as tree_sum<16> batches (rows beyond the
+// pose's count +0.0 in their place), then tree_sum<16> over the groups.  All 32 slots; one 256-byte row per pose, written
+// straight into the page-locked result.
+__global__ __launch_bounds__(512) void evaluate_fold_kernel(const double* __restrict__ rows, uint32_t rows_per_pose,
+                                                            double* __restrict__ out) {
+  constexpr int kGroups = 512 / kSlots;
+  constexpr int kBatch = 16;
+  __shared__ double fin[kGroups][kSlots];
+  const uint32_t tid = threadIdx.x, slot = tid & (kSlots - 1), group = tid / kSlots;
+  const double* prev = rows + (size_t)blockIdx.x * rows_per_pose * kSlots;
+  double row[kBatch];
+#pragma unroll
+  for (int u = 0; u < kBatch; ++u) {
+    const uint32_t b = group + u * kGroups;
+    row[u] = b < rows_per_pose ? prev[(size_t)b * kSlots + slot] : 0.0;
+  }
+  double s = tree_sum<kBatch>(row);
+  for (uint32_t b0 = group + kBatch * kGroups; b0 < rows_per_pose; b0 += kGroups * kBatch) {
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u) {
+      const uint32_t b = b0 + u * kGroups;
+      row[u] = b < rows_per_pose ? prev[(size_t)b * kSlots + slot] : 0.0;
+    }
+    s += tree_sum<kBatch>(row);
+  }
+  fin[group][slot] = s;
+  __syncthreads();
+  if (tid < kSlots) {
+    double part[kGroups];
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) part[g] = fin[g][tid];
+    out[(size_t)blockIdx.x * kSlots + tid] = tree_sum<kGroups>(part);
+  }
 }
 
 // Test hook (vgicp_solve_step): the tail of one round on given normal equations, run by ONE wave with
@@ -2074,6 +2202,21 @@ hipError_t launch_close(hipStream_t s, const IterArgs& args, int block) {
     case 1024: ++g_kernel_launches; hipLaunchKernelGGL(close_kernel<1024>, dim3(1), dim3(1024), 0, s, args); break;
     default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+// 512 threads as iterate_kernel<512>, whatever the context's loop uses: the persistent launches' summation order.
+hipError_t launch_evaluate(hipStream_t s, const EvalArgs& args, uint32_t rows_per_pose, uint32_t poses) {
+  if (rows_per_pose < 1 || rows_per_pose > (uint32_t)kMaxIterBlocks || poses < 1 ||
+      (uint64_t)rows_per_pose * poses > (uint64_t)kEvalRowBudget || args.poses == nullptr || args.rows == nullptr)
+    return hipErrorInvalidValue;
+  ++g_kernel_launches; hipLaunchKernelGGL(evaluate_kernel<512>, dim3(rows_per_pose, poses), dim3(512), 0, s, args);
+  return hipGetLastError();
+}
+
+hipError_t launch_evaluate_fold(hipStream_t s, const double* rows, uint32_t rows_per_pose, uint32_t poses, double* out) {
+  if (rows_per_pose < 1 || poses < 1 || (uint64_t)rows_per_pose * poses > (uint64_t)kEvalRowBudget) return hipErrorInvalidValue;
+  ++g_kernel_launches; hipLaunchKernelGGL(evaluate_fold_kernel, dim3(poses), dim3(512), 0, s, rows, rows_per_pose, out);
   return hipGetLastError();
 }
 

@@ -346,6 +346,7 @@ extern "C" int vgicp_create_multi(const int* device_ids, int n_devices, vgicp_ct
     ++multiplicity[(size_t)device_ids[r]];
   }
   vgicp_ctx* parent = new vgicp_ctx;
+  parent->id = ++g_context_ids;   // never 0: vgicp_last_error tells this handle's text from a staging thread's by the id
   vgicp_multi* g = new vgicp_multi;
   parent->multi = g;
   g->n = n_devices;

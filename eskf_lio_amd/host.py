@@ -64,6 +64,9 @@ def load_library() -> C.CDLL:
     i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
     lib.host_icp_align_hypotheses.argtypes = [vp, sz, dp, dp, vp, sz, dp, dp, i32p, i32p, u64p, i32p, dp, i32p]
     lib.host_frame_hypotheses.argtypes = [vp, vp, vp, vp, sz, dp, dp, i32p, i32p, u64p, i32p, i32p]
+    lib.host_icp_evaluate.argtypes = [vp, sz, dp, dp, vp, sz, dp, dp, i32p]
+    lib.host_icp_align_best_by_score.argtypes = [vp, sz, dp, dp, vp, sz, dp, i32p, dp, i32p, i32p, dp]
+    lib.host_frame_evaluate.argtypes = [vp, vp, vp, vp, sz, dp, C.c_int, dp, i32p]
     lib.host_preprocessor_create.restype = vp
     lib.host_preprocessor_create.argtypes = [C.c_double, dp, C.c_int, C.c_int]
     lib.host_frame_begin.restype = vp
@@ -247,6 +250,38 @@ class ICP:
         self.best, self.iterations, self.converged = int(best.value), int(it[0]), bool(conv[0])
         return capi.pose_from_abi(pose)
 
+    def evaluate(self, points, covs, localMap: LocalMap, poses):
+        """ICP::evaluate on a cloud made from the arrays (one upload) -> [capi.PoseEvaluation], one per pose."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        cvs = np.ascontiguousarray(covs, dtype=np.float64).reshape(-1, 9)
+        g = _fan_buffers(poses)[0]
+        out = np.zeros((g.shape[0], 31))
+        res = C.c_int32()
+        _check(self._lib, self._lib.host_icp_evaluate(self._h, pts.shape[0], _dp(pts), _dp(cvs), localMap._h,
+                                                      g.shape[0], _dp(g), _dp(out), C.byref(res)))
+        self.used_resident = bool(res.value)
+        return [_evaluation(row) for row in out]
+
+    def alignBestByScore(self, points, covs, localMap: LocalMap, guesses) -> np.ndarray:
+        """ICP::alignBestByScore -> the chosen pose; self.best is the chosen index, self.iterations / self.converged
+        describe that hypothesis and self.evaluation is ICP::lastEvaluation()."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        cvs = np.ascontiguousarray(covs, dtype=np.float64).reshape(-1, 9)
+        g = _fan_buffers(guesses)[0]
+        best, pose, it, conv, ev = C.c_int32(-1), np.zeros(16), C.c_int32(), C.c_int32(), np.zeros(31)
+        _check(self._lib, self._lib.host_icp_align_best_by_score(
+            self._h, pts.shape[0], _dp(pts), _dp(cvs), localMap._h, g.shape[0], _dp(g), C.byref(best), _dp(pose),
+            C.byref(it), C.byref(conv), _dp(ev)))
+        self.best, self.iterations, self.converged = int(best.value), int(it.value), bool(conv.value)
+        self.evaluation = _evaluation(ev)
+        return capi.pose_from_abi(pose)
+
+
+def _evaluation(row) -> "capi.PoseEvaluation":
+    """31 doubles of vgicp_host.cpp's packEvaluation -> capi.PoseEvaluation."""
+    return capi.PoseEvaluation(points=int(row[0]), correspondences=int(row[1]), cost=float(row[2]),
+                               sq_error=float(row[3]), normal_eq=np.array(row[4:31], dtype=np.float64))
+
 
 def _i32(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
@@ -336,6 +371,16 @@ class Frame:
         _check(self._lib, self._lib.host_frame_run(self._h, preprocessor._h, icp._h, localMap._h, _dp(g),
                                                    1 if first_frame else 0, int(mutate),
                                                    stage_next._h if stage_next is not None else None, int(bool(move_cloud))))
+
+    def evaluate(self, preprocessor: "CloudPreprocessor", icp: "ICP", localMap: "LocalMap", poses, mutate: int = 0):
+        """process(states, meas), optionally an edit of the prepared cloud (mutate as run()), then ICP::evaluate on it
+        (no map update) -> ([capi.PoseEvaluation], used_resident)."""
+        g = _fan_buffers(poses)[0]
+        out = np.zeros((g.shape[0], 31))
+        res = C.c_int32()
+        _check(self._lib, self._lib.host_frame_evaluate(self._h, preprocessor._h, icp._h, localMap._h, g.shape[0],
+                                                        _dp(g), int(mutate), _dp(out), C.byref(res)))
+        return [_evaluation(row) for row in out], bool(res.value)
 
     def hypotheses(self, preprocessor: "CloudPreprocessor", icp: "ICP", localMap: "LocalMap", guesses):
         """process(states, meas), then ICP::alignHypotheses on the cloud it left resident (no map update) ->

@@ -245,6 +245,53 @@ int host_icp_align_hypotheses(
     });
 }
 
+// One ICP::Evaluation as 31 doubles: points, correspondences (both exact), cost, squaredError, the 27 normal equations.
+static void packEvaluation(const ICP::Evaluation & e, double * out)
+{
+  out[0] = static_cast<double>(e.points);
+  out[1] = static_cast<double>(e.correspondences);
+  out[2] = e.cost;
+  out[3] = e.squaredError;
+  for (size_t k = 0; k < 27; ++k) {out[4 + k] = e.normalEquations[k];}
+}
+
+// icp->evaluate(cloud, localMap, poses) on a cloud built from the arrays (not resident: one upload); out: k x 31.
+int host_icp_evaluate(
+  ICP * icp, size_t n, const double * points, const double * covs, const LocalMap * map, size_t k,
+  const double * poses, double * out, int32_t * used_resident)
+{
+  return guarded(
+    [&] {
+      const PointCloud cloud = makeCloud(n, points, covs);
+      std::vector<Isometry3d> g(k);
+      for (size_t h = 0; h < k; ++h) {g[h] = ESKF_LIO::shim::poseFromData(poses + 16 * h);}
+      const auto all = icp->evaluate(cloud, *map, g);
+      for (size_t h = 0; h < all.size(); ++h) {packEvaluation(all[h], out + 31 * h);}
+      if (used_resident) {*used_resident = icp->lastUsedResidentScan() ? 1 : 0;}
+    });
+}
+
+// icp->alignBestByScore(cloud, localMap, guesses): *best the chosen index, best_pose its pose, iterations / converged
+// of that hypothesis, evaluation (31 doubles) = icp->lastEvaluation().
+int host_icp_align_best_by_score(
+  ICP * icp, size_t n, const double * points, const double * covs, const LocalMap * map, size_t k,
+  const double * guesses, int32_t * best, double best_pose[16], int32_t * iterations, int32_t * converged,
+  double * evaluation)
+{
+  return guarded(
+    [&] {
+      const PointCloud cloud = makeCloud(n, points, covs);
+      std::vector<Isometry3d> g(k);
+      for (size_t h = 0; h < k; ++h) {g[h] = ESKF_LIO::shim::poseFromData(guesses + 16 * h);}
+      const Isometry3d T = icp->alignBestByScore(cloud, *map, g);
+      *best = static_cast<int32_t>(icp->lastBestHypothesis());
+      std::memcpy(best_pose, ESKF_LIO::shim::poseData(T), 16 * sizeof(double));
+      if (iterations) {*iterations = icp->lastStats().iterations;}
+      if (converged) {*converged = icp->lastStats().converged ? 1 : 0;}
+      if (evaluation) {packEvaluation(icp->lastEvaluation(), evaluation);}
+    });
+}
+
 // Developer aid (tools/probe_eager.py): switch the classes' host-time trace on / off; out (optional) receives
 // Trace::Slots seconds followed by Trace::Slots call counts (as doubles) and is then reset.
 void host_trace(int enable, double * out)
@@ -381,6 +428,29 @@ int host_frame_hypotheses(
       }
       if (used_resident) {*used_resident = icp->lastUsedResidentScan() ? 1 : 0;}
       if (per_launch) {*per_launch = icp->lastHypothesesPerLaunch();}
+    });
+}
+
+// process(states, meas), optionally an edit of the prepared cloud (mutate as host_frame_run), then
+// icp->evaluate(*meas.cloud, localMap, poses); out: k x 31 (packEvaluation).
+int host_frame_evaluate(
+  HostFrame * f, const CloudPreprocessor * p, ICP * icp, LocalMap * map, size_t k, const double * poses, int mutate,
+  double * out, int32_t * used_resident)
+{
+  return guarded(
+    [&] {
+      p->process(f->states, f->meas);
+      if (mutate) {ESKF_LIO::shim::materialize(map->context(), *f->meas->cloud);}
+      if (mutate == 1 && !f->meas->cloud->points_.empty()) {f->meas->cloud->points_[0](0) += 1e-3;}
+      if (mutate == 2 && f->meas->cloud->points_.size() > 1) {
+        f->meas->cloud->points_.pop_back();
+        f->meas->cloud->covariances_.pop_back();
+      }
+      std::vector<Isometry3d> g(k);
+      for (size_t h = 0; h < k; ++h) {g[h] = ESKF_LIO::shim::poseFromData(poses + 16 * h);}
+      const auto all = icp->evaluate(*f->meas->cloud, *map, g);
+      for (size_t h = 0; h < all.size(); ++h) {packEvaluation(all[h], out + 31 * h);}
+      if (used_resident) {*used_resident = icp->lastUsedResidentScan() ? 1 : 0;}
     });
 }
 

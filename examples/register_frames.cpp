@@ -4,6 +4,7 @@
 //     localMap->updateLocalMap(cloud0, Identity)              // first frame builds the map
 //     for each later frame:
 //         T = icp->align(*cloud, *localMap, guess)            // ErrorStateKF::update
+//         icp->evaluate(*cloud, *localMap, {T})               // added: how good is T? (vgicp_hip_evaluate.h)
 //         localMap->updateLocalMap(cloud, T)                  // Odometry::run
 //
 // No Eigen / Open3D / ROS here: ShimTypes.hpp supplies layout-identical stand-ins; with those libraries
@@ -119,6 +120,17 @@ int main()
         f, icp.lastStats().iterations, (int)icp.lastStats().converged, estimate.matrix()(0, 3),
         estimate.matrix()(1, 3), estimate.matrix()(2, 3), err, localMap.size());
       if (!(err < 5e-3) || !icp.lastStats().converged) {++lost;}
+      // the returned pose, scored between align() and updateLocalMap(): what an integrator would gate the frame on
+      // (this cloud was made on the host, so evaluate() uploads it once more; a cloud that CloudPreprocessor::process
+      // left on the device is scored where it is)
+      try {
+        const ICP::Evaluation ev = icp.evaluate(*cloud, localMap, {estimate}).front();
+        std::printf("  returned pose: fitness %.4f (%llu of %llu points), inlier rmse %.4f m, cost %.2f, score %.2f\n",
+          ev.fitness(), (unsigned long long)ev.correspondences, (unsigned long long)ev.points, ev.inlierRmse(), ev.cost,
+          ev.score());
+      } catch (const std::runtime_error & e) {
+        std::printf("  returned pose not scored: %s\n", e.what());   // a multi-device context shards the scan
+      }
       localMap.updateLocalMap(cloud, estimate);                   // src/Odometry.cpp:86
     }
     return lost == 0 ? 0 : 2;

@@ -13,9 +13,13 @@
 // error throws std::runtime_error (the reference has no error path at all).
 // Added (no counterpart in the reference): alignHypotheses / alignBest register the cloud from a fan of guesses in one
 // call (vgicp_hip_batch.h) — for an integrator without a prior, after a stall, or on re-entry into an earlier map.
+// evaluate / selectBestByScore / alignBestByScore score poses of a cloud (vgicp_hip_evaluate.h): fitness, inlier RMSE,
+// the VGICP objective and the information matrix at a pose, as an Open3D-style RegistrationResult carries them.
 #ifndef ESKF_LIO_SHIM_REGISTRATION_HPP_
 #define ESKF_LIO_SHIM_REGISTRATION_HPP_
 
+#include <array>
+#include <cmath>
 #include <cstdint>
 #include <iostream>
 #include <stdexcept>
@@ -24,6 +28,7 @@
 
 #include "LocalMap.hpp"
 #include "../vgicp_hip_batch.h"
+#include "../vgicp_hip_evaluate.h"
 
 namespace ESKF_LIO
 {
@@ -266,7 +271,125 @@ public:
     return all[best].pose;
   }
 
+  // A pose of a cloud, scored against the map (one vgicp_evaluation).
+  struct Evaluation
+  {
+    uint64_t points = 0;            // of the cloud
+    uint64_t correspondences = 0;   // points whose voxel is in the map at the pose
+    double cost = 0.0;              // sum over the correspondences of e^T (R C R^T + C_voxel)^-1 e: ICP::align's objective
+    double squaredError = 0.0;      // sum over the correspondences of |e|^2
+    std::array<double, 27> normalEquations{};   // packed as vgicp_evaluation::normal_eq
+
+    double fitness() const {return points ? static_cast<double>(correspondences) / static_cast<double>(points) : 0.0;}
+    double inlierRmse() const
+    {
+      return correspondences ? std::sqrt(squaredError / static_cast<double>(correspondences)) : 0.0;
+    }
+    // J^T Sigma^-1 J at the pose, 6 x 6 (symmetric; translation first, then rotation, as the normal equations): the
+    // information matrix of the registration, for an integrator that wants a pose covariance instead of a fixed one.
+    std::array<double, 36> information() const
+    {
+      std::array<double, 36> m{};
+      int k = 0;
+      for (int r = 0; r < 6; ++r) {
+        for (int c = 0; c <= r; ++c, ++k) {m[r + 6 * c] = m[c + 6 * r] = normalEquations[static_cast<size_t>(k)];}
+      }
+      return m;
+    }
+    // The objective with every point that found no voxel charged missPenalty, like a rejected measurement.  The default
+    // is the 0.99 quantile of chi-squared with 3 degrees of freedom: the cost at which a matched point would itself be
+    // called an outlier.
+    double score(double missPenalty = 11.345) const
+    {
+      return cost + missPenalty * static_cast<double>(points - correspondences);
+    }
+  };
+
+  // Scores `cloud` at every pose (at most VGICP_EVAL_MAX) in one call of vgicp_evaluate_resident: the resident scan when
+  // the cloud still is what CloudPreprocessor::process left on the device (as alignHypotheses decides it), else ONE
+  // upload of the cloud.  Changes neither the map nor what a later align returns.
+  std::vector<Evaluation> evaluate(
+    const PointCloud & cloud, const LocalMap & localMap, const std::vector<Isometry3d> & poses)
+  {
+    std::vector<Evaluation> out;
+    const size_t k = poses.size();
+    if (k == 0) {return out;}
+    if (k > static_cast<size_t>(VGICP_EVAL_MAX)) {
+      throw std::runtime_error("ICP::evaluate: more than VGICP_EVAL_MAX poses");
+    }
+    vgicp_ctx * ctx = localMap.context();
+    bool resident = false;
+    {
+      shim::TraceScope ts(shim::Trace::AlignVerify);
+      resident = shim::residentStampOf(ctx, cloud) != nullptr;
+    }
+    shim::TraceScope tsCall(shim::Trace::AlignCall);
+    if (!resident) {
+      const size_t n = cloud.points_.size();
+      if (cloud.covariances_.size() != n) {
+        throw std::runtime_error(
+                "ICP::evaluate: the cloud has " + std::to_string(n) + " points but " +
+                std::to_string(cloud.covariances_.size()) + " covariances (a cloud prepared with a deferred host "
+                "copy and changed since? call shim::materialize first)");
+      }
+      const double * pts = n ? cloud.points_.data()->data() : nullptr;
+      const double * covs = n ? cloud.covariances_.data()->data() : nullptr;
+      shim::check(ctx, vgicp_scan_upload(ctx, n, pts, covs), "vgicp_scan_upload");
+    }
+    lastUsedResidentScan_ = resident;
+    return evaluateResidentScan(ctx, poses);
+  }
+
+  // Which hypothesis of a fan to keep, by the score of its RETURNED pose: a converged one goes before one that is not;
+  // among equals the lowest Evaluation::score(missPenalty) wins, ties go to the lower index.  hypotheses must not be
+  // empty; evaluations[h] scores hypotheses[h].pose.
+  static size_t selectBestByScore(
+    const std::vector<Hypothesis> & hypotheses, const std::vector<Evaluation> & evaluations,
+    double missPenalty = 11.345)
+  {
+    if (hypotheses.size() != evaluations.size()) {
+      throw std::runtime_error("ICP::selectBestByScore: one evaluation per hypothesis");
+    }
+    size_t best = 0;
+    for (size_t h = 1; h < hypotheses.size(); ++h) {
+      const bool a = hypotheses[h].converged, b = hypotheses[best].converged;
+      if ((a && !b) || (a == b && evaluations[h].score(missPenalty) < evaluations[best].score(missPenalty))) {
+        best = h;
+      }
+    }
+    return best;
+  }
+
+  // alignHypotheses, evaluate of the returned poses, then the pose of selectBestByScore's choice.  lastStats(),
+  // lastBestHypothesis() and lastEvaluation() describe that hypothesis.
+  Isometry3d alignBestByScore(
+    const PointCloud & cloud, const LocalMap & localMap, const std::vector<Isometry3d> & guesses)
+  {
+    if (guesses.empty()) {throw std::runtime_error("ICP::alignBestByScore: no guess");}
+    const std::vector<Hypothesis> all = alignHypotheses(cloud, localMap, guesses);
+    std::vector<Isometry3d> returned;
+    returned.reserve(all.size());
+    for (const Hypothesis & h : all) {returned.push_back(h.pose);}
+    // the fan left the cloud resident (its own upload, or the preparation's): no second upload for the scores
+    const std::vector<Evaluation> scores = evaluateResidentScan(localMap.context(), returned);
+    const size_t best = selectBestByScore(all, scores);
+    lastBest_ = best;
+    lastEvaluation_ = scores[best];
+    lastStats_.iterations = all[best].iterations;
+    lastStats_.converged = all[best].converged;
+    lastStats_.seconds = fanSeconds_;
+    lastStats_.deviceSeconds = fanDeviceSeconds_;
+    lastStats_.correspondenceCounts.assign(
+      fanCounts_.begin() + static_cast<std::ptrdiff_t>(best * fanRounds_),
+      fanCounts_.begin() + static_cast<std::ptrdiff_t>(best * fanRounds_ + static_cast<size_t>(all[best].iterations)));
+    if (!lastStats_.converged) {
+      std::cout << "ICP not converged!\n";
+    }
+    return all[best].pose;
+  }
+
   const Stats & lastStats() const {return lastStats_;}
+  const Evaluation & lastEvaluation() const {return lastEvaluation_;}     // of the last alignBestByScore()
   size_t lastBestHypothesis() const {return lastBest_;}                   // of the last alignBest()
   int lastHypothesesPerLaunch() const {return lastHypothesesPerLaunch_;}  // of the last alignHypotheses(): 1 = one by one
   // whether the last align() found its cloud resident on the device (prepared there by CloudPreprocessor::process)
@@ -274,6 +397,29 @@ public:
 
 private:
   ICP() = delete;
+
+  // vgicp_evaluate_resident on whatever scan is resident (1 <= poses.size() <= VGICP_EVAL_MAX)
+  static std::vector<Evaluation> evaluateResidentScan(vgicp_ctx * ctx, const std::vector<Isometry3d> & poses)
+  {
+    const size_t k = poses.size();
+    std::vector<Evaluation> out;
+    std::vector<double> in(16 * k);
+    for (size_t h = 0; h < k; ++h) {
+      const double * g = shim::poseData(poses[h]);
+      for (int e = 0; e < 16; ++e) {in[16 * h + e] = g[e];}
+    }
+    std::vector<vgicp_evaluation> ev(k);
+    shim::check(ctx, vgicp_evaluate_resident(ctx, k, in.data(), ev.data(), nullptr), "vgicp_evaluate_resident");
+    out.resize(k);
+    for (size_t h = 0; h < k; ++h) {
+      out[h].points = ev[h].points;
+      out[h].correspondences = ev[h].correspondences;
+      out[h].cost = ev[h].cost;
+      out[h].squaredError = ev[h].sq_error;
+      for (size_t e = 0; e < 27; ++e) {out[h].normalEquations[e] = ev[h].normal_eq[e];}
+    }
+    return out;
+  }
 
   int maxIteration_;
   double translationSquaredThreshold_;
@@ -286,6 +432,7 @@ private:
   double fanSeconds_ = 0.0, fanDeviceSeconds_ = 0.0;
   size_t lastBest_ = 0;
   int lastHypothesesPerLaunch_ = 0;
+  Evaluation lastEvaluation_;
 };
 
 }  // namespace ESKF_LIO
