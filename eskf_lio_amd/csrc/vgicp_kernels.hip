@@ -30,6 +30,20 @@
 namespace vgicp {
 namespace {
 
+// The 96-byte payload {mean, covariance} as six 16-byte pieces that lie PIECES double2 apart: 1 in a record, the number
+// of worker threads in the plane-major neighbour-prefetch area of the persistent launch's LDS.
+template <int PIECES = 1>
+__device__ __forceinline__ void unpack_payload(const double2* pay, double (&mu)[3], double (&S)[9]) {
+  const double2 a0 = pay[0 * PIECES], a1 = pay[1 * PIECES], a2 = pay[2 * PIECES],
+                a3 = pay[3 * PIECES], a4 = pay[4 * PIECES], a5 = pay[5 * PIECES];
+  mu[0] = a0.x; mu[1] = a0.y; mu[2] = a1.x;
+  S[0] = a1.y; S[1] = a2.x; S[2] = a2.y; S[3] = a3.x; S[4] = a3.y; S[5] = a4.x;
+  S[6] = a4.y; S[7] = a5.x; S[8] = a5.y;
+}
+// Payload of a record whose slot is known (an unchanged key that hit last round): one round trip.
+__device__ __forceinline__ void load_payload(const VoxelRecord* rec, double (&mu)[3], double (&S)[9]) {
+  unpack_payload(reinterpret_cast<const double2*>(rec->mean), mu, S);  // 16-byte aligned
+}
 // Lookup + payload: probe the key word(s), then fetch the 96-byte payload of the matching record as
 // six 16-byte loads (same 128-byte line as the key, so they are L1/L2 hits).  Requesting key and
 // payload together was measured slower: every lane addresses its own line, so each extra wave-level
@@ -39,11 +53,7 @@ __device__ __forceinline__ bool find_and_load(const VoxelRecord* table, uint32_t
                                               double (&S)[9]) {
   const VoxelRecord* rec = find_voxel(table, mask, kx, ky, kz);
   if (rec == nullptr) return false;
-  const double2* pay = reinterpret_cast<const double2*>(rec->mean);  // 16-byte aligned
-  const double2 a0 = pay[0], a1 = pay[1], a2 = pay[2], a3 = pay[3], a4 = pay[4], a5 = pay[5];
-  mu[0] = a0.x; mu[1] = a0.y; mu[2] = a1.x;
-  S[0] = a1.y; S[1] = a2.x; S[2] = a2.y; S[3] = a3.x; S[4] = a3.y; S[5] = a4.x;
-  S[6] = a4.y; S[7] = a5.x; S[8] = a5.y;
+  load_payload(rec, mu, S);
   return true;
 }
 
@@ -94,6 +104,18 @@ __device__ __forceinline__ void fold_swap(double (&v)[kSlots]) {
                           : __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
     v[j] = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
   }
+}
+
+// The wave's part of a round's reduction: the 32-slot halving butterfly, after which lane l holds slot (l >> 1) summed
+// over the 64 lanes, handed to the workgroup through the wave's row of LDS.
+__device__ __forceinline__ void wave_fold_to_lds(double (&v)[kSlots], uint32_t lane, double* red_row) {
+  fold_swap<32, false>(v);
+  fold_swap<16, true>(v);
+  fold<8, 8>(v, (lane & 8) != 0);
+  fold<4, 4>(v, (lane & 4) != 0);
+  fold<2, 2>(v, (lane & 2) != 0);
+  const double wsum = v[0] + xor_lane_f64<1>(v[0]);
+  if ((lane & 1) == 0) red_row[lane >> 1] = wsum;
 }
 
 // 1 / d for a normal, finite d by v_rcp_f64 (good to 2^-24) + ONE third-order step y (1 + e + e^2), e = 1 - d y: three
@@ -290,6 +312,20 @@ __device__ __forceinline__ double tree_sum(const double* v) {
   else return tree_sum<N / 2>(v) + tree_sum<N - N / 2>(v + N / 2);
 }
 
+// A pose as 12 doubles in memory (global, LDS, kernel arguments): R column-major, then t.
+__device__ __forceinline__ void load_pose(const double* src, Pose& T) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) T.R[k] = src[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) T.t[k] = src[9 + k];
+}
+__device__ __forceinline__ void store_pose(double* dst, const Pose& T) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) dst[k] = T.R[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dst[9 + k] = T.t[k];
+}
+
 // What every wave needs to run a round: the total pose, or the news that the loop has ended.
 struct RoundHead {
   Pose total;
@@ -331,10 +367,7 @@ __device__ __forceinline__ RoundHead prologue_fold(const IterArgs& a, PrologueSh
     row[u] = b < a.prev_rows ? a.prev[(size_t)b * kSlots + slot] : 0.0;
   }
   RoundHead head;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) head.total.R[k] = in->pose[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) head.total.t[k] = in->pose[9 + k];
+  load_pose(in->pose, head.total);
   it = in->iteration;
   max_it = in->max_iteration;
   cos_thr = in->cosine_threshold;
@@ -387,16 +420,13 @@ __device__ __forceinline__ void prologue_solve(const IterArgs& a, PrologueShared
   const bool conv = converged(step, cos_thr, tsq_thr);
   const bool stop = conv || (it + 1 >= max_it);
   if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) sh.pose[k] = next.R[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sh.pose[9 + k] = next.t[k];
+    store_pose(sh.pose, next);
     sh.stop = stop ? 1 : 0;
   }
   if (blockIdx.x == 0) {
-    AlignState* out = a.state_out;
     if (lane < kSlots) a.log[(size_t)it * kSlots + lane] = tot;
     if (lane == 0) {
+      AlignState* out = a.state_out;
 #pragma unroll
       for (int k = 0; k < 9; ++k) { out->pose[k] = next.R[k]; out->step[k] = step.R[k]; }
 #pragma unroll
@@ -509,15 +539,6 @@ __device__ __forceinline__ void accumulate_match(const double* R, const double (
 
 constexpr uint32_t kMemoMiss = 0xFFFFFFFFu;  // memo.w of a point whose voxel is not in the map
 constexpr uint32_t kMemoNone = 0xFFFFFFFEu;  // nothing looked up
-
-// Payload of a record whose slot is known (an unchanged key that hit last round): one round trip.
-__device__ __forceinline__ void load_payload(const VoxelRecord* rec, double (&mu)[3], double (&S)[9]) {
-  const double2* pay = reinterpret_cast<const double2*>(rec->mean);
-  const double2 a0 = pay[0], a1 = pay[1], a2 = pay[2], a3 = pay[3], a4 = pay[4], a5 = pay[5];
-  mu[0] = a0.x; mu[1] = a0.y; mu[2] = a1.x;
-  S[0] = a1.y; S[1] = a2.x; S[2] = a2.y; S[3] = a3.x; S[4] = a3.y; S[5] = a4.x;
-  S[6] = a4.y; S[7] = a5.x; S[8] = a5.y;
-}
 
 // One VGICP round.  Launch j reads state j&1 and the rows launch j-1 wrote, writes state (j+1)&1
 // and its own rows; the host alternates the buffers; the kernel boundary is the only synchronisation
@@ -655,18 +676,9 @@ __global__ __launch_bounds__(BLOCK) void iterate_kernel(IterArgs a) {
   }
   const uint64_t t_loop = a.stamps ? wall_clock64() : 0;
 
-  // ---- wave: 32-slot halving butterfly; lane l ends with slot (l >> 1) summed over 64 lanes ----
-  if (worker) {
-    fold_swap<32, false>(v);
-    fold_swap<16, true>(v);
-    fold<8, 8>(v, (lane & 8) != 0);
-    fold<4, 4>(v, (lane & 4) != 0);
-    fold<2, 2>(v, (lane & 2) != 0);
-    const double wsum = v[0] + xor_lane_f64<1>(v[0]);
-    if ((lane & 1) == 0) red[wave][lane >> 1] = wsum;
-  }
+  if (worker) wave_fold_to_lds(v, lane, red[wave]);
   __syncthreads();
-  // ---- workgroup: fixed-order sum over the worker waves, one plain 256-byte row per workgroup ----
+  // one plain 256-byte row per workgroup
   if (tid < kSlots) {
     double w_sum[kWaves - 1];
 #pragma unroll
@@ -766,15 +778,7 @@ __global__ __launch_bounds__(BLOCK) void evaluate_kernel(EvalArgs a) {
     first = false;
   }
 
-  if (worker) {
-    fold_swap<32, false>(v);
-    fold_swap<16, true>(v);
-    fold<8, 8>(v, (lane & 8) != 0);
-    fold<4, 4>(v, (lane & 4) != 0);
-    fold<2, 2>(v, (lane & 2) != 0);
-    const double wsum = v[0] + xor_lane_f64<1>(v[0]);
-    if ((lane & 1) == 0) red[wave][lane >> 1] = wsum;
-  }
+  if (worker) wave_fold_to_lds(v, lane, red[wave]);
   __syncthreads();
   if (tid < kSlots) {
     double w_sum[kWaves - 1];
@@ -881,9 +885,10 @@ __global__ __launch_bounds__(64) void solve_step_kernel(const double* __restrict
 // round j exists, so every row of round j was published, so every workgroup had finished reading round
 // j - 1.  Ordered: the producer's next publication (round j + 1) waits for its own stores to complete
 // first (s_waitcnt vmcnt(0)), and a consumer polls buffer (j - 1) % 3 again only in round j + 2, after it
-// has seen a part of round j + 1 that depends on that publication.  At the end of the launch every
-// workgroup re-arms its row of the last round, arrives at the exit counter, and the LAST arriver (everyone
-// has read the last parts by then) re-arms the parts: the buffers are all kRowUnset between launches.
+// has seen a part of round j + 1 that depends on that publication.  Nothing is tidied up when a launch ends: the
+// round number runs on from launch to launch (PersistArgs::round0 = rounds executed on this context before), so the
+// next launch's first rounds re-arm what this launch published last — every workgroup of that launch has published
+// by then, hence left this launch and its reads behind.  There is no exit counter and no last arriver.
 // What stays on chip across rounds: a thread's first point with the voxel record it used (registers);
 // for scans larger than the grid, per further point its last key and table slot (16-byte memo in LDS: an
 // unchanged key that missed costs no table access at all — the map is immutable during align,
@@ -1211,14 +1216,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
               if (m.x == kx && m.y == ky && m.z == kz && (uint32_t)m.w != kMemoNone) {
                 served = true;
                 hit = (uint32_t)m.w != kMemoMiss;
-                if (hit) {
-                  const double2* pay = pf_pay + (tid - 64);
-                  const double2 a0 = pay[0 * kWorkers], a1 = pay[1 * kWorkers], a2 = pay[2 * kWorkers],
-                                a3 = pay[3 * kWorkers], a4 = pay[4 * kWorkers], a5 = pay[5 * kWorkers];
-                  mu[0] = a0.x; mu[1] = a0.y; mu[2] = a1.x;
-                  Sv[0] = a1.y; Sv[1] = a2.x; Sv[2] = a2.y; Sv[3] = a3.x; Sv[4] = a3.y; Sv[5] = a4.x;
-                  Sv[6] = a4.y; Sv[7] = a5.x; Sv[8] = a5.y;
-                }
+                if (hit) unpack_payload<kWorkers>(pf_pay + (tid - 64), mu, Sv);
               }
             }
             if (!served) hit = find_and_load(a.table, a.mask, kx, ky, kz, mu, Sv);
@@ -1310,13 +1308,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
           one_point(q, e, Flag<false>{});
         }
       }
-      fold_swap<32, false>(v);
-      fold_swap<16, true>(v);
-      fold<8, 8>(v, (lane & 8) != 0);
-      fold<4, 4>(v, (lane & 4) != 0);
-      fold<2, 2>(v, (lane & 2) != 0);
-      const double wsum = v[0] + xor_lane_f64<1>(v[0]);
-      if ((lane & 1) == 0) red[wave][lane >> 1] = wsum;
+      wave_fold_to_lds(v, lane, red[wave]);
     }
     __syncthreads();
     if (STAMPS) { const uint64_t n = wall_clock64(); acc_body += n - t_mark; t_mark = n; }
@@ -1370,7 +1362,6 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
         double w_sum[kWaves];
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) w_sum[w] = red[w][lane];
-        // all eight waves when wave 0 carries points too, else waves 1..7 (iterate_kernel<512>'s order)
         const double row_sum = MANY ? tree_sum<kWaves>(w_sum) : tree_sum<kWaves - 1>(w_sum + 1);
         store_through_bits(rows + (size_t)my_row * kSlots + lane, publishable(row_sum));
       }
@@ -1473,10 +1464,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
       // the round's row of the log: still in LDS (written again only after the next round's barrier)
       if (blk == 0 && lane_here < kSlots) a.log[(size_t)it * kSlots + lane_here] = totals[lane_here];
     }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) total.R[k] = pose_sh[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) total.t[k] = pose_sh[9 + k];
+    load_pose(pose_sh, total);
     ++it;
     if (STAMPS) { const uint64_t n = wall_clock64(); acc_solve += n - t_mark; t_mark = n; }
     if (stop) break;
