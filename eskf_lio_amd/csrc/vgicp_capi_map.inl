@@ -59,27 +59,20 @@ int vgicp_map_upsert(vgicp_ctx* ctx, size_t n, const int32_t* keys, const double
   int rc = ensure_table(ctx, n);
   if (rc != VGICP_OK) return rc;
   const size_t kb = n * 3 * sizeof(int32_t), mb = n * 3 * sizeof(double), cb = n * 9 * sizeof(double);
-  const size_t koff = 0, moff = (kb + 255) & ~size_t(255), coff = moff + mb, qoff = (coff + cb + 255) & ~size_t(255);
-  rc = ensure_stage(ctx, qoff + n * sizeof(uint32_t));
-  if (rc != VGICP_OK) return rc;
-  char* base = static_cast<char*>(ctx->d_stage);
+  StageLayout lay;
+  const size_t o_keys = lay.take(kb), o_means = lay.take(mb), o_covs = lay.take(cb), o_queue = lay.take(n * sizeof(uint32_t));
+  VG_RC(ensure_stage(ctx, lay.total));
+  int32_t* d_keys = stage_at<int32_t>(ctx, o_keys);
+  double *d_means = stage_at<double>(ctx, o_means), *d_covs = stage_at<double>(ctx, o_covs);
   arena_reset(ctx);
-  VG_RC(user_h2d(ctx, base + koff, keys, kb));
-  VG_RC(user_h2d(ctx, base + moff, means, mb));
-  VG_RC(user_h2d(ctx, base + coff, covs, cb));
+  VG_RC(user_h2d(ctx, d_keys, keys, kb));
+  VG_RC(user_h2d(ctx, d_means, means, mb));
+  VG_RC(user_h2d(ctx, d_covs, covs, cb));
   VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
   ++ctx->map_version;
-  VG_HIP(ctx, launch_upsert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), (uint32_t)n,
-                            reinterpret_cast<const int32_t*>(base + koff),
-                            reinterpret_cast<const double*>(base + moff),
-                            reinterpret_cast<const double*>(base + coff), ctx->d_counters,
-                            reinterpret_cast<uint32_t*>(base + qoff)));
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 4 * sizeof(uint32_t),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->voxels += ctx->h_counters[0];
-  if (ctx->h_counters[1] != 0) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table probe sequence exhausted");
-  return VGICP_OK;
+  VG_HIP(ctx, launch_upsert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), (uint32_t)n, d_keys, d_means, d_covs,
+                            ctx->d_counters, stage_at<uint32_t>(ctx, o_queue)));
+  return finish_insert(ctx, nullptr);   // (no raw points here: refused above)
 }
 
 int vgicp_map_erase(vgicp_ctx* ctx, size_t n, const int32_t* keys) {
@@ -134,22 +127,20 @@ int vgicp_map_insert_scan(vgicp_ctx* ctx, size_t n, const double* points, const 
   int rc = ensure_table(ctx, n);  // every point may open a voxel
   if (rc == VGICP_OK) rc = ensure_raw(ctx, n);  // ... and be kept
   if (rc != VGICP_OK) return rc;
-  const size_t pb = ((n * 3 * sizeof(double)) + 255) & ~size_t(255);
-  const size_t cb = ((n * 9 * sizeof(double)) + 255) & ~size_t(255);
   const size_t sb = map_insert_scratch_bytes((uint32_t)n);
-  rc = ensure_stage(ctx, pb + cb + sb);
-  if (rc != VGICP_OK) return rc;
-  char* base = static_cast<char*>(ctx->d_stage);
+  StageLayout lay;
+  const size_t o_pts = lay.take(n * 3 * sizeof(double)), o_covs = lay.take(n * 9 * sizeof(double)), o_scratch = lay.take(sb);
+  VG_RC(ensure_stage(ctx, lay.total));
+  double *d_pts = stage_at<double>(ctx, o_pts), *d_covs = stage_at<double>(ctx, o_covs);
   double pose12[12];
   pose_to_state(transform, pose12);
   arena_reset(ctx);
-  VG_RC(user_h2d(ctx, base, points, n * 3 * sizeof(double)));
-  VG_RC(user_h2d(ctx, base + pb, covs, n * 9 * sizeof(double)));
+  VG_RC(user_h2d(ctx, d_pts, points, n * 3 * sizeof(double)));
+  VG_RC(user_h2d(ctx, d_covs, covs, n * 9 * sizeof(double)));
   VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
   ++ctx->map_version;
-  VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size,
-                                reinterpret_cast<const double*>(base), reinterpret_cast<const double*>(base + pb),
-                                (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, base + pb + cb, sb,
+  VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size, d_pts, d_covs,
+                                (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, stage_at<char>(ctx, o_scratch), sb,
                                 ctx->d_counters, false, raw_log(ctx)));
   return finish_insert(ctx, new_voxels);
 }
@@ -269,23 +260,20 @@ int vgicp_map_export(vgicp_ctx* ctx, size_t capacity, int32_t* keys, double* mea
   if (!keys || !means || !covs || !counts) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL array pointer");
   VG_HIP(ctx, hipSetDevice(ctx->device));
   const size_t cap = std::min<size_t>(capacity, ctx->voxels);
-  const size_t kb = (cap * 3 * sizeof(int32_t) + 255) & ~size_t(255);
-  const size_t mb = (cap * 3 * sizeof(double) + 255) & ~size_t(255);
-  const size_t cb = (cap * 9 * sizeof(double) + 255) & ~size_t(255);
-  const size_t nb = cap * sizeof(uint64_t);
-  int rc = ensure_stage(ctx, kb + mb + cb + nb);
-  if (rc != VGICP_OK) return rc;
-  char* b = static_cast<char*>(ctx->d_stage);
+  StageLayout lay;
+  const size_t o_keys = lay.take(cap * 3 * sizeof(int32_t)), o_means = lay.take(cap * 3 * sizeof(double));
+  const size_t o_covs = lay.take(cap * 9 * sizeof(double)), o_counts = lay.take(cap * sizeof(uint64_t));
+  VG_RC(ensure_stage(ctx, lay.total));
+  int32_t* d_keys = stage_at<int32_t>(ctx, o_keys);
+  double *d_means = stage_at<double>(ctx, o_means), *d_covs = stage_at<double>(ctx, o_covs);
+  uint64_t* d_counts = stage_at<uint64_t>(ctx, o_counts);
   VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
-  VG_HIP(ctx, launch_map_export(ctx->stream, ctx->table, ctx->slots, (uint32_t)cap,
-                                reinterpret_cast<int32_t*>(b), reinterpret_cast<double*>(b + kb),
-                                reinterpret_cast<double*>(b + kb + mb), reinterpret_cast<uint64_t*>(b + kb + mb + cb),
-                                ctx->d_counters));
+  VG_HIP(ctx, launch_map_export(ctx->stream, ctx->table, ctx->slots, (uint32_t)cap, d_keys, d_means, d_covs, d_counts, ctx->d_counters));
   arena_reset(ctx);
-  VG_RC(user_d2h(ctx, keys, b, cap * 3 * sizeof(int32_t)));
-  VG_RC(user_d2h(ctx, means, b + kb, cap * 3 * sizeof(double)));
-  VG_RC(user_d2h(ctx, covs, b + kb + mb, cap * 9 * sizeof(double)));
-  VG_RC(user_d2h(ctx, counts, b + kb + mb + cb, cap * sizeof(uint64_t)));
+  VG_RC(user_d2h(ctx, keys, d_keys, cap * 3 * sizeof(int32_t)));
+  VG_RC(user_d2h(ctx, means, d_means, cap * 3 * sizeof(double)));
+  VG_RC(user_d2h(ctx, covs, d_covs, cap * 9 * sizeof(double)));
+  VG_RC(user_d2h(ctx, counts, d_counts, cap * sizeof(uint64_t)));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   user_copies_finish(ctx);
   *written = cap;
@@ -295,12 +283,7 @@ int vgicp_map_export(vgicp_ctx* ctx, size_t capacity, int32_t* keys, double* mea
 // ---- the raw points of the map (include/vgicp_hip_map_points.h) ----
 int vgicp_map_points_size(const vgicp_ctx* ctx, size_t* points, size_t* capacity) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {
-    vgicp_ctx* lead = vgicp_multi_api::first(ctx);
-    const int rc = vgicp_map_points_size(lead, points, capacity);
-    if (rc != VGICP_OK) ctx->err = lead->err;
-    return rc;
-  }
+  if (ctx->multi) return forward_to_first(ctx, [&](vgicp_ctx* lead) { return vgicp_map_points_size(lead, points, capacity); });
   vgicp_ctx* c = const_cast<vgicp_ctx*>(ctx);
   { const int rc_settle = settle(c); if (rc_settle != VGICP_OK) return rc_settle; }
   if (!c->raw_on) return fail(c, VGICP_ERR_NOT_READY, "the map keeps no raw points: set VGICP_OPTION_MAP_RAW_POINTS");
@@ -321,12 +304,7 @@ int vgicp_map_points_size(const vgicp_ctx* ctx, size_t* points, size_t* capacity
 
 int vgicp_map_points_export(vgicp_ctx* ctx, size_t capacity, int32_t* keys, double* points, size_t* written) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {
-    vgicp_ctx* lead = vgicp_multi_api::first(ctx);
-    const int rc = vgicp_map_points_export(lead, capacity, keys, points, written);
-    if (rc != VGICP_OK) ctx->err = lead->err;
-    return rc;
-  }
+  if (ctx->multi) return forward_to_first(ctx, [&](vgicp_ctx* lead) { return vgicp_map_points_export(lead, capacity, keys, points, written); });
   if (!written) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "written is NULL");
   *written = 0;
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
@@ -338,12 +316,13 @@ int vgicp_map_points_export(vgicp_ctx* ctx, size_t capacity, int32_t* keys, doub
   // the live points are at most the entries appended (exact after the settle): room for that many, or for capacity
   const uint32_t used = (uint32_t)std::min<uint64_t>(ctx->raw_used_upper, ctx->raw_capacity);
   const size_t room = std::min<size_t>(capacity, used);
-  const size_t ob = (ctx->slots * sizeof(uint32_t) + 255) & ~size_t(255);
-  const size_t kb = (room * 3 * sizeof(int32_t) + 255) & ~size_t(255);
-  int rc = ensure_stage(ctx, ob + kb + room * 3 * sizeof(double));
-  if (rc != VGICP_OK) return rc;
-  char* b = static_cast<char*>(ctx->d_stage);
-  uint32_t* offsets = reinterpret_cast<uint32_t*>(b);
+  StageLayout lay;
+  const size_t o_offsets = lay.take(ctx->slots * sizeof(uint32_t)), o_keys = lay.take(room * 3 * sizeof(int32_t));
+  const size_t o_pts = lay.take(room * 3 * sizeof(double));
+  VG_RC(ensure_stage(ctx, lay.total));
+  uint32_t* offsets = stage_at<uint32_t>(ctx, o_offsets);
+  int32_t* d_keys = stage_at<int32_t>(ctx, o_keys);
+  double* d_pts = stage_at<double>(ctx, o_pts);
   // 1. every voxel's place in the output (its count points from there) and the total
   VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
   VG_HIP(ctx, launch_raw_offsets(ctx->stream, ctx->table, ctx->slots, offsets, ctx->d_counters));
@@ -353,10 +332,10 @@ int vgicp_map_points_export(vgicp_ctx* ctx, size_t capacity, int32_t* keys, doub
   if (cap == 0) return VGICP_OK;
   // 2. every live entry to its voxel's place + ordinal
   VG_HIP(ctx, launch_raw_scatter(ctx->stream, ctx->d_raw, used, ctx->d_ins_counters + 4, ctx->table, ctx->slots, offsets, (uint32_t)cap,
-                                 reinterpret_cast<int32_t*>(b + ob), reinterpret_cast<double*>(b + ob + kb)));
+                                 d_keys, d_pts));
   arena_reset(ctx);
-  VG_RC(user_d2h(ctx, keys, b + ob, cap * 3 * sizeof(int32_t)));
-  VG_RC(user_d2h(ctx, points, b + ob + kb, cap * 3 * sizeof(double)));
+  VG_RC(user_d2h(ctx, keys, d_keys, cap * 3 * sizeof(int32_t)));
+  VG_RC(user_d2h(ctx, points, d_pts, cap * 3 * sizeof(double)));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   user_copies_finish(ctx);
   *written = cap;

@@ -18,6 +18,14 @@ int settle_insert(vgicp_ctx* ctx);
 // So copies of 512 KB - 16 MB go through a page-locked arena of the context instead (smaller ones the runtime stages
 // itself; larger ones -- a 10 M-voxel map, a 100 k-point scan -- go up directly, once).  VGICP_STAGE_LIMIT=0: never.
 constexpr size_t kArenaBytes = 16u << 20, kArenaMin = 512u << 10;
+// VGICP_STAGE_LIMIT, read once per process (nullptr: unset); what a value means is its reader's business (0 switches the
+// arena and the scan upload's staging off, the scan preparation stages sweeps up to this many bytes)
+const size_t* stage_limit_env() {
+  static const char* const text = std::getenv("VGICP_STAGE_LIMIT");
+  static const size_t value = text ? (size_t)std::atoll(text) : 0;
+  return text ? &value : nullptr;
+}
+bool staging_off() { return stage_limit_env() && *stage_limit_env() == 0; }
 
 // The CPU copy into page-locked staging memory sets the pace of a frame's first phase (the device idles until the sweep
 // has arrived).  The destination is read next by the DMA engine, never by this CPU: streaming stores write it without
@@ -123,14 +131,13 @@ void arena_reset(vgicp_ctx* ctx) {
   ctx->pending_out.clear();
 }
 char* arena_take(vgicp_ctx* ctx, size_t bytes) {
-  static const bool off = std::getenv("VGICP_STAGE_LIMIT") && std::atoll(std::getenv("VGICP_STAGE_LIMIT")) == 0;
-  if (off || bytes <= kArenaMin || bytes > kArenaBytes - ctx->arena_used) return nullptr;
+  if (staging_off() || bytes <= kArenaMin || bytes > kArenaBytes - ctx->arena_used) return nullptr;
   if (!ctx->h_arena && hipHostMalloc(reinterpret_cast<void**>(&ctx->h_arena), kArenaBytes, 0) != hipSuccess) {
     ctx->h_arena = nullptr;
     return nullptr;
   }
   char* p = ctx->h_arena + ctx->arena_used;
-  ctx->arena_used += (bytes + 255) & ~size_t(255);
+  ctx->arena_used += align256(bytes);
   return p;
 }
 // page-locked memory (hipHostMalloc / vgicp_host_register): the DMA engine reads it in place, nothing to stage
@@ -184,6 +191,35 @@ int ensure_stage(vgicp_ctx* ctx, size_t bytes) {
   VG_HIP(ctx, hipMalloc(&ctx->d_stage, want));
   ctx->stage_bytes = want;
   return VGICP_OK;
+}
+
+// ctx->d_stage carved into pieces: taken in order, each at a 256-byte boundary.  First every piece's offset and the total
+// (for ensure_stage), then stage_at<T>() turns an offset into a pointer.
+struct StageLayout {
+  size_t total = 0;
+  size_t take(size_t bytes) { const size_t at = total; total += align256(bytes); return at; }
+};
+template <class T> T* stage_at(const vgicp_ctx* ctx, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(ctx->d_stage) + offset); }
+
+// A page-locked buffer of the context's owner thread is replaced by one of `bytes`, its first `zero_bytes` wiped.  *cap is
+// zeroed with the old buffer; the caller sets it (in its own unit) once everything that goes with the new one is in place.
+template <class T> int grow_pinned(vgicp_ctx* ctx, T** buf, size_t* cap, size_t bytes, size_t zero_bytes) {
+  if (*buf) VG_HIP(ctx, hipHostFree(*buf));
+  *buf = nullptr;
+  *cap = 0;
+  VG_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(buf), bytes, 0));
+  if (zero_bytes) std::memset(*buf, 0, zero_bytes);
+  return VGICP_OK;
+}
+
+// A call that is one device's work on a multi-device context: its first sub-context does it, and the error text comes
+// back with the status — or, stage_text, stays with the calling thread (vgicp_sweep_stage*: fail_stage keeps it per thread).
+template <class Call> int forward_to_first(const vgicp_ctx* ctx, Call call, bool stage_text = false) {
+  vgicp_ctx* first = vgicp_multi_api::first(ctx);
+  const int rc = call(first);
+  if (rc != VGICP_OK && stage_text) g_stage_error_ctx = ctx->id;
+  else if (rc != VGICP_OK) ctx->err = first->err;
+  return rc;
 }
 
 int alloc_table(vgicp_ctx* ctx, uint64_t slots, VoxelRecord** out) {
@@ -383,6 +419,20 @@ int ensure_scan(vgicp_ctx* ctx, size_t n) {
 void forget_fetch(vgicp_ctx* ctx) {
   ctx->fetch_open = false;
   ctx->fetch_sums_valid = false;
+}
+
+// A new resident scan begins: room for n points, the old scan's fetch void, and what vgicp_scan_info reports reset — it
+// belongs to a PREPARED scan (prep_voxel > 0), not to one that was uploaded or adopted as it came.
+int begin_scan(vgicp_ctx* ctx, size_t n, double prep_voxel, bool with_deskew) {
+  VG_RC(ensure_scan(ctx, n));
+  ++ctx->scan_generation;
+  forget_fetch(ctx);
+  ctx->scan_ready = false;
+  ctx->prep_voxel = prep_voxel;
+  ctx->prep_with_deskew = with_deskew;
+  ctx->prep_deskewed = ctx->prep_indefinite = 0;
+  ctx->stride = ctx->scan_capacity;
+  return VGICP_OK;
 }
 
 int ensure_log(vgicp_ctx* ctx, int iterations) {

@@ -158,17 +158,8 @@ int adopt_device_scan(vgicp_ctx* ctx, int src_device, const double* d_points, co
   VG_HIP(ctx, hipSetDevice(ctx->device));
   int rc = settle(ctx);
   if (rc != VGICP_OK) return rc;
-  rc = ensure_scan(ctx, n);
-  if (rc != VGICP_OK) return rc;
-  ++ctx->scan_generation;
-  forget_fetch(ctx);
-  ctx->scan_ready = false;
-  ctx->prep_voxel = prep_voxel;
-  ctx->prep_with_deskew = false;
-  ctx->prep_deskewed = 0;
-  ctx->prep_indefinite = 0;
+  VG_RC(begin_scan(ctx, n, prep_voxel, false));   // the source's down-sampling still describes the points
   ctx->n = (uint32_t)n;
-  ctx->stride = ctx->scan_capacity;
   if (ready) VG_HIP(ctx, hipStreamWaitEvent(ctx->stream, ready, 0));
   if (n > 0) {
     double* aos_pts = ctx->d_scan_aos;
@@ -181,7 +172,7 @@ int adopt_device_scan(vgicp_ctx* ctx, int src_device, const double* d_points, co
       VG_HIP(ctx, hipMemcpyAsync(aos_pts, d_points, n * 3 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
       VG_HIP(ctx, hipMemcpyAsync(aos_cov, d_covs, n * 9 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     }
-    if (++ctx->scan_seq == 0) ++ctx->scan_seq;
+    next_nonzero(ctx->scan_seq);
     ctx->scan_sym_known = true;
     VG_HIP(ctx, launch_pack_scan(ctx->stream, aos_pts, aos_cov, (uint32_t)n, ctx->d_scan, ctx->stride,
                                  ctx->d_ins_counters + 2, ctx->scan_seq));

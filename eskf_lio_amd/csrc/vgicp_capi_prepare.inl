@@ -27,49 +27,19 @@ struct DeskewOnDevice {
   uint32_t max_hits = 0;   // deskew_table: the largest hit count of any point (ordered queues)
   uint32_t* ends = nullptr;
 };
-// The raw points of a preparation that are still to be copied into page-locked staging memory (scan_prepare_enqueue):
-// enqueue_prepare launches the kernels that read them, copies (this thread and the crew's helpers), and launches the rest.
+// The raw points of a preparation as page-locked staging memory holds them (scan_prepare_enqueue): staged ahead of time,
+// or still being copied there by the crew — enqueue_prepare launches the kernels that read them, joins the copy (this
+// thread and the crew's helpers), and launches the rest.
 struct StagedPoints {
-  const double* points = nullptr;   // the caller's, n x 3; nullptr: the staging memory holds them already (vgicp_sweep_stage)
   char* stage = nullptr;            // page-locked, n x 24 bytes (+ padding)
-  uint32_t* flags = nullptr;        // one 64-byte line per unit
   hipEvent_t done = nullptr;        // recorded behind the last kernel that reads the staging memory
   uint32_t step = 0, off[3] = {0, 0, 0};   // staged ahead as sensor records (vgicp_sweep_stage_cloud2): PrepareArgs::src_step
-  uint32_t job = 0, seq = 0;        // the copy crew's job (posted by scan_prepare_enqueue: a helper is copying already)
-  bool helpers = false;
-  double t_post = 0.0;
+  CopyJob copy;                     // the crew's job (posted by scan_prepare_enqueue: a helper is copying already)
   CopyCrew* open_with = nullptr;    // the job is open: whoever leaves early has to finish it (the caller's buffer is read)
   ~StagedPoints() {
-    if (open_with) { open_with->work(job); (void)open_with->finish(); }
+    if (open_with) { open_with->work(copy.ticket); (void)open_with->finish(); }
   }
 };
-// The copy of a sweep's points into `stage`, opened to the crew: the helpers (if any are awake or worth waking) start at
-// once, the caller joins through crew->work(job) when it has launched the kernels that read the staging memory.
-void post_sweep_copy(vgicp_ctx* ctx, size_t n, StagedPoints* sp, const double* times = nullptr, double* times_stage = nullptr) {
-  if (++ctx->scan_seq == 0) ++ctx->scan_seq;
-  sp->seq = ctx->scan_seq;
-  const uint32_t unit = pack_arena_unit();
-  sp->helpers = ctx->upload_threads > 1 && n * 3 * sizeof(double) >= (1u << 20);
-  if (!ctx->crew) ctx->crew = new CopyCrew;
-  CopyCrew* crew = ctx->crew;
-  if (sp->helpers && crew->th.empty()) crew->start(ctx->upload_threads - 1);
-  crew->pts = reinterpret_cast<const char*>(sp->points);
-  crew->cov = reinterpret_cast<const char*>(times);           // a unit's capture times travel with its points (or nullptr)
-  crew->apts = sp->stage;
-  crew->acov = reinterpret_cast<char*>(times_stage);
-  crew->flags = sp->flags;
-  crew->n = (uint32_t)n;
-  crew->unit = unit;
-  crew->units = (uint32_t)((n + unit - 1) / unit);
-  crew->seq = sp->seq;
-  crew->size_a = 24;
-  crew->size_b = times ? 8 : 0;
-  crew->copy = stage_copy;
-  crew->copy_b_form = nullptr;
-  sp->t_post = now_seconds();
-  sp->job = crew->post(sp->helpers);
-  sp->open_with = crew;
-}
 int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, int knn, const double* extrinsic16,
                     const DeskewOnDevice& dk, void* scratch, double* d_out_pts, double* d_out_covs,
                     unsigned long long* d_out_idx, double* soa, uint64_t soa_stride, StagedPoints* staged = nullptr) {
@@ -78,7 +48,7 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
   if (rc != VGICP_OK) return rc;
   const int debug = ctx->dev.debug_prep;
   if (debug) VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 72 * sizeof(uint32_t), ctx->stream));
-  if (++ctx->prep_epoch == 0) ++ctx->prep_epoch;
+  next_nonzero(ctx->prep_epoch);
   PrepareArgs a;
   std::memset(&a, 0, sizeof a);
   a.pts = d_pts;
@@ -111,7 +81,7 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
   if (ctx->stage_events) ctx->ev_stage_set[6] = true;
   if (!staged) {
     VG_HIP(ctx, launch_prepare(ctx->stream, a));
-  } else if (!staged->points) {
+  } else if (!staged->open_with) {
     // staged ahead of time: the prologue reads the page-locked copy where it lies, nothing to wait for
     a.src_points = staged->stage;
     a.src_flags = nullptr;
@@ -123,30 +93,21 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
   } else {
     // the sweep's points go up without a copy command: the copy threads fill the staging memory unit by unit, the
     // prologue (launched FIRST) reads the units over PCIe as they are published (see scan_upload_enqueue)
-    const uint32_t spin_limit = ctx->dev.pack_spin_limit ? ctx->dev.pack_spin_limit : kPackSpinLimit;
-    const long debug_delay_us = ctx->dev.debug_upload_delay_us;
-    CopyCrew* crew = ctx->crew;
-    const bool want_helpers = staged->helpers;
-    const uint32_t job = staged->job;
-    const double t_post = staged->t_post;
     a.src_points = staged->stage;
-    a.src_flags = staged->flags;
-    a.src_seq = staged->seq;
+    a.src_flags = staged->copy.flags;
+    a.src_seq = staged->copy.seq;
     a.src_unit = pack_arena_unit();
-    a.src_spin = spin_limit;
+    a.src_spin = ctx->dev.pack_spin_limit ? ctx->dev.pack_spin_limit : kPackSpinLimit;
     const hipError_t e_head = launch_prepare_head(ctx->stream, a);
-    if (debug_delay_us > 0 && !want_helpers) std::this_thread::sleep_for(std::chrono::microseconds(debug_delay_us));
-    crew->work(job);
-    const bool crew_done = crew->finish();   // always: the caller's buffer is free again on return
-    staged->open_with = nullptr;
+    bool slow = false;
+    staged->open_with = nullptr;   // joined here, whatever the outcome: the caller's buffer is free again on return
+    rc = crew_join(ctx, staged->copy, &slow);
     if (e_head != hipSuccess) return fail_hip(ctx, e_head, "launch_prepare_head");
-    if (!crew_done) return crew_gave_up(ctx);
-    if (now_seconds() - t_post > kCrewSlowSeconds) {
+    if (rc != VGICP_OK) return rc;
+    if (slow) {
       // the copy threads were held up so long that a workgroup of the prologue may have stopped waiting (and said so in
       // the counter block under this epoch): everything is staged now — the head once more, nothing to wait for
-      ++ctx->upload_slow;
-      if (++ctx->prep_epoch == 0) ++ctx->prep_epoch;
-      a.epoch = ctx->prep_epoch;
+      a.epoch = next_nonzero(ctx->prep_epoch);
       a.src_flags = nullptr;
       VG_HIP(ctx, launch_prepare_head(ctx->stream, a));
     }
@@ -257,7 +218,7 @@ struct VoxelKeyHostHash {   // open3d::utility::hash_eigen<Eigen::Vector3i>: boo
   }
 };
 // perm[o] = the ascending-order slot of the point the reference emits o-th.  pts: m x 3, the kept points in ascending input index.
-void reference_order_of(const double* pts, size_t m, double voxel_size, std::vector<uint32_t>* perm) {
+int reference_order_of(vgicp_ctx* ctx, const double* pts, size_t m, double voxel_size, std::vector<uint32_t>* perm) {
   std::unordered_map<std::array<int32_t, 3>, uint32_t, VoxelKeyHostHash> grid;
   for (size_t i = 0; i < m; ++i) {
     std::array<int32_t, 3> key;   // the preprocessor's getVoxelIndex: floor(p / voxel) as int (src/CloudPreprocessor.cpp:129-133)
@@ -267,6 +228,8 @@ void reference_order_of(const double* pts, size_t m, double voxel_size, std::vec
   perm->clear();
   perm->reserve(grid.size());
   for (const auto& kv : grid) perm->push_back(kv.second);
+  if (perm->size() != m) return fail(ctx, VGICP_ERR_HIP, "reference order: the kept points do not lie in distinct voxels");
+  return VGICP_OK;
 }
 // The resident scan (just prepared, stream synchronised, ctx->n kept points) is put into the reference's order in place.
 int reorder_resident_scan(vgicp_ctx* ctx, double voxel_size) {
@@ -276,15 +239,12 @@ int reorder_resident_scan(vgicp_ctx* ctx, double voxel_size) {
   VG_HIP(ctx, hipMemcpyAsync(pts.data(), ctx->d_scan_aos, m * 24, hipMemcpyDeviceToHost, ctx->stream));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   std::vector<uint32_t> perm;
-  reference_order_of(pts.data(), m, voxel_size, &perm);
-  if (perm.size() != m) return fail(ctx, VGICP_ERR_HIP, "reference order: the kept points do not lie in distinct voxels");
-  const size_t pb = (m * 24 + 255) & ~size_t(255), cb = (m * 72 + 255) & ~size_t(255), ib = (m * 4 + 255) & ~size_t(255);
-  const int rc = ensure_stage(ctx, pb + cb + ib);
-  if (rc != VGICP_OK) return rc;
-  char* base = static_cast<char*>(ctx->d_stage);
-  double* t_pts = reinterpret_cast<double*>(base);
-  double* t_cov = reinterpret_cast<double*>(base + pb);
-  uint32_t* d_perm = reinterpret_cast<uint32_t*>(base + pb + cb);
+  VG_RC(reference_order_of(ctx, pts.data(), m, voxel_size, &perm));
+  StageLayout lay;
+  const size_t o_pts = lay.take(m * 24), o_cov = lay.take(m * 72), o_perm = lay.take(m * 4);
+  VG_RC(ensure_stage(ctx, lay.total));
+  double *t_pts = stage_at<double>(ctx, o_pts), *t_cov = stage_at<double>(ctx, o_cov);
+  uint32_t* d_perm = stage_at<uint32_t>(ctx, o_perm);
   double* aos_cov = ctx->d_scan_aos + 3 * ctx->scan_capacity;
   VG_HIP(ctx, hipMemcpyAsync(d_perm, perm.data(), m * 4, hipMemcpyHostToDevice, ctx->stream));
   VG_HIP(ctx, launch_gather_scan(ctx->stream, d_perm, (uint32_t)m, ctx->d_scan_aos, aos_cov, nullptr, t_pts, t_cov, nullptr));
@@ -309,12 +269,10 @@ int vgicp_preprocess(vgicp_ctx* ctx, size_t n, const double* points, double voxe
                      size_t capacity, double* out_points, double* out_covs, uint64_t* out_index,
                      size_t* kept) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {  // scan preparation with the result returned to the host: one device's work
-    vgicp_ctx* first = vgicp_multi_api::first(ctx);
-    const int rc = vgicp_preprocess(first, n, points, voxel_size, knn, capacity, out_points, out_covs, out_index, kept);
-    if (rc != VGICP_OK) ctx->err = first->err;
-    return rc;
-  }
+  if (ctx->multi)   // scan preparation with the result returned to the host: one device's work
+    return forward_to_first(ctx, [&](vgicp_ctx* first) {
+      return vgicp_preprocess(first, n, points, voxel_size, knn, capacity, out_points, out_covs, out_index, kept);
+    });
   if (!kept) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "kept is NULL");
   *kept = 0;
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
@@ -323,21 +281,17 @@ int vgicp_preprocess(vgicp_ctx* ctx, size_t n, const double* points, double voxe
   if (n == 0) return VGICP_OK;
   if (!points) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL scan pointer");
   VG_HIP(ctx, hipSetDevice(ctx->device));
-  // stage: [points 3n][out points 3n][out covs 9n][out index n][scratch]
-  const size_t pb = (n * 3 * sizeof(double) + 255) & ~size_t(255);
-  const size_t cb = (n * 9 * sizeof(double) + 255) & ~size_t(255);
-  const size_t ib = (n * sizeof(uint64_t) + 255) & ~size_t(255);
-  const size_t sb = preprocess_scratch_bytes((uint32_t)n);
-  rc = ensure_stage(ctx, pb + pb + cb + ib + sb);
-  if (rc != VGICP_OK) return rc;
-  char* base = static_cast<char*>(ctx->d_stage);
-  double* d_out_pts = reinterpret_cast<double*>(base + pb);
-  double* d_out_covs = reinterpret_cast<double*>(base + 2 * pb);
-  unsigned long long* d_out_idx = reinterpret_cast<unsigned long long*>(base + 2 * pb + cb);
+  StageLayout lay;
+  const size_t o_in = lay.take(n * 3 * sizeof(double)), o_pts = lay.take(n * 3 * sizeof(double));
+  const size_t o_covs = lay.take(n * 9 * sizeof(double)), o_idx = lay.take(n * sizeof(uint64_t));
+  const size_t o_scratch = lay.take(preprocess_scratch_bytes((uint32_t)n));
+  VG_RC(ensure_stage(ctx, lay.total));
+  double *d_in = stage_at<double>(ctx, o_in), *d_out_pts = stage_at<double>(ctx, o_pts), *d_out_covs = stage_at<double>(ctx, o_covs);
+  unsigned long long* d_out_idx = stage_at<unsigned long long>(ctx, o_idx);
   arena_reset(ctx);
-  VG_RC(user_h2d(ctx, base, points, n * 3 * sizeof(double)));
-  rc = enqueue_prepare(ctx, reinterpret_cast<double*>(base), n, voxel_size, knn, nullptr, DeskewOnDevice(),
-                       base + 2 * pb + cb + ib, d_out_pts, d_out_covs, d_out_idx, nullptr, 0);
+  VG_RC(user_h2d(ctx, d_in, points, n * 3 * sizeof(double)));
+  rc = enqueue_prepare(ctx, d_in, n, voxel_size, knn, nullptr, DeskewOnDevice(), stage_at<char>(ctx, o_scratch), d_out_pts,
+                       d_out_covs, d_out_idx, nullptr, 0);
   if (rc != VGICP_OK) return rc;
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   uint32_t m = 0;
@@ -354,8 +308,7 @@ int vgicp_preprocess(vgicp_ctx* ctx, size_t n, const double* points, double voxe
   user_copies_finish(ctx);
   if (ctx->reference_order && m > 1) {   // VGICP_OPTION_REFERENCE_ORDER: the host arrays, through copies
     std::vector<uint32_t> perm;
-    reference_order_of(out_points, m, voxel_size, &perm);
-    if (perm.size() != m) return fail(ctx, VGICP_ERR_HIP, "reference order: the kept points do not lie in distinct voxels");
+    VG_RC(reference_order_of(ctx, out_points, m, voxel_size, &perm));
     std::vector<double> p(out_points, out_points + 3 * (size_t)m), c(out_covs, out_covs + 9 * (size_t)m);
     std::vector<uint64_t> ix;
     if (out_index) ix.assign(out_index, out_index + m);
@@ -485,12 +438,8 @@ bool deskew_table(size_t n, const double* point_time, size_t num_states, const d
 int vgicp_deskew(vgicp_ctx* ctx, size_t n, double* points, const double* point_time, size_t num_states,
                  const double* states, int64_t* transformed) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {
-    vgicp_ctx* first = vgicp_multi_api::first(ctx);
-    const int rc = vgicp_deskew(first, n, points, point_time, num_states, states, transformed);
-    if (rc != VGICP_OK) ctx->err = first->err;
-    return rc;
-  }
+  if (ctx->multi)
+    return forward_to_first(ctx, [&](vgicp_ctx* first) { return vgicp_deskew(first, n, points, point_time, num_states, states, transformed); });
   if (!transformed) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "transformed is NULL");
   *transformed = 0;
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
@@ -505,17 +454,12 @@ int vgicp_deskew(vgicp_ctx* ctx, size_t n, double* points, const double* point_t
     return VGICP_OK;
   }
   VG_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t pb = (n * 3 * sizeof(double) + 255) & ~size_t(255);
-  const size_t tb = (n * sizeof(double) + 255) & ~size_t(255);
-  const size_t sb = (used * 13 * sizeof(double) + 255) & ~size_t(255);
-  const size_t eb = (deskew_scratch_words((uint32_t)used) * sizeof(uint32_t) + 255) & ~size_t(255);
-  int rc = ensure_stage(ctx, pb + tb + sb + eb);
-  if (rc != VGICP_OK) return rc;
-  char* base = static_cast<char*>(ctx->d_stage);
-  double* d_pts = reinterpret_cast<double*>(base);
-  double* d_time = reinterpret_cast<double*>(base + pb);
-  double* d_states = reinterpret_cast<double*>(base + pb + tb);
-  uint32_t* d_ends = reinterpret_cast<uint32_t*>(base + pb + tb + sb);
+  StageLayout lay;
+  const size_t o_pts = lay.take(n * 3 * sizeof(double)), o_time = lay.take(n * sizeof(double));
+  const size_t o_states = lay.take(used * 13 * sizeof(double)), o_ends = lay.take(deskew_scratch_words((uint32_t)used) * sizeof(uint32_t));
+  VG_RC(ensure_stage(ctx, lay.total));
+  double *d_pts = stage_at<double>(ctx, o_pts), *d_time = stage_at<double>(ctx, o_time), *d_states = stage_at<double>(ctx, o_states);
+  uint32_t* d_ends = stage_at<uint32_t>(ctx, o_ends);
   arena_reset(ctx);
   VG_RC(user_h2d(ctx, d_pts, points, n * 3 * sizeof(double)));
   VG_RC(user_h2d(ctx, d_time, point_time, n * sizeof(double)));
@@ -530,47 +474,60 @@ int vgicp_deskew(vgicp_ctx* ctx, size_t n, double* points, const double* point_t
 }
 
 namespace {
+bool trace_prepare() { static const bool on = std::getenv("VGICP_TRACE_PREPARE") != nullptr; return on; }   // developer aid: where the host time of the enqueue goes
+
+// The slot's raw-sweep memory for n points: [unit flags][points, padded][capture times], the flags wiped.
+struct RawSweepSlot { uint32_t* flags; char* points; double* times; };
+int raw_sweep_slot(vgicp_ctx* ctx, uint32_t slot, size_t n, RawSweepSlot* out) {
+  const size_t flag_bytes = ((n + pack_arena_unit() - 1) / pack_arena_unit() + 1) * 64;
+  const size_t pts_room = align256(n * 3 * sizeof(double) + 16);
+  const size_t need = flag_bytes + pts_room + n * sizeof(double);
+  if (ctx->raw_stage_cap[slot] < need) {
+    const size_t cap = need * 5 / 4 + 4096;   // a quarter more; all of it flags of "no sweep yet" (a sequence number is never 0)
+    VG_RC(grow_pinned(ctx, &ctx->h_raw_stage[slot], &ctx->raw_stage_cap[slot], cap, cap));
+    ctx->raw_stage_cap[slot] = cap;
+  }
+  char* stage = ctx->h_raw_stage[slot];
+  // a flag only ever means "this unit of THIS sweep": the flag area moves with the sweep's size, so it is wiped
+  std::memset(stage, 0, flag_bytes);
+  *out = {reinterpret_cast<uint32_t*>(stage), stage + flag_bytes, reinterpret_cast<double*>(stage + flag_bytes + pts_room)};
+  return VGICP_OK;
+}
+
 // CloudPreprocessor::process enqueued on the context's stream with the prepared scan left resident: upload of the
 // raw sweep, then launch_prepare writing the AoS scan AND the SoA planes the registration reads. Nothing is waited
-// for: the scan is `pending` (its size is on the device, ctx->n_upper bounds it).
+// for: the scan is `pending` (its size is on the device, ctx->n_upper bounds it).  How the sweep reaches the device —
+// route, capture times, the slot's event — is plan_prepare's decision (vgicp_prepare_plan.h); this function carries it out.
 // ahead: the sweep was staged by vgicp_sweep_stage (points / point_time then point INTO that page-locked slot and nothing
 // is copied here; its `done` event is recorded behind the kernels that read it).
 int scan_prepare_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const double* point_time, size_t num_states,
                          const double* states, const double extrinsic[16], double voxel_size, int knn,
                          vgicp_ctx::AheadSlot* ahead = nullptr) {
-  int rc = check_preprocess_args(ctx, n, voxel_size, knn);
-  if (rc != VGICP_OK) return rc;
+  // ---- check ----
+  VG_RC(check_preprocess_args(ctx, n, voxel_size, knn));
   if ((ctx->comm || ctx->peers_connected) && !ctx->owner) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the prepared scan is whole: not available on a communicator (shards)");
   if (n > 0 && !points) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL scan pointer");
   const bool with_deskew = n > 0 && num_states > 0;
   if (with_deskew && (!point_time || !states)) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pointer");
   if (num_states > 0x7FFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "state queue too large");
   VG_HIP(ctx, hipSetDevice(ctx->device));
-  rc = ensure_scan(ctx, n);
-  if (rc != VGICP_OK) return rc;
-  ++ctx->scan_generation;
-  forget_fetch(ctx);
-  ctx->scan_ready = false;
+  // ---- the new scan ----
+  VG_RC(begin_scan(ctx, n, voxel_size, with_deskew));
   ctx->scan_pending = false;
-  ctx->n = 0;
-  ctx->n_upper = 0;
-  ctx->stride = ctx->scan_capacity;
-  ctx->prep_with_deskew = with_deskew;
-  ctx->prep_voxel = voxel_size;
-  ctx->prep_deskewed = 0;
-  ctx->prep_indefinite = 0;
+  ctx->n = ctx->n_upper = 0;
   if (n == 0) {
     ctx->scan_ready = true;
     return VGICP_OK;
   }
+  // ---- the deskew's table ----
   std::vector<double> host;
   size_t used = 0;
   bool ordered = false;
   uint32_t max_hits = 0;
-  static const bool trace_table = std::getenv("VGICP_TRACE_PREPARE") != nullptr;
-  const double tt0 = trace_table ? now_seconds() : 0.0;
+  const bool trace = trace_prepare();
+  const double tt0 = trace ? now_seconds() : 0.0;
   const bool table_ok = !with_deskew || deskew_table(n, point_time, num_states, states, host, used, ordered, &max_hits);
-  if (trace_table) std::fprintf(stderr, "[vgicp trace] deskew_table %.3f ms\n", (now_seconds() - tt0) * 1e3);
+  if (trace) std::fprintf(stderr, "[vgicp trace] deskew_table %.3f ms\n", (now_seconds() - tt0) * 1e3);
   if (!table_ok) {
     ctx->prep_deskewed = -1;
     return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the IMU states do not bracket the end of the sweep");
@@ -578,24 +535,22 @@ int scan_prepare_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const d
   // the fused prologue keeps the segment ends of the states that can own points in LDS (4 bytes each, 64 KB by default)
   if (used > kPrepareMaxStates)
     return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "more than 16000 IMU states inside one sweep: use vgicp_deskew + vgicp_preprocess");
-  // stage: [points 3n][times n][state table][segment ends + first hits][kept index n][scratch]
-  const size_t pb = (n * 3 * sizeof(double) + 255) & ~size_t(255);
-  const size_t tb = (n * sizeof(double) + 255) & ~size_t(255);
-  const size_t sb = (used * 13 * sizeof(double) + 255) & ~size_t(255);
-  const size_t eb = (deskew_scratch_words((uint32_t)used) * sizeof(uint32_t) + 255) & ~size_t(255);
-  const size_t ib = (n * sizeof(uint64_t) + 255) & ~size_t(255);
-  rc = ensure_stage(ctx, pb + tb + sb + eb + ib + preprocess_scratch_bytes((uint32_t)n));
-  if (rc != VGICP_OK) return rc;
-  char* base = static_cast<char*>(ctx->d_stage);
-  double* d_pts = reinterpret_cast<double*>(base);
-  double* d_time = reinterpret_cast<double*>(base + pb);
-  double* d_states = reinterpret_cast<double*>(base + pb + tb);
-  unsigned long long* d_idx = reinterpret_cast<unsigned long long*>(base + pb + tb + sb + eb);
-  void* scratch = base + pb + tb + sb + eb + ib;
+  // ---- the plan ----
+  PrepareFacts facts;
+  facts.n = n, facts.with_deskew = with_deskew, facts.used = used, facts.ordered = ordered, facts.ahead = ahead != nullptr;
+  if (stage_limit_env()) facts.stage_limit = *stage_limit_env();
+  facts.bounds_fused = prepare_bounds_fused((uint32_t)n, (uint32_t)used, ordered);
+  const PreparePlan plan = plan_prepare(facts);
+  // ---- the layout: [points 3n][times n][state table][segment ends + first hits][kept index n][scratch] ----
+  StageLayout lay;
+  const size_t o_pts = lay.take(n * 3 * sizeof(double)), o_time = lay.take(n * sizeof(double));
+  const size_t o_states = lay.take(used * 13 * sizeof(double)), o_ends = lay.take(deskew_scratch_words((uint32_t)used) * sizeof(uint32_t));
+  const size_t o_idx = lay.take(n * sizeof(uint64_t)), o_scratch = lay.take(preprocess_scratch_bytes((uint32_t)n));
+  VG_RC(ensure_stage(ctx, lay.total));
+  double *d_pts = stage_at<double>(ctx, o_pts), *d_time = stage_at<double>(ctx, o_time), *d_states = stage_at<double>(ctx, o_states);
   if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[0], ctx->stream)); ctx->ev_stage_set[0] = true; }
-  static const bool trace = std::getenv("VGICP_TRACE_PREPARE") != nullptr;   // developer aid: where the host time of the enqueue goes
   const double tr0 = trace ? now_seconds() : 0.0;
-  // two pinned slots in turn, guarded by one event each (recorded behind the last copy out of the slot)
+  // two pinned slots in turn (state table, crew-staged raw sweep), guarded by one event each (recorded behind the last copy out of the slot)
   const uint32_t slot = ctx->state_table_next++ & 1u;
   if (ctx->ev_state_table[slot]) {
     // the copies out of this slot two preparations ago: long complete, normally (no host wait then)
@@ -603,94 +558,71 @@ int scan_prepare_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const d
   } else {
     VG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_state_table[slot], hipEventDisableTiming));
   }
-  const size_t raw_bytes = n * 3 * sizeof(double) + (with_deskew ? n * sizeof(double) : 0);
-  static const size_t stage_limit = std::getenv("VGICP_STAGE_LIMIT") ? (size_t)std::atoll(std::getenv("VGICP_STAGE_LIMIT")) : (16u << 20);
-  const bool staged = ahead != nullptr || raw_bytes <= stage_limit;   // larger sweeps go up straight from the caller's memory
-  const bool walk = with_deskew && !(ordered && used <= kDeskewMaxStates);   // the serial bounds walk reads the times many times over: on the device
+  // ---- the sweep, by the plan's route ----
   StagedPoints sp;
-  const double* time_src = nullptr;   // where the deskew's first kernel reads the capture times
-  if (ahead) {
-    sp.points = nullptr;
-    sp.stage = const_cast<char*>(reinterpret_cast<const char*>(points));
-    sp.done = ahead->done;
-    sp.step = ahead->step;
-    for (int k = 0; k < 3; ++k) sp.off[k] = ahead->off[k];
-    if (with_deskew) {
-      time_src = point_time;
-      if (walk) VG_HIP(ctx, hipMemcpyAsync(d_time, point_time, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
-  } else if (staged) {
-    // slot layout: [unit flags][points, padded][capture times]
-    const size_t pts_bytes = n * 3 * sizeof(double);
-    const size_t flag_bytes = ((n + pack_arena_unit() - 1) / pack_arena_unit() + 1) * 64;
-    const size_t pts_room = (pts_bytes + 16 + 255) & ~size_t(255);
-    if (ctx->raw_stage_cap[slot] < flag_bytes + pts_room + n * sizeof(double)) {
-      if (ctx->h_raw_stage[slot]) VG_HIP(ctx, hipHostFree(ctx->h_raw_stage[slot]));
-      ctx->h_raw_stage[slot] = nullptr;
-      ctx->raw_stage_cap[slot] = 0;
-      const size_t cap = (flag_bytes + pts_room + n * sizeof(double)) * 5 / 4 + 4096;   // a quarter more
-      VG_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_raw_stage[slot]), cap, 0));
-      std::memset(ctx->h_raw_stage[slot], 0, cap);   // flags of "no sweep yet" (a sequence number is never 0)
-      ctx->raw_stage_cap[slot] = cap;
-    }
-    char* stage = ctx->h_raw_stage[slot];
-    // a flag only ever means "this unit of THIS sweep": the flag area moves with the sweep's size, so it is wiped
-    std::memset(stage, 0, flag_bytes);
-    sp.points = points;
-    sp.flags = reinterpret_cast<uint32_t*>(stage);
-    sp.stage = stage + flag_bytes;
-    sp.done = ctx->ev_state_table[slot];
-    double* times_stage = reinterpret_cast<double*>(stage + flag_bytes + pts_room);
-    // the prologue finds the deskew's segments itself and reads a workgroup's capture times behind the wait for its
-    // unit: they are staged unit by unit with the points, by whoever copies the unit
-    const bool times_by_unit = with_deskew && !walk && prepare_bounds_fused((uint32_t)n, (uint32_t)used, ordered);
-    post_sweep_copy(ctx, n, &sp, times_by_unit ? point_time : nullptr, times_by_unit ? times_stage : nullptr);   // a helper that is awake starts now
-    if (times_by_unit) {
-      time_src = times_stage;
-    } else if (with_deskew) {
+  const double* staged_times = nullptr;   // page-locked capture times (TimeSource::Ahead / Staged, TimeCopy::FromAhead / FromStaged)
+  switch (plan.route) {
+    case PrepareRoute::Ahead:
+      sp.stage = const_cast<char*>(reinterpret_cast<const char*>(points));
+      sp.done = ahead->done;
+      sp.step = ahead->step;
+      for (int k = 0; k < 3; ++k) sp.off[k] = ahead->off[k];
+      staged_times = point_time;
+      break;
+    case PrepareRoute::Staged: {
+      RawSweepSlot raw;
+      VG_RC(raw_sweep_slot(ctx, slot, n, &raw));
+      sp.stage = raw.points;
+      sp.done = ctx->ev_state_table[slot];
+      staged_times = raw.times;
+      CopyJob& job = sp.copy;
+      job.flags = raw.flags;
+      job.src_a = points, job.dst_a = raw.points, job.size_a = 3 * sizeof(double);
+      // the prologue finds the deskew's segments itself and reads a workgroup's capture times behind the wait for its
+      // unit: they are staged unit by unit with the points, by whoever copies the unit
+      if (plan.times_by_unit) job.src_b = point_time, job.dst_b = reinterpret_cast<char*>(raw.times), job.size_b = sizeof(double);
+      job.n = n, job.seq = next_nonzero(ctx->scan_seq);
+      job.bytes = n * 3 * sizeof(double), job.wake_bytes = 1u << 20;
+      crew_post(ctx, &job);   // a helper that is awake starts now
+      sp.open_with = ctx->crew;
       // this thread: the capture times first (a sixth of the bytes): the deskew's bounds need nothing else, and its
       // kernel reads them where they are staged
-      stage_copy(times_stage, point_time, n * sizeof(double));
-      time_src = times_stage;
-      if (walk) VG_HIP(ctx, hipMemcpyAsync(d_time, times_stage, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      if (plan.times_by_owner) stage_copy(raw.times, point_time, n * sizeof(double));
+      break;
     }
-  } else {
-    VG_HIP(ctx, hipMemcpyAsync(d_pts, points, n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (with_deskew) VG_HIP(ctx, hipMemcpyAsync(d_time, point_time, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    case PrepareRoute::InPlace:
+      VG_HIP(ctx, hipMemcpyAsync(d_pts, points, n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      break;
   }
+  if (plan.time_copy != TimeCopy::None)
+    VG_HIP(ctx, hipMemcpyAsync(d_time, plan.time_copy == TimeCopy::FromCaller ? point_time : staged_times, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   const double tr1 = trace ? now_seconds() : 0.0;
+  // ---- the deskew as the device sees it ----
   DeskewOnDevice dk;
   if (with_deskew) {
+    // the table through the slot's pinned copy (an enqueue-only preparation returns before the copy has run)
     if (ctx->state_table_cap[slot] < used * 13) {
-      if (ctx->h_state_table[slot]) VG_HIP(ctx, hipHostFree(ctx->h_state_table[slot]));
-      ctx->h_state_table[slot] = nullptr;
-      ctx->state_table_cap[slot] = 0;
       const size_t cap = std::max<size_t>(used * 13 * 2, 13 * 256);
-      VG_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_state_table[slot]), cap * sizeof(double), 0));
+      VG_RC(grow_pinned(ctx, &ctx->h_state_table[slot], &ctx->state_table_cap[slot], cap * sizeof(double), 0));
       ctx->state_table_cap[slot] = cap;
     }
     std::memcpy(ctx->h_state_table[slot], host.data(), used * 13 * sizeof(double));
     VG_HIP(ctx, hipMemcpyAsync(d_states, ctx->h_state_table[slot], used * 13 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    dk.point_time = (staged && !walk) ? time_src : d_time;
-    dk.state_time = d_states;
-    dk.poses = d_states + used;
-    dk.states = (uint32_t)used;
-    dk.ordered = ordered;
-    dk.max_hits = max_hits;
-    dk.ends = reinterpret_cast<uint32_t*>(base + pb + tb + sb);
+    dk = {plan.time_source == TimeSource::Device ? d_time : staged_times, d_states, d_states + used, (uint32_t)used, ordered,
+          max_hits, stage_at<uint32_t>(ctx, o_ends)};
   }
-  if (!staged) {
+  if (plan.event == StateTableEvent::BeforeAndWait) {
     VG_HIP(ctx, hipEventRecord(ctx->ev_state_table[slot], ctx->stream));   // behind the last copy out of this slot's pinned buffers
     // a sweep too large to stage was handed to the runtime in place: its copies have to be over before the call returns,
     // because the caller's buffers are free again on return whatever the size (the drop-in releases the capture times at once)
     VG_HIP(ctx, hipEventSynchronize(ctx->ev_state_table[slot]));
   }
   const double tr2 = trace ? now_seconds() : 0.0;
-  // (staged: the slot's event is recorded inside, behind the kernels that read the staging memory)
-  rc = enqueue_prepare(ctx, d_pts, n, voxel_size, knn, extrinsic, dk, scratch, ctx->d_scan_aos,
-                       ctx->d_scan_aos + 3 * ctx->scan_capacity, d_idx, ctx->d_scan, ctx->stride, staged ? &sp : nullptr);
-  if (rc != VGICP_OK) return rc;
-  if (ahead) VG_HIP(ctx, hipEventRecord(ctx->ev_state_table[slot], ctx->stream));   // (the state table's pinned slot)
+  // ---- the kernels (StateTableEvent::Inside: the slot's event is sp.done, recorded behind those that read the slot) ----
+  VG_RC(enqueue_prepare(ctx, d_pts, n, voxel_size, knn, extrinsic, dk, stage_at<char>(ctx, o_scratch), ctx->d_scan_aos,
+                        ctx->d_scan_aos + 3 * ctx->scan_capacity, stage_at<unsigned long long>(ctx, o_idx), ctx->d_scan, ctx->stride,
+                        plan.route == PrepareRoute::InPlace ? nullptr : &sp));
+  if (plan.event == StateTableEvent::After) VG_HIP(ctx, hipEventRecord(ctx->ev_state_table[slot], ctx->stream));   // (the state table's pinned slot)
   if (trace)
     std::fprintf(stderr, "[vgicp trace] prepare enqueue: staging + points copy %.3f ms, times + states copies %.3f ms, kernels %.3f ms\n",
                  (tr1 - tr0) * 1e3, (tr2 - tr1) * 1e3, (now_seconds() - tr2) * 1e3);
@@ -703,8 +635,7 @@ int scan_prepare_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const d
   if (ctx->reference_order) {
     // the parity mode: this preparation is waited for, and its result put into the reference's sequence, before anything
     // else sees it (an "async" preparation is synchronous under this option)
-    rc = settle(ctx);
-    if (rc != VGICP_OK) return rc;
+    VG_RC(settle(ctx));
     return reorder_resident_scan(ctx, voxel_size);
   }
   return VGICP_OK;
@@ -751,7 +682,7 @@ int stage_sweep_ahead(vgicp_ctx* ctx, size_t n, const void* data, const double* 
   }
   if (!slot) return fail_stage(ctx, VGICP_ERR_NOT_READY, "three sweeps are staged ahead already: prepare one (or vgicp_sweep_unstage it) first");
   const size_t rec = step ? step : 3 * sizeof(double);
-  const size_t pts_room = (n * rec + 16 + 255) & ~size_t(255);
+  const size_t pts_room = align256(n * rec + 16);
   const bool has_times = step ? off_time != SIZE_MAX : times != nullptr;
   const size_t need = pts_room + n * sizeof(double);
   if (slot->cap < need) {
@@ -790,11 +721,7 @@ int stage_sweep_ahead(vgicp_ctx* ctx, size_t n, const void* data, const double* 
 int vgicp_sweep_stage(vgicp_ctx* ctx, size_t n, const double* points, const double* point_time, uint64_t* ticket) {
   if (!ctx || !ticket) return VGICP_ERR_BAD_ARGUMENT;
   *ticket = 0;
-  if (ctx->multi) {
-    const int rc = vgicp_sweep_stage(vgicp_multi_api::first(ctx), n, points, point_time, ticket);
-    if (rc != VGICP_OK) g_stage_error_ctx = ctx->id;
-    return rc;
-  }
+  if (ctx->multi) return forward_to_first(ctx, [&](vgicp_ctx* first) { return vgicp_sweep_stage(first, n, points, point_time, ticket); }, true);
   if (n == 0 || !points) return fail_stage(ctx, VGICP_ERR_BAD_ARGUMENT, "empty sweep");
   if (n > 0xFFFFFFFFull) return fail_stage(ctx, VGICP_ERR_BAD_ARGUMENT, "sweep too large");
   const uint32_t none[3] = {0, 0, 0};
@@ -805,11 +732,10 @@ int vgicp_sweep_stage_cloud2(vgicp_ctx* ctx, size_t n, const void* data, size_t 
                              size_t off_z, size_t off_time, uint64_t* ticket) {
   if (!ctx || !ticket) return VGICP_ERR_BAD_ARGUMENT;
   *ticket = 0;
-  if (ctx->multi) {
-    const int rc = vgicp_sweep_stage_cloud2(vgicp_multi_api::first(ctx), n, data, point_step, off_x, off_y, off_z, off_time, ticket);
-    if (rc != VGICP_OK) g_stage_error_ctx = ctx->id;
-    return rc;
-  }
+  if (ctx->multi)
+    return forward_to_first(ctx, [&](vgicp_ctx* first) {
+      return vgicp_sweep_stage_cloud2(first, n, data, point_step, off_x, off_y, off_z, off_time, ticket);
+    }, true);
   if (n == 0 || !data) return fail_stage(ctx, VGICP_ERR_BAD_ARGUMENT, "empty sweep");
   if (n > 0xFFFFFFFFull) return fail_stage(ctx, VGICP_ERR_BAD_ARGUMENT, "sweep too large");
   if (point_step < 12 || point_step > 64 || point_step % 4 != 0)
@@ -823,11 +749,7 @@ int vgicp_sweep_stage_cloud2(vgicp_ctx* ctx, size_t n, const void* data, size_t 
 
 int vgicp_sweep_unstage(vgicp_ctx* ctx, uint64_t ticket) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {
-    const int rc = vgicp_sweep_unstage(vgicp_multi_api::first(ctx), ticket);
-    if (rc != VGICP_OK) g_stage_error_ctx = ctx->id;
-    return rc;
-  }
+  if (ctx->multi) return forward_to_first(ctx, [&](vgicp_ctx* first) { return vgicp_sweep_unstage(first, ticket); }, true);
   std::lock_guard<std::mutex> lk(ctx->ahead_mutex);
   for (auto& s : ctx->ahead)
     if (ticket != 0 && s.state == 1 && s.ticket == ticket) {
@@ -887,11 +809,8 @@ int vgicp_scan_prepare(vgicp_ctx* ctx, size_t n, const double* points, const dou
                        size_t num_states, const double* states, const double extrinsic[16],
                        double voxel_size, int knn, size_t* kept, int64_t* deskewed) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {
-    if (!kept) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "kept is NULL");
-    return vgicp_multi_api::scan_prepare(ctx, n, points, point_time, num_states, states, extrinsic, voxel_size, knn, kept, deskewed, false);
-  }
   if (!kept) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "kept is NULL");
+  if (ctx->multi) return vgicp_multi_api::scan_prepare(ctx, n, points, point_time, num_states, states, extrinsic, voxel_size, knn, kept, deskewed, false);
   *kept = 0;
   if (deskewed) *deskewed = 0;
   int rc = settle(ctx);
@@ -924,14 +843,10 @@ constexpr double kFetchPatienceSeconds = 5.0;
 int ensure_fetch_stage(vgicp_ctx* ctx, size_t points) {
   if (points <= ctx->fetch_cap_points && ctx->h_fetch) return VGICP_OK;
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->h_fetch) VG_HIP(ctx, hipHostFree(ctx->h_fetch));
-  ctx->h_fetch = nullptr;
-  ctx->fetch_cap_points = 0;
   const size_t cap = std::max<size_t>(points + points / 4, 4096);
-  const size_t data = (((cap * 24u) + 255u) & ~size_t(255)) + cap * 72u + 256u;
+  const size_t data = align256(cap * 24u) + cap * 72u + 256u;
   const size_t flag_bytes = (data / kFetchPiece + 2) * 64;
-  VG_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_fetch), flag_bytes + data, 0));
-  std::memset(ctx->h_fetch, 0, flag_bytes);
+  VG_RC(grow_pinned(ctx, &ctx->h_fetch, &ctx->fetch_cap_points, flag_bytes + data, flag_bytes));
   void* dev = nullptr;
   VG_HIP(ctx, hipHostGetDevicePointer(&dev, ctx->h_fetch, 0));
   ctx->h_fetch_dev = static_cast<char*>(dev);
@@ -953,7 +868,7 @@ int vgicp_scan_fetch_begin(vgicp_ctx* ctx, size_t* kept) {
   VG_HIP(ctx, hipSetDevice(ctx->device));
   int rc = ensure_fetch_stage(ctx, ctx->n_upper);
   if (rc != VGICP_OK) return rc;
-  if (++ctx->fetch_seq == 0) ++ctx->fetch_seq;
+  next_nonzero(ctx->fetch_seq);
   VG_HIP(ctx, launch_fetch(ctx->stream, ctx->d_scan_aos, ctx->d_scan_aos + 3 * ctx->scan_capacity, ctx->d_counters, ctx->prep_epoch,
                            (uint32_t)std::min<size_t>(ctx->fetch_cap_points, ctx->n_upper),
                            ctx->h_fetch_dev + ctx->fetch_flag_bytes, reinterpret_cast<uint32_t*>(ctx->h_fetch_dev),
@@ -997,7 +912,7 @@ int vgicp_scan_fetch_end(vgicp_ctx* ctx, size_t capacity, double* points, double
   if (kept > 0 && (capacity < kept || !points || !covs)) {
     rc_copy = fail(ctx, VGICP_ERR_BAD_ARGUMENT, "capacity smaller than the prepared scan (or a NULL output pointer)");
   } else if (kept > 0) {
-    const size_t pb = kept * 24u, pb_pad = (pb + 255u) & ~size_t(255), total = pb_pad + kept * 72u;
+    const size_t pb = kept * 24u, pb_pad = align256(pb), total = pb_pad + kept * 72u;
     const uint32_t pieces = (uint32_t)((total + kFetchPiece - 1) / kFetchPiece);
     const uint32_t* flags = reinterpret_cast<const uint32_t*>(ctx->h_fetch);
     const char* stage = ctx->h_fetch + ctx->fetch_flag_bytes;

@@ -17,11 +17,10 @@ int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   VG_RC(persistent_args(ctx, guess, params, &a));
   FusedUpload f;
   std::memset(&f, 0, sizeof f);
-  CopyCrew* crew = ctx->crew;
-  f.apts = crew->apts;
-  f.acov = crew->acov;
-  f.flags = crew->flags;
-  f.unit = crew->unit;
+  f.apts = up.copy.dst_a;
+  f.acov = up.copy.dst_b;
+  f.flags = up.copy.flags;
+  f.unit = pack_arena_unit();
   f.seq = ctx->scan_seq;
   f.spin_limit = ctx->dev.pack_spin_limit ? ctx->dev.pack_spin_limit : kPackSpinLimit;
   f.soa = ctx->d_scan;
@@ -30,12 +29,12 @@ int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   f.asym = ctx->d_ins_counters + 2;
   f.unit_clock = ctx->d_unit_clock;
   const bool trace = trace_align();   // where the host time goes
-  scan_upload_post(ctx, &up);
+  crew_post(ctx, &up.copy);
   const double ta0 = trace ? now_seconds() : 0.0;
   const hipError_t e_launch = launch_persistent_fused(ctx->stream, a, f, ctx->persist_grid);
   const double ta1 = trace ? now_seconds() : 0.0;
   bool slow = false;
-  const int rc = scan_upload_copy(ctx, up, &slow);
+  const int rc = crew_join(ctx, up.copy, &slow);
   if (rc != VGICP_OK) {
     // a copy thread never delivered: the launch has given up waiting for its unit by now (crew_gave_up synchronised)
     (void)reset_persistent_exchange(ctx);
@@ -120,11 +119,8 @@ int vgicp_accumulate(vgicp_ctx* ctx, size_t n, const double* points, const doubl
                      const double pose[16], double JTJ[36], double JTr[6], uint64_t* count) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
   if (ctx->multi) {  // a hook that works on one device ("local rank only"): the whole scan on sub-context 0
-    vgicp_ctx* first = vgicp_multi_api::first(ctx);
     vgicp_multi_api::scan_replaced(ctx);
-    const int rc = vgicp_accumulate(first, n, points, covs, pose, JTJ, JTr, count);
-    if (rc != VGICP_OK) ctx->err = first->err;
-    return rc;
+    return forward_to_first(ctx, [&](vgicp_ctx* first) { return vgicp_accumulate(first, n, points, covs, pose, JTJ, JTr, count); });
   }
   if (!pose || !JTJ || !JTr) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL output pointer");
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
@@ -162,12 +158,10 @@ int vgicp_solve_step(vgicp_ctx* ctx, const double JTJ[36], const double JTr[6], 
                      double translation_sq_threshold, uint32_t flags, double se3[6], double step[16],
                      int32_t* used_pivoted, int32_t* converged) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {
-    vgicp_ctx* first = vgicp_multi_api::first(ctx);
-    const int rc = vgicp_solve_step(first, JTJ, JTr, cosine_threshold, translation_sq_threshold, flags, se3, step, used_pivoted, converged);
-    if (rc != VGICP_OK) ctx->err = first->err;
-    return rc;
-  }
+  if (ctx->multi)
+    return forward_to_first(ctx, [&](vgicp_ctx* first) {
+      return vgicp_solve_step(first, JTJ, JTr, cosine_threshold, translation_sq_threshold, flags, se3, step, used_pivoted, converged);
+    });
   if (!JTJ || !JTr || !se3 || !step) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pointer");
   VG_HIP(ctx, hipSetDevice(ctx->device));
   int rc = ensure_stage(ctx, 64 * sizeof(double));
@@ -198,12 +192,10 @@ int vgicp_match(vgicp_ctx* ctx, size_t n, const double* points, const double* co
                 double* src_points, double* src_covs, double* map_points, double* map_covs,
                 uint64_t* src_index, size_t* matched) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {  // the map is replicated: any replica answers
-    vgicp_ctx* first = vgicp_multi_api::first(ctx);
-    const int rc = vgicp_match(first, n, points, covs, src_points, src_covs, map_points, map_covs, src_index, matched);
-    if (rc != VGICP_OK) ctx->err = first->err;
-    return rc;
-  }
+  if (ctx->multi)   // the map is replicated: any replica answers
+    return forward_to_first(ctx, [&](vgicp_ctx* first) {
+      return vgicp_match(first, n, points, covs, src_points, src_covs, map_points, map_covs, src_index, matched);
+    });
   if (!matched) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "matched is NULL");
   *matched = 0;
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
@@ -214,38 +206,34 @@ int vgicp_match(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   if (n > 0xFFFFFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "scan too large");
   VG_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t nb = match_blocks((uint32_t)n);
-  // staging layout: in_pts | in_cov | out src_pts | src_cov | map_pts | map_cov | index | counts
-  const size_t pb = n * 3 * sizeof(double), cb = n * 9 * sizeof(double), ib = n * sizeof(uint64_t);
-  const size_t nbb = ((size_t)nb * sizeof(uint32_t) + 255) & ~size_t(255);
-  const size_t total = 3 * pb + 3 * cb + ib + nbb + 256;
-  int rc = ensure_stage(ctx, total);
-  if (rc != VGICP_OK) return rc;
-  char* b = static_cast<char*>(ctx->d_stage);
-  double* in_pts = reinterpret_cast<double*>(b);
-  double* in_cov = reinterpret_cast<double*>(b + pb);
-  double* o_sp = reinterpret_cast<double*>(b + pb + cb);
-  double* o_sc = reinterpret_cast<double*>(b + 2 * pb + cb);
-  double* o_mp = reinterpret_cast<double*>(b + 2 * pb + 2 * cb);
-  double* o_mc = reinterpret_cast<double*>(b + 3 * pb + 2 * cb);
-  uint64_t* o_ix = reinterpret_cast<uint64_t*>(b + 3 * pb + 3 * cb);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(b + 3 * pb + 3 * cb + ib);
-  uint32_t* d_total = reinterpret_cast<uint32_t*>(b + 3 * pb + 3 * cb + ib + nbb);
+  // staging layout: in_pts | in_cov | out src_pts | src_cov | map_pts | map_cov | index | counts | total
+  const size_t pb = n * 3 * sizeof(double), cb = n * 9 * sizeof(double);
+  StageLayout lay;
+  const size_t o_in_pts = lay.take(pb), o_in_cov = lay.take(cb), o_sp = lay.take(pb), o_sc = lay.take(cb), o_mp = lay.take(pb);
+  const size_t o_mc = lay.take(cb), o_ix = lay.take(n * sizeof(uint64_t)), o_counts = lay.take((size_t)nb * sizeof(uint32_t));
+  const size_t o_total = lay.take(sizeof(uint32_t));
+  VG_RC(ensure_stage(ctx, lay.total));
+  double *in_pts = stage_at<double>(ctx, o_in_pts), *in_cov = stage_at<double>(ctx, o_in_cov);
+  double *o_src_p = stage_at<double>(ctx, o_sp), *o_src_c = stage_at<double>(ctx, o_sc);
+  double *o_map_p = stage_at<double>(ctx, o_mp), *o_map_c = stage_at<double>(ctx, o_mc);
+  uint64_t* o_index = stage_at<uint64_t>(ctx, o_ix);
+  uint32_t *counts = stage_at<uint32_t>(ctx, o_counts), *d_total = stage_at<uint32_t>(ctx, o_total);
   arena_reset(ctx);
   VG_RC(user_h2d(ctx, in_pts, points, pb));
   VG_RC(user_h2d(ctx, in_cov, covs, cb));
   VG_HIP(ctx, launch_match(ctx->stream, in_pts, in_cov, (uint32_t)n, ctx->table,
-                           (uint32_t)(ctx->slots - 1), ctx->voxel_size, counts, d_total, o_sp, o_sc,
-                           o_mp, o_mc, o_ix));
+                           (uint32_t)(ctx->slots - 1), ctx->voxel_size, counts, d_total, o_src_p, o_src_c,
+                           o_map_p, o_map_c, o_index));
   VG_HIP(ctx, hipMemcpyAsync(ctx->h_counters, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const size_t m = ctx->h_counters[0];
   if (m > 0) {
     arena_reset(ctx);   // the inputs have been consumed (synchronised above)
-    VG_RC(user_d2h(ctx, src_points, o_sp, m * 3 * sizeof(double)));
-    VG_RC(user_d2h(ctx, src_covs, o_sc, m * 9 * sizeof(double)));
-    VG_RC(user_d2h(ctx, map_points, o_mp, m * 3 * sizeof(double)));
-    VG_RC(user_d2h(ctx, map_covs, o_mc, m * 9 * sizeof(double)));
-    if (src_index) VG_RC(user_d2h(ctx, src_index, o_ix, m * sizeof(uint64_t)));
+    VG_RC(user_d2h(ctx, src_points, o_src_p, m * 3 * sizeof(double)));
+    VG_RC(user_d2h(ctx, src_covs, o_src_c, m * 9 * sizeof(double)));
+    VG_RC(user_d2h(ctx, map_points, o_map_p, m * 3 * sizeof(double)));
+    VG_RC(user_d2h(ctx, map_covs, o_map_c, m * 9 * sizeof(double)));
+    if (src_index) VG_RC(user_d2h(ctx, src_index, o_index, m * sizeof(uint64_t)));
     VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     user_copies_finish(ctx);
   }
@@ -255,12 +243,7 @@ int vgicp_match(vgicp_ctx* ctx, size_t n, const double* points, const double* co
 
 int vgicp_voxel_index(vgicp_ctx* ctx, size_t n, const double* points, int32_t* keys) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (ctx->multi) {
-    vgicp_ctx* first = vgicp_multi_api::first(ctx);
-    const int rc = vgicp_voxel_index(first, n, points, keys);
-    if (rc != VGICP_OK) ctx->err = first->err;
-    return rc;
-  }
+  if (ctx->multi) return forward_to_first(ctx, [&](vgicp_ctx* first) { return vgicp_voxel_index(first, n, points, keys); });
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
   if (n == 0) return VGICP_OK;
   if (!points || !keys) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL array pointer");

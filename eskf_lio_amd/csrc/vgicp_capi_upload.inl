@@ -40,13 +40,10 @@ int crew_gave_up(vgicp_ctx* ctx) {
 int ensure_upload_stage(vgicp_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->upload_cap) return VGICP_OK;
   if (ctx->upload_in_flight) { VG_HIP(ctx, hipEventSynchronize(ctx->ev_upload)); ctx->upload_in_flight = false; }
-  if (ctx->h_upload) VG_HIP(ctx, hipHostFree(ctx->h_upload));
-  ctx->h_upload = nullptr;
-  ctx->upload_cap = 0;
   const size_t want = std::max<size_t>(bytes + bytes / 4, 4u << 20);
   const size_t flag_bytes = (want / ((size_t)pack_arena_unit() * kScanPlanes * sizeof(double)) + 2) * 64;
-  VG_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_upload), flag_bytes + want, 0));
-  std::memset(ctx->h_upload, 0, flag_bytes);   // "no upload yet" (a sequence number is never 0)
+  // the flag area: "no upload yet" (a sequence number is never 0)
+  VG_RC(grow_pinned(ctx, &ctx->h_upload, &ctx->upload_cap, flag_bytes + want, flag_bytes));
   ctx->upload_cap = want;
   ctx->upload_flag_bytes = flag_bytes;
   return VGICP_OK;
@@ -54,45 +51,92 @@ int ensure_upload_stage(vgicp_ctx* ctx, size_t bytes) {
 
 // Whether scan_upload_enqueue stages this scan through the copy threads (else the runtime copies it in place).
 bool upload_is_staged(const vgicp_ctx* ctx, size_t n, const double* points, const double* covs) {
-  static const bool stage_off = std::getenv("VGICP_STAGE_LIMIT") && std::atoll(std::getenv("VGICP_STAGE_LIMIT")) == 0;
   const size_t bytes = n * kScanPlanes * sizeof(double);
   const size_t whole_bytes = ctx->upload_whole_hint ? ctx->upload_whole_hint : bytes;
-  return !stage_off && whole_bytes <= ctx->upload_stage_limit && bytes > (256u << 10) &&
+  return !staging_off() && whole_bytes <= ctx->upload_stage_limit && bytes > (256u << 10) &&
          !(is_pagelocked(points) && is_pagelocked(covs));
 }
 
-// A scan upload in three steps — stage (everything up to the copy), post + copy (the copy threads), finish — so that the
-// fused align can put its launch between the first two (vgicp_align).
-struct UploadJob {
-  bool staged = false;         // false: scan_upload_stage did the whole upload (n == 0 or the runtime's copy)
-  bool helpers = false;
-  uint32_t job = 0;
-  double t0 = 0.0, t_post = 0.0;
+// One job of the copy crew: n points of the caller's array a (and b, if any) into page-locked staging memory, unit by
+// unit (pack_arena_unit() points), every unit published through its flag line under `seq`.
+struct CopyJob {
+  const void *src_a = nullptr, *src_b = nullptr;
+  char *dst_a = nullptr, *dst_b = nullptr;
+  uint32_t size_a = 0, size_b = 0;   // bytes per point (size_b = 0: one array only)
+  uint32_t (*copy_b_form)(void*, const void*, size_t) = nullptr;   // CopyCrew::copy_b_form
+  uint32_t* flags = nullptr;
+  size_t n = 0;
+  uint32_t seq = 0;
+  size_t bytes = 0, wake_bytes = 0;  // the helpers are woken (started) for jobs of wake_bytes and more
+  bool helpers = false;              // from here on: set by crew_post
+  uint32_t ticket = 0;
+  double t_post = 0.0;
 };
 
-// The scan's bookkeeping; a staged upload's memory and the copy job's fields (not posted yet).  A scan that is not staged
-// is enqueued here whole (copies + pack_scan_kernel).
+// The copy threads start on the job: the helpers (if any are awake or worth waking) at once, the caller joins through
+// crew_join when it has launched the kernel that reads the staging memory.
+void crew_post(vgicp_ctx* ctx, CopyJob* job) {
+  const uint32_t unit = pack_arena_unit();
+  job->helpers = ctx->upload_threads > 1 && job->bytes >= job->wake_bytes;
+  if (!ctx->crew) ctx->crew = new CopyCrew;
+  CopyCrew* crew = ctx->crew;
+  if (job->helpers && crew->th.empty()) crew->start(ctx->upload_threads - 1);
+  crew->pts = static_cast<const char*>(job->src_a);
+  crew->cov = static_cast<const char*>(job->src_b);
+  crew->apts = job->dst_a;
+  crew->acov = job->dst_b;
+  crew->flags = job->flags;
+  crew->n = (uint32_t)job->n;
+  crew->unit = unit;
+  crew->units = (uint32_t)((job->n + unit - 1) / unit);
+  crew->seq = job->seq;
+  crew->size_a = job->size_a;
+  crew->size_b = job->size_b;
+  crew->copy = stage_copy;
+  crew->copy_b_form = job->copy_b_form;
+  job->t_post = now_seconds();
+  job->ticket = crew->post(job->helpers);
+}
+
+// This thread copies too, then waits for the helpers: the caller's buffers are free again on return.  *slow: the copy
+// threads were held up for so long (kCrewSlowSeconds) that a kernel waiting for their units may have stopped waiting —
+// counted here, once.  A helper that never delivers ends the upload (crew_gave_up).
+int crew_join(vgicp_ctx* ctx, const CopyJob& job, bool* slow) {
+  *slow = false;
+  // test aid: a copy thread that is held up
+  const long debug_delay_us = ctx->dev.debug_upload_delay_us;
+  if (debug_delay_us > 0 && !job.helpers) std::this_thread::sleep_for(std::chrono::microseconds(debug_delay_us));
+  ctx->crew->work(job.ticket);
+  if (!ctx->crew->finish()) return crew_gave_up(ctx);   // always: the caller's buffers must not be in use on return
+  if (now_seconds() - job.t_post > kCrewSlowSeconds) {
+    *slow = true;
+    ++ctx->upload_slow;
+  }
+  return VGICP_OK;
+}
+
+// A scan upload in three steps — stage (everything up to the copy), crew_post + crew_join (the copy threads), finish — so
+// that the fused align can put its launch between the first two (vgicp_align).
+struct UploadJob {
+  bool staged = false;         // false: scan_upload_stage did the whole upload (n == 0 or the runtime's copy)
+  double t0 = 0.0;
+  CopyJob copy;
+};
+
+// The scan's bookkeeping; a staged upload's memory and its copy job (not posted yet).  A scan that is not staged is
+// enqueued here whole (copies + pack_scan_kernel).
 int scan_upload_stage(vgicp_ctx* ctx, size_t n, const double* points, const double* covs, UploadJob* up) {
   *up = UploadJob{};
   if (n > 0 && (!points || !covs)) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL scan pointer");
   if (n > 0xFFFFFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "scan too large");
   VG_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_scan(ctx, n);
-  if (rc != VGICP_OK) return rc;
-  ++ctx->scan_generation;
-  forget_fetch(ctx);
-  ctx->scan_ready = false;
-  ctx->prep_voxel = 0.0;
-  ctx->prep_with_deskew = false;   // what vgicp_scan_info reports belongs to a PREPARED scan, not to this one
-  ctx->prep_deskewed = 0;
-  ctx->prep_indefinite = 0;
+  VG_RC(begin_scan(ctx, n, 0.0, false));
   ctx->n = (uint32_t)n;
-  ctx->stride = ctx->scan_capacity;
   if (n == 0) return VGICP_OK;
   up->t0 = now_seconds();
   double* aos_pts = ctx->d_scan_aos;
   double* aos_cov = ctx->d_scan_aos + 3 * ctx->scan_capacity;
-  if (++ctx->scan_seq == 0) ++ctx->scan_seq;
+  next_nonzero(ctx->scan_seq);
   ctx->scan_sym_known = true;
   const size_t bytes = n * kScanPlanes * sizeof(double);
   if (!upload_is_staged(ctx, n, points, covs)) {
@@ -104,55 +148,19 @@ int scan_upload_stage(vgicp_ctx* ctx, size_t n, const double* points, const doub
     ctx->upload_seconds += now_seconds() - up->t0;  // host side: the copy calls + the enqueue of the pack kernel
     return VGICP_OK;
   }
-  const uint32_t unit = pack_arena_unit(), units = (uint32_t)((n + unit - 1) / unit);
-  const size_t pb = (n * 3 * sizeof(double) + 255 + 16) & ~size_t(255), cb = (n * 9 * sizeof(double) + 255 + 16) & ~size_t(255);
-  rc = ensure_upload_stage(ctx, pb + cb);
-  if (rc != VGICP_OK) return rc;
+  const size_t pb = align256(n * 3 * sizeof(double) + 16), cb = align256(n * 9 * sizeof(double) + 16);
+  VG_RC(ensure_upload_stage(ctx, pb + cb));
   if (!ctx->ev_upload) VG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
   // the kernel that read the staging memory last has long finished (every align ends in a synchronisation); make sure
   if (ctx->upload_in_flight && hipEventQuery(ctx->ev_upload) != hipSuccess) VG_HIP(ctx, hipEventSynchronize(ctx->ev_upload));
   ctx->upload_in_flight = false;
   up->staged = true;
-  up->helpers = ctx->upload_threads > 1 && bytes >= (2u << 20);
-  if (!ctx->crew) ctx->crew = new CopyCrew;
-  CopyCrew* crew = ctx->crew;
-  if (up->helpers && crew->th.empty()) crew->start(ctx->upload_threads - 1);
-  crew->pts = reinterpret_cast<const char*>(points);
-  crew->cov = reinterpret_cast<const char*>(covs);
-  crew->flags = reinterpret_cast<uint32_t*>(ctx->h_upload);
-  crew->apts = ctx->h_upload + ctx->upload_flag_bytes;
-  crew->acov = crew->apts + pb;
-  crew->n = (uint32_t)n;
-  crew->unit = unit;
-  crew->units = units;
-  crew->seq = ctx->scan_seq;
-  crew->size_a = 3 * sizeof(double);
-  crew->size_b = 9 * sizeof(double);
-  crew->copy = stage_copy;
-  crew->copy_b_form = stage_cov_unit;
-  return VGICP_OK;
-}
-
-// The copy threads start on the staged job.
-void scan_upload_post(vgicp_ctx* ctx, UploadJob* up) {
-  up->t_post = now_seconds();
-  up->job = ctx->crew->post(up->helpers);
-}
-
-// This thread copies too, then waits for the helpers: the caller's buffers are free again on return.  *slow: the copy
-// threads were held up for so long (kCrewSlowSeconds) that a kernel waiting for their units may have stopped waiting —
-// counted here, once.  A helper that never delivers ends the upload (crew_gave_up).
-int scan_upload_copy(vgicp_ctx* ctx, const UploadJob& up, bool* slow) {
-  *slow = false;
-  // test aid: a copy thread that is held up
-  const long debug_delay_us = ctx->dev.debug_upload_delay_us;
-  if (debug_delay_us > 0 && !up.helpers) std::this_thread::sleep_for(std::chrono::microseconds(debug_delay_us));
-  ctx->crew->work(up.job);
-  if (!ctx->crew->finish()) return crew_gave_up(ctx);   // always: the caller's buffers must not be in use on return
-  if (now_seconds() - up.t_post > kCrewSlowSeconds) {
-    *slow = true;
-    ++ctx->upload_slow;
-  }
+  CopyJob& job = up->copy;
+  job.flags = reinterpret_cast<uint32_t*>(ctx->h_upload);
+  job.src_a = points, job.dst_a = ctx->h_upload + ctx->upload_flag_bytes, job.size_a = 3 * sizeof(double);
+  job.src_b = covs, job.dst_b = job.dst_a + pb, job.size_b = 9 * sizeof(double), job.copy_b_form = stage_cov_unit;
+  job.n = n, job.seq = ctx->scan_seq;
+  job.bytes = bytes, job.wake_bytes = 2u << 20;
   return VGICP_OK;
 }
 
@@ -170,11 +178,11 @@ int scan_upload_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const do
   UploadJob up;
   int rc = scan_upload_stage(ctx, n, points, covs, &up);
   if (rc != VGICP_OK || !up.staged) return rc;
-  scan_upload_post(ctx, &up);
+  crew_post(ctx, &up.copy);
   // the launch first (it starts reading as soon as unit 0 is published), then this thread copies too
   const hipError_t e_launch = launch_pack_staged(ctx, true);
   bool slow = false;
-  rc = scan_upload_copy(ctx, up, &slow);
+  rc = crew_join(ctx, up.copy, &slow);
   if (e_launch != hipSuccess) return fail_hip(ctx, e_launch, "launch_pack_arena");
   if (rc != VGICP_OK) return rc;
   // the copy threads were held up for so long that a workgroup of the launch may have stopped waiting: everything is
@@ -192,23 +200,20 @@ int vgicp_scan_upload(vgicp_ctx* ctx, size_t n, const double* points, const doub
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
   if (ctx->multi) return vgicp_multi_api::scan_upload(ctx, n, points, covs);
   { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
-  const double t0 = now_seconds();
   int rc = scan_upload_enqueue(ctx, n, points, covs);
   if (rc != VGICP_OK) return rc;
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  (void)t0;
   ctx->scan_ready = true;
   return VGICP_OK;
 }
 
 int vgicp_host_register(vgicp_ctx* ctx, const void* buffer, size_t bytes) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
+  if (!buffer || bytes == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL / empty buffer");
   if (ctx->multi) {  // page-locked once, for every device (portable)
-    if (!buffer || bytes == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL / empty buffer");
     VG_HIP(ctx, hipHostRegister(const_cast<void*>(buffer), bytes, hipHostRegisterPortable));
     return VGICP_OK;
   }
-  if (!buffer || bytes == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL / empty buffer");
   VG_HIP(ctx, hipSetDevice(ctx->device));
   VG_HIP(ctx, hipHostRegister(const_cast<void*>(buffer), bytes, hipHostRegisterDefault));
   return VGICP_OK;
@@ -216,15 +221,14 @@ int vgicp_host_register(vgicp_ctx* ctx, const void* buffer, size_t bytes) {
 
 int vgicp_host_unregister(vgicp_ctx* ctx, const void* buffer) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
+  if (!buffer) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL buffer");
   if (ctx->multi) {
-    if (!buffer) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL buffer");
     size_t unused = 0;
     const int rc_sync = vgicp_multi_api::map_size(ctx, &unused, nullptr);  // settles every sub-context: no copy in flight
     if (rc_sync != VGICP_OK) return rc_sync;
     VG_HIP(ctx, hipHostUnregister(const_cast<void*>(buffer)));
     return VGICP_OK;
   }
-  if (!buffer) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL buffer");
   VG_HIP(ctx, hipSetDevice(ctx->device));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));  // no copy out of the buffer may still be in flight
   VG_HIP(ctx, hipHostUnregister(const_cast<void*>(buffer)));

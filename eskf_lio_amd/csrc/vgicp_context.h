@@ -27,6 +27,7 @@
 #include "../../include/vgicp_hip_evaluate.h"
 #include "vgicp_device.h"
 #include "vgicp_align_plan.h"
+#include "vgicp_prepare_plan.h"
 
 using namespace vgicp;
 
@@ -76,6 +77,13 @@ inline uint64_t next_pow2(uint64_t v) {
   return p;
 }
 
+inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+// sequence numbers (scan_seq, prep_epoch, fetch_seq): 0 means "none yet" in every flag and header word, so it is skipped
+inline uint32_t next_nonzero(uint32_t& seq) {
+  if (++seq == 0) ++seq;
+  return seq;
+}
+
 constexpr uint64_t kMinSlots = 1024;
 // words behind the counter block (d_ins_counters): [0] [1] the deferred insertion's running totals, [2] [3] the
 // resident scan's symmetry verdicts, [4] [5] [6] the raw-point log (RawLog::ctr), [7] spare
@@ -85,6 +93,7 @@ constexpr uint64_t kRawMaxEntries = 1ull << 31;   // 64 GiB of raw points; ordin
 constexpr int kDefaultChunk = 4;
 constexpr int kMaxChunksInFlight = 2;
 static_assert(kPlanTeamsMax == (uint32_t)kTeamsMax, "vgicp_align_plan.h plans with the team kernel's width");
+static_assert(kPlanDeskewMaxStates == kDeskewMaxStates, "vgicp_prepare_plan.h plans with the parallel deskew bounds' limit");
 constexpr int kPersistentCooldownAligns = 8;  // aligns on the per-launch loop after the single launch gave up
 
 }  // namespace vgicp
@@ -195,7 +204,7 @@ struct CopyCrew {
   // everything of the job is in place: open it (to the helpers too if asked); the caller then works on it itself
   // (work(job)) and waits for the units others took (finish())
   uint32_t post(bool wake_helpers) {
-    if (++job == 0) ++job;
+    next_nonzero(job);
     finished.store((uint64_t)job << 32, std::memory_order_relaxed);
     next.store((uint64_t)job << 32, std::memory_order_release);
     if (wake_helpers && !broken && !th.empty()) {
