@@ -73,6 +73,13 @@ OPTION_STAGE_EVENTS = 1
 OPTION_UPLOAD_STAGE_KB = 2   # scans up to this many KiB are staged through page-locked memory of the context; 0 = in place (vgicp_hip.h)
 OPTION_REFERENCE_ORDER = 3   # != 0: scan preparations emit the kept points in the reference's unordered_map order (vgicp_hip.h)
 OPTION_MAP_RAW_POINTS = 4    # != 0: the map keeps every voxel's raw points on the device (vgicp_hip_map_points.h)
+# robust rounds (vgicp_hip_robust.h): three options, no entry point of their own
+OPTION_ROBUST_KERNEL = 5        # ROBUST_NONE (default), ROBUST_HUBER, ROBUST_CAUCHY
+OPTION_ROBUST_SCALE_MICRO = 6   # c = value / 1e6, value >= 1; default 1 000 000
+OPTION_GATE_MICRO = 7           # gate on d^2 = value / 1e6; 0 = no gate (default)
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2
+ROBUST_EXPORTS = ()
+ROBUST_KERNELS = {"none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY}
 COUNTER_UPLOAD_SLOW = 6
 
 
@@ -733,6 +740,21 @@ class Context:
 
     def set_option(self, option: int, value: int):
         self._check(self._lib.vgicp_set_option(self._h, int(option), int(value)))
+
+    def set_robust(self, kernel=ROBUST_NONE, scale: float = 1.0, gate: float = 0.0):
+        """The robust round of vgicp_hip_robust.h for every later align of this context: kernel (ROBUST_* or "none" /
+        "huber" / "cauchy"), its scale c and the gate on d^2 (0 = none), in the library's regularised units (~0.1, not
+        ~3).  The ABI takes millionths: returns (kernel, c, gate) as the library will use them.  Nothing is changed when
+        a value is refused."""
+        kind = ROBUST_KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+        scale_micro, gate_micro = int(round(float(scale) * 1e6)), int(round(float(gate) * 1e6))
+        if kind not in (ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY) or not 1 <= scale_micro <= 2**31 - 1 or \
+                not 0 <= gate_micro <= 2**31 - 1:
+            raise ValueError("robust kernel must be none / huber / cauchy, scale in [1e-6, 2147.48], gate in [0, 2147.48]")
+        self.set_option(OPTION_ROBUST_KERNEL, kind)
+        self.set_option(OPTION_ROBUST_SCALE_MICRO, scale_micro)
+        self.set_option(OPTION_GATE_MICRO, gate_micro)
+        return kind, scale_micro / 1000000.0, gate_micro / 1000000.0
 
     def host_register(self, array: np.ndarray):
         self._check(self._lib.vgicp_host_register(self._h, array.ctypes.data, array.nbytes))

@@ -43,6 +43,7 @@ struct AlignFacts {
   bool mailboxes = false;        // Group: the device-initiated exchange is wired
   int world_size = 1, peer_world = 1, cooldown = 0;
   uint32_t grid = 0;             // workgroups of every persistent launch
+  bool robust = false;           // a robust kernel or a gate is set (include/vgicp_hip_robust.h)
 };
 
 struct AlignPlan {
@@ -57,6 +58,7 @@ struct AlignPlan {
 // team, as many teams as fit the grid vgicp_create verified to be resident; 1 = no team launch.
 inline uint32_t team_width(const AlignFacts& f, uint32_t* team_wgs) {
   *team_wgs = 0;
+  if (f.robust) return 1;   // the robust round has no team kernel
   const bool one_device = f.world_size == 1 && !f.owner && !f.comm && !f.peers_connected;
   if (!one_device || !f.persistent_enabled || f.stamps || f.n == 0 || !one_point_per_thread(f.n, f.grid)) return 1;
   const uint32_t T = (uint32_t)((f.n + kPointsPerPass - 1) / kPointsPerPass);
@@ -67,6 +69,15 @@ inline uint32_t team_width(const AlignFacts& f, uint32_t* team_wgs) {
 }
 
 inline AlignPlan plan_align(const AlignFacts& f) {
+  if (f.robust) {
+    // The robust round has instantiations of the single-device launch and of the loop only: an upload never takes the
+    // fused launch (it uploads, then plans as a Resident call), a batch is k single aligns.
+    AlignFacts g = f;
+    g.robust = false;
+    g.no_fused = true;
+    g.k = 1;
+    return plan_align(g);
+  }
   AlignPlan p;
   const bool loop_asked = f.profile || f.no_persistent || f.max_iteration <= 0;
   if (f.call == AlignCall::Group) {

@@ -286,6 +286,7 @@ int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* par
   if (ctx->dev.no_memo) a.memo_points = 0;
   a.prefetch_margin = (a.memo_points == 0 && a.stash_points == 0 && one_point_per_thread(ctx->n, grid)) ? ctx->prefetch_margin : 0.0;
   a.stamps = ctx->d_stamps;
+  if (robust_on(ctx)) robust_args(ctx, &a);   // launch_persistent then takes the robust instantiation
   a.world = multi ? (uint32_t)ctx->peer_world : 1u;
   a.rank = multi ? (uint32_t)ctx->peer_rank : 0u;
   a.mail = ctx->d_mail_table;
@@ -374,6 +375,9 @@ int align_ready(vgicp_ctx* ctx, const vgicp_params* params) {
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
   VG_RC(check_params(ctx, params));
+  if (robust_on(ctx) && (ctx->comm != nullptr || ctx->peers_connected || ctx->owner != nullptr))
+    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the robust round (vgicp_hip_robust.h) is set on this context: it aligns on a "
+                "single device only, not with a communicator or connected peers");
   return ensure_log(ctx, params->max_iteration);
 }
 
@@ -442,7 +446,8 @@ int align_on_loop(vgicp_ctx* ctx, const double* guess, const vgicp_params* param
   // when the map changed since; storage was made with the table, nothing is allocated)
   bool usable = false;
   if (large_table(ctx)) VG_RC(ensure_dense(ctx, &usable));
-  const IterArgs base = base_args(ctx);
+  IterArgs base = base_args(ctx);
+  if (robust_on(ctx)) robust_args(ctx, &base);   // launch_iterate then takes the robust instantiation
   const uint32_t grid = iterate_grid(ctx);
   const bool use_comm = ctx->comm != nullptr;
   int total_launches = 0;

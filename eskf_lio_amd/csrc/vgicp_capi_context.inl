@@ -409,6 +409,19 @@ int vgicp_set_option(vgicp_ctx* ctx, int option, int value) {
       }
       return VGICP_OK;
     }
+    case VGICP_OPTION_ROBUST_KERNEL:
+      if (value != VGICP_ROBUST_NONE && value != VGICP_ROBUST_HUBER && value != VGICP_ROBUST_CAUCHY)
+        return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "robust kernel must be VGICP_ROBUST_NONE, _HUBER or _CAUCHY");
+      ctx->robust_kernel = value;
+      return VGICP_OK;
+    case VGICP_OPTION_ROBUST_SCALE_MICRO:
+      if (value < 1) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "robust scale must be at least 1 (millionths)");
+      ctx->robust_scale_micro = value;
+      return VGICP_OK;
+    case VGICP_OPTION_GATE_MICRO:
+      if (value < 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "negative gate");
+      ctx->robust_gate_micro = value;
+      return VGICP_OK;
     default:
       return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "unknown option");
   }

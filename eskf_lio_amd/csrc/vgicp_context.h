@@ -25,6 +25,7 @@
 #include "../../include/vgicp_hip_map_points.h"
 #include "../../include/vgicp_hip_batch.h"
 #include "../../include/vgicp_hip_evaluate.h"
+#include "../../include/vgicp_hip_robust.h"
 #include "vgicp_device.h"
 #include "vgicp_align_plan.h"
 #include "vgicp_prepare_plan.h"
@@ -361,6 +362,10 @@ struct vgicp_ctx {
   uint32_t scan_seq = 0;             // uploads so far; pack_scan_kernel marks an asymmetric covariance with it
   bool scan_sym_known = false;       // the resident scan went through pack_scan_kernel (not a scan prepared on the device)
   int64_t prep_deskewed = 0;
+  // the robust round (include/vgicp_hip_robust.h), as vgicp_set_option left it; kernel 0 and gate 0 = the plain round
+  int robust_kernel = 0;             // VGICP_OPTION_ROBUST_KERNEL
+  int robust_scale_micro = 1000000;  // VGICP_OPTION_ROBUST_SCALE_MICRO: c = value / 1e6
+  int robust_gate_micro = 0;         // VGICP_OPTION_GATE_MICRO: gate on d^2 = value / 1e6, 0 = none
   bool reference_order = false;      // VGICP_OPTION_REFERENCE_ORDER: prepared scans come in the reference's unordered_map order
   bool prep_with_deskew = false;
   double prep_voxel = 0.0;           // > 0: the resident scan was down-sampled on the device to one point per voxel of this size
@@ -482,6 +487,15 @@ inline AlignFacts call_facts(AlignCall call, uint32_t flags, int max_iteration) 
   f.no_persistent = (flags & VGICP_FLAG_NO_PERSISTENT) != 0;
   return f;
 }
+inline bool robust_on(const vgicp_ctx* ctx) { return ctx->robust_kernel != 0 || ctx->robust_gate_micro != 0; }
+// The settings as the kernels take them (the three fields at the end of IterArgs / PersistArgs).
+template <typename Args>
+inline void robust_args(const vgicp_ctx* ctx, Args* a) {
+  const double c = (double)ctx->robust_scale_micro / 1000000.0;
+  a->robust_kernel = (uint32_t)ctx->robust_kernel;
+  a->robust_scale2 = c * c;
+  a->robust_gate = (double)ctx->robust_gate_micro / 1000000.0;
+}
 inline AlignFacts align_facts(const vgicp_ctx* ctx, const vgicp_params* params, AlignCall call, uint64_t n, size_t k = 1) {
   AlignFacts f = call_facts(call, params ? params->flags : 0u, params ? params->max_iteration : 0);
   f.n = n;
@@ -498,6 +512,7 @@ inline AlignFacts align_facts(const vgicp_ctx* ctx, const vgicp_params* params, 
   f.peer_world = ctx->peer_world;
   f.cooldown = ctx->persistent_cooldown;
   f.grid = ctx->persist_grid;
+  f.robust = robust_on(ctx);
   return f;
 }
 

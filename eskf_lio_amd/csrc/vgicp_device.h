@@ -89,6 +89,10 @@ struct IterArgs {
   uint32_t scan_seq;        // with asym_dev: *asym_dev != scan_seq = every covariance of the scan is bitwise symmetric
   const uint32_t* asym_dev; // (nine planes are read instead of twelve); nullptr = unknown, read all
   const VoxelRecord* dense; // dense copy of the FULL records (tables beyond the caches' reach), or nullptr
+  // the robust round (include/vgicp_hip_robust.h); all zero = the plain round (vgicp_accumulate, a group's loop: always)
+  uint32_t robust_kernel;   // VGICP_ROBUST_*
+  double robust_scale2;     // c^2
+  double robust_gate;       // gate on d^2; 0 = none
 };
 
 // Arguments of the persistent single-launch align (single GPU): every round of the loop runs inside
@@ -158,6 +162,10 @@ struct PersistArgs {
                            // voxel sizes to a face of its voxel has the neighbour behind that face looked up
                            // into LDS while the workers wait for the exchange
   uint64_t* stamps;
+  // the robust round, as IterArgs has it; all zero = the plain round (the fused and the team launch: always)
+  uint32_t robust_kernel;
+  double robust_scale2;
+  double robust_gate;
 };
 
 // The fused align (vgicp_align, one point per thread, one device): the persistent launch is enqueued BEFORE the copy

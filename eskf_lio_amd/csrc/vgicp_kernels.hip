@@ -482,13 +482,52 @@ __device__ __forceinline__ void inverse3_cofactor(const double (&S)[9], double (
   W[2] = c02 * id; W[5] = c12 * id; W[8] = c22 * id;
 }
 
+// The robust round (include/vgicp_hip_robust.h): the settings as a kernel holds them, made once per launch from the
+// three fields at the end of IterArgs / PersistArgs, and the weight of one correspondence from its squared Mahalanobis
+// residual raw = e^T W e.  d^2 = max(raw, 0); the gate is asked of raw itself, so a NaN residual is rejected.  Huber:
+// c / sqrt(d^2) = c^2 rsq(c^2 d^2), v_rsq_f64 + one third-order step y (1 + h/2 + 3 h^2/8), h = 1 - x y^2; Cauchy:
+// c^2 / (c^2 + d^2) by rcp_newton.  Everything here but raw is uniform and stays in scalar registers: no lane takes a
+// path of its own, a rejected correspondence has weight 0.
+constexpr uint32_t kRobustHuber = 1, kRobustCauchy = 2;
+struct RobustSetting {
+  uint32_t kernel = 0;
+  bool gated = false;
+  double c2 = 1.0, gate = 0.0;
+};
+__device__ __forceinline__ RobustSetting robust_setting(uint32_t kernel, double scale2, double gate) {
+  RobustSetting r;
+  r.kernel = kernel;
+  r.c2 = scale2;
+  r.gated = gate > 0.0;
+  r.gate = gate;
+  return r;
+}
+__device__ __forceinline__ double robust_weight(const RobustSetting& r, double raw) {
+  const double d2 = fmax(raw, 0.0);
+  double w = 1.0;
+  if (r.kernel == kRobustCauchy) {
+    w = r.c2 * rcp_newton(r.c2 + d2);
+  } else if (r.kernel == kRobustHuber) {
+    const double x = r.c2 * d2;
+    const double y = __builtin_amdgcn_rsq(x);
+    const double h = fma(-x * y, y, 1.0);
+    const double rs = fma(y * h, fma(h, 0.375, 0.5), y);
+    w = d2 <= r.c2 ? 1.0 : r.c2 * rs;
+  }
+  const bool keep = !r.gated || raw <= r.gate;
+  return keep ? w : 0.0;
+}
+
 // FIRST: v holds nothing yet (the thread's first match of the round): the 28 values are stored, not added to
 // zeros — 28 dependent-latency adds less per round in the one-point-per-thread case.  Both loop variants make the
 // same choice for the same point, so they still agree bit for bit.
-template <bool FIRST>
+// ROBUST: every one of the 27 sums takes the correspondence's weight as a factor (through W), the count takes (w > 0); a
+// weight of exactly 1.0 leaves the plain bits.
+template <bool FIRST, bool ROBUST = false>
 __device__ __forceinline__ void accumulate_match(const double* R, const double (&p)[3],
                                                  const double (&C)[9], const double (&mu)[3],
-                                                 double (&S)[9], double (&v)[kSlots]) {
+                                                 double (&S)[9], double (&v)[kSlots],
+                                                 const RobustSetting& robust = RobustSetting()) {
   // S = R C R^T + C_voxel
   double RC[9];
 #pragma unroll
@@ -506,6 +545,18 @@ __device__ __forceinline__ void accumulate_match(const double* R, const double (
   inverse3_cofactor(S, W);
   auto acc = [](double& dst, double x) { if (FIRST) dst = x; else dst += x; };
   const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
+  if constexpr (ROBUST) {
+    // d^2 = e^T W e from W e, the weight from d^2; the count now, and W takes the weight as a factor BEFORE anything is
+    // made of it: every one of the 27 sums below is linear in W, so each carries the factor w (nine products instead
+    // of 27, and w is dead before Q is live).  w = 1.0 leaves W's bits, w = 0 leaves +-0.
+    const double g0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
+    const double g1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
+    const double g2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
+    const double w = robust_weight(robust, e0 * g0 + e1 * g1 + e2 * g2);
+    acc(v[kCountSlot], w > 0.0 ? 1.0 : 0.0);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) W[k] = W[k] * w;
+  }
   // Q = [p]x W  (rows 3..5, columns 0..2 of J^T Sigma^-1 J)
   double Q[9];  // Q[r + 3c]
 #pragma unroll
@@ -534,7 +585,7 @@ __device__ __forceinline__ void accumulate_match(const double* R, const double (
   acc(v[24], Q[0] * e0 + Q[3] * e1 + Q[6] * e2);
   acc(v[25], Q[1] * e0 + Q[4] * e1 + Q[7] * e2);
   acc(v[26], Q[2] * e0 + Q[5] * e1 + Q[8] * e2);
-  acc(v[kCountSlot], 1.0);
+  if constexpr (!ROBUST) acc(v[kCountSlot], 1.0);
 }
 
 constexpr uint32_t kMemoMiss = 0xFFFFFFFFu;  // memo.w of a point whose voxel is not in the map
@@ -558,7 +609,9 @@ constexpr uint32_t kMemoNone = 0xFFFFFFFEu;  // nothing looked up
 // 1-5 transformed with the OLD pose, hashed and probed every point in every launch: 1.66 x the algorithmic bytes at C2);
 // nine instead of twelve planes of a scan whose covariances are all bitwise symmetric; the dense record copy of tables
 // beyond the caches' reach.  The arithmetic per match is unchanged, so the loop still returns the persistent launch's bits.
-template <int BLOCK>
+// ROBUST: the weighted round of include/vgicp_hip_robust.h — an instantiation of its own, so that the plain one keeps its
+// code; nothing but accumulate_match's contribution differs.
+template <int BLOCK, bool ROBUST = false>
 __global__ __launch_bounds__(BLOCK) void iterate_kernel(IterArgs a) {
   constexpr int kWaves = BLOCK / 64;
   constexpr int kWorkers = BLOCK - 64;
@@ -574,6 +627,8 @@ __global__ __launch_bounds__(BLOCK) void iterate_kernel(IterArgs a) {
   const bool cov_sym = a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
   const bool remembered = a.memo != nullptr && a.memo_valid != 0;           // uniform: an earlier launch of this align wrote the memos
   const VoxelRecord* pay_base = a.dense ? a.dense : a.table;                // uniform: where a remembered record's payload is read from
+  RobustSetting robust;
+  if constexpr (ROBUST) robust = robust_setting(a.robust_kernel, a.robust_scale2, a.robust_gate);  // uniform
   uint32_t i = worker ? blockIdx.x * kWorkers + (tid - 64) : a.n;
 
   double q[kScanPlanes];
@@ -669,8 +724,8 @@ __global__ __launch_bounds__(BLOCK) void iterate_kernel(IterArgs a) {
       }
     }
     if (hit) {
-      if (first) accumulate_match<true>(R, p, C, mu, S, v);  // the thread's first point of the round
-      else accumulate_match<false>(R, p, C, mu, S, v);
+      if (first) accumulate_match<true, ROBUST>(R, p, C, mu, S, v, robust);  // the thread's first point of the round
+      else accumulate_match<false, ROBUST>(R, p, C, mu, S, v, robust);
     }
     first = false;
   }
@@ -1093,8 +1148,11 @@ struct TeamView {
   uint32_t folder_rows = 0;  // U
   uint32_t* abort_word = nullptr;
 };
-template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool FUSED = false, bool TEAM = false>
+// ROBUST: the weighted round (include/vgicp_hip_robust.h), single device, !STAMPS, !FUSED, !TEAM: accumulate_match's
+// contribution takes the weight, everything else is the plain body's.
+template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool FUSED = false, bool TEAM = false, bool ROBUST = false>
 __device__ __forceinline__ void persistent_body(const PersistArgs& a, const FusedUpload& up, const TeamView& tv = TeamView()) {
+  static_assert(!ROBUST || (!MULTI && !STAMPS && !FUSED && !TEAM), "the robust round runs the single-device bodies only");
   static_assert(!FUSED || (!MULTI && !STAMPS && !MANY), "the fused upload serves the single-device one-point-per-thread body");
   static_assert(!TEAM || (!MULTI && !STAMPS && !MANY && !FUSED), "teams run the single-device one-point-per-thread body");
   static_assert(BLOCK / kSlots == kFolders, "the exchange reproduces the fold order of iterate_kernel<512>");
@@ -1166,6 +1224,8 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
   const int max_it = a.max_iteration;
   const double inv_voxel = 1.0 / a.voxel_size;
   const double same_margin = 0x1p-20 * a.voxel_size;  // same_voxel_coord
+  RobustSetting robust;
+  if constexpr (ROBUST) robust = robust_setting(a.robust_kernel, a.robust_scale2, a.robust_gate);  // uniform
 
   double q0[kScanPlanes];
 #pragma unroll
@@ -1226,7 +1286,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
           if (hit) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) S[k] = Sv[k];
-            accumulate_match<true>(R, p, C, mu, S, v);
+            accumulate_match<true, ROBUST>(R, p, C, mu, S, v, robust);
           }
         }
       } else {
@@ -1272,7 +1332,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
           if (got) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) C[k] = q[3 + k];
-            accumulate_match<decltype(first_of_round)::value>(R, p, C, m2, S, v);
+            accumulate_match<decltype(first_of_round)::value, ROBUST>(R, p, C, m2, S, v, robust);
           }
         };
         // the thread's first point stays in registers (its voxel record does not: the memo finds it), the next
@@ -1536,17 +1596,17 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
 // after all, the workgroups run the one-point-per-thread body — the mapping, the sums and hence the bits of the launch
 // that a settled scan of that size gets (without the neighbour prefetch, which changes no result) — so the chain that
 // does not wait returns the bits of the one that does, whatever the sweep's raw size.
-template <int BLOCK, bool MULTI, bool STAMPS, bool MANY>
+template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false>
 __global__ __launch_bounds__(BLOCK) void persistent_kernel(PersistArgs a) {
   const FusedUpload none{};
   if constexpr (MANY) {
     const uint32_t n_pts = a.n_dev ? (*a.n_dev < a.n ? *a.n_dev : a.n) : a.n;  // uniform
     if (n_pts <= gridDim.x * (uint32_t)(BLOCK - 64)) {
-      persistent_body<BLOCK, MULTI, STAMPS, false>(a, none);
+      persistent_body<BLOCK, MULTI, STAMPS, false, false, false, ROBUST>(a, none);
       return;
     }
   }
-  persistent_body<BLOCK, MULTI, STAMPS, MANY>(a, none);
+  persistent_body<BLOCK, MULTI, STAMPS, MANY, false, false, ROBUST>(a, none);
 }
 
 // The fused align: the upload's packing happens inside round 0 (a separate kernel, so that the production
@@ -2021,6 +2081,15 @@ inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((w
 }  // namespace
 
 hipError_t launch_iterate(hipStream_t s, const IterArgs& args, uint32_t grid, int block) {
+  if (args.robust_kernel != 0 || args.robust_gate > 0.0) {   // the weighted round: instantiations of their own
+    switch (block) {
+      case 256: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<256, true>), dim3(grid), dim3(256), 0, s, args); break;
+      case 512: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<512, true>), dim3(grid), dim3(512), 0, s, args); break;
+      case 1024: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<1024, true>), dim3(grid), dim3(1024), 0, s, args); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (block) {
     case 256: ++g_kernel_launches; hipLaunchKernelGGL(iterate_kernel<256>, dim3(grid), dim3(256), 0, s, args); break;
     case 512: ++g_kernel_launches; hipLaunchKernelGGL(iterate_kernel<512>, dim3(grid), dim3(512), 0, s, args); break;
@@ -2088,15 +2157,15 @@ void persistent_exchange_image(uint32_t grid, unsigned long long* rows_words, un
 }
 
 namespace {
-template <bool MULTI, bool STAMPS, bool MANY>
+template <bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false>
 hipError_t launch_persistent_as(hipStream_t s, const PersistArgs& args, uint32_t grid, size_t dyn, int device) {
   (void)device;
-  ++g_kernel_launches; hipLaunchKernelGGL((persistent_kernel<512, MULTI, STAMPS, MANY>), dim3(grid), dim3(512), dyn, s, args);
+  ++g_kernel_launches; hipLaunchKernelGGL((persistent_kernel<512, MULTI, STAMPS, MANY, ROBUST>), dim3(grid), dim3(512), dyn, s, args);
   return hipGetLastError();
 }
-template <bool MULTI, bool STAMPS, bool MANY>
+template <bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false>
 hipError_t raise_lds_limit() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&persistent_kernel<512, MULTI, STAMPS, MANY>),
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&persistent_kernel<512, MULTI, STAMPS, MANY, ROBUST>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
 }
 }  // namespace
@@ -2116,6 +2185,8 @@ hipError_t persistent_prepare_device() {
   if (e == hipSuccess) e = raise_lds_limit<true, false, true>();
   if (e == hipSuccess) e = raise_lds_limit<true, true, false>();
   if (e == hipSuccess) e = raise_lds_limit<true, true, true>();
+  if (e == hipSuccess) e = raise_lds_limit<false, false, false, true>();   // the robust round: single device, no stamps
+  if (e == hipSuccess) e = raise_lds_limit<false, false, true, true>();
   return e;
 }
 
@@ -2132,6 +2203,11 @@ hipError_t launch_persistent(hipStream_t s, const PersistArgs& args, uint32_t gr
   if (dyn > kPersistDynLds) return hipErrorInvalidValue;
   const bool multi = args.world > 1, stamps = args.stamps != nullptr;
   const bool many = (uint64_t)args.n > (uint64_t)grid * kPersistWorkers;
+  if (args.robust_kernel != 0 || args.robust_gate > 0.0) {   // the weighted round: one device, no stamps
+    if (multi) return hipErrorInvalidValue;
+    return many ? launch_persistent_as<false, false, true, true>(s, args, grid, dyn, device)
+                : launch_persistent_as<false, false, false, true>(s, args, grid, dyn, device);
+  }
   if (many) {
     if (multi) return stamps ? launch_persistent_as<true, true, true>(s, args, grid, dyn, device)
                              : launch_persistent_as<true, false, true>(s, args, grid, dyn, device);
@@ -2170,14 +2246,19 @@ hipError_t launch_persistent_teams(hipStream_t s, const PersistArgs& args, const
 // Whether `grid` 512-thread workgroups of the persistent kernel with this much dynamic LDS can all be
 // resident at once on the current device (the in-kernel exchange requires it).
 hipError_t persistent_max_resident(uint32_t dyn_lds_bytes, int cu_count, uint32_t* max_grid) {
-  int per_cu = 0;
-  const void* fn = reinterpret_cast<const void*>(&persistent_kernel<512, true, false, true>);
-  // more than the default 64 KB of LDS per workgroup has to be asked for before the occupancy query can say yes
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
-  if (e != hipSuccess) return e;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 512, dyn_lds_bytes);
-  if (e != hipSuccess) return e;
-  *max_grid = per_cu > 0 ? (uint32_t)cu_count : 0u;  // one workgroup per CU is what the design uses
+  // the plain kernel with the most registers, and the robust round's (a body of its own: asked on its own)
+  const void* fns[2] = {reinterpret_cast<const void*>(&persistent_kernel<512, true, false, true>),
+                        reinterpret_cast<const void*>(&persistent_kernel<512, false, false, true, true>)};
+  *max_grid = (uint32_t)cu_count;  // one workgroup per CU is what the design uses
+  for (const void* fn : fns) {
+    int per_cu = 0;
+    // more than the default 64 KB of LDS per workgroup has to be asked for before the occupancy query can say yes
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
+    if (e != hipSuccess) return e;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 512, dyn_lds_bytes);
+    if (e != hipSuccess) return e;
+    if (per_cu <= 0) *max_grid = 0u;
+  }
   return hipSuccess;
 }
 

@@ -767,6 +767,8 @@ int get_frame_stats(vgicp_ctx* ctx, vgicp_frame_stats* out, int reset) {
 int set_option(vgicp_ctx* ctx, int option, int value) {
   vgicp_multi* g = ctx->multi;
   // the raw points are read from the first device only (vgicp_map_points_export, like vgicp_map_export): only it keeps them
+  if (option == VGICP_OPTION_ROBUST_KERNEL || option == VGICP_OPTION_ROBUST_SCALE_MICRO || option == VGICP_OPTION_GATE_MICRO)
+    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the robust round (vgicp_hip_robust.h) runs on a single-device context only");
   if (option == VGICP_OPTION_MAP_RAW_POINTS) return sub_fail(ctx, g->subs[0], vgicp_set_option(g->subs[0], option, value));
   return run_all(ctx, [&](int r) { return vgicp_set_option(g->subs[(size_t)r], option, value); });
 }

@@ -58,6 +58,10 @@ def load_library() -> C.CDLL:
     lib.host_localmap_counter.argtypes = [vp, C.c_int]
     lib.host_icp_create.restype = vp
     lib.host_icp_create.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int]
+    lib.host_icp_create_robust.restype = vp
+    lib.host_icp_create_robust.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, C.c_char_p, C.c_double, C.c_double]
+    lib.host_icp_set_robust.argtypes = [vp, C.c_int, C.c_double, C.c_double, dp]
+    lib.host_icp_hypotheses_per_launch.argtypes = [vp]
     lib.host_icp_destroy.argtypes = [vp]
     lib.host_icp_align.argtypes = [vp, sz, dp, dp, vp, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_uint64), sz]
@@ -194,11 +198,21 @@ class ICP:
     """ESKF_LIO::ICP: config keys as in registration.* of the reference's YAML."""
 
     def __init__(self, max_iteration: int, translation_sq_threshold: float, cosine_threshold: float,
-                 chunk_iterations: int = 0):
+                 chunk_iterations: int = 0, robust_kernel: Optional[str] = None, robust_scale: float = 1.0,
+                 gate: float = 0.0):
+        """robust_kernel ("none" / "huber" / "cauchy"), robust_scale, gate: the optional keys of registration.* that
+        switch the robust round on (vgicp_hip_robust.h); absent = the reference's plain least squares."""
         self._lib = load_library()
         self.max_iteration = int(max_iteration)
-        self._h = self._lib.host_icp_create(self.max_iteration, float(translation_sq_threshold),
-                                            float(cosine_threshold), int(chunk_iterations))
+        if robust_kernel is None and robust_scale == 1.0 and gate == 0.0:
+            self._h = self._lib.host_icp_create(self.max_iteration, float(translation_sq_threshold),
+                                                float(cosine_threshold), int(chunk_iterations))
+        else:
+            self._h = self._lib.host_icp_create_robust(
+                self.max_iteration, float(translation_sq_threshold), float(cosine_threshold), int(chunk_iterations),
+                None if robust_kernel is None else str(robust_kernel).encode(), float(robust_scale), float(gate))
+            if not self._h:
+                raise ValueError(self._lib.host_last_error().decode())
         self.iterations = 0
         self.converged = False
         self.correspondence_counts = np.zeros(0, dtype=np.uint64)
@@ -207,6 +221,18 @@ class ICP:
         if getattr(self, "_h", None):
             self._lib.host_icp_destroy(self._h)
             self._h = None
+
+    def setRobust(self, kind: int, scale: float, gate: float):
+        """ICP::setRobust -> (kind, scale, gate) as the library will use them; ValueError for what it refuses."""
+        out = np.zeros(3)
+        if self._lib.host_icp_set_robust(self._h, int(kind), float(scale), float(gate), _dp(out)) != 0:
+            raise ValueError(self._lib.host_last_error().decode())
+        return int(out[0]), float(out[1]), float(out[2])
+
+    @property
+    def hypotheses_per_launch(self) -> int:
+        """ICP::lastHypothesesPerLaunch(): of the last alignHypotheses; 1 = one by one."""
+        return int(self._lib.host_icp_hypotheses_per_launch(self._h))
 
     def align(self, points, covs, localMap: LocalMap, guess) -> np.ndarray:
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)

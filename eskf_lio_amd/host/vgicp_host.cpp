@@ -191,6 +191,41 @@ ICP * host_icp_create(
   c.chunkIterations = chunk_iterations;
   return new ICP(c);
 }
+// The same with the optional keys registration.robust_kernel (NULL = absent) / robust_scale / gate, as the YAML
+// constructor reads them.
+ICP * host_icp_create_robust(
+  int max_iteration, double translation_sq_threshold, double cosine_threshold, int chunk_iterations,
+  const char * robust_kernel, double robust_scale, double gate)
+{
+  ICP * out = nullptr;
+  guarded(
+    [&] {
+      ESKF_LIO::RegistrationConfig c;
+      c.maxIteration = max_iteration;
+      c.translationSquaredThreshold = translation_sq_threshold;
+      c.cosineThreshold = cosine_threshold;
+      c.chunkIterations = chunk_iterations;
+      if (robust_kernel) {c.robustKernel = ESKF_LIO::RegistrationConfig::robustKernelFromName(robust_kernel);}
+      c.robustScale = robust_scale;
+      c.robustGate = gate;
+      out = new ICP(c);
+    });
+  return out;
+}
+// icp->setRobust(kind, scale, gate); out3 (optional): kind, scale and gate as the library will use them
+int host_icp_set_robust(ICP * icp, int kind, double scale, double gate, double * out3)
+{
+  return guarded(
+    [&] {
+      icp->setRobust(kind, scale, gate);
+      if (out3) {
+        out3[0] = icp->robustKernel();
+        out3[1] = icp->robustScale();
+        out3[2] = icp->robustGate();
+      }
+    });
+}
+int host_icp_hypotheses_per_launch(const ICP * icp) {return icp->lastHypothesesPerLaunch();}
 void host_icp_destroy(ICP * icp) {delete icp;}
 
 // icp->align(cloud, localMap, guess)

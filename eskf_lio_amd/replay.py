@@ -623,7 +623,10 @@ class GpuBackend:
                                       removing_period=lm["removing_period"],
                                       device_resident=device_resident_map))
         reg = config["registration"]
-        self.icp = host.ICP(reg["max_iteration"], reg["translation_sq_threshold"], reg["cosine_threshold"])
+        # optional keys (vgicp_hip_robust.h): absent = the reference's plain least squares
+        self.icp = host.ICP(reg["max_iteration"], reg["translation_sq_threshold"], reg["cosine_threshold"],
+                            robust_kernel=reg.get("robust_kernel"), robust_scale=float(reg.get("robust_scale", 1.0)),
+                            gate=float(reg.get("gate", 0.0)))
         self.pre = host.CloudPreprocessor(config["cloud_preprocessor"]["voxel_size"], config["lidar_extrinsic"])
         self.iterations: List[int] = []
 
@@ -665,6 +668,9 @@ class DeviceBackend:
         self.last_evict = time.perf_counter()
         self.prev: Optional[np.ndarray] = None
         self.reg = config["registration"]
+        if self.reg.get("robust_kernel") is not None or self.reg.get("gate"):   # optional keys (vgicp_hip_robust.h)
+            self.ctx.set_robust(self.reg.get("robust_kernel") or "none", float(self.reg.get("robust_scale", 1.0)),
+                                float(self.reg.get("gate", 0.0)))
         self.voxel = config["cloud_preprocessor"]["voxel_size"]
         self.T_il = np.asarray(config["lidar_extrinsic"], dtype=np.float64)
         self.iterations: List[int] = []

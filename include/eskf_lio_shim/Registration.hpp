@@ -15,6 +15,9 @@
 // call (vgicp_hip_batch.h) — for an integrator without a prior, after a stall, or on re-entry into an earlier map.
 // evaluate / selectBestByScore / alignBestByScore score poses of a cloud (vgicp_hip_evaluate.h): fitness, inlier RMSE,
 // the VGICP objective and the information matrix at a pose, as an Open3D-style RegistrationResult carries them.
+// setRobust / the optional keys registration.robust_kernel, robust_scale, gate: a Huber or Cauchy weight and a gate on the
+// squared Mahalanobis residual in every round (vgicp_hip_robust.h, which also says in which units).  Absent keys mean
+// the reference's plain least squares.
 #ifndef ESKF_LIO_SHIM_REGISTRATION_HPP_
 #define ESKF_LIO_SHIM_REGISTRATION_HPP_
 
@@ -29,6 +32,7 @@
 #include "LocalMap.hpp"
 #include "../vgicp_hip_batch.h"
 #include "../vgicp_hip_evaluate.h"
+#include "../vgicp_hip_robust.h"
 
 namespace ESKF_LIO
 {
@@ -40,6 +44,19 @@ struct RegistrationConfig
   double translationSquaredThreshold = 1.0e-6;
   double cosineThreshold = 0.9999;
   int chunkIterations = 0;  // vgicp_params.chunk_iterations; 0 = library default
+  // robust rounds (vgicp_hip_robust.h; not in the reference's file): registration.robust_kernel / robust_scale / gate
+  int robustKernel = VGICP_ROBUST_NONE;
+  double robustScale = 1.0;   // c, in the library's regularised units (~0.1, not ~3)
+  double robustGate = 0.0;    // gate on d^2; 0 = none
+
+  // registration.robust_kernel: none | huber | cauchy
+  static int robustKernelFromName(const std::string & name)
+  {
+    if (name == "none") {return VGICP_ROBUST_NONE;}
+    if (name == "huber") {return VGICP_ROBUST_HUBER;}
+    if (name == "cauchy") {return VGICP_ROBUST_CAUCHY;}
+    throw std::invalid_argument("registration.robust_kernel must be none, huber or cauchy, not '" + name + "'");
+  }
 };
 
 class ICP
@@ -65,6 +82,7 @@ public:
     , cosineThreshold_(config.cosineThreshold)
     , chunkIterations_(config.chunkIterations)
   {
+    setRobust(config.robustKernel, config.robustScale, config.robustGate);
   }
 
 #if defined(ESKF_LIO_SHIM_HAVE_YAML)
@@ -73,12 +91,48 @@ public:
     , translationSquaredThreshold_(config["registration"]["translation_sq_threshold"].as<double>())
     , cosineThreshold_(config["registration"]["cosine_threshold"].as<double>())
   {
+    // optional keys, not in the reference's file; absent = the reference's plain least squares
+    const YAML::Node reg = config["registration"];
+    RegistrationConfig c;
+    if (reg["robust_kernel"].IsDefined()) {
+      c.robustKernel = RegistrationConfig::robustKernelFromName(reg["robust_kernel"].as<std::string>());
+    }
+    if (reg["robust_scale"].IsDefined()) {c.robustScale = reg["robust_scale"].as<double>();}
+    if (reg["gate"].IsDefined()) {c.robustGate = reg["gate"].as<double>();}
+    setRobust(c.robustKernel, c.robustScale, c.robustGate);
   }
 #endif
+
+  // The robust round of every later align / alignHypotheses of this ICP (vgicp_hip_robust.h): kind = VGICP_ROBUST_NONE,
+  // _HUBER or _CAUCHY, its scale c, and the gate on the squared Mahalanobis residual (0 = none), in the library's
+  // regularised units.  The library takes millionths: scale and gate are rounded to them.  Throws std::invalid_argument
+  // for anything the library would refuse, and changes nothing then.  While a kernel or a gate is set,
+  // alignHypotheses registers its guesses one by one (lastHypothesesPerLaunch() == 1) and evaluate() still scores the
+  // plain objective.
+  void setRobust(int kind, double scale, double gate)
+  {
+    if (kind != VGICP_ROBUST_NONE && kind != VGICP_ROBUST_HUBER && kind != VGICP_ROBUST_CAUCHY) {
+      throw std::invalid_argument("ICP::setRobust: kind must be VGICP_ROBUST_NONE, _HUBER or _CAUCHY");
+    }
+    const double scaleMicro = std::round(scale * 1e6), gateMicro = std::round(gate * 1e6);
+    if (!(scaleMicro >= 1.0 && scaleMicro <= 2147483647.0)) {
+      throw std::invalid_argument("ICP::setRobust: scale must be in [1e-6, 2147.48]");
+    }
+    if (!(gateMicro >= 0.0 && gateMicro <= 2147483647.0)) {
+      throw std::invalid_argument("ICP::setRobust: gate must be in [0, 2147.48]");
+    }
+    robustKernel_ = kind;
+    robustScaleMicro_ = static_cast<int>(scaleMicro);
+    robustGateMicro_ = static_cast<int>(gateMicro);
+  }
+  int robustKernel() const {return robustKernel_;}
+  double robustScale() const {return robustScaleMicro_ / 1000000.0;}   // as the library uses it
+  double robustGate() const {return robustGateMicro_ / 1000000.0;}
 
   Isometry3d align(const PointCloud & cloud, const LocalMap & localMap, const Isometry3d & guess)
   {
     vgicp_ctx * ctx = localMap.context();
+    applyRobust(ctx);
     vgicp_params params{};
     params.max_iteration = maxIteration_;
     params.chunk_iterations = chunkIterations_;
@@ -178,6 +232,7 @@ public:
       throw std::runtime_error("ICP::alignHypotheses: more than VGICP_BATCH_MAX guesses");
     }
     vgicp_ctx * ctx = localMap.context();
+    applyRobust(ctx);
     vgicp_params params{};
     params.max_iteration = maxIteration_;
     params.chunk_iterations = chunkIterations_;
@@ -398,6 +453,26 @@ public:
 private:
   ICP() = delete;
 
+  // The context may serve several ICP objects: THIS one's robust settings are put on it before each of its aligns.  With
+  // the mode off a refusal is not an error (a multi-device context refuses the options and never has the mode on; a
+  // stand-in of the C ABI may lack vgicp_set_option, which LocalMap.hpp references weakly); with it on, it is.
+  void applyRobust(vgicp_ctx * ctx) const
+  {
+    const bool on = robustKernel_ != VGICP_ROBUST_NONE || robustGateMicro_ != 0;
+    if (!vgicp_set_option) {
+      if (on) {throw std::runtime_error("ICP::setRobust: the linked vgicp module has no vgicp_set_option");}
+      return;
+    }
+    const int rcKernel = vgicp_set_option(ctx, VGICP_OPTION_ROBUST_KERNEL, robustKernel_);
+    const int rcScale = vgicp_set_option(ctx, VGICP_OPTION_ROBUST_SCALE_MICRO, robustScaleMicro_);
+    const int rcGate = vgicp_set_option(ctx, VGICP_OPTION_GATE_MICRO, robustGateMicro_);
+    if (on) {
+      shim::check(ctx, rcKernel, "vgicp_set_option(VGICP_OPTION_ROBUST_KERNEL)");
+      shim::check(ctx, rcScale, "vgicp_set_option(VGICP_OPTION_ROBUST_SCALE_MICRO)");
+      shim::check(ctx, rcGate, "vgicp_set_option(VGICP_OPTION_GATE_MICRO)");
+    }
+  }
+
   // vgicp_evaluate_resident on whatever scan is resident (1 <= poses.size() <= VGICP_EVAL_MAX)
   static std::vector<Evaluation> evaluateResidentScan(vgicp_ctx * ctx, const std::vector<Isometry3d> & poses)
   {
@@ -425,6 +500,9 @@ private:
   double translationSquaredThreshold_;
   double cosineThreshold_;
   int chunkIterations_ = 0;
+  int robustKernel_ = VGICP_ROBUST_NONE;
+  int robustScaleMicro_ = 1000000;
+  int robustGateMicro_ = 0;
   Stats lastStats_;
   bool lastUsedResidentScan_ = false;
   std::vector<uint64_t> fanCounts_;   // the last fan's per-round counts, hypothesis-major

@@ -8,6 +8,8 @@ options: --out traj.tum   --device-map (keep the voxel grid on the GPU only)   -
          --resident (the scan never leaves the GPU between the raw sweep and the pose)
          --raw-points-on-device (with --resident: the map keeps its raw points, VGICP_OPTION_MAP_RAW_POINTS; their
          export is timed at the end)
+         --robust-kernel none|huber|cauchy  --robust-scale C  --gate G (robust rounds, include/vgicp_hip_robust.h: in the
+         library's regularised units, ~0.1; off by default)
 The configuration is the reference's config/hilti_config.yaml as a dict (eskf_lio_amd/replay.py:DEFAULT_CONFIG);
 --config file.yaml overrides it with a file of the reference's own layout."""
 import argparse
@@ -63,6 +65,11 @@ def main():
                     help="scan stays on the GPU from the raw sweep to the pose (vgicp_scan_prepare chain)")
     ap.add_argument("--raw-points-on-device", action="store_true",
                     help="with --resident: the device map keeps every voxel's raw points (VGICP_OPTION_MAP_RAW_POINTS)")
+    ap.add_argument("--robust-kernel", choices=("none", "huber", "cauchy"), default=None,
+                    help="robust weight of every registration round (registration.robust_kernel)")
+    ap.add_argument("--robust-scale", type=float, default=None, help="its scale c (registration.robust_scale)")
+    ap.add_argument("--gate", type=float, default=None,
+                    help="gate on the squared Mahalanobis residual, 0 = none (registration.gate)")
     args = ap.parse_args()
     if args.raw_points_on_device and not args.resident:
         ap.error("--raw-points-on-device needs --resident")
@@ -70,6 +77,10 @@ def main():
     if args.config:
         cfg, imu_topic, lidar_topic = config_from_yaml(args.config)
     imu_topic, lidar_topic = args.imu_topic or imu_topic, args.lidar_topic or lidar_topic
+    robust = {k: v for k, v in (("robust_kernel", args.robust_kernel), ("robust_scale", args.robust_scale),
+                                ("gate", args.gate)) if v is not None}
+    if robust:
+        cfg = dict(cfg, registration=dict(cfg["registration"], **robust))
     truth = None
     if args.bag:
         events = replay.read_rosbag2(args.bag, imu_topic, lidar_topic)
