@@ -19,9 +19,9 @@ IterArgs base_args(const vgicp_ctx* ctx) {
   a.mask = (uint32_t)(ctx->slots - 1);
   a.table = ctx->table;
   a.voxel_size = ctx->voxel_size;
-  a.log = ctx->d_log;
+  a.log = ctx->d_log_rows();
   a.stamps = ctx->d_stamps;
-  a.memo = static_cast<int4*>(ctx->d_memo);
+  a.memo = static_cast<int4*>(ctx->d_memo.get());
   a.memo_valid = 0;   // the caller knows which launch of the align this is
   a.scan_seq = ctx->scan_seq;
   a.asym_dev = (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
@@ -113,7 +113,7 @@ void state_to_pose(const double* pose12, double* m16) {
 // at context creation and after a launch that gave up.
 int reset_persistent_exchange(vgicp_ctx* ctx) {
   const size_t rw = persistent_rows_words(), pw = persistent_parts_words();
-  unsigned long long* img = static_cast<unsigned long long*>(ctx->h_exchange_image);
+  unsigned long long* img = static_cast<unsigned long long*>(ctx->h_exchange_image.get());
   persistent_exchange_image(ctx->persist_grid, img, img + rw);
   VG_HIP(ctx, hipMemcpyAsync(ctx->d_rows_persist, img, rw * 8, hipMemcpyHostToDevice, ctx->stream));
   VG_HIP(ctx, hipMemcpyAsync(ctx->d_parts_persist, img + rw, pw * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -136,19 +136,17 @@ int reserve_dense(vgicp_ctx* ctx) {
   if (!ctx->table || ctx->dense_slots_threshold == 0 || ctx->slots < ctx->dense_slots_threshold) return VGICP_OK;
   const uint64_t cap = ctx->slots / 2;
   if (cap > ctx->dense_capacity) {
-    if (ctx->d_dense) { VG_HIP(ctx, hipStreamSynchronize(ctx->stream)); VG_HIP(ctx, hipFree(ctx->d_dense)); }
-    ctx->d_dense = nullptr;
+    if (ctx->d_dense) VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->dense_capacity = 0;
     ctx->dense_version = 0;
-    VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_dense), cap * sizeof(VoxelRecord)));
+    VG_HIP(ctx, ctx->d_dense.alloc(cap * sizeof(VoxelRecord)));
     ctx->dense_capacity = cap;
   }
   const uint32_t nb = table_dense_blocks(ctx->slots);
   if (nb + 1 > ctx->dense_counts_capacity) {
-    if (ctx->d_dense_counts) { VG_HIP(ctx, hipStreamSynchronize(ctx->stream)); VG_HIP(ctx, hipFree(ctx->d_dense_counts)); }
-    ctx->d_dense_counts = nullptr;
+    if (ctx->d_dense_counts) VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->dense_counts_capacity = 0;
-    VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_dense_counts), (size_t)(nb + 1) * sizeof(uint32_t)));
+    VG_HIP(ctx, ctx->d_dense_counts.alloc((size_t)(nb + 1) * sizeof(uint32_t)));
     ctx->dense_counts_capacity = nb + 1;
   }
   return VGICP_OK;
@@ -274,8 +272,8 @@ int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* par
   a.round0 = ctx->persist_round0;
   // final state and per-round log go straight into pinned host memory (posted PCIe writes, 5.4 KB per align):
   // no copy-back to enqueue after the launch
-  a.state = reinterpret_cast<AlignState*>(ctx->h_log_dev - kSlots);
-  a.log = ctx->h_log_dev;
+  a.state = reinterpret_cast<AlignState*>(ctx->h_log.dev());
+  a.log = ctx->h_log_rows_dev();
   // between GPUs the ranks' host threads reach the launch at slightly different times: a rank waits much longer
   // for a peer (~1 s) than for a workgroup of its own device (~50 ms) before it gives up
   const bool multi = ctx->peers_connected && ctx->peer_world > 1;
@@ -293,7 +291,7 @@ int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* par
   a.mail_round0 = ctx->mail_round0;
   a.mail_seq = multi ? ++ctx->mail_seq : 0u;
   // the launch reports into the header row of the pinned log: who gave up (any workgroup) and workgroup 0's verdict
-  AlignState* header = reinterpret_cast<AlignState*>(ctx->h_log - kSlots);
+  AlignState* header = reinterpret_cast<AlignState*>(ctx->h_log.get());
   header->abort_seq = 0;
   header->outcome = kOutcomeNone;
   return fetch_insert_totals(ctx);   // normally carried by the preparation's copy
@@ -323,14 +321,14 @@ int align_persistent(vgicp_ctx* ctx, const double* guess, const vgicp_params* pa
     std::fprintf(stderr, "[vgicp trace] align: enqueue %.3f ms, hipStreamSynchronize %.3f ms, the launch itself %.3f ms (events)\n",
                  (ta1 - ta0) * 1e3, (ta2 - ta1) * 1e3, (double)ms);
   AlignState* result = &ctx->h_state[0];
-  std::memcpy(result, ctx->h_log - kSlots, sizeof(AlignState));
+  std::memcpy(result, ctx->h_log, sizeof(AlignState));
   ++ctx->persistent_launches;
   VG_RC(settle_after_launch(ctx, *result, a.seq, multi));
   if (launch_committed(*result, a.seq, result->abort_seq)) {
     advance_exchange(ctx, *result, multi);
     if (ctx->stage_events) ctx->ev_stage_set[3] = true;
     *ran = true;
-    return report_align(ctx, *result, ctx->h_log, plan.peer_path ? ctx->peer_world : 1, 1, ms * 1e-3, t0, out_pose, stats);
+    return report_align(ctx, *result, ctx->h_log_rows(), plan.peer_path ? ctx->peer_world : 1, 1, ms * 1e-3, t0, out_pose, stats);
   }
   // An in-kernel wait timed out (a workgroup was not resident: something else holds CUs of this device; or a peer GPU
   // did not deliver).  Put the exchange back into its initial state, use the per-launch loop for this align and the
@@ -399,8 +397,8 @@ int loop_launches(vgicp_ctx* ctx, const vgicp_params* params, int* total_launche
   *total_launches = params->max_iteration > 0 ? params->max_iteration + 1 : 0;
   if ((params->flags & VGICP_FLAG_PROFILE) == 0) return VGICP_OK;
   for (size_t k = ctx->ev_prof.size(); k < 2 * (size_t)*total_launches; ++k) {
-    ctx->ev_prof.push_back(nullptr);
-    VG_HIP(ctx, hipEventCreate(&ctx->ev_prof.back()));
+    ctx->ev_prof.emplace_back();
+    VG_HIP(ctx, ctx->ev_prof.back().create());
   }
   return VGICP_OK;
 }
@@ -415,7 +413,7 @@ int report_loop(vgicp_ctx* ctx, const vgicp_params* params, int launched, int wo
   VG_HIP(ctx, hipMemcpyAsync(hf, ctx->d_state + (launched & 1), sizeof(AlignState), hipMemcpyDeviceToHost, ctx->stream));
   const bool want_log = stats && (stats->corr_count || stats->normal_eq);
   if (want_log && max_it > 0)
-    VG_HIP(ctx, hipMemcpyAsync(ctx->h_log, ctx->d_log, (size_t)max_it * kSlots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    VG_HIP(ctx, hipMemcpyAsync(ctx->h_log_rows(), ctx->d_log_rows(), (size_t)max_it * kSlots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   float ms = 0.f;
   if (stats) VG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
@@ -427,7 +425,7 @@ int report_loop(vgicp_ctx* ctx, const vgicp_params* params, int launched, int wo
       stats->kernel_ms[it] = k;
     }
   }
-  return report_align(ctx, *hf, ctx->h_log, world, launched, ms * 1e-3, t0, out_pose, stats);
+  return report_align(ctx, *hf, ctx->h_log_rows(), world, launched, ms * 1e-3, t0, out_pose, stats);
 }
 
 // One launch per round for the resident scan, which must be settled (RCCL, VGICP_FLAG_NO_PERSISTENT / _PROFILE, a

@@ -37,7 +37,7 @@ int run_batch_teams(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp
   t.team_wgs = team_wgs;
   t.folder_rows = (team_wgs + kFolders - 1) / kFolders;
   t.slot_words = (uint32_t)slot_words;
-  t.abort_word = reinterpret_cast<uint32_t*>(ctx->h_batch_dev + (size_t)VGICP_BATCH_MAX * slot_words);
+  t.abort_word = reinterpret_cast<uint32_t*>(ctx->h_batch.dev() + (size_t)VGICP_BATCH_MAX * slot_words);
   *abort_host = 0;
   for (size_t h = 0; h < k; ++h) {
     AlignState* st = batch_state(ctx, h);
@@ -50,8 +50,8 @@ int run_batch_teams(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp
   for (size_t h0 = 0; h0 < k; h0 += width, ++launches) {
     t.teams = (uint32_t)std::min<size_t>(width, k - h0);
     for (uint32_t h = 0; h < t.teams; ++h) pose_to_state(guesses + 16 * (h0 + h), t.pose0[h]);
-    a.state = reinterpret_cast<AlignState*>(ctx->h_batch_dev + h0 * slot_words);
-    a.log = ctx->h_batch_dev + h0 * slot_words + kSlots;
+    a.state = reinterpret_cast<AlignState*>(ctx->h_batch.dev() + h0 * slot_words);
+    a.log = ctx->h_batch.dev() + h0 * slot_words + kSlots;
     // T, and with it the owner of every exchange word, changes with the scan, and teams end in different rounds: every
     // launch starts from words that are unset throughout (0xFF bytes = kRowUnset)
     VG_HIP(ctx, hipMemsetAsync(ctx->d_batch_exchange, 0xFF, exchange_bytes, ctx->stream));

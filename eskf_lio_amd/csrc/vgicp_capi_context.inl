@@ -1,12 +1,14 @@
 // vgicp_capi_context.inl — part of vgicp_capi.hip.
 // The context: creation (device checks, buffers, the environment's switches — read here, once), destruction, error
-// text, device info, counters, frame statistics, options.
+// text, device info, counters, frame statistics, options.  The context's members own their memory, events and stream
+// (vgicp_owned.h): a creation that fails half way returns and nothing stays behind, and vgicp_destroy is only what is
+// not ownership — waiting for the stream, the copy crew, the peers, RCCL — before `delete ctx` releases the rest.
 namespace {
 int ensure_mailbox(vgicp_ctx* ctx) {
   if (ctx->d_mail) return VGICP_OK;
   // fine-grained: stores of another GPU's kernel become visible to this GPU's running kernel
-  VG_HIP(ctx, hipExtMallocWithFlags(reinterpret_cast<void**>(&ctx->d_mail), kMailWords * 8, hipDeviceMallocFinegrained));
-  VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_mail_table), kMaxRanks * sizeof(double*)));
+  VG_HIP(ctx, ctx->d_mail.alloc(kMailWords * 8, true));
+  VG_HIP(ctx, ctx->d_mail_table.alloc(kMaxRanks * sizeof(double*)));
   return VGICP_OK;
 }
 
@@ -45,77 +47,56 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(nullptr, VGICP_ERR_NO_DEVICE,
                 std::string("device is ") + prop.gcnArchName + ", this module is built for gfx950 only");
-  vgicp_ctx* ctx = new vgicp_ctx;
+  // held here until the last step: an early return frees what was made so far
+  std::unique_ptr<vgicp_ctx> ctx(new vgicp_ctx);
   ctx->id = ++g_context_ids;
   ctx->device = device_id;
   ctx->cu_count = prop.multiProcessorCount;
   ctx->hbm_bytes = prop.totalGlobalMem;
   ctx->arch = prop.gcnArchName;
-  auto bail = [&](hipError_t err, const char* what) {
-    int rc = fail_hip(nullptr, err, what);
-    delete ctx;
-    return rc;
-  };
-#define VG_CREATE(call)                                  \
-  do {                                                   \
-    hipError_t e__ = (call);                             \
-    if (e__ != hipSuccess) return bail(e__, #call);      \
-  } while (0)
-  VG_CREATE(hipSetDevice(device_id));
-  VG_CREATE(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+  VG_HIP(nullptr, hipSetDevice(device_id));
+  VG_HIP(nullptr, ctx->stream.create());
   // the insertion's running totals (4 words) sit right behind the counter block: ONE copy after a preparation brings
   // both back, so a deferred insertion needs no copy of its own in the frame chain
   // ... and behind those the raw-point log's words (kInsertWords: 4 + 4)
-  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_counters), (kCounterWords + kInsertWords) * sizeof(uint32_t)));
-  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_counters), kCounterWords * sizeof(uint32_t), 0));
-  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_prep), (kCounterWords + kInsertWords) * sizeof(uint32_t), 0));
-  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_raw_ctr), 4 * sizeof(uint32_t), 0));
-  VG_CREATE(hipMalloc(&ctx->d_tiles, preprocess_tile_bytes()));
-  VG_CREATE(hipMemset(ctx->d_tiles, 0, preprocess_tile_bytes()));
-  VG_CREATE(hipMemset(ctx->d_counters, 0, (kCounterWords + kInsertWords) * sizeof(uint32_t)));
+  VG_HIP(nullptr, ctx->d_counters.alloc((kCounterWords + kInsertWords) * sizeof(uint32_t)));
+  VG_HIP(nullptr, ctx->h_counters.alloc(kCounterWords * sizeof(uint32_t)));
+  VG_HIP(nullptr, ctx->h_prep.alloc((kCounterWords + kInsertWords) * sizeof(uint32_t)));
+  VG_HIP(nullptr, ctx->h_raw_ctr.alloc(4 * sizeof(uint32_t)));
+  VG_HIP(nullptr, ctx->d_tiles.alloc(preprocess_tile_bytes()));
+  VG_HIP(nullptr, hipMemset(ctx->d_tiles, 0, preprocess_tile_bytes()));
+  VG_HIP(nullptr, hipMemset(ctx->d_counters, 0, (kCounterWords + kInsertWords) * sizeof(uint32_t)));
   ctx->d_ins_counters = ctx->d_counters + kCounterWords;
-  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_fetch_hdr), 640, 0));
+  VG_HIP(nullptr, ctx->h_fetch_hdr.alloc_mapped(640));
   std::memset(ctx->h_fetch_hdr, 0, 640);
-  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_fetch_sums), 65 * sizeof(unsigned long long)));
-  VG_CREATE(hipMemset(ctx->d_fetch_sums, 0, 65 * sizeof(unsigned long long)));
-  { void* dev = nullptr; VG_CREATE(hipHostGetDevicePointer(&dev, ctx->h_fetch_hdr, 0)); ctx->h_fetch_hdr_dev = static_cast<unsigned long long*>(dev); }
-  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_ins_counters), kInsertWords * sizeof(uint32_t), 0));
+  VG_HIP(nullptr, ctx->d_fetch_sums.alloc(65 * sizeof(unsigned long long)));
+  VG_HIP(nullptr, hipMemset(ctx->d_fetch_sums, 0, 65 * sizeof(unsigned long long)));
+  VG_HIP(nullptr, ctx->h_ins_counters.alloc(kInsertWords * sizeof(uint32_t)));
   ctx->h_ins_counters[0] = ctx->h_ins_counters[1] = 0;
   if (const char* se = std::getenv("VGICP_STAGE_EVENTS"); se && se[0] == '1') {
-    for (auto& e : ctx->ev_stage) VG_CREATE(hipEventCreate(&e));
+    for (auto& e : ctx->ev_stage) VG_HIP(nullptr, e.create());
     ctx->stage_events = true;
   }
   ctx->stat_launches0 = g_kernel_launches;
   ctx->stat_copies0 = g_copy_ops;
   ctx->stat_syncs0 = g_sync_ops;
-  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_state), 2 * sizeof(AlignState)));
-  VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_state),
-                          (1 + kMaxChunksInFlight) * sizeof(AlignState), 0));
-  for (int k = 0; k < 2; ++k)
-    VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_rows[k]),
-                        (size_t)kMaxIterBlocks * kSlots * sizeof(double)));
-  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_rows_persist), persistent_rows_words() * 8));
-  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_parts_persist), persistent_parts_words() * 8));
-  VG_CREATE(hipHostMalloc(&ctx->h_exchange_image, (persistent_rows_words() + persistent_parts_words()) * 8, 0));
+  VG_HIP(nullptr, ctx->d_state.alloc(2 * sizeof(AlignState)));
+  VG_HIP(nullptr, ctx->h_state.alloc((1 + kMaxChunksInFlight) * sizeof(AlignState)));
+  for (auto& rows : ctx->d_rows) VG_HIP(nullptr, rows.alloc((size_t)kMaxIterBlocks * kSlots * sizeof(double)));
+  VG_HIP(nullptr, ctx->d_rows_persist.alloc(persistent_rows_words() * 8));
+  VG_HIP(nullptr, ctx->d_parts_persist.alloc(persistent_parts_words() * 8));
+  VG_HIP(nullptr, ctx->h_exchange_image.alloc((persistent_rows_words() + persistent_parts_words()) * 8));
   {
     // the batched align's storage: nothing is allocated inside vgicp_align_resident_batch
     const size_t batch_bytes = ((size_t)VGICP_BATCH_MAX * kBatchSlotRows + 1) * kSlots * sizeof(double);
-    VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_batch_exchange), (team_rows_words() + team_parts_words()) * 8));
-    VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_batch), batch_bytes, 0));
+    VG_HIP(nullptr, ctx->d_batch_exchange.alloc((team_rows_words() + team_parts_words()) * 8));
+    VG_HIP(nullptr, ctx->h_batch.alloc_mapped(batch_bytes));
     std::memset(ctx->h_batch, 0, batch_bytes);
-    void* dev = nullptr;
-    VG_CREATE(hipHostGetDevicePointer(&dev, ctx->h_batch, 0));
-    ctx->h_batch_dev = static_cast<double*>(dev);
-  }
-  {
     // ... and vgicp_evaluate_resident's: the rows of one launch pair, results and poses page-locked
     const size_t eval_bytes = (size_t)VGICP_EVAL_MAX * (kSlots + 12) * sizeof(double);
-    VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_eval_rows), (size_t)kEvalRowBudget * kSlots * sizeof(double)));
-    VG_CREATE(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_eval), eval_bytes, 0));
+    VG_HIP(nullptr, ctx->d_eval_rows.alloc((size_t)kEvalRowBudget * kSlots * sizeof(double)));
+    VG_HIP(nullptr, ctx->h_eval.alloc_mapped(eval_bytes));
     std::memset(ctx->h_eval, 0, eval_bytes);
-    void* dev = nullptr;
-    VG_CREATE(hipHostGetDevicePointer(&dev, ctx->h_eval, 0));
-    ctx->h_eval_dev = static_cast<double*>(dev);
   }
   ctx->persist_grid = (uint32_t)std::min<int>(ctx->cu_count, kExchangeRows);
   if (max_persist_grid >= 1 && max_persist_grid < ctx->persist_grid) ctx->persist_grid = max_persist_grid;
@@ -144,8 +125,8 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
     // a launch plan asks for (memo + parked points of a scan bigger than the grid: 150 KB) must fit a CU — checked
     // once here instead of found out by a timeout on every align
     uint32_t resident = 0;
-    VG_CREATE(persistent_prepare_device());
-    VG_CREATE(persistent_max_resident(persistent_max_dyn_lds_bytes(), ctx->cu_count, &resident));
+    VG_HIP(nullptr, persistent_prepare_device());
+    VG_HIP(nullptr, persistent_max_resident(persistent_max_dyn_lds_bytes(), ctx->cu_count, &resident));
     if (resident < ctx->persist_grid) {
       ctx->persistent_enabled = false;
       std::fprintf(stderr, "[vgicp] a persistent workgroup with %u bytes of LDS does not fit a compute unit of this device: "
@@ -156,32 +137,78 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
     const int b = std::atoi(blk);
     if (b == 256 || b == 512 || b == 1024) ctx->iter_block = b;
   }
-  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_sums), kSlots * sizeof(double)));
-  VG_CREATE(hipMemset(ctx->d_state, 0, 2 * sizeof(AlignState)));
+  VG_HIP(nullptr, ctx->d_sums.alloc(kSlots * sizeof(double)));
+  VG_HIP(nullptr, hipMemset(ctx->d_state, 0, 2 * sizeof(AlignState)));
   if (const char* dbg = std::getenv("VGICP_DEBUG_STAMPS"); dbg && (dbg[0] == '1' || dbg[0] == '2')) {
-    VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_stamps), (32 + kExchangeRows) * sizeof(uint64_t)));
-    VG_CREATE(hipMemset(ctx->d_stamps, 0, (32 + kExchangeRows) * sizeof(uint64_t)));
+    VG_HIP(nullptr, ctx->d_stamps.alloc((32 + kExchangeRows) * sizeof(uint64_t)));
+    VG_HIP(nullptr, hipMemset(ctx->d_stamps, 0, (32 + kExchangeRows) * sizeof(uint64_t)));
   }
-  VG_CREATE(hipMalloc(reinterpret_cast<void**>(&ctx->d_unit_clock), sizeof(unsigned long long)));
-  VG_CREATE(hipMemset(ctx->d_unit_clock, 0, sizeof(unsigned long long)));
+  VG_HIP(nullptr, ctx->d_unit_clock.alloc(sizeof(unsigned long long)));
+  VG_HIP(nullptr, hipMemset(ctx->d_unit_clock, 0, sizeof(unsigned long long)));
   {
     int khz = 0;
-    VG_CREATE(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device));
+    VG_HIP(nullptr, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device));
     ctx->wall_clock_hz = khz > 0 ? khz * 1e3 : 0.0;
   }
-  VG_CREATE(hipEventCreate(&ctx->ev_begin));
-  VG_CREATE(hipEventCreate(&ctx->ev_end));
-  for (int k = 0; k < kMaxChunksInFlight; ++k)
-    VG_CREATE(hipEventCreateWithFlags(&ctx->ev_chunk[k], hipEventDisableTiming));
-#undef VG_CREATE
-  if (reset_persistent_exchange(ctx) != VGICP_OK) {
+  VG_HIP(nullptr, ctx->ev_begin.create());
+  VG_HIP(nullptr, ctx->ev_end.create());
+  for (auto& e : ctx->ev_chunk) VG_HIP(nullptr, e.create(false));
+  if (reset_persistent_exchange(ctx.get()) != VGICP_OK) {
     g_create_error = ctx->err;
-    vgicp_destroy(ctx);
+    vgicp_destroy(ctx.release());
     return VGICP_ERR_HIP;
   }
-  *out = ctx;
+  *out = ctx.release();
   return VGICP_OK;
 }
+
+namespace {
+// VGICP_DEBUG_STAMPS: what the kernels' clock stamps add up to, printed when the context goes
+void report_stamps(vgicp_ctx* ctx) {
+  if (!ctx->d_stamps) return;
+  uint64_t h[32] = {0};
+  if (hipMemcpy(h, ctx->d_stamps, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[4] > 0) {
+    const double k = 0.01 / (double)h[4];  // 100 MHz ticks -> us per launch
+    std::fprintf(stderr, "[vgicp stamps] body launches %llu | workgroup 0, first worker lane: loads+fold+barrier %.2f us, "
+                 "speculative probe || solve, to 2nd barrier %.2f us, verify+accumulate loop %.2f us, "
+                 "butterfly+row store %.2f us | solver wave: solve+publish %.2f us\n", (unsigned long long)h[4], h[0] * k,
+                 h[5] * k, h[1] * k, h[2] * k, h[6] * k);
+  }
+  if (hipMemcpy(h, ctx->d_stamps, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[13] > 0) {
+    for (int o = 8; o <= 16; o += 8) {
+      const double k = 0.01 / (double)h[o + 5];  // 100 MHz ticks -> us per round
+      std::fprintf(stderr, "[vgicp stamps] persistent, workgroup 0 %s, %llu rounds: accumulate+butterfly (to the barrier) "
+                   "%.2f us, publish + level-1 fold %.2f us, level-2 poll %.2f us, solve+broadcast %.2f us\n",
+                   o == 8 ? "solver wave" : "first worker lane", (unsigned long long)h[o + 5], h[o] * k, h[o + 1] * k,
+                   h[o + 2] * k, h[o + 3] * k);
+    }
+    const double kf = 0.01 / (double)h[13];
+    std::fprintf(stderr, "[vgicp stamps] inside solve+broadcast (solver wave of workgroup 0): re-arm + totals through LDS to registers "
+                 "%.3f us, LDL^T %.3f us, exponential + compose + test %.3f us, pose to LDS (+ state, workgroup 0) %.3f us, the rest "
+                 "(barrier, pose read by every wave) %.3f us\n", h[24] * kf, h[25] * kf, h[26] * kf, h[27] * kf,
+                 (h[11] - h[24] - h[25] - h[26] - h[27]) * kf);
+  }
+  uint64_t wg[kExchangeRows];
+  if (h[13] > 0 && hipMemcpy(wg, ctx->d_stamps + 32, sizeof wg, hipMemcpyDeviceToHost) == hipSuccess) {
+    const double k = 0.01 / (double)h[13];
+    double lo = 1e30, hi = 0.0, sum = 0.0;
+    int hi_at = 0;
+    const int g = (int)ctx->persist_grid;
+    for (int b = 0; b < g; ++b) {
+      const double v = wg[b] * k;
+      sum += v;
+      if (v < lo) lo = v;
+      if (v > hi) { hi = v; hi_at = b; }
+    }
+    std::fprintf(stderr, "[vgicp stamps] persistent, time to the first barrier per workgroup (mean over rounds): min %.2f us, "
+                 "mean %.2f us, max %.2f us (workgroup %d)\n", lo, sum / g, hi, hi_at);
+    if (const char* all = std::getenv("VGICP_DEBUG_STAMPS"); all && all[0] == '2') {  // every workgroup's figure
+      for (int b = 0; b < g; ++b) std::fprintf(stderr, "%s%.2f", b % 16 ? " " : "\n[vgicp stamps wg] ", wg[b] * k);
+      std::fprintf(stderr, "\n");
+    }
+  }
+}
+}  // namespace
 
 extern "C" {
 
@@ -190,114 +217,20 @@ int vgicp_destroy(vgicp_ctx* ctx) {
   if (ctx->multi) return vgicp_multi_api::destroy(ctx);
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  bool crew_lost = false;   // a copy thread that never came back may still write the staging memory: both are leaked then
   if (ctx->crew) {
-    crew_lost = ctx->crew->broken;
     ctx->crew->stop();
-    if (!crew_lost) delete ctx->crew;
-    ctx->crew = nullptr;
-  }
-  if (ctx->h_upload && !crew_lost) (void)hipHostFree(ctx->h_upload);
-  if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
-  for (auto& s : ctx->ahead) {
-    if (s.mem) (void)hipHostFree(s.mem);
-    if (s.done) (void)hipEventDestroy(s.done);
+    if (ctx->crew->broken) {
+      // a copy thread that never came back may still write the staging memory and look at the crew: all of it is leaked
+      (void)ctx->crew.release();
+      (void)ctx->h_upload.release();
+      for (auto& stage : ctx->h_raw_stage) (void)stage.release();
+    }
   }
   close_peers(ctx);
-  if (ctx->d_mail) (void)hipFree(ctx->d_mail);
-  if (ctx->d_mail_table) (void)hipFree(ctx->d_mail_table);
-  if (ctx->d_unit_clock) (void)hipFree(ctx->d_unit_clock);
   if (ctx->comm && ctx->rccl.CommDestroy) ctx->rccl.CommDestroy(ctx->comm);
-  if (ctx->d_stamps) {
-    uint64_t h[32] = {0};
-    if (hipMemcpy(h, ctx->d_stamps, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[4] > 0) {
-      const double k = 0.01 / (double)h[4];  // 100 MHz ticks -> us per launch
-      std::fprintf(stderr, "[vgicp stamps] body launches %llu | workgroup 0, first worker lane: loads+fold+barrier %.2f us, "
-                   "speculative probe || solve, to 2nd barrier %.2f us, verify+accumulate loop %.2f us, "
-                   "butterfly+row store %.2f us | solver wave: solve+publish %.2f us\n", (unsigned long long)h[4], h[0] * k,
-                   h[5] * k, h[1] * k, h[2] * k, h[6] * k);
-    }
-    if (hipMemcpy(h, ctx->d_stamps, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[13] > 0) {
-      for (int o = 8; o <= 16; o += 8) {
-        const double k = 0.01 / (double)h[o + 5];  // 100 MHz ticks -> us per round
-        std::fprintf(stderr, "[vgicp stamps] persistent, workgroup 0 %s, %llu rounds: accumulate+butterfly (to the barrier) "
-                     "%.2f us, publish + level-1 fold %.2f us, level-2 poll %.2f us, solve+broadcast %.2f us\n",
-                     o == 8 ? "solver wave" : "first worker lane", (unsigned long long)h[o + 5], h[o] * k, h[o + 1] * k,
-                     h[o + 2] * k, h[o + 3] * k);
-      }
-      const double kf = 0.01 / (double)h[13];
-      std::fprintf(stderr, "[vgicp stamps] inside solve+broadcast (solver wave of workgroup 0): re-arm + totals through LDS to registers "
-                   "%.3f us, LDL^T %.3f us, exponential + compose + test %.3f us, pose to LDS (+ state, workgroup 0) %.3f us, the rest "
-                   "(barrier, pose read by every wave) %.3f us\n", h[24] * kf, h[25] * kf, h[26] * kf, h[27] * kf,
-                   (h[11] - h[24] - h[25] - h[26] - h[27]) * kf);
-    }
-    uint64_t wg[kExchangeRows];
-    if (h[13] > 0 && hipMemcpy(wg, ctx->d_stamps + 32, sizeof wg, hipMemcpyDeviceToHost) == hipSuccess) {
-      const double k = 0.01 / (double)h[13];
-      double lo = 1e30, hi = 0.0, sum = 0.0;
-      int hi_at = 0;
-      const int g = (int)ctx->persist_grid;
-      for (int b = 0; b < g; ++b) {
-        const double v = wg[b] * k;
-        sum += v;
-        if (v < lo) lo = v;
-        if (v > hi) { hi = v; hi_at = b; }
-      }
-      std::fprintf(stderr, "[vgicp stamps] persistent, time to the first barrier per workgroup (mean over rounds): min %.2f us, "
-                   "mean %.2f us, max %.2f us (workgroup %d)\n", lo, sum / g, hi, hi_at);
-      if (const char* all = std::getenv("VGICP_DEBUG_STAMPS"); all && all[0] == '2') {  // every workgroup's figure
-        for (int b = 0; b < g; ++b) std::fprintf(stderr, "%s%.2f", b % 16 ? " " : "\n[vgicp stamps wg] ", wg[b] * k);
-        std::fprintf(stderr, "\n");
-      }
-    }
-    (void)hipFree(ctx->d_stamps);
-  }
-  (void)hipFree(ctx->table);
-  (void)hipFree(ctx->d_raw);
-  (void)hipHostFree(ctx->h_raw_ctr);
-  (void)hipFree(ctx->d_dense);
-  (void)hipFree(ctx->d_dense_counts);
-  (void)hipFree(ctx->d_counters);
-  (void)hipHostFree(ctx->h_counters);
-  (void)hipHostFree(ctx->h_prep);
-  (void)hipFree(ctx->d_tiles);
-  (void)hipHostFree(ctx->h_ins_counters);
-  for (int k = 0; k < 2; ++k) {
-    if (ctx->h_state_table[k]) (void)hipHostFree(ctx->h_state_table[k]);
-    if (ctx->h_raw_stage[k] && !crew_lost) (void)hipHostFree(ctx->h_raw_stage[k]);
-    if (k == 0 && ctx->h_arena) (void)hipHostFree(ctx->h_arena);
-    if (ctx->ev_state_table[k]) (void)hipEventDestroy(ctx->ev_state_table[k]);
-  }
-  for (auto& e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);
-  if (ctx->h_fetch_hdr) (void)hipHostFree(ctx->h_fetch_hdr);
-  (void)hipFree(ctx->d_fetch_sums);
-  if (ctx->h_fetch) (void)hipHostFree(ctx->h_fetch);
-  (void)hipFree(ctx->d_stage);
-  (void)hipFree(ctx->d_cells);
-  (void)hipFree(ctx->d_scan);
-  (void)hipFree(ctx->d_scan_aos);
-  (void)hipFree(ctx->d_memo);
-  (void)hipFree(ctx->d_state);
-  (void)hipHostFree(ctx->h_state);
-  (void)hipFree(ctx->d_rows_persist);
-  (void)hipFree(ctx->d_parts_persist);
-  (void)hipHostFree(ctx->h_exchange_image);
-  (void)hipFree(ctx->d_batch_exchange);
-  if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
-  (void)hipFree(ctx->d_eval_rows);
-  if (ctx->h_eval) (void)hipHostFree(ctx->h_eval);
-  (void)hipFree(ctx->d_rows[0]);
-  (void)hipFree(ctx->d_rows[1]);
-  (void)hipFree(ctx->d_sums);
-  if (ctx->d_log) (void)hipFree(ctx->d_log - kSlots);
-  if (ctx->h_log) (void)hipHostFree(ctx->h_log - kSlots);
-  if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
-  if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-  for (auto& e : ctx->ev_chunk) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->ev_prof) if (e) (void)hipEventDestroy(e);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+  report_stamps(ctx);
   if (g_stage_error_ctx == ctx->id) g_stage_error_ctx = 0;
-  delete ctx;
+  delete ctx;   // every buffer and event, and the stream last (vgicp_context.h)
   return VGICP_OK;
 }
 
@@ -376,7 +309,7 @@ int vgicp_set_option(vgicp_ctx* ctx, int option, int value) {
     case VGICP_OPTION_STAGE_EVENTS:
       VG_HIP(ctx, hipSetDevice(ctx->device));
       if (value && !ctx->ev_stage[0])
-        for (auto& e : ctx->ev_stage) VG_HIP(ctx, hipEventCreate(&e));
+        for (auto& e : ctx->ev_stage) VG_HIP(ctx, e.create());
       ctx->stage_events = value != 0;
       for (bool& b : ctx->ev_stage_set) b = false;
       return VGICP_OK;
@@ -393,8 +326,7 @@ int vgicp_set_option(vgicp_ctx* ctx, int option, int value) {
         return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the raw-point store is switched only while the map holds no voxel");
       VG_HIP(ctx, hipSetDevice(ctx->device));
       if (value == 0) {
-        if (ctx->d_raw) VG_HIP(ctx, hipFree(ctx->d_raw));
-        ctx->d_raw = nullptr;
+        ctx->d_raw.reset();
         ctx->raw_capacity = 0;
         ctx->raw_used_upper = 0;
         ctx->raw_on = false;

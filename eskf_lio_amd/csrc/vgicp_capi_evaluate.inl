@@ -48,10 +48,10 @@ int vgicp_evaluate_resident(vgicp_ctx* ctx, size_t k, const double* poses, vgicp
   VG_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
   for (size_t h0 = 0; h0 < k; h0 += per_launch) {
     const uint32_t m = (uint32_t)std::min<size_t>(per_launch, k - h0);
-    a.poses = ctx->h_eval_dev + (size_t)VGICP_EVAL_MAX * kSlots + 12 * h0;
+    a.poses = ctx->h_eval.dev() + (size_t)VGICP_EVAL_MAX * kSlots + 12 * h0;
     // stream order: this pair's rows are written after the previous pair's fold has read its own
     VG_HIP(ctx, launch_evaluate(ctx->stream, a, rows, m));
-    VG_HIP(ctx, launch_evaluate_fold(ctx->stream, ctx->d_eval_rows, rows, m, ctx->h_eval_dev + h0 * kSlots));
+    VG_HIP(ctx, launch_evaluate_fold(ctx->stream, ctx->d_eval_rows, rows, m, ctx->h_eval.dev() + h0 * kSlots));
     launches += 2;
   }
   VG_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));

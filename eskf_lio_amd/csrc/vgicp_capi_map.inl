@@ -25,8 +25,7 @@ int vgicp_map_reset(vgicp_ctx* ctx, double voxel_size, size_t capacity_hint) {
     return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "voxel_size must be positive and finite");
   VG_HIP(ctx, hipSetDevice(ctx->device));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->table) VG_HIP(ctx, hipFree(ctx->table));
-  ctx->table = nullptr;
+  ctx->table.reset();
   ctx->slots = ctx->voxels = ctx->tombstones = 0;
   ++ctx->map_version;
   ctx->voxel_size = voxel_size;
@@ -92,7 +91,7 @@ int vgicp_map_erase(vgicp_ctx* ctx, size_t n, const int32_t* keys) {
   VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
   ++ctx->map_version;
   VG_HIP(ctx, launch_erase(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), (uint32_t)n,
-                           static_cast<const int32_t*>(ctx->d_stage), ctx->d_counters));
+                           static_cast<const int32_t*>(ctx->d_stage.get()), ctx->d_counters));
   VG_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 4 * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, ctx->stream));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));

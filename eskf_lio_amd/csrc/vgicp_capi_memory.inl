@@ -1,7 +1,9 @@
 // vgicp_capi_memory.inl — part of vgicp_capi.hip (one translation unit, cut by concern; see that file).
 // Copies between the caller's pageable memory and the device (the page-locked arena, the streaming CPU copies, the
-// symmetric-covariance compaction of the scan upload), and the context's device buffers: staging area, voxel table
-// (growth / rehash policy), scan, log.
+// symmetric-covariance compaction of the scan upload), and WHEN the context's buffers grow: staging area, voxel table
+// (growth / rehash policy), raw-point log, scan, log.  The buffers are owners (vgicp_owned.h): a grow path decides the
+// size and waits for whatever still reads the old block; alloc() frees that block and then allocates, a temporary is a
+// local owner, and a new block is installed by a move.  An error return leaves nothing behind.
 namespace {
 
 int settle(vgicp_ctx* ctx);         // defined with the scan preparation below
@@ -132,10 +134,7 @@ void arena_reset(vgicp_ctx* ctx) {
 }
 char* arena_take(vgicp_ctx* ctx, size_t bytes) {
   if (staging_off() || bytes <= kArenaMin || bytes > kArenaBytes - ctx->arena_used) return nullptr;
-  if (!ctx->h_arena && hipHostMalloc(reinterpret_cast<void**>(&ctx->h_arena), kArenaBytes, 0) != hipSuccess) {
-    ctx->h_arena = nullptr;
-    return nullptr;
-  }
+  if (!ctx->h_arena && ctx->h_arena.alloc(kArenaBytes) != hipSuccess) return nullptr;
   char* p = ctx->h_arena + ctx->arena_used;
   ctx->arena_used += align256(bytes);
   return p;
@@ -183,13 +182,8 @@ void user_copies_finish(vgicp_ctx* ctx) {
 #define VG_RC(call) do { const int rc__ = (call); if (rc__ != VGICP_OK) return rc__; } while (0)
 
 int ensure_stage(vgicp_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->stage_bytes) return VGICP_OK;
-  if (ctx->d_stage) VG_HIP(ctx, hipFree(ctx->d_stage));
-  ctx->d_stage = nullptr;
-  ctx->stage_bytes = 0;
-  const size_t want = bytes + bytes / 2;
-  VG_HIP(ctx, hipMalloc(&ctx->d_stage, want));
-  ctx->stage_bytes = want;
+  if (bytes <= ctx->d_stage.bytes()) return VGICP_OK;
+  VG_HIP(ctx, ctx->d_stage.alloc(bytes + bytes / 2));
   return VGICP_OK;
 }
 
@@ -199,16 +193,14 @@ struct StageLayout {
   size_t total = 0;
   size_t take(size_t bytes) { const size_t at = total; total += align256(bytes); return at; }
 };
-template <class T> T* stage_at(const vgicp_ctx* ctx, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(ctx->d_stage) + offset); }
+template <class T> T* stage_at(const vgicp_ctx* ctx, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(ctx->d_stage.get()) + offset); }
 
 // A page-locked buffer of the context's owner thread is replaced by one of `bytes`, its first `zero_bytes` wiped.  *cap is
 // zeroed with the old buffer; the caller sets it (in its own unit) once everything that goes with the new one is in place.
-template <class T> int grow_pinned(vgicp_ctx* ctx, T** buf, size_t* cap, size_t bytes, size_t zero_bytes) {
-  if (*buf) VG_HIP(ctx, hipHostFree(*buf));
-  *buf = nullptr;
+template <class T> int grow_pinned(vgicp_ctx* ctx, PinnedBuf<T>* buf, size_t* cap, size_t bytes, size_t zero_bytes, bool mapped = false) {
   *cap = 0;
-  VG_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(buf), bytes, 0));
-  if (zero_bytes) std::memset(*buf, 0, zero_bytes);
+  VG_HIP(ctx, mapped ? buf->alloc_mapped(bytes) : buf->alloc(bytes));
+  if (zero_bytes) std::memset(buf->get(), 0, zero_bytes);
   return VGICP_OK;
 }
 
@@ -222,14 +214,13 @@ template <class Call> int forward_to_first(const vgicp_ctx* ctx, Call call, bool
   return rc;
 }
 
-int alloc_table(vgicp_ctx* ctx, uint64_t slots, VoxelRecord** out) {
+// an empty table of `slots` in *out (whatever *out held is freed first)
+int alloc_table(vgicp_ctx* ctx, uint64_t slots, DeviceBuf<VoxelRecord>* out) {
   if (slots > (1ull << 32)) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table would exceed 2^32 slots");
-  VoxelRecord* t = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&t), slots * sizeof(VoxelRecord));
+  const hipError_t e = out->alloc(slots * sizeof(VoxelRecord));
   if (e != hipSuccess)
     return fail(ctx, VGICP_ERR_TABLE_FULL, std::string("hipMalloc(voxel table): ") + hipGetErrorString(e));
-  VG_HIP(ctx, launch_table_clear(ctx->stream, t, slots));
-  *out = t;
+  VG_HIP(ctx, launch_table_clear(ctx->stream, *out, slots));
   return VGICP_OK;
 }
 
@@ -244,17 +235,13 @@ RawLog raw_log(const vgicp_ctx* ctx) {
   return r;
 }
 
-// An empty log of `entries` in place of the current one (the stream is idle as far as the old one goes: hipFree).
+// An empty log of `entries` in place of the current one (the stream is idle as far as the old one goes: the free).
 int raw_replace(vgicp_ctx* ctx, uint64_t entries) {
-  if (ctx->d_raw) VG_HIP(ctx, hipFree(ctx->d_raw));
-  ctx->d_raw = nullptr;
   ctx->raw_capacity = 0;
   ctx->raw_used_upper = 0;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->d_raw), entries * sizeof(RawPoint));
-  if (e != hipSuccess) {
-    ctx->d_raw = nullptr;
+  const hipError_t e = ctx->d_raw.alloc(entries * sizeof(RawPoint));
+  if (e != hipSuccess)
     return fail(ctx, VGICP_ERR_TABLE_FULL, std::string("hipMalloc(raw-point log): ") + hipGetErrorString(e));
-  }
   ctx->raw_capacity = (uint32_t)entries;
   ctx->raw_broken = false;
   VG_HIP(ctx, hipMemsetAsync(ctx->d_ins_counters + 4, 0, 3 * sizeof(uint32_t), ctx->stream));
@@ -283,6 +270,14 @@ int raw_note(vgicp_ctx* ctx, const uint32_t* words) {
   return VGICP_OK;
 }
 
+// Declared BEHIND local owners whose memory enqueued work may touch (so it goes first): an early return waits for the
+// stream before they free.
+struct StreamIdleOnExit {
+  hipStream_t stream;
+  bool armed = true;
+  ~StreamIdleOnExit() { if (armed) (void)hipStreamSynchronize(stream); }
+};
+
 // Room for the points an insertion of n may accept (all of them).  Only when the bound says the log could fill: one
 // synchronisation, the live entries (slot FULL) compacted into a fresh log that is twice as large as needed, geometric.
 int ensure_raw(vgicp_ctx* ctx, uint64_t n) {
@@ -290,44 +285,35 @@ int ensure_raw(vgicp_ctx* ctx, uint64_t n) {
   { const int rc = raw_refuse_if_broken(ctx); if (rc != VGICP_OK) return rc; }
   if (ctx->raw_used_upper + n <= ctx->raw_capacity) return VGICP_OK;
   uint32_t* ctr = ctx->d_ins_counters + 4;
-  RawPoint* tmp = nullptr;
-  VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)ctx->raw_capacity * sizeof(RawPoint)));
+  DeviceBuf<RawPoint> tmp, grown;
+  VG_HIP(ctx, tmp.alloc((size_t)ctx->raw_capacity * sizeof(RawPoint)));
+  StreamIdleOnExit idle{ctx->stream};
   VG_HIP(ctx, hipMemsetAsync(ctr + 2, 0, sizeof(uint32_t), ctx->stream));
   VG_HIP(ctx, launch_raw_compact(ctx->stream, ctx->d_raw, (uint32_t)std::min<uint64_t>(ctx->raw_used_upper, ctx->raw_capacity),
                                  ctr, ctx->table, ctx->slots, nullptr, tmp, ctx->raw_capacity, ctr + 2));
   VG_HIP(ctx, hipMemcpyAsync(ctx->h_raw_ctr, ctr, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->h_raw_ctr[1] != 0) {
-    (void)hipFree(tmp);
-    return raw_overflowed(ctx);
-  }
+  if (ctx->h_raw_ctr[1] != 0) return raw_overflowed(ctx);
   const uint64_t live = ctx->h_raw_ctr[2];
   uint64_t cap = ctx->raw_capacity;
   while (cap < kRawMaxEntries && 2 * (live + n) > cap) cap *= 2;
-  if (live + n > cap) {
-    (void)hipFree(tmp);
-    return fail(ctx, VGICP_ERR_TABLE_FULL, "raw-point log would exceed 2^31 points");
-  }
+  if (live + n > cap) return fail(ctx, VGICP_ERR_TABLE_FULL, "raw-point log would exceed 2^31 points");
   VG_HIP(ctx, hipMemcpyAsync(ctr, ctr + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
   if (cap == ctx->raw_capacity) {
-    VG_HIP(ctx, hipFree(ctx->d_raw));
-    ctx->d_raw = tmp;
+    ctx->d_raw = std::move(tmp);
   } else {
-    RawPoint* grown = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&grown), cap * sizeof(RawPoint));
-    if (e != hipSuccess) {
-      (void)hipFree(tmp);
+    const hipError_t e = grown.alloc(cap * sizeof(RawPoint));
+    if (e != hipSuccess)
       return fail(ctx, VGICP_ERR_TABLE_FULL, std::string("hipMalloc(raw-point log): ") + hipGetErrorString(e));
-    }
     if (live) {
       VG_HIP(ctx, hipMemcpyAsync(grown, tmp, live * sizeof(RawPoint), hipMemcpyDeviceToDevice, ctx->stream));
       VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    VG_HIP(ctx, hipFree(tmp));
-    VG_HIP(ctx, hipFree(ctx->d_raw));
-    ctx->d_raw = grown;
+    tmp.reset();
+    ctx->d_raw = std::move(grown);
     ctx->raw_capacity = (uint32_t)cap;
   }
+  idle.armed = false;
   ctx->raw_used_upper = live;
   return VGICP_OK;
 }
@@ -338,48 +324,35 @@ int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
   const uint64_t used = ctx->voxels + ctx->tombstones + incoming + ctx->insert_pending_upper;
   if (ctx->table && used * 2 <= ctx->slots) return VGICP_OK;
   const uint64_t slots = next_pow2(std::max<uint64_t>(kMinSlots, (ctx->voxels + incoming) * 4));
-  VoxelRecord* fresh = nullptr;
+  // the new table; one scratch word per OLD slot between the claim and the write launch (its own allocation: the staging
+  // area may hold the batch that made the table grow); with the raw-point store, the log the live entries move to
+  DeviceBuf<VoxelRecord> fresh;
+  DeviceBuf<uint32_t> claimed;
+  DeviceBuf<RawPoint> moved;
   int rc = alloc_table(ctx, slots, &fresh);
   if (rc != VGICP_OK) return rc;
+  // a failure on the way keeps nothing of the new table (what was enqueued is waited for before the three are freed)
+  StreamIdleOnExit idle{ctx->stream};
   int rc_raw = VGICP_OK;
   if (ctx->table) {
     if (ctx->voxels > 0) {
-      // one scratch word per OLD slot between the claim and the write launch (its own allocation: the staging area may
-      // hold the batch that made the table grow); with the raw-point store, the log the live entries move to
-      uint32_t* claimed = nullptr;
-      RawPoint* moved = nullptr;
       uint32_t* ctr = ctx->d_ins_counters + 4;
-      // a failure on the way keeps nothing of the new table (what was enqueued is waited for before it is freed)
-      auto give_up = [&](hipError_t e, const char* what) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(claimed);
-        (void)hipFree(moved);
-        (void)hipFree(fresh);
-        return fail_hip(ctx, e, what);
-      };
-#define VG_REHASH(call)                                                   \
-  do {                                                                    \
-    const hipError_t e__ = (call);                                        \
-    if (e__ != hipSuccess) return give_up(e__, #call);                    \
-  } while (0)
-      VG_REHASH(hipMalloc(reinterpret_cast<void**>(&claimed), ctx->slots * sizeof(uint32_t)));
-      if (ctx->raw_on) VG_REHASH(hipMalloc(reinterpret_cast<void**>(&moved), (size_t)ctx->raw_capacity * sizeof(RawPoint)));
-      VG_REHASH(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
-      VG_REHASH(launch_rehash(ctx->stream, ctx->table, ctx->slots, fresh, (uint32_t)(slots - 1), ctx->d_counters, claimed));
+      VG_HIP(ctx, claimed.alloc(ctx->slots * sizeof(uint32_t)));
+      if (ctx->raw_on) VG_HIP(ctx, moved.alloc((size_t)ctx->raw_capacity * sizeof(RawPoint)));
+      VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
+      VG_HIP(ctx, launch_rehash(ctx->stream, ctx->table, ctx->slots, fresh, (uint32_t)(slots - 1), ctx->d_counters, claimed));
       // the raw points follow their voxels to the new slots (claimed maps old -> new); the dead ones stay behind
       if (ctx->raw_on) {
-        VG_REHASH(hipMemsetAsync(ctr + 2, 0, sizeof(uint32_t), ctx->stream));
-        VG_REHASH(launch_raw_compact(ctx->stream, ctx->d_raw, (uint32_t)std::min<uint64_t>(ctx->raw_used_upper, ctx->raw_capacity),
-                                     ctr, ctx->table, ctx->slots, claimed, moved, ctx->raw_capacity, ctr + 2));
-        VG_REHASH(hipMemcpyAsync(ctr, ctr + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-        VG_REHASH(hipMemcpyAsync(ctx->h_raw_ctr, ctr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VG_HIP(ctx, hipMemsetAsync(ctr + 2, 0, sizeof(uint32_t), ctx->stream));
+        VG_HIP(ctx, launch_raw_compact(ctx->stream, ctx->d_raw, (uint32_t)std::min<uint64_t>(ctx->raw_used_upper, ctx->raw_capacity),
+                                       ctr, ctx->table, ctx->slots, claimed, moved, ctx->raw_capacity, ctr + 2));
+        VG_HIP(ctx, hipMemcpyAsync(ctr, ctr + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        VG_HIP(ctx, hipMemcpyAsync(ctx->h_raw_ctr, ctr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
       }
-      VG_REHASH(hipStreamSynchronize(ctx->stream));
-#undef VG_REHASH
-      VG_HIP(ctx, hipFree(claimed));
+      VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      claimed.reset();
       if (ctx->raw_on) {
-        VG_HIP(ctx, hipFree(ctx->d_raw));
-        ctx->d_raw = moved;
+        ctx->d_raw = std::move(moved);
         rc_raw = raw_note(ctx, ctx->h_raw_ctr);
       }
     } else if (ctx->raw_on) {   // no voxel left: every entry is dead, and the new table's slots will be claimed afresh
@@ -387,9 +360,9 @@ int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
       ctx->raw_used_upper = 0;
     }
     VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    VG_HIP(ctx, hipFree(ctx->table));
   }
-  ctx->table = fresh;
+  idle.armed = false;
+  ctx->table = std::move(fresh);
   ctx->slots = slots;
   ctx->tombstones = 0;
   ++ctx->map_version;
@@ -399,17 +372,15 @@ int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
 
 int ensure_scan(vgicp_ctx* ctx, size_t n) {
   if (n <= ctx->scan_capacity && ctx->d_scan) return VGICP_OK;
-  if (ctx->d_scan) VG_HIP(ctx, hipFree(ctx->d_scan));
-  if (ctx->d_scan_aos) VG_HIP(ctx, hipFree(ctx->d_scan_aos));
-  if (ctx->d_memo) VG_HIP(ctx, hipFree(ctx->d_memo));
-  ctx->d_scan = ctx->d_scan_aos = nullptr;
-  ctx->d_memo = nullptr;
+  ctx->d_scan.reset();
+  ctx->d_scan_aos.reset();
+  ctx->d_memo.reset();
   ctx->scan_capacity = 0;
   size_t cap = std::max<size_t>(n + n / 4, 1024);
   cap = (cap + 63) & ~size_t(63);  // planes stay 512-byte aligned
-  VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_scan), cap * kScanPlanes * sizeof(double)));
-  VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_scan_aos), cap * kScanPlanes * sizeof(double)));
-  VG_HIP(ctx, hipMalloc(&ctx->d_memo, cap * 16));
+  VG_HIP(ctx, ctx->d_scan.alloc(cap * kScanPlanes * sizeof(double)));
+  VG_HIP(ctx, ctx->d_scan_aos.alloc(cap * kScanPlanes * sizeof(double)));
+  VG_HIP(ctx, ctx->d_memo.alloc(cap * 16));
   ctx->scan_capacity = cap;
   return VGICP_OK;
 }
@@ -437,23 +408,14 @@ int begin_scan(vgicp_ctx* ctx, size_t n, double prep_voxel, bool with_deskew) {
 
 int ensure_log(vgicp_ctx* ctx, int iterations) {
   if (iterations <= ctx->log_capacity) return VGICP_OK;
-  if (ctx->d_log) VG_HIP(ctx, hipFree(ctx->d_log - kSlots));
-  if (ctx->h_log) VG_HIP(ctx, hipHostFree(ctx->h_log - kSlots));
-  ctx->d_log = ctx->h_log = nullptr;
+  ctx->d_log.reset();
+  ctx->h_log.reset();
   ctx->log_capacity = 0;
-  // one header row in front of the log: the persistent launch leaves its final AlignState there, so a
-  // single device-to-host copy brings state and log back
+  // one header row in front of the iterations' rows (vgicp_context.h: d_log_rows, h_log_rows)
   const int cap = std::max(iterations, 128);
-  double* d = nullptr;
-  double* h = nullptr;
-  VG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&d), (size_t)(cap + 1) * kSlots * sizeof(double)));
-  VG_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&h), (size_t)(cap + 1) * kSlots * sizeof(double), 0));
-  VG_HIP(ctx, hipMemset(d, 0, kSlots * sizeof(double)));
-  void* hd = nullptr;
-  VG_HIP(ctx, hipHostGetDevicePointer(&hd, h, 0));
-  ctx->d_log = d + kSlots;
-  ctx->h_log = h + kSlots;
-  ctx->h_log_dev = static_cast<double*>(hd) + kSlots;
+  VG_HIP(ctx, ctx->d_log.alloc((size_t)(cap + 1) * kSlots * sizeof(double)));
+  VG_HIP(ctx, ctx->h_log.alloc_mapped((size_t)(cap + 1) * kSlots * sizeof(double)));
+  VG_HIP(ctx, hipMemset(ctx->d_log, 0, kSlots * sizeof(double)));
   ctx->log_capacity = cap;
   return VGICP_OK;
 }

@@ -123,7 +123,7 @@ int align_host_summed(vgicp_ctx* const* subs, int n, const double guess[16], con
         VG_HIP(ctx, launch_iterate(ctx->stream, a, grid[(size_t)r], ctx->iter_block));
         VG_HIP(ctx, launch_fold_rows(ctx->stream, a.rows, grid[(size_t)r], a.state_out, ctx->d_sums));
         // the rank's row goes to pinned memory (the header row of the pinned log: unused outside a persistent launch)
-        VG_HIP(ctx, hipMemcpyAsync(ctx->h_log - kSlots, ctx->d_sums, kSlots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        VG_HIP(ctx, hipMemcpyAsync(ctx->h_log, ctx->d_sums, kSlots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
       }
       if (profile && r == 0) VG_HIP(ctx, hipEventRecord(ctx->ev_prof[2 * j + 1], ctx->stream));
       VG_HIP(ctx, hipMemcpyAsync(&ctx->h_state[1], a.state_out, sizeof(AlignState), hipMemcpyDeviceToHost, ctx->stream));
@@ -138,14 +138,14 @@ int align_host_summed(vgicp_ctx* const* subs, int n, const double guess[16], con
     double total[kSlots];
     for (int sl = 0; sl < kSlots; ++sl) {
       double x[kMaxRanks];
-      for (int q = 0; q < kMaxRanks; ++q) x[q] = (q < n && sl <= kCountSlot) ? (subs[q]->h_log - kSlots)[sl] : 0.0;
+      for (int q = 0; q < kMaxRanks; ++q) x[q] = (q < n && sl <= kCountSlot) ? subs[q]->h_log[sl] : 0.0;
       total[sl] = tree_sum_host(x, kMaxRanks);
     }
     for (int r = 0; r < n; ++r) {
       vgicp_ctx* ctx = subs[r];
       VG_HIP(ctx, hipSetDevice(ctx->device));
-      std::memcpy(ctx->h_log - kSlots, total, sizeof total);
-      VG_HIP(ctx, hipMemcpyAsync(ctx->d_sums, ctx->h_log - kSlots, kSlots * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      std::memcpy(ctx->h_log, total, sizeof total);
+      VG_HIP(ctx, hipMemcpyAsync(ctx->d_sums, ctx->h_log, kSlots * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
   }
   VG_HIP(lead, hipSetDevice(lead->device));

@@ -109,7 +109,7 @@ int vgicp_comm_init(vgicp_ctx* ctx, int world_size, int rank, const void* id128)
       !ctx->peers_connected) {
     std::string why;
     char mine[VGICP_PEER_HANDLE_BYTES];
-    char* d_all = nullptr;
+    DeviceBuf<char> d_all;
     std::vector<char> all((size_t)world_size * VGICP_PEER_HANDLE_BYTES);
     bool ok = vgicp_peer_export(ctx, mine) == VGICP_OK;
     if (!ok) why = ctx->err;
@@ -117,7 +117,7 @@ int vgicp_comm_init(vgicp_ctx* ctx, int world_size, int rank, const void* id128)
     if (!ok) std::memset(mine, 0, sizeof mine);
     // (a rank that could not even allocate these few bytes cannot take part in the collectives below and fails
     // the whole call; its peers would wait for it inside RCCL as they would for any rank that died)
-    if (hipMalloc(reinterpret_cast<void**>(&d_all), all.size() + VGICP_PEER_HANDLE_BYTES) != hipSuccess)
+    if (d_all.alloc(all.size() + VGICP_PEER_HANDLE_BYTES) != hipSuccess)
       return fail(ctx, VGICP_ERR_HIP, "hipMalloc(handle exchange) failed");
     {
       char* d_mine = d_all + all.size();
@@ -136,7 +136,7 @@ int vgicp_comm_init(vgicp_ctx* ctx, int world_size, int rank, const void* id128)
       if (ok && vgicp_peer_connect(ctx, world_size, rank, all.data()) != VGICP_OK) { ok = false; why = ctx->err; }
       // agreement + barrier: the sum of the ranks' verdicts; the peer path is used only if all of them connected
       double verdict = ok ? 1.0 : 0.0;
-      double* d_v = reinterpret_cast<double*>(d_all);
+      double* d_v = reinterpret_cast<double*>(d_all.get());
       if (coll && hipMemcpyAsync(d_v, &verdict, sizeof verdict, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
           ctx->rccl.AllReduce(d_v, d_v, 1, kNcclDouble, kNcclSum, ctx->comm, ctx->stream) == 0 &&
           hipMemcpyAsync(&verdict, d_v, sizeof verdict, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
@@ -152,7 +152,7 @@ int vgicp_comm_init(vgicp_ctx* ctx, int world_size, int rank, const void* id128)
         ctx->world_size = world_size;
         ctx->rank = rank;
       }
-      (void)hipFree(d_all);
+      d_all.reset();
     }
     if (!ctx->peers_connected && ctx->dev.verbose)
       std::fprintf(stderr, "[vgicp] rank %d: no device-initiated exchange (%s); using RCCL all-reduce per iteration\n", rank,

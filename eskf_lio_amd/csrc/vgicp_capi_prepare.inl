@@ -5,12 +5,8 @@ extern "C" {
 
 namespace {
 int ensure_cells(vgicp_ctx* ctx, size_t need) {
-  if (need <= ctx->cells_bytes) return VGICP_OK;
-  if (ctx->d_cells) VG_HIP(ctx, hipFree(ctx->d_cells));
-  ctx->d_cells = nullptr;
-  ctx->cells_bytes = 0;
-  VG_HIP(ctx, hipMalloc(&ctx->d_cells, need));
-  ctx->cells_bytes = need;
+  if (need <= ctx->d_cells.bytes()) return VGICP_OK;
+  VG_HIP(ctx, ctx->d_cells.alloc(need));
   return VGICP_OK;
 }
 
@@ -73,7 +69,7 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
   a.soa = soa;
   a.soa_stride = soa_stride;
   a.counters = ctx->d_counters;
-  a.host_kept = ctx->h_fetch_hdr_dev;
+  a.host_kept = ctx->h_fetch_hdr.dev();
   a.tiles = ctx->d_tiles;
   a.epoch = ctx->prep_epoch;
   a.debug = debug;
@@ -556,7 +552,7 @@ int scan_prepare_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const d
     // the copies out of this slot two preparations ago: long complete, normally (no host wait then)
     if (hipEventQuery(ctx->ev_state_table[slot]) != hipSuccess) VG_HIP(ctx, hipEventSynchronize(ctx->ev_state_table[slot]));
   } else {
-    VG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_state_table[slot], hipEventDisableTiming));
+    VG_HIP(ctx, ctx->ev_state_table[slot].create(false));
   }
   // ---- the sweep, by the plan's route ----
   StagedPoints sp;
@@ -584,7 +580,7 @@ int scan_prepare_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const d
       job.n = n, job.seq = next_nonzero(ctx->scan_seq);
       job.bytes = n * 3 * sizeof(double), job.wake_bytes = 1u << 20;
       crew_post(ctx, &job);   // a helper that is awake starts now
-      sp.open_with = ctx->crew;
+      sp.open_with = ctx->crew.get();
       // this thread: the capture times first (a sixth of the bytes): the deskew's bounds need nothing else, and its
       // kernel reads them where they are staged
       if (plan.times_by_owner) stage_copy(raw.times, point_time, n * sizeof(double));
@@ -687,10 +683,8 @@ int stage_sweep_ahead(vgicp_ctx* ctx, size_t n, const void* data, const double* 
   const size_t need = pts_room + n * sizeof(double);
   if (slot->cap < need) {
     if (hipSetDevice(ctx->device) != hipSuccess) { slot->state = 0; return fail_stage(ctx, VGICP_ERR_HIP, "hipSetDevice"); }
-    if (slot->mem) (void)hipHostFree(slot->mem);
-    slot->mem = nullptr;
     slot->cap = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&slot->mem), need * 5 / 4 + 4096, 0) != hipSuccess) {
+    if (slot->mem.alloc(need * 5 / 4 + 4096) != hipSuccess) {
       slot->state = 0;
       return fail_stage(ctx, VGICP_ERR_HIP, "hipHostMalloc(sweep staging)");
     }
@@ -778,9 +772,9 @@ int vgicp_scan_prepare_staged_async(vgicp_ctx* ctx, uint64_t ticket, size_t num_
   if (!slot) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "no sweep staged under this ticket (staged by vgicp_sweep_stage, used once)");
   if (without_times) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the sweep was staged without capture times");
   hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess && !slot->done) e = hipEventCreateWithFlags(&slot->done, hipEventDisableTiming);
+  if (e == hipSuccess && !slot->done) e = slot->done.create(false);
   const int rc = e != hipSuccess ? fail_hip(ctx, e, "vgicp_scan_prepare_staged_async")
-                                 : scan_prepare_enqueue(ctx, slot->n, reinterpret_cast<const double*>(slot->mem),
+                                 : scan_prepare_enqueue(ctx, slot->n, reinterpret_cast<const double*>(slot->mem.get()),
                                                         reinterpret_cast<const double*>(slot->mem + slot->times_at), num_states,
                                                         states, extrinsic, voxel_size, knn, slot);
   std::lock_guard<std::mutex> lk(ctx->ahead_mutex);
@@ -846,10 +840,7 @@ int ensure_fetch_stage(vgicp_ctx* ctx, size_t points) {
   const size_t cap = std::max<size_t>(points + points / 4, 4096);
   const size_t data = align256(cap * 24u) + cap * 72u + 256u;
   const size_t flag_bytes = (data / kFetchPiece + 2) * 64;
-  VG_RC(grow_pinned(ctx, &ctx->h_fetch, &ctx->fetch_cap_points, flag_bytes + data, flag_bytes));
-  void* dev = nullptr;
-  VG_HIP(ctx, hipHostGetDevicePointer(&dev, ctx->h_fetch, 0));
-  ctx->h_fetch_dev = static_cast<char*>(dev);
+  VG_RC(grow_pinned(ctx, &ctx->h_fetch, &ctx->fetch_cap_points, flag_bytes + data, flag_bytes, true));
   ctx->fetch_cap_points = cap;
   ctx->fetch_flag_bytes = flag_bytes;
   return VGICP_OK;
@@ -871,13 +862,13 @@ int vgicp_scan_fetch_begin(vgicp_ctx* ctx, size_t* kept) {
   next_nonzero(ctx->fetch_seq);
   VG_HIP(ctx, launch_fetch(ctx->stream, ctx->d_scan_aos, ctx->d_scan_aos + 3 * ctx->scan_capacity, ctx->d_counters, ctx->prep_epoch,
                            (uint32_t)std::min<size_t>(ctx->fetch_cap_points, ctx->n_upper),
-                           ctx->h_fetch_dev + ctx->fetch_flag_bytes, reinterpret_cast<uint32_t*>(ctx->h_fetch_dev),
-                           ctx->h_fetch_hdr_dev + 8, ctx->fetch_seq, kFetchPiece, ctx->d_fetch_sums, ctx->h_fetch_hdr_dev + 16));
+                           ctx->h_fetch.dev() + ctx->fetch_flag_bytes, reinterpret_cast<uint32_t*>(ctx->h_fetch.dev()),
+                           ctx->h_fetch_hdr.dev() + 8, ctx->fetch_seq, kFetchPiece, ctx->d_fetch_sums, ctx->h_fetch_hdr.dev() + 16));
   ctx->fetch_open = true;
   // how many points the down-sampling kept (or the fetch kernel's first word: the preparation is through, refused or not)
   const double t0 = now_seconds();
   for (uint32_t spins = 0;; ++spins) {
-    const unsigned long long k = __atomic_load_n(ctx->h_fetch_hdr, __ATOMIC_ACQUIRE);
+    const unsigned long long k = __atomic_load_n(ctx->h_fetch_hdr.get(), __ATOMIC_ACQUIRE);
     if ((uint32_t)(k >> 32) == ctx->prep_epoch) {
       if ((uint32_t)k == 0) {   // a scan of n > 0 points keeps none only when it was refused (or gave up): say why now
         ctx->fetch_open = false;
@@ -914,7 +905,7 @@ int vgicp_scan_fetch_end(vgicp_ctx* ctx, size_t capacity, double* points, double
   } else if (kept > 0) {
     const size_t pb = kept * 24u, pb_pad = align256(pb), total = pb_pad + kept * 72u;
     const uint32_t pieces = (uint32_t)((total + kFetchPiece - 1) / kFetchPiece);
-    const uint32_t* flags = reinterpret_cast<const uint32_t*>(ctx->h_fetch);
+    const uint32_t* flags = reinterpret_cast<const uint32_t*>(ctx->h_fetch.get());
     const char* stage = ctx->h_fetch + ctx->fetch_flag_bytes;
     const double t0 = now_seconds();
     for (uint32_t piece = 0; piece < pieces && rc_copy == VGICP_OK; ++piece) {

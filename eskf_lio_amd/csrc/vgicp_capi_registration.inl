@@ -54,7 +54,7 @@ int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* co
                  (ta1 - ta0) * 1e3, (ta2 - ta1) * 1e3, (ta3 - ta2) * 1e3);
   ++ctx->persistent_launches;
   AlignState* hf = &ctx->h_state[0];
-  std::memcpy(hf, reinterpret_cast<const AlignState*>(ctx->h_log - kSlots), sizeof(AlignState));
+  std::memcpy(hf, reinterpret_cast<const AlignState*>(ctx->h_log.get()), sizeof(AlignState));
   VG_RC(settle_after_launch(ctx, *hf, a.seq, /*multi=*/false));
   if (!launch_committed(*hf, a.seq, hf->abort_seq)) {
     // A wait inside the launch ran out.  The copy threads have delivered everything by now: pack the scan behind the
@@ -71,7 +71,7 @@ int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   // the registration's device time, the upload excluded: from the moment the last workgroup found its units to the
   // end of the launch, on the device's constant clock
   const double device_seconds = ctx->wall_clock_hz > 0.0 ? (double)hf->unit_to_end_ticks / ctx->wall_clock_hz : 0.0;
-  return report_align(ctx, *hf, ctx->h_log, 1, 1, device_seconds, t0, out_pose, stats);
+  return report_align(ctx, *hf, ctx->h_log_rows(), 1, 1, device_seconds, t0, out_pose, stats);
 }
 }  // namespace
 
@@ -141,9 +141,9 @@ int vgicp_accumulate(vgicp_ctx* ctx, size_t n, const double* points, const doubl
   if (rc != VGICP_OK) return rc;
   rc = enqueue_launch(ctx, base, 1, grid, true, false);
   if (rc != VGICP_OK) return rc;
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_log, ctx->d_log, kSlots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_log_rows(), ctx->d_log_rows(), kSlots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const double* row = ctx->h_log;
+  const double* row = ctx->h_log_rows();
   for (int r = 0; r < 6; ++r)
     for (int c = 0; c <= r; ++c) {
       JTJ[r + 6 * c] = row[tri6(r, c)];
@@ -170,7 +170,7 @@ int vgicp_solve_step(vgicp_ctx* ctx, const double JTJ[36], const double JTr[6], 
   for (int r = 0; r < 6; ++r)
     for (int c = 0; c <= r; ++c) packed[tri6(r, c)] = JTJ[r + 6 * c];  // the lower triangle, as Eigen's LDLT reads it
   for (int k = 0; k < 6; ++k) packed[21 + k] = JTr[k];
-  double* d_in = static_cast<double*>(ctx->d_stage);
+  double* d_in = static_cast<double*>(ctx->d_stage.get());
   double* d_out = d_in + 32;
   double out[20];
   VG_HIP(ctx, hipMemcpyAsync(d_in, packed, sizeof packed, hipMemcpyHostToDevice, ctx->stream));
@@ -253,7 +253,7 @@ int vgicp_voxel_index(vgicp_ctx* ctx, size_t n, const double* points, int32_t* k
   const size_t pb = n * 3 * sizeof(double), kb = n * 3 * sizeof(int32_t);
   int rc = ensure_stage(ctx, pb + kb);
   if (rc != VGICP_OK) return rc;
-  char* b = static_cast<char*>(ctx->d_stage);
+  char* b = static_cast<char*>(ctx->d_stage.get());
   arena_reset(ctx);
   VG_RC(user_h2d(ctx, b, points, pb));
   VG_HIP(ctx, launch_voxel_index(ctx->stream, reinterpret_cast<const double*>(b), (uint32_t)n,

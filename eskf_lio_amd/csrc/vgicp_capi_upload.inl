@@ -28,10 +28,11 @@ int crew_gave_up(vgicp_ctx* ctx) {
   ctx->scan_ready = false;
   ctx->upload_threads = 1;
   (void)hipStreamSynchronize(ctx->stream);
-  // that thread may still write the staging memory it was copying into: later uploads get memory of their own
-  ctx->h_upload = nullptr;
+  // that thread may still write the staging memory it was copying into: it is given up (leaked), later uploads get
+  // memory of their own
+  (void)ctx->h_upload.release();
   ctx->upload_cap = ctx->upload_flag_bytes = 0;
-  for (int k = 0; k < 2; ++k) { ctx->h_raw_stage[k] = nullptr; ctx->raw_stage_cap[k] = 0; }
+  for (int k = 0; k < 2; ++k) { (void)ctx->h_raw_stage[k].release(); ctx->raw_stage_cap[k] = 0; }
   return fail(ctx, VGICP_ERR_TIMEOUT,
               "a copy thread of the scan upload did not deliver its unit within 10 s (dead or never scheduled): the scan is "
               "not resident, this context stages alone from now on; that thread may still read the caller's buffer");
@@ -78,8 +79,8 @@ struct CopyJob {
 void crew_post(vgicp_ctx* ctx, CopyJob* job) {
   const uint32_t unit = pack_arena_unit();
   job->helpers = ctx->upload_threads > 1 && job->bytes >= job->wake_bytes;
-  if (!ctx->crew) ctx->crew = new CopyCrew;
-  CopyCrew* crew = ctx->crew;
+  if (!ctx->crew) ctx->crew.reset(new CopyCrew);
+  CopyCrew* crew = ctx->crew.get();
   if (job->helpers && crew->th.empty()) crew->start(ctx->upload_threads - 1);
   crew->pts = static_cast<const char*>(job->src_a);
   crew->cov = static_cast<const char*>(job->src_b);
@@ -150,13 +151,13 @@ int scan_upload_stage(vgicp_ctx* ctx, size_t n, const double* points, const doub
   }
   const size_t pb = align256(n * 3 * sizeof(double) + 16), cb = align256(n * 9 * sizeof(double) + 16);
   VG_RC(ensure_upload_stage(ctx, pb + cb));
-  if (!ctx->ev_upload) VG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
+  if (!ctx->ev_upload) VG_HIP(ctx, ctx->ev_upload.create(false));
   // the kernel that read the staging memory last has long finished (every align ends in a synchronisation); make sure
   if (ctx->upload_in_flight && hipEventQuery(ctx->ev_upload) != hipSuccess) VG_HIP(ctx, hipEventSynchronize(ctx->ev_upload));
   ctx->upload_in_flight = false;
   up->staged = true;
   CopyJob& job = up->copy;
-  job.flags = reinterpret_cast<uint32_t*>(ctx->h_upload);
+  job.flags = reinterpret_cast<uint32_t*>(ctx->h_upload.get());
   job.src_a = points, job.dst_a = ctx->h_upload + ctx->upload_flag_bytes, job.size_a = 3 * sizeof(double);
   job.src_b = covs, job.dst_b = job.dst_a + pb, job.size_b = 9 * sizeof(double), job.copy_b_form = stage_cov_unit;
   job.n = n, job.seq = ctx->scan_seq;
@@ -167,7 +168,7 @@ int scan_upload_stage(vgicp_ctx* ctx, size_t n, const double* points, const doub
 // pack_arena_kernel over the staging memory of the current scan (wait: behind the copy threads, with the pack's patience)
 hipError_t launch_pack_staged(vgicp_ctx* ctx, bool wait) {
   const uint32_t spin_limit = ctx->dev.pack_spin_limit ? ctx->dev.pack_spin_limit : kPackSpinLimit;
-  CopyCrew* crew = ctx->crew;
+  CopyCrew* crew = ctx->crew.get();
   return launch_pack_arena(ctx->stream, crew->apts, crew->acov, ctx->n, crew->flags, wait, ctx->scan_seq, wait ? spin_limit : 0,
                            ctx->d_scan_aos, ctx->d_scan_aos + 3 * ctx->scan_capacity, ctx->d_scan, ctx->stride,
                            ctx->d_ins_counters + 2);

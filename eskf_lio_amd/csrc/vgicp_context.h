@@ -12,6 +12,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <cmath>
@@ -27,6 +28,7 @@
 #include "../../include/vgicp_hip_evaluate.h"
 #include "../../include/vgicp_hip_robust.h"
 #include "vgicp_device.h"
+#include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
 #include "vgicp_prepare_plan.h"
 
@@ -96,6 +98,33 @@ constexpr int kMaxChunksInFlight = 2;
 static_assert(kPlanTeamsMax == (uint32_t)kTeamsMax, "vgicp_align_plan.h plans with the team kernel's width");
 static_assert(kPlanDeskewMaxStates == kDeskewMaxStates, "vgicp_prepare_plan.h plans with the parallel deskew bounds' limit");
 constexpr int kPersistentCooldownAligns = 8;  // aligns on the per-launch loop after the single launch gave up
+
+// ---- ownership (vgicp_owned.h): the HIP calls behind the owners.  The ONLY place of the host code that allocates or
+// frees device memory, page-locked memory, events and the stream ----
+struct HipBackend {
+  using error = hipError_t;
+  static constexpr error ok = hipSuccess;
+  using event = hipEvent_t;
+  using stream = hipStream_t;
+  // fine_grained: stores of another GPU's kernel become visible to this GPU's running kernel (the mailbox)
+  static error device_alloc(void** p, size_t bytes, bool fine_grained) {
+    return fine_grained ? hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained) : hipMalloc(p, bytes);
+  }
+  static void device_free(void* p) { (void)hipFree(p); }
+  static error pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, 0); }
+  static void pinned_free(void* p) { (void)hipHostFree(p); }
+  static error pinned_alias(void** dev, void* host) { return hipHostGetDevicePointer(dev, host, 0); }
+  static error event_create(event* e, bool timing) {
+    return timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming);
+  }
+  static void event_destroy(event e) { (void)hipEventDestroy(e); }
+  static error stream_create(stream* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
+  static void stream_destroy(stream s) { (void)hipStreamDestroy(s); }
+};
+template <class T> using DeviceBuf = owned::DeviceBuf<T, HipBackend>;
+template <class T> using PinnedBuf = owned::PinnedBuf<T, HipBackend>;
+using EventHandle = owned::EventHandle<HipBackend>;
+using StreamHandle = owned::StreamHandle<HipBackend>;
 
 }  // namespace vgicp
 using namespace vgicp;
@@ -263,7 +292,9 @@ struct vgicp_ctx {
   int device = -1;
   vgicp_multi* multi = nullptr;   // this handle IS a multi-device context: every entry point forwards to vgicp_multi.hip
   vgicp_multi* owner = nullptr;   // this context is one of a multi-device context's sub-contexts (rank = peer_rank)
-  hipStream_t stream = nullptr;
+  // Members are destroyed in reverse order: the stream is declared before every buffer and event, so it outlives
+  // everything that may have been enqueued on it.  A new buffer is one member below; nothing else releases it.
+  StreamHandle stream;
   mutable std::string err;
   std::string peer_status;   // "" while the device-initiated exchange is wired (or nothing to exchange); else why it is not (vgicp_peer_status)
   int cu_count = 0;
@@ -272,57 +303,53 @@ struct vgicp_ctx {
 
   // voxel table
   double voxel_size = 0.0;
-  VoxelRecord* table = nullptr;
+  DeviceBuf<VoxelRecord> table;
   uint64_t slots = 0;
   uint64_t voxels = 0;      // FULL records
   uint64_t tombstones = 0;
-  uint32_t* d_counters = nullptr;  // 8 words + 64 of developer histograms (VGICP_DEBUG_PREP=2)
-  uint32_t* h_counters = nullptr;  // pinned
+  DeviceBuf<uint32_t> d_counters;  // 8 words + 64 of developer histograms (VGICP_DEBUG_PREP=2)
+  PinnedBuf<uint32_t> h_counters;  // pinned
 
   // dense copy of the FULL records for tables far beyond the caches' reach (PersistArgs::dense): rebuilt lazily before
   // an align when the map has changed since (map_version counts every mutation)
-  VoxelRecord* d_dense = nullptr;
+  DeviceBuf<VoxelRecord> d_dense;
   uint64_t dense_capacity = 0;      // records
-  uint32_t* d_dense_counts = nullptr;
+  DeviceBuf<uint32_t> d_dense_counts;
   uint32_t dense_counts_capacity = 0;
   uint64_t map_version = 1, dense_version = 0;
   uint64_t dense_slots_threshold = 1ull << 24;   // tables of this many slots (2 GiB) and more; VGICP_DENSE_SLOTS at creation, 0 = never
   // batch staging (upsert / erase / hooks)
-  void* d_stage = nullptr;
-  size_t stage_bytes = 0;
-  void* d_cells = nullptr;  // cell table of the scan preparation (vgicp_preprocess)
-  size_t cells_bytes = 0;
+  DeviceBuf<void> d_stage;
+  DeviceBuf<void> d_cells;  // cell table of the scan preparation (vgicp_preprocess)
 
   // resident scan
-  double* d_scan_aos = nullptr;  // points (3n) then covs (9n)
-  double* d_scan = nullptr;      // SoA planes
-  void* d_memo = nullptr;        // per point {key, slot}: the launch-per-round loop's memory between launches (IterArgs::memo)
+  DeviceBuf<double> d_scan_aos;  // points (3n) then covs (9n)
+  DeviceBuf<double> d_scan;      // SoA planes
+  DeviceBuf<void> d_memo;        // per point {key, slot}: the launch-per-round loop's memory between launches (IterArgs::memo)
   size_t scan_capacity = 0;      // points
   uint32_t n = 0;
   uint64_t stride = 0;
   bool scan_ready = false;
 
   // align state
-  AlignState* d_state = nullptr;  // two, ping-pong: launch j reads [j&1], writes [(j+1)&1]
-  AlignState* h_state = nullptr;  // pinned, kMaxChunksInFlight + 1 slots
-  double* d_rows[2] = {nullptr, nullptr};  // partial rows, ping-pong like the state
-  double* d_sums = nullptr;       // one row: the all-reduce message (multi-GPU)
+  DeviceBuf<AlignState> d_state;  // two, ping-pong: launch j reads [j&1], writes [(j+1)&1]
+  PinnedBuf<AlignState> h_state;  // pinned, kMaxChunksInFlight + 1 slots
+  DeviceBuf<double> d_rows[2];    // partial rows, ping-pong like the state
+  DeviceBuf<double> d_sums;       // one row: the all-reduce message (multi-GPU)
   // persistent single-launch align (single GPU)
   uint32_t persist_round0 = 0;       // rounds the persistent launches of this context have executed, mod 3
   uint32_t persist_seq = 0;
   uint32_t persist_lds_budget = 0;   // dynamic LDS a persistent workgroup may plan with (0 = the whole CU); sub-contexts that share a device take less
   uint32_t persist_grid = 0;         // workgroups of every persistent launch: min(CUs, kExchangeRows), all resident
-  double* d_rows_persist = nullptr;  // [3][kExchangeRows][kSlots] (vgicp_device.h, PersistArgs)
-  double* d_parts_persist = nullptr; // [3][kFolders][kSlots]
-  void* h_exchange_image = nullptr;  // pinned: what the two buffers hold between launches
+  DeviceBuf<double> d_rows_persist;  // [3][kExchangeRows][kSlots] (vgicp_device.h, PersistArgs)
+  DeviceBuf<double> d_parts_persist; // [3][kFolders][kSlots]
+  PinnedBuf<void> h_exchange_image;  // pinned: what the two buffers hold between launches
   // the batched align (vgicp_hip_batch.h): storage of its own, made with the context
-  double* d_batch_exchange = nullptr;  // team rows, then team parts (team_rows_words() + team_parts_words()); all unset before a launch
-  double* h_batch = nullptr;           // pinned: VGICP_BATCH_MAX blocks of kBatchSlotRows rows (state, then log), then the abort word's row
-  double* h_batch_dev = nullptr;       // the same memory as the device addresses it
+  DeviceBuf<double> d_batch_exchange;  // team rows, then team parts (team_rows_words() + team_parts_words()); all unset before a launch
+  PinnedBuf<double> h_batch;           // pinned: VGICP_BATCH_MAX blocks of kBatchSlotRows rows (state, then log), then the abort word's row; .dev(): as the device addresses it
   // scoring poses (vgicp_hip_evaluate.h): storage of its own, made with the context
-  double* d_eval_rows = nullptr;       // kEvalRowBudget rows: [poses of a launch][rows per pose][kSlots]
-  double* h_eval = nullptr;            // pinned: VGICP_EVAL_MAX result rows of kSlots doubles, then VGICP_EVAL_MAX poses of 12
-  double* h_eval_dev = nullptr;        // the same memory as the device addresses it
+  DeviceBuf<double> d_eval_rows;       // kEvalRowBudget rows: [poses of a launch][rows per pose][kSlots]
+  PinnedBuf<double> h_eval;            // pinned: VGICP_EVAL_MAX result rows of kSlots doubles, then VGICP_EVAL_MAX poses of 12; .dev() likewise
   bool persistent_enabled = true;    // cleared by VGICP_PERSISTENT=0 or when a workgroup does not fit a CU
   double prefetch_margin = 0.015;    // see PersistArgs::prefetch_margin; VGICP_PREFETCH_MARGIN overrides (0 = off).  Round 6: 0.03 -> 0.015
                                      // once the workgroups that are no folders stopped polling early (C2: 0 7.18, 0.01 6.41, 0.015 6.34, 0.02 6.35, 0.03 6.52, 0.04 6.66 us per round)
@@ -341,20 +368,20 @@ struct vgicp_ctx {
     long debug_upload_delay_us = 0;
     bool no_fused = false;            // A/B: vgicp_align keeps the pack launch in front of the persistent one
   } dev;
-  CopyCrew* crew = nullptr;          // the upload's copy threads, created with the first upload that wants a helper
+  std::unique_ptr<CopyCrew> crew;    // the upload's copy threads, created with the first upload that wants a helper
   int upload_threads = 3;            // threads that copy a scan into the staging memory, the caller's included (VGICP_UPLOAD_THREADS).
                                      // Round 6: 2 -> 3 — with symmetric covariances crossing the link as six doubles the HOST copy out of
                                      // never-seen pages became the limit at two threads (C2 from fresh clouds: 2 threads 0.366 ms per align
                                      // with or without the compaction, 3 threads 0.321, 4 threads 0.316 - 0.321)
-  char* h_upload = nullptr;          // page-locked staging memory of the scan upload: [unit flags][points][covariances]
+  PinnedBuf<char> h_upload;          // page-locked staging memory of the scan upload: [unit flags][points][covariances]
   size_t upload_cap = 0;             // bytes behind the flags
   size_t upload_flag_bytes = 0;      // one 64-byte line per unit the capacity can hold; never holds anything but flags
-  hipEvent_t ev_upload = nullptr;    // behind the kernel that read h_upload last (the next upload overwrites it)
+  EventHandle ev_upload;             // behind the kernel that read h_upload last (the next upload overwrites it)
   bool upload_in_flight = false;
   uint64_t upload_slow = 0;          // uploads whose copy threads took so long that the packing was repeated behind them
   // scan preparation without host round trips
-  void* d_tiles = nullptr;           // tile slots of the two device-wide scans
-  uint32_t* h_prep = nullptr;        // pinned: the counter block as a preparation left it (kCounterWords)
+  DeviceBuf<void> d_tiles;           // tile slots of the two device-wide scans
+  PinnedBuf<uint32_t> h_prep;        // pinned: the counter block as a preparation left it (kCounterWords)
   uint32_t prep_epoch = 0;
   bool scan_pending = false;         // a prepared scan is resident but the host has not read its size / verdict yet
   uint32_t n_upper = 0;              // raw points of the pending scan (>= its kept points)
@@ -379,7 +406,7 @@ struct vgicp_ctx {
   // the scan of a vgicp_align up to 4 MB): one page-locked arena.  A copy of more than 512 KB goes through it (h2d: CPU
   // copy in, then DMA; d2h: DMA, then CPU copy out after the call's synchronisation) -- never through the runtime's
   // pin-on-the-fly path, whose registrations stall the whole process when the caller frees the buffer
-  char* h_arena = nullptr;
+  PinnedBuf<char> h_arena;
   size_t arena_used = 0;
   size_t upload_stage_limit = 512u << 20;   // scans up to this many bytes are staged by the copy crew; larger ones (and
                                             // all of them with the limit 0) are handed to the runtime in place
@@ -388,14 +415,12 @@ struct vgicp_ctx {
   struct PendingOut { void* dst; const char* src; size_t bytes; };
   std::vector<PendingOut> pending_out;
   // vgicp_scan_fetch_*: the prepared scan written into page-locked memory by a kernel, piece by piece
-  unsigned long long* h_fetch_hdr = nullptr;      // pinned: word 0 epoch << 32 | kept (run_scan_kernel), word 8 seq << 32 | refused (fetch_kernel), words 16 .. 79 the checksums
-  unsigned long long* h_fetch_hdr_dev = nullptr;  // the same as the device addresses it
-  char* h_fetch = nullptr;           // pinned: [one 64-byte flag line per piece][points, padded to 256 bytes][covariances]
-  char* h_fetch_dev = nullptr;
+  PinnedBuf<unsigned long long> h_fetch_hdr;      // pinned: word 0 epoch << 32 | kept (run_scan_kernel), word 8 seq << 32 | refused (fetch_kernel), words 16 .. 79 the checksums
+  PinnedBuf<char> h_fetch;           // pinned: [one 64-byte flag line per piece][points, padded to 256 bytes][covariances]
   size_t fetch_cap_points = 0;       // points the staging area can hold
   size_t fetch_flag_bytes = 0;
   uint32_t fetch_seq = 0;
-  unsigned long long* d_fetch_sums = nullptr;   // device, 65 words, zero between launches (fetch_kernel's checksums + ticket)
+  DeviceBuf<unsigned long long> d_fetch_sums;   // device, 65 words, zero between launches (fetch_kernel's checksums + ticket)
   bool fetch_sums_valid = false;     // the page-locked copy (h_fetch_hdr + 16 .. + 80) holds the sums of the last completed fetch
   bool fetch_open = false;           // a fetch kernel is enqueued behind the pending preparation
   uint32_t fetch_kept = 0;
@@ -403,7 +428,7 @@ struct vgicp_ctx {
   // page-locked memory when it arrives; vgicp_scan_prepare_staged_async consumes it by ticket).  Guarded by
   // ahead_mutex: the one part of a context that another thread may enter while the owner thread is inside a call.
   struct AheadSlot {
-    char* mem = nullptr;
+    PinnedBuf<char> mem;
     size_t cap = 0, n = 0;
     uint64_t ticket = 0;
     bool has_times = false;
@@ -411,20 +436,20 @@ struct vgicp_ctx {
     size_t times_at = 0;           // byte offset of the capture times (n doubles) inside mem
     int state = 0;                 // 0 free, 1 staged, 2 handed to the device (`done` recorded behind its readers), 3 being filled,
                                    // 4 being handed to the device (vgicp_scan_prepare_staged_async is enqueuing its readers)
-    hipEvent_t done = nullptr;
+    EventHandle done;
   };
   AheadSlot ahead[3];
   std::mutex ahead_mutex;
   uint64_t ahead_tickets = 0;
-  char* h_raw_stage[2] = {nullptr, nullptr};
+  PinnedBuf<char> h_raw_stage[2];
   size_t raw_stage_cap[2] = {0, 0};
-  double* h_state_table[2] = {nullptr, nullptr};
+  PinnedBuf<double> h_state_table[2];
   size_t state_table_cap[2] = {0, 0};
-  hipEvent_t ev_state_table[2] = {nullptr, nullptr};
+  EventHandle ev_state_table[2];
   uint32_t state_table_next = 0;
   // deferred map insertion (vgicp_map_insert_resident_async): running totals on the device, read at the next sync
-  uint32_t* d_ins_counters = nullptr;
-  uint32_t* h_ins_counters = nullptr;  // pinned
+  uint32_t* d_ins_counters = nullptr;  // not owned: d_counters + kCounterWords
+  PinnedBuf<uint32_t> h_ins_counters;  // pinned
   uint32_t ins_seen[2] = {0, 0};
   bool insert_pending = false;
   bool ins_copy_enqueued = false;    // some device-to-host copy behind the pending insertion carries its totals ...
@@ -435,33 +460,38 @@ struct vgicp_ctx {
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
   // insertion, and the log grows (one synchronisation) only when it could fill
   bool raw_on = false;
-  RawPoint* d_raw = nullptr;
+  DeviceBuf<RawPoint> d_raw;
   uint32_t raw_capacity = 0;         // entries
   uint64_t raw_used_upper = 0;       // entries appended so far, at most
   size_t raw_hint = 0;               // the last vgicp_map_reset's capacity_hint
   bool raw_broken = false;           // an append did not fit: the store refuses every call until it is made anew
-  uint32_t* h_raw_ctr = nullptr;     // pinned, 4 words: the log's device words after a synchronous call
+  PinnedBuf<uint32_t> h_raw_ctr;     // pinned, 4 words: the log's device words after a synchronous call
   // frame statistics
   uint64_t stat_launches0 = 0, stat_copies0 = 0, stat_syncs0 = 0;
   bool stage_events = false;
-  hipEvent_t ev_stage[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [6]: behind the prologue
+  EventHandle ev_stage[7];  // [6]: behind the prologue
   bool ev_stage_set[7] = {false, false, false, false, false, false, false};
   int iter_block = 512;           // threads per workgroup of the iteration kernel (measured best at C2)
-  double* d_log = nullptr;
-  double* h_log = nullptr;  // pinned
-  double* h_log_dev = nullptr;  // the same memory as the device addresses it (the persistent launch writes state + log there)
+  // the log: each block begins with ONE HEADER ROW (the persistent launch leaves its final AlignState there, so a single
+  // device-to-host copy brings state and log back); the iterations' rows follow it
+  DeviceBuf<double> d_log;
+  PinnedBuf<double> h_log;  // .dev(): the same memory as the device addresses it (the persistent launch writes state + log there)
+  double* d_log_rows() const { return d_log + kSlots; }
+  double* h_log_rows() const { return h_log + kSlots; }
+  double* h_log_rows_dev() const { return h_log.dev() + kSlots; }
   int log_capacity = 0;     // iterations
-  uint64_t* d_stamps = nullptr;  // only with VGICP_DEBUG_STAMPS=1
-  unsigned long long* d_unit_clock = nullptr;  // FusedUpload::unit_clock
+  DeviceBuf<uint64_t> d_stamps;  // only with VGICP_DEBUG_STAMPS=1
+  DeviceBuf<unsigned long long> d_unit_clock;  // FusedUpload::unit_clock
   double wall_clock_hz = 0.0;    // the device's constant clock (s_memrealtime)
-  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-  hipEvent_t ev_chunk[kMaxChunksInFlight] = {nullptr, nullptr};
-  std::vector<hipEvent_t> ev_prof;
+  EventHandle ev_begin, ev_end;
+  EventHandle ev_chunk[kMaxChunksInFlight];
+  std::vector<EventHandle> ev_prof;
 
   // device-initiated exchange between GPUs: peer-mapped mailboxes (vgicp_peer_*)
-  double* d_mail = nullptr;            // this rank's mailbox, fine-grained device memory, [3][kMaxRanks][kSlots]
-  double* peer_mail[kMaxRanks] = {nullptr};  // every rank's mailbox as mapped here ([peer_rank] = d_mail)
-  double** d_mail_table = nullptr;     // device copy of peer_mail
+  DeviceBuf<double> d_mail;            // this rank's mailbox, fine-grained device memory, [3][kMaxRanks][kSlots]
+  double* peer_mail[kMaxRanks] = {nullptr};  // every rank's mailbox as mapped here ([peer_rank] = d_mail).  Not owned: IPC
+                                       // mappings that close_peers closes, or plain pointers of sibling contexts
+  DeviceBuf<double*> d_mail_table;     // device copy of peer_mail
   int peer_world = 1, peer_rank = 0;
   bool peers_connected = false;
   bool peer_mail_is_ipc = true;        // false: plain pointers of the same process (sub-contexts), nothing to close

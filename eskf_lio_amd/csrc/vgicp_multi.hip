@@ -113,9 +113,9 @@ struct vgicp_multi {
   bool prep_pending = false;      // vgicp_scan_prepare_async on device 0: size not read yet
   uint64_t scan_generation = 0;   // replacements of the resident scan as the CALLER sees it (dealing it out is not one)
   // whole-scan AoS copies for the map insertion on the devices that hold a shard only (points 3 cap, then covs 9 cap)
-  std::vector<double*> d_full;
+  std::vector<DeviceBuf<double>> d_full;
   std::vector<size_t> full_cap;
-  std::vector<hipEvent_t> ev_gather;
+  std::vector<EventHandle> ev_gather;
   uint64_t stat_launches0 = 0, stat_copies0 = 0, stat_syncs0 = 0;   // caller's thread
   std::vector<uint64_t> w_launches0, w_copies0, w_syncs0;           // worker threads
 };
@@ -159,14 +159,10 @@ int ensure_full(vgicp_ctx* parent, int r, size_t n) {
   vgicp_multi* g = parent->multi;
   if (n <= g->full_cap[(size_t)r] && g->d_full[(size_t)r]) return VGICP_OK;
   VG_HIP(parent, hipSetDevice(g->subs[(size_t)r]->device));
-  if (g->d_full[(size_t)r]) {
-    VG_HIP(parent, hipStreamSynchronize(g->subs[(size_t)r]->stream));
-    VG_HIP(parent, hipFree(g->d_full[(size_t)r]));
-  }
-  g->d_full[(size_t)r] = nullptr;
+  if (g->d_full[(size_t)r]) VG_HIP(parent, hipStreamSynchronize(g->subs[(size_t)r]->stream));
   g->full_cap[(size_t)r] = 0;
   const size_t cap = std::max<size_t>(n + n / 4, 1024);
-  VG_HIP(parent, hipMalloc(reinterpret_cast<void**>(&g->d_full[(size_t)r]), cap * kScanPlanes * sizeof(double)));
+  VG_HIP(parent, g->d_full[(size_t)r].alloc(cap * kScanPlanes * sizeof(double)));
   g->full_cap[(size_t)r] = cap;
   return VGICP_OK;
 }
@@ -351,9 +347,9 @@ extern "C" int vgicp_create_multi(const int* device_ids, int n_devices, vgicp_ct
   parent->multi = g;
   g->n = n_devices;
   g->workers.assign((size_t)n_devices, nullptr);
-  g->d_full.assign((size_t)n_devices, nullptr);
+  g->d_full.resize((size_t)n_devices);
   g->full_cap.assign((size_t)n_devices, 0);
-  g->ev_gather.assign((size_t)n_devices, nullptr);
+  g->ev_gather.resize((size_t)n_devices);
   g->w_launches0.assign((size_t)n_devices, 0);
   g->w_copies0.assign((size_t)n_devices, 0);
   g->w_syncs0.assign((size_t)n_devices, 0);
@@ -380,7 +376,7 @@ extern "C" int vgicp_create_multi(const int* device_ids, int n_devices, vgicp_ct
     // WHOLE compute units were seen not to become resident side by side (4 and 8 queues, 150 KB per workgroup)
     if (m > 1) sub->persist_lds_budget = 64u * 1024u;
     g->subs.push_back(sub);
-    if (hipSetDevice(dev) != hipSuccess || hipEventCreateWithFlags(&g->ev_gather[(size_t)r], hipEventDisableTiming) != hipSuccess)
+    if (hipSetDevice(dev) != hipSuccess || g->ev_gather[(size_t)r].create(false) != hipSuccess)
       return bail(VGICP_ERR_HIP, "hipEventCreate failed");
   }
   g->verbose = std::getenv("VGICP_VERBOSE") != nullptr;
@@ -451,14 +447,11 @@ int destroy(vgicp_ctx* ctx) {
     (void)hipSetDevice(sub->device);
     if (sub->stream) (void)(hipStreamSynchronize)(sub->stream);
   }
-  for (size_t r = 0; r < g->subs.size(); ++r) {
-    (void)hipSetDevice(g->subs[r]->device);
-    if (r < g->d_full.size() && g->d_full[r]) (void)hipFree(g->d_full[r]);
-    if (r < g->ev_gather.size() && g->ev_gather[r]) (void)hipEventDestroy(g->ev_gather[r]);
-    g->subs[r]->owner = nullptr;
-    vgicp_destroy(g->subs[r]);
+  for (vgicp_ctx* sub : g->subs) {
+    sub->owner = nullptr;
+    vgicp_destroy(sub);
   }
-  delete g;
+  delete g;   // the group's own copies and events: every stream that used them was waited for above
   ctx->multi = nullptr;
   delete ctx;
   return VGICP_OK;
