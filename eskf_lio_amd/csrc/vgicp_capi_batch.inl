@@ -124,7 +124,7 @@ int vgicp_align_resident_batch(vgicp_ctx* ctx, size_t k, const double* guesses, 
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
   if (k < 1 || k > (size_t)VGICP_BATCH_MAX) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "k must be 1 .. VGICP_BATCH_MAX");
   if (!guesses || !out_poses) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pose pointer");
-  { const int rc_params = check_params(ctx, params); if (rc_params != VGICP_OK) return rc_params; }
+  VG_RC(check_params(ctx, params));
   const double t0 = now_seconds();
   int first_bad = VGICP_OK;
   int rc;
@@ -163,7 +163,7 @@ int vgicp_align_batch_width(vgicp_ctx* ctx, size_t* hypotheses_per_launch) {
   if (!hypotheses_per_launch) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "hypotheses_per_launch is NULL");
   *hypotheses_per_launch = 1;
   if (ctx->multi) return vgicp_multi_api::align_batch_width(ctx, hypotheses_per_launch);
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
   uint32_t team_wgs = 0;
   *hypotheses_per_launch = team_width(align_facts(ctx, nullptr, AlignCall::Batch, ctx->n), &team_wgs);

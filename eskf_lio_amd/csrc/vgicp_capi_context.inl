@@ -262,8 +262,7 @@ int vgicp_get_counter(const vgicp_ctx* ctx, int which, uint64_t* value) {
     case VGICP_COUNTER_UPLOAD_NANOSECONDS: *value = (uint64_t)(ctx->upload_seconds * 1e9); break;
     case VGICP_COUNTER_PREP_INDEFINITE: {
       // a preparation that was only enqueued has not reported yet: bring it up to date like every other reader
-      const int rc_settle = settle(const_cast<vgicp_ctx*>(ctx));
-      if (rc_settle != VGICP_OK) return rc_settle;
+      VG_RC(settle(const_cast<vgicp_ctx*>(ctx)));
       *value = ctx->prep_indefinite;
       break;
     }
@@ -321,7 +320,7 @@ int vgicp_set_option(vgicp_ctx* ctx, int option, int value) {
       ctx->reference_order = value != 0;
       return VGICP_OK;
     case VGICP_OPTION_MAP_RAW_POINTS: {
-      { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+      VG_RC(settle(ctx));
       if (ctx->voxels != 0)
         return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the raw-point store is switched only while the map holds no voxel");
       VG_HIP(ctx, hipSetDevice(ctx->device));

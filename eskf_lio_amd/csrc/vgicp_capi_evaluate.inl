@@ -26,7 +26,7 @@ int vgicp_evaluate_resident(vgicp_ctx* ctx, size_t k, const double* poses, vgicp
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
   // the launch geometry is made from the kept count: a pending scan (and a pending insertion with it) is settled first
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
 
   const uint32_t rows = evaluate_rows(ctx->n);

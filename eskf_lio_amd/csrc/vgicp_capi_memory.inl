@@ -1,9 +1,10 @@
 // vgicp_capi_memory.inl — part of vgicp_capi.hip (one translation unit, cut by concern; see that file).
 // Copies between the caller's pageable memory and the device (the page-locked arena, the streaming CPU copies, the
 // symmetric-covariance compaction of the scan upload), and WHEN the context's buffers grow: staging area, voxel table
-// (growth / rehash policy), raw-point log, scan, log.  The buffers are owners (vgicp_owned.h): a grow path decides the
-// size and waits for whatever still reads the old block; alloc() frees that block and then allocates, a temporary is a
-// local owner, and a new block is installed by a move.  An error return leaves nothing behind.
+// (rehash), raw-point log, scan, log.  The buffers are owners (vgicp_owned.h): a grow path decides the size (the voxel
+// table's and the raw-point log's come from vgicp_map_plan.h) and waits for whatever still reads the old block; alloc()
+// frees that block and then allocates, a temporary is a local owner, and a new block is installed by a move.  An error
+// return leaves nothing behind.
 namespace {
 
 int settle(vgicp_ctx* ctx);         // defined with the scan preparation below
@@ -179,7 +180,6 @@ void user_copies_finish(vgicp_ctx* ctx) {
   for (const auto& o : ctx->pending_out) std::memcpy(o.dst, o.src, o.bytes);
   ctx->pending_out.clear();
 }
-#define VG_RC(call) do { const int rc__ = (call); if (rc__ != VGICP_OK) return rc__; } while (0)
 
 int ensure_stage(vgicp_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->d_stage.bytes()) return VGICP_OK;
@@ -214,9 +214,10 @@ template <class Call> int forward_to_first(const vgicp_ctx* ctx, Call call, bool
   return rc;
 }
 
-// an empty table of `slots` in *out (whatever *out held is freed first)
-int alloc_table(vgicp_ctx* ctx, uint64_t slots, DeviceBuf<VoxelRecord>* out) {
-  if (slots > (1ull << 32)) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table would exceed 2^32 slots");
+// an empty table as planned (vgicp_map_plan.h) in *out (whatever *out held is freed first)
+int alloc_table(vgicp_ctx* ctx, const TableGrowth& plan, DeviceBuf<VoxelRecord>* out) {
+  if (plan.too_large) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table would exceed 2^32 slots");
+  const uint64_t slots = plan.slots;
   const hipError_t e = out->alloc(slots * sizeof(VoxelRecord));
   if (e != hipSuccess)
     return fail(ctx, VGICP_ERR_TABLE_FULL, std::string("hipMalloc(voxel table): ") + hipGetErrorString(e));
@@ -247,10 +248,8 @@ int raw_replace(vgicp_ctx* ctx, uint64_t entries) {
   VG_HIP(ctx, hipMemsetAsync(ctx->d_ins_counters + 4, 0, 3 * sizeof(uint32_t), ctx->stream));
   return VGICP_OK;
 }
-// sized from the map's capacity hint like the table: 4 entries per voxel hinted
-int raw_reset(vgicp_ctx* ctx) {
-  return raw_replace(ctx, std::min(kRawMaxEntries, next_pow2(std::max<uint64_t>(kRawMinEntries, (uint64_t)ctx->raw_hint * 4))));
-}
+// sized from the map's capacity hint like the table
+int raw_reset(vgicp_ctx* ctx) { return raw_replace(ctx, plan_first_raw_log(ctx->raw_hint)); }
 
 // An append that did not fit leaves entries counted that nobody wrote: from then on the store refuses every call that
 // would read or extend it, until vgicp_map_reset (or the option switched on again) makes it anew.
@@ -282,8 +281,8 @@ struct StreamIdleOnExit {
 // synchronisation, the live entries (slot FULL) compacted into a fresh log that is twice as large as needed, geometric.
 int ensure_raw(vgicp_ctx* ctx, uint64_t n) {
   if (!ctx->raw_on) return VGICP_OK;
-  { const int rc = raw_refuse_if_broken(ctx); if (rc != VGICP_OK) return rc; }
-  if (ctx->raw_used_upper + n <= ctx->raw_capacity) return VGICP_OK;
+  VG_RC(raw_refuse_if_broken(ctx));
+  if (!raw_log_needs_compaction(ctx->raw_used_upper, n, ctx->raw_capacity)) return VGICP_OK;
   uint32_t* ctr = ctx->d_ins_counters + 4;
   DeviceBuf<RawPoint> tmp, grown;
   VG_HIP(ctx, tmp.alloc((size_t)ctx->raw_capacity * sizeof(RawPoint)));
@@ -295,9 +294,9 @@ int ensure_raw(vgicp_ctx* ctx, uint64_t n) {
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (ctx->h_raw_ctr[1] != 0) return raw_overflowed(ctx);
   const uint64_t live = ctx->h_raw_ctr[2];
-  uint64_t cap = ctx->raw_capacity;
-  while (cap < kRawMaxEntries && 2 * (live + n) > cap) cap *= 2;
-  if (live + n > cap) return fail(ctx, VGICP_ERR_TABLE_FULL, "raw-point log would exceed 2^31 points");
+  const RawGrowth plan = plan_raw_growth(live, n, ctx->raw_capacity);
+  const uint64_t cap = plan.capacity;
+  if (plan.too_large) return fail(ctx, VGICP_ERR_TABLE_FULL, "raw-point log would exceed 2^31 points");
   VG_HIP(ctx, hipMemcpyAsync(ctr, ctr + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
   if (cap == ctx->raw_capacity) {
     ctx->d_raw = std::move(tmp);
@@ -319,18 +318,18 @@ int ensure_raw(vgicp_ctx* ctx, uint64_t n) {
 }
 
 int reserve_dense(vgicp_ctx* ctx);
-// Keep load (FULL + TOMB + incoming) <= 1/2 at all times; size new tables for load <= 1/4.
+// Room for `incoming` new voxels: when plan_table_growth (vgicp_map_plan.h) says so, a table of the size it says.
 int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
-  const uint64_t used = ctx->voxels + ctx->tombstones + incoming + ctx->insert_pending_upper;
-  if (ctx->table && used * 2 <= ctx->slots) return VGICP_OK;
-  const uint64_t slots = next_pow2(std::max<uint64_t>(kMinSlots, (ctx->voxels + incoming) * 4));
+  const TableGrowth plan = plan_table_growth(ctx->table != nullptr, ctx->slots, ctx->voxels, ctx->tombstones,
+                                             ctx->insert_pending_upper, incoming);
+  if (!plan.grow) return VGICP_OK;
+  const uint64_t slots = plan.slots;
   // the new table; one scratch word per OLD slot between the claim and the write launch (its own allocation: the staging
   // area may hold the batch that made the table grow); with the raw-point store, the log the live entries move to
   DeviceBuf<VoxelRecord> fresh;
   DeviceBuf<uint32_t> claimed;
   DeviceBuf<RawPoint> moved;
-  int rc = alloc_table(ctx, slots, &fresh);
-  if (rc != VGICP_OK) return rc;
+  VG_RC(alloc_table(ctx, plan, &fresh));
   // a failure on the way keeps nothing of the new table (what was enqueued is waited for before the three are freed)
   StreamIdleOnExit idle{ctx->stream};
   int rc_raw = VGICP_OK;
@@ -366,8 +365,8 @@ int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
   ctx->slots = slots;
   ctx->tombstones = 0;
   ++ctx->map_version;
-  rc = reserve_dense(ctx);   // the dense copy's storage follows the table's size here, never inside an align
-  return rc != VGICP_OK ? rc : rc_raw;
+  VG_RC(reserve_dense(ctx));   // the dense copy's storage follows the table's size here, never inside an align
+  return rc_raw;
 }
 
 int ensure_scan(vgicp_ctx* ctx, size_t n) {

@@ -6,12 +6,6 @@ namespace vgicp_internal {
 
 int settle_context(vgicp_ctx* ctx) { return settle(ctx); }
 
-bool insertion_lists_stay_short_for(const vgicp_ctx* ctx, double prep_voxel) {
-  if (!(prep_voxel > 0.0) || ctx->dev.insert_sort) return false;
-  const double per_axis = std::ceil(ctx->voxel_size / prep_voxel) + 1.0;
-  return per_axis * per_axis * per_axis <= 64.0;
-}
-
 // Whether an align of n points / max_it rounds would have to (re)allocate on this context, and the allocation itself.
 // hipFree waits for the whole DEVICE: sub-contexts that share a device must not meet one between their launches (a
 // neighbour's persistent kernel is already running and waiting for this sub-context's), so the multi-device context
@@ -22,12 +16,10 @@ bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it) {
 }
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it) {
   VG_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = settle(ctx);
-  if (rc != VGICP_OK) return rc;
+  VG_RC(settle(ctx));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (!ctx->d_scan || n > ctx->scan_capacity) {
-    rc = ensure_scan(ctx, n);
-    if (rc != VGICP_OK) return rc;
+    VG_RC(ensure_scan(ctx, n));
     ctx->scan_ready = false;   // whatever was resident went with the old buffers
     ctx->n = 0;
     forget_fetch(ctx);
@@ -53,8 +45,7 @@ int wire_mailboxes(vgicp_ctx* const* subs, int n) {
   for (int r = 0; r < n; ++r) {
     vgicp_ctx* ctx = subs[r];
     VG_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = ensure_mailbox(ctx);
-    if (rc != VGICP_OK) return rc;
+    VG_RC(ensure_mailbox(ctx));
     // this rank's mailbox: the rows the ranks write are unset, the others +0.0 for good; verdict words 0
     std::vector<unsigned long long> img(kMailWords, 0ull);
     for (int buf = 0; buf < 3; ++buf)
@@ -156,8 +147,7 @@ int adopt_device_scan(vgicp_ctx* ctx, int src_device, const double* d_points, co
                       double prep_voxel, hipEvent_t ready) {
   if (n > 0xFFFFFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "scan too large");
   VG_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = settle(ctx);
-  if (rc != VGICP_OK) return rc;
+  VG_RC(settle(ctx));
   VG_RC(begin_scan(ctx, n, prep_voxel, false));   // the source's down-sampling still describes the points
   ctx->n = (uint32_t)n;
   if (ready) VG_HIP(ctx, hipStreamWaitEvent(ctx->stream, ready, 0));
@@ -184,43 +174,12 @@ int adopt_device_scan(vgicp_ctx* ctx, int src_device, const double* d_points, co
 int map_insert_device(vgicp_ctx* ctx, const double* d_points, const double* d_covs, size_t n, const double transform[16],
                       size_t max_points_per_voxel, bool short_lists, bool deferred, size_t* new_voxels) {
   if (new_voxels) *new_voxels = 0;
-  if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
-  if (!transform) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pointer");
-  if (max_points_per_voxel == 0) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be >= 1");
-  if (ctx->raw_on && max_points_per_voxel > 0xFFFFFFFFull)
-    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "max_points_per_voxel must be < 2^32 while the map keeps raw points");
-  if (n > 0x7FFFFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "scan too large");
+  const InsertVerdict v = insert_verdict(ctx, InsertEntry::Device, transform != nullptr, max_points_per_voxel, n);
+  if (v.status != VGICP_OK) return fail(ctx, v.status, v.text);
   VG_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = (ctx->scan_pending || ctx->insert_pending) ? settle(ctx) : VGICP_OK;
-  if (rc != VGICP_OK) return rc;
-  if (n == 0) return VGICP_OK;
-  rc = ensure_table(ctx, n);
-  if (rc == VGICP_OK) rc = ensure_raw(ctx, n);
-  if (rc != VGICP_OK) return rc;
-  const size_t sb = map_insert_scratch_bytes((uint32_t)n);
-  rc = ensure_stage(ctx, sb);
-  if (rc != VGICP_OK) return rc;
-  double pose12[12];
-  pose_to_state(transform, pose12);
-  if (deferred) {
-    if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[4], ctx->stream)); ctx->ev_stage_set[4] = true; }
-    ++ctx->map_version;
-  VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size, d_points, d_covs,
-                                  (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, ctx->d_stage, sb, ctx->d_ins_counters,
-                                  short_lists, raw_log(ctx)));
-    if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[5], ctx->stream)); ctx->ev_stage_set[5] = true; }
-    ctx->insert_pending = true;
-    ctx->ins_copy_enqueued = false;
-    ctx->insert_pending_upper = n;
-    if (ctx->raw_on) ctx->raw_used_upper += n;
-    return VGICP_OK;
-  }
-  VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(uint32_t), ctx->stream));
-  ++ctx->map_version;
-  VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size, d_points, d_covs,
-                                (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, ctx->d_stage, sb, ctx->d_counters, short_lists,
-                                raw_log(ctx)));
-  return finish_insert(ctx, new_voxels);
+  VG_RC(settle_if_pending(ctx));
+  if (v.nothing_to_do) return VGICP_OK;
+  return insert_points(ctx, d_points, d_covs, n, transform, max_points_per_voxel, nullptr, short_lists, deferred, new_voxels);
 }
 
 }  // namespace vgicp_internal

@@ -18,7 +18,7 @@ int vgicp_peer_export(vgicp_ctx* ctx, void* handle64) {
 int vgicp_peer_connect(vgicp_ctx* ctx, int world_size, int rank, const void* handles) {
   if (!ctx || !handles) return VGICP_ERR_BAD_ARGUMENT;
   if (ctx->multi || ctx->owner) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "a multi-device context has its exchange built in: communicators and hand-wired peers are for one-process-per-GPU hosts");
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   if (world_size < 1 || world_size > kMaxRanks || rank < 0 || rank >= world_size)
     return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "bad world_size / rank (at most 16 ranks)");
   if (ctx->peers_connected) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "peers already connected");
@@ -86,7 +86,7 @@ int vgicp_comm_unique_id(vgicp_ctx* ctx, void* id128) {
 int vgicp_comm_init(vgicp_ctx* ctx, int world_size, int rank, const void* id128) {
   if (!ctx || !id128) return VGICP_ERR_BAD_ARGUMENT;
   if (ctx->multi || ctx->owner) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "a multi-device context has its exchange built in: communicators and hand-wired peers are for one-process-per-GPU hosts");
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   if (world_size < 1 || rank < 0 || rank >= world_size)
     return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "bad world_size / rank");
   if (ctx->comm) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "communicator already initialised");

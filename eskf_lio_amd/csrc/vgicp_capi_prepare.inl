@@ -192,7 +192,7 @@ int settle_scan(vgicp_ctx* ctx) {
 int settle(vgicp_ctx* ctx) {
   if (!ctx->scan_pending && !ctx->insert_pending) return VGICP_OK;
   VG_HIP(ctx, hipSetDevice(ctx->device));
-  { const int rc_copy = fetch_insert_totals(ctx); if (rc_copy != VGICP_OK) return rc_copy; }
+  VG_RC(fetch_insert_totals(ctx));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int rc_scan = settle_scan(ctx);
   const int rc_ins = settle_insert(ctx);
@@ -271,7 +271,7 @@ int vgicp_preprocess(vgicp_ctx* ctx, size_t n, const double* points, double voxe
     });
   if (!kept) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "kept is NULL");
   *kept = 0;
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   int rc = check_preprocess_args(ctx, n, voxel_size, knn);
   if (rc != VGICP_OK) return rc;
   if (n == 0) return VGICP_OK;
@@ -438,7 +438,7 @@ int vgicp_deskew(vgicp_ctx* ctx, size_t n, double* points, const double* point_t
     return forward_to_first(ctx, [&](vgicp_ctx* first) { return vgicp_deskew(first, n, points, point_time, num_states, states, transformed); });
   if (!transformed) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "transformed is NULL");
   *transformed = 0;
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   if (n == 0 || num_states == 0) return VGICP_OK;
   if (!points || !point_time || !states) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pointer");
   if (n > 0x7FFFFFFFull || num_states > 0x7FFFFFull) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "scan or state queue too large");
@@ -933,8 +933,7 @@ int vgicp_scan_fetch_end(vgicp_ctx* ctx, size_t capacity, double* points, double
     }
   }
   // the preparation's own verdict and counters, the pending map insertion's totals: as every synchronising entry point
-  const int rc = settle(ctx);
-  if (rc != VGICP_OK) return rc;
+  VG_RC(settle(ctx));
   if (rc_copy != VGICP_OK) return rc_copy;
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
   if (ctx->n != kept) return fail(ctx, VGICP_ERR_HIP, "the preparation reported two different sizes");
@@ -956,7 +955,7 @@ int vgicp_scan_download(vgicp_ctx* ctx, size_t capacity, double* points, double*
   if (ctx->multi) return vgicp_multi_api::scan_download(ctx, capacity, points, covs, n);
   if (!n) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "n is NULL");
   *n = 0;
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload or vgicp_scan_prepare first");
   *n = ctx->n;
   if (ctx->n == 0 || (!points && !covs)) return VGICP_OK;  // both NULL: size query

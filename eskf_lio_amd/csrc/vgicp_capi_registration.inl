@@ -94,7 +94,7 @@ int vgicp_align(vgicp_ctx* ctx, size_t n, const double* points, const double* co
     if (!guess || !out_pose) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pose pointer");
     return vgicp_multi_api::align(ctx, n, points, covs, guess, params, out_pose, stats);
   }
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   const double t0 = now_seconds();
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
   AlignFacts facts = align_facts(ctx, params, AlignCall::Upload, n);
@@ -198,7 +198,7 @@ int vgicp_match(vgicp_ctx* ctx, size_t n, const double* points, const double* co
     });
   if (!matched) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "matched is NULL");
   *matched = 0;
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
   if (n == 0) return VGICP_OK;
   if (!points || !covs || !src_points || !src_covs || !map_points || !map_covs)
@@ -244,7 +244,7 @@ int vgicp_match(vgicp_ctx* ctx, size_t n, const double* points, const double* co
 int vgicp_voxel_index(vgicp_ctx* ctx, size_t n, const double* points, int32_t* keys) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
   if (ctx->multi) return forward_to_first(ctx, [&](vgicp_ctx* first) { return vgicp_voxel_index(first, n, points, keys); });
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   if (n == 0) return VGICP_OK;
   if (!points || !keys) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL array pointer");
   if (!(ctx->voxel_size > 0.0)) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel size: call vgicp_map_reset first");

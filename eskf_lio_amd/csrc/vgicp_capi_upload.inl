@@ -200,7 +200,7 @@ int scan_upload_enqueue(vgicp_ctx* ctx, size_t n, const double* points, const do
 int vgicp_scan_upload(vgicp_ctx* ctx, size_t n, const double* points, const double* covs) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
   if (ctx->multi) return vgicp_multi_api::scan_upload(ctx, n, points, covs);
-  { const int rc_settle = settle(ctx); if (rc_settle != VGICP_OK) return rc_settle; }
+  VG_RC(settle(ctx));
   int rc = scan_upload_enqueue(ctx, n, points, covs);
   if (rc != VGICP_OK) return rc;
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -31,6 +31,7 @@
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
 #include "vgicp_prepare_plan.h"
+#include "vgicp_map_plan.h"
 
 using namespace vgicp;
 
@@ -74,12 +75,6 @@ inline double now_seconds() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-inline uint64_t next_pow2(uint64_t v) {
-  uint64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 // sequence numbers (scan_seq, prep_epoch, fetch_seq): 0 means "none yet" in every flag and header word, so it is skipped
 inline uint32_t next_nonzero(uint32_t& seq) {
@@ -87,12 +82,9 @@ inline uint32_t next_nonzero(uint32_t& seq) {
   return seq;
 }
 
-constexpr uint64_t kMinSlots = 1024;
 // words behind the counter block (d_ins_counters): [0] [1] the deferred insertion's running totals, [2] [3] the
 // resident scan's symmetry verdicts, [4] [5] [6] the raw-point log (RawLog::ctr), [7] spare
 constexpr int kInsertWords = 8;
-constexpr uint64_t kRawMinEntries = 4096;
-constexpr uint64_t kRawMaxEntries = 1ull << 31;   // 64 GiB of raw points; ordinals and offsets stay 32-bit
 constexpr int kDefaultChunk = 4;
 constexpr int kMaxChunksInFlight = 2;
 static_assert(kPlanTeamsMax == (uint32_t)kTeamsMax, "vgicp_align_plan.h plans with the team kernel's width");
@@ -572,6 +564,8 @@ inline int fail_hip(const vgicp_ctx* ctx, hipError_t e, const char* what) {
     hipError_t e__ = (call);                                           \
     if (e__ != hipSuccess) return fail_hip((ctx), e__, #call);         \
   } while (0)
+// ... and a call of this library's own that returns a status: anything but VGICP_OK is returned as it is
+#define VG_RC(call) do { const int rc__ = (call); if (rc__ != VGICP_OK) return rc__; } while (0)
 
 // ---- what vgicp_multi.hip needs from vgicp_capi.hip besides the public entry points ----
 namespace vgicp_internal {
@@ -604,7 +598,6 @@ int align_batch_sequential(vgicp_ctx* ctx, size_t k, const double* guesses, cons
                            vgicp_batch_stats* stats, bool loop_only, int* first_bad);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
-bool insertion_lists_stay_short_for(const vgicp_ctx* ctx, double prep_voxel);
 }  // namespace vgicp_internal
 
 // ---- vgicp_multi.hip: the entry points of a multi-device context (ctx->multi != nullptr) ----

@@ -560,7 +560,7 @@ int map_insert_resident(vgicp_ctx* ctx, const double transform[16], size_t max_p
   const size_t n = g->n_total;
   if (n == 0) return VGICP_OK;
   const bool prepared = g->resident != Resident::Sharded;
-  const bool short_lists = prepared && vgicp_internal::insertion_lists_stay_short_for(lead, g->prep_voxel);
+  const bool short_lists = prepared && insertion_lists_stay_short(lead->voxel_size, g->prep_voxel, lead->dev.insert_sort);
   std::vector<const double*> pts((size_t)g->n, nullptr), cov((size_t)g->n, nullptr);
   for (int r = 0; r < g->n; ++r) {
     vgicp_ctx* sub = g->subs[(size_t)r];
