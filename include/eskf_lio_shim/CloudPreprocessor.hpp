@@ -55,7 +55,7 @@ struct CloudPreprocessorConfig
   enum class HostCopy {Eager, Deferred};
   HostCopy hostCopy = defaultHostCopy();
   // how ICP::align / LocalMap::updateLocalMap later recognise "this host cloud is still the scan process() left on the
-  // device" (LocalMap.hpp, shim::ResidentCheck): FullHash (default) sees an in-place edit of ANY element and falls back
+  // device" (ResidentScan.hpp, shim::ResidentCheck): FullHash (default) sees an in-place edit of ANY element and falls back
   // to uploading the cloud, as the reference reads the host cloud every time; Sampled (~0.1 ms per frame cheaper) sees
   // resizes, reallocations and edits of 64 sampled elements only
   shim::ResidentCheck residentCheck = shim::ResidentCheck::FullHash;
@@ -189,14 +189,7 @@ public:
   {
     PointCloud & cloud = *lidarMeas->cloud;
     const size_t n = cloud.points_.size();
-    std::vector<double> packed(states.size() * 8);
-    size_t k = 0;
-    for (const auto & state : states) {
-      packed[k++] = state.timestamp;
-      for (int a = 0; a < 3; ++a) {packed[k++] = state.position(a);}
-      const double * q = shim::quatData(state.attitude);
-      for (int a = 0; a < 4; ++a) {packed[k++] = q[a];}
-    }
+    const std::vector<double> packed = packStates(states);
     static_assert(sizeof(Vector3d) == 3 * sizeof(double), "points must be packed xyz triples");
     uint64_t ticket = 0;   // staged when it arrived (stage())?
     {
@@ -300,14 +293,7 @@ public:
     const std::deque<State> & states, const std::vector<double> & pointTime,
     std::vector<Vector3d> & points) const
   {
-    std::vector<double> packed(states.size() * 8);
-    size_t k = 0;
-    for (const auto & state : states) {
-      packed[k++] = state.timestamp;
-      for (int a = 0; a < 3; ++a) {packed[k++] = state.position(a);}
-      const double * q = shim::quatData(state.attitude);
-      for (int a = 0; a < 4; ++a) {packed[k++] = q[a];}
-    }
+    const std::vector<double> packed = packStates(states);
     int64_t moved = 0;
     shim::check(
       ctx_,
@@ -322,6 +308,20 @@ public:
 
 private:
   CloudPreprocessor() = delete;
+
+  // the state queue as the C ABI takes it: 8 doubles per state (timestamp, position, attitude x y z w)
+  static std::vector<double> packStates(const std::deque<State> & states)
+  {
+    std::vector<double> packed(states.size() * 8);
+    size_t k = 0;
+    for (const auto & state : states) {
+      packed[k++] = state.timestamp;
+      for (int a = 0; a < 3; ++a) {packed[k++] = state.position(a);}
+      const double * q = shim::quatData(state.attitude);
+      for (int a = 0; a < 4; ++a) {packed[k++] = q[a];}
+    }
+    return packed;
+  }
 
   double voxelSize_;
   int knn_;

@@ -133,11 +133,7 @@ public:
   {
     vgicp_ctx * ctx = localMap.context();
     applyRobust(ctx);
-    vgicp_params params{};
-    params.max_iteration = maxIteration_;
-    params.chunk_iterations = chunkIterations_;
-    params.translation_sq_threshold = translationSquaredThreshold_;
-    params.cosine_threshold = cosineThreshold_;
+    const vgicp_params params = paramsOf();
     std::vector<uint64_t> counts(static_cast<size_t>(maxIteration_ > 0 ? maxIteration_ : 1), 0);
     vgicp_stats stats{};
     stats.corr_count = counts.data();
@@ -184,13 +180,7 @@ public:
       rc = vgicp_align_resident(ctx, shim::poseData(guess), &params, pose, &stats);
       lastUsedResidentScan_ = true;
     } else {
-      const size_t n = cloud.points_.size();
-      if (cloud.covariances_.size() != n) {
-        throw std::runtime_error(
-                "ICP::align: the cloud has " + std::to_string(n) + " points but " +
-                std::to_string(cloud.covariances_.size()) + " covariances (a cloud prepared with a deferred host "
-                "copy and changed since? call shim::materialize first)");
-      }
+      const size_t n = pointsWithCovariances(cloud, "align");
       const double * pts = n ? cloud.points_.data()->data() : nullptr;
       const double * covs = n ? cloud.covariances_.data()->data() : nullptr;
       rc = vgicp_align(ctx, n, pts, covs, shim::poseData(guess), &params, pose, &stats);
@@ -233,30 +223,9 @@ public:
     }
     vgicp_ctx * ctx = localMap.context();
     applyRobust(ctx);
-    vgicp_params params{};
-    params.max_iteration = maxIteration_;
-    params.chunk_iterations = chunkIterations_;
-    params.translation_sq_threshold = translationSquaredThreshold_;
-    params.cosine_threshold = cosineThreshold_;
-    bool resident = false;
-    {
-      shim::TraceScope ts(shim::Trace::AlignVerify);
-      resident = shim::residentStampOf(ctx, cloud) != nullptr;
-    }
+    const vgicp_params params = paramsOf();
+    lastUsedResidentScan_ = residentScanOrUpload(ctx, cloud, "alignHypotheses");
     shim::TraceScope tsCall(shim::Trace::AlignCall);
-    if (!resident) {
-      const size_t n = cloud.points_.size();
-      if (cloud.covariances_.size() != n) {
-        throw std::runtime_error(
-                "ICP::alignHypotheses: the cloud has " + std::to_string(n) + " points but " +
-                std::to_string(cloud.covariances_.size()) + " covariances (a cloud prepared with a deferred host "
-                "copy and changed since? call shim::materialize first)");
-      }
-      const double * pts = n ? cloud.points_.data()->data() : nullptr;
-      const double * covs = n ? cloud.covariances_.data()->data() : nullptr;
-      shim::check(ctx, vgicp_scan_upload(ctx, n, pts, covs), "vgicp_scan_upload");
-    }
-    lastUsedResidentScan_ = resident;
     const size_t rounds = static_cast<size_t>(maxIteration_ > 0 ? maxIteration_ : 0);
     std::vector<double> in(16 * k), poses(16 * k);
     for (size_t h = 0; h < k; ++h) {
@@ -373,25 +342,8 @@ public:
       throw std::runtime_error("ICP::evaluate: more than VGICP_EVAL_MAX poses");
     }
     vgicp_ctx * ctx = localMap.context();
-    bool resident = false;
-    {
-      shim::TraceScope ts(shim::Trace::AlignVerify);
-      resident = shim::residentStampOf(ctx, cloud) != nullptr;
-    }
+    lastUsedResidentScan_ = residentScanOrUpload(ctx, cloud, "evaluate");
     shim::TraceScope tsCall(shim::Trace::AlignCall);
-    if (!resident) {
-      const size_t n = cloud.points_.size();
-      if (cloud.covariances_.size() != n) {
-        throw std::runtime_error(
-                "ICP::evaluate: the cloud has " + std::to_string(n) + " points but " +
-                std::to_string(cloud.covariances_.size()) + " covariances (a cloud prepared with a deferred host "
-                "copy and changed since? call shim::materialize first)");
-      }
-      const double * pts = n ? cloud.points_.data()->data() : nullptr;
-      const double * covs = n ? cloud.covariances_.data()->data() : nullptr;
-      shim::check(ctx, vgicp_scan_upload(ctx, n, pts, covs), "vgicp_scan_upload");
-    }
-    lastUsedResidentScan_ = resident;
     return evaluateResidentScan(ctx, poses);
   }
 
@@ -452,6 +404,46 @@ public:
 
 private:
   ICP() = delete;
+
+  vgicp_params paramsOf() const
+  {
+    vgicp_params params{};
+    params.max_iteration = maxIteration_;
+    params.chunk_iterations = chunkIterations_;
+    params.translation_sq_threshold = translationSquaredThreshold_;
+    params.cosine_threshold = cosineThreshold_;
+    return params;
+  }
+
+  // the size of a cloud that is about to go up as it is: one covariance per point, or `method` throws
+  static size_t pointsWithCovariances(const PointCloud & cloud, const char * method)
+  {
+    const size_t n = cloud.points_.size();
+    if (cloud.covariances_.size() != n) {
+      throw std::runtime_error(
+              std::string("ICP::") + method + ": the cloud has " + std::to_string(n) + " points but " +
+              std::to_string(cloud.covariances_.size()) + " covariances (a cloud prepared with a deferred host "
+              "copy and changed since? call shim::materialize first)");
+    }
+    return n;
+  }
+
+  // Use the resident scan or upload this cloud: true when the cloud still is what CloudPreprocessor::process left on the
+  // device (the stamp and the hash of the host data say so), else ONE upload of the cloud, which is resident from then on.
+  // (align() does not come here: vgicp_align uploads for it, and it may register beside the hash.)
+  static bool residentScanOrUpload(vgicp_ctx * ctx, const PointCloud & cloud, const char * method)
+  {
+    {
+      shim::TraceScope ts(shim::Trace::AlignVerify);
+      if (shim::residentStampOf(ctx, cloud)) {return true;}
+    }
+    shim::TraceScope tsCall(shim::Trace::AlignCall);
+    const size_t n = pointsWithCovariances(cloud, method);
+    const double * pts = n ? cloud.points_.data()->data() : nullptr;
+    const double * covs = n ? cloud.covariances_.data()->data() : nullptr;
+    shim::check(ctx, vgicp_scan_upload(ctx, n, pts, covs), "vgicp_scan_upload");
+    return false;
+  }
 
   // The context may serve several ICP objects: THIS one's robust settings are put on it before each of its aligns.  With
   // the mode off a refusal is not an error (a multi-device context refuses the options and never has the mode on; a

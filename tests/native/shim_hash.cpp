@@ -1,4 +1,4 @@
-// CPU check of the drop-in's "is this host cloud still the resident scan" hash (include/eskf_lio_shim/LocalMap.hpp,
+// CPU check of the drop-in's "is this host cloud still the resident scan" hash (include/eskf_lio_shim/ResidentScan.hpp,
 // shim::bufferHash / sampleHash): the AVX2 lanes and the plain ones give the same value, every single-bit edit of a
 // buffer changes it, so do a swap of two words inside one lane and a shifted run; ResidentCheck::Sampled sees an edit of a
 // sampled element and misses one of an unsampled element (the documented price of that mode), FullHash sees both.
@@ -11,7 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#include "eskf_lio_shim/LocalMap.hpp"
+#include "eskf_lio_shim/ResidentScan.hpp"
 
 using namespace ESKF_LIO;
 

@@ -316,6 +316,54 @@ def test_shadow_grid_of_the_dropin_map_on_the_cpu(tmp_path):
     assert run.returncode == 0 and "ok 40 frames" in run.stdout and "ThreadSanitizer" not in run.stderr, run.stderr[-3000:]
 
 
+def test_dropin_routes_make_the_recorded_calls_on_the_cpu(tmp_path):
+    """Which C-ABI calls LocalMap::updateLocalMap / save and ICP::align / alignHypotheses / alignBest / evaluate /
+    alignBestByScore make, in which order and with which bytes (include/eskf_lio_shim/): tests/native/shim_routes.cpp stubs
+    the C ABI so that every call writes a line (name, scalars, count and FNV-1a hash of every array), drives 8 map
+    configurations x 7 kinds of cloud x 3 frames and the ICP methods, and its output equals tests/golden/shim_routes.txt byte
+    for byte — recorded from the headers as they were before updateLocalMap's routes were brought under one plan (commit
+    59bbaa7, `g++ -O1 -std=c++17 -pthread -Wall -I include tests/native/shim_routes.cpp -o shim_routes && ./shim_routes
+    <scratch dir> > tests/golden/shim_routes.txt`).  The same under ThreadSanitizer (shadow worker, hash helpers)."""
+    src = os.path.join(ROOT, "tests", "native", "shim_routes.cpp")
+    golden = open(os.path.join(ROOT, "tests", "golden", "shim_routes.txt"), "rb").read()
+    exe = tmp_path / "shim_routes"
+    out = subprocess.run(["g++", "-O1", "-std=c++17", "-pthread", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), src],
+                         capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-3000:]
+    run = subprocess.run([str(exe), str(tmp_path)], capture_output=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-800:]
+    assert run.stdout == golden, _first_difference(run.stdout, golden)
+    tsan = tmp_path / "shim_routes_tsan"
+    out = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=thread", "-I" + os.path.join(ROOT, "include"),
+                          "-o", str(tsan), src], capture_output=True, text=True)
+    if out.returncode != 0:
+        pytest.skip("no ThreadSanitizer runtime for this compiler: " + out.stderr[-200:])
+    run = subprocess.run([str(tsan), str(tmp_path)], capture_output=True, timeout=600)
+    assert run.returncode == 0 and b"ThreadSanitizer" not in run.stderr, run.stderr[-3000:]
+    assert run.stdout == golden, _first_difference(run.stdout, golden)
+
+
+def _first_difference(got, want):
+    a, b = got.decode(errors="replace").splitlines(), want.decode(errors="replace").splitlines()
+    for i in range(max(len(a), len(b))):
+        if i >= len(a) or i >= len(b) or a[i] != b[i]:
+            return "line %d:\n got  %s\n want %s" % (i + 1, a[i] if i < len(a) else "<end>", b[i] if i < len(b) else "<end>")
+    return "the same lines, different line ends"
+
+
+def test_update_plan_of_the_dropin_map_on_the_cpu(tmp_path):
+    """include/eskf_lio_shim/UpdatePlan.hpp decides what one LocalMap::updateLocalMap does (route, insertion, eviction,
+    where the host cloud is transformed, the hand-over to the shadow grid's worker, whether the shadow stays complete) from
+    the frame's facts alone.  tests/native/update_plan.cpp enumerates every combination of the facts and asserts the
+    invariants the routes had when they were written out one after the other."""
+    exe = tmp_path / "update_plan"
+    out = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), "-o", str(exe),
+                          os.path.join(ROOT, "tests", "native", "update_plan.cpp")], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-3000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout.startswith("ok"), run.stdout[-800:] + run.stderr[-800:]
+
+
 def test_same_voxel_shortcut_implies_an_unchanged_key():
     """The persistent launch asks "is the point still inside last round's voxel?" before it makes a key
     (`same_voxel_coord`, eskf_lio_amd/csrc/vgicp_device_fn.h): r = fma(-k, h, x); yes iff 0 <= r and h - r > 2^-20 h.
