@@ -50,6 +50,11 @@ BATCH_MAX = 64
 EVALUATE_EXPORTS = ("vgicp_evaluate_resident",)
 EVAL_MAX = 64
 
+# every symbol include/vgicp_hip_prior.h declares: an extension header whose two entry points live in a library of their
+# own beside the module (PRIOR_LIB_PATH), so that libvgicp_hip.so exports exactly the lists above
+PRIOR_EXPORTS = ("vgicp_set_pose_prior", "vgicp_pose_prior_chart")
+PRIOR_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_prior.so")
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -185,6 +190,15 @@ def load_library() -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("vgicp_last_error", "vgicp_peer_status"):
             fn.restype = C.c_int
+    # the pose prior's library, where it was built beside the module (a module of an earlier commit, loaded through
+    # VGICP_LIB_PATH for a comparison, has none): its two entry points are reached through the same object
+    if os.path.exists(PRIOR_LIB_PATH):
+        prior = C.CDLL(PRIOR_LIB_PATH, mode=C.RTLD_GLOBAL)
+        prior.vgicp_set_pose_prior.argtypes = [vp, dp, dp]
+        prior.vgicp_pose_prior_chart.argtypes = [dp, dp, dp, dp]
+        for name in PRIOR_EXPORTS:
+            getattr(prior, name).restype = C.c_int
+            setattr(lib, name, getattr(prior, name))
     _lib = lib
     return lib
 
@@ -756,6 +770,19 @@ class Context:
         self.set_option(OPTION_GATE_MICRO, gate_micro)
         return kind, scale_micro / 1000000.0, gate_micro / 1000000.0
 
+    def set_pose_prior(self, prior_pose=None, information=None):
+        """vgicp_set_pose_prior (vgicp_hip_prior.h): a Gaussian prior on the pose for every later align of this context
+        — prior_pose 4x4, information 6x6 in the filter's chart [t - t0; Log(R0^T R)].  None for either, or an all-zero
+        information, clears it.  Nothing is changed when a value is refused."""
+        if prior_pose is None or information is None:
+            self._check(self._lib.vgicp_set_pose_prior(self._h, None, None))
+            return
+        info = np.ascontiguousarray(np.asarray(information, dtype=np.float64).reshape(6, 6).T).reshape(36)
+        self._check(self._lib.vgicp_set_pose_prior(self._h, _dp(pose_to_abi(prior_pose)), _dp(info)))
+
+    def clear_pose_prior(self):
+        self.set_pose_prior(None, None)
+
     def host_register(self, array: np.ndarray):
         self._check(self._lib.vgicp_host_register(self._h, array.ctypes.data, array.nbytes))
 
@@ -802,3 +829,26 @@ class Context:
 
     def peer_disconnect(self):
         self._check(self._lib.vgicp_peer_disconnect(self._h))
+
+
+def pose_prior_chart(prior_pose, pose):
+    """vgicp_pose_prior_chart (vgicp_hip_prior.h), host only: (d (6), G (6 x 6)) of the prior's chart for `pose` against
+    `prior_pose`, by the formulas the kernels use."""
+    lib = load_library()
+    d, G = np.zeros(6), np.zeros(36)
+    rc = lib.vgicp_pose_prior_chart(_dp(pose_to_abi(prior_pose)), _dp(pose_to_abi(pose)), _dp(d), _dp(G))
+    if rc != OK:
+        raise VgicpError(rc, "vgicp_pose_prior_chart: a pose is missing or not finite")
+    return d, G.reshape(6, 6).T.copy()
+
+
+def posterior_information(normal_eq, prior_pose, pose, information):
+    """G^-T A G^-1 + information: the information of `pose` in the filter's chart around prior_pose, from the data's
+    normal equations at that pose (27 doubles as vgicp_stats.normal_eq lays them out: the xi chart) and the prior's."""
+    A = np.zeros((6, 6))
+    rows, cols = np.tril_indices(6)
+    A[rows, cols] = np.asarray(normal_eq, dtype=np.float64)[:21]
+    A = A + np.tril(A, -1).T
+    _, G = pose_prior_chart(prior_pose, pose)
+    G_inv = np.linalg.inv(G)
+    return G_inv.T @ A @ G_inv + np.asarray(information, dtype=np.float64).reshape(6, 6)

@@ -44,6 +44,7 @@ struct AlignFacts {
   int world_size = 1, peer_world = 1, cooldown = 0;
   uint32_t grid = 0;             // workgroups of every persistent launch
   bool robust = false;           // a robust kernel or a gate is set (include/vgicp_hip_robust.h)
+  bool prior = false;            // a pose prior is set (include/vgicp_hip_prior.h): planned exactly as `robust` is
 };
 
 struct AlignPlan {
@@ -58,7 +59,7 @@ struct AlignPlan {
 // team, as many teams as fit the grid vgicp_create verified to be resident; 1 = no team launch.
 inline uint32_t team_width(const AlignFacts& f, uint32_t* team_wgs) {
   *team_wgs = 0;
-  if (f.robust) return 1;   // the robust round has no team kernel
+  if (f.robust || f.prior) return 1;   // the robust round and the pose prior have no team kernel
   const bool one_device = f.world_size == 1 && !f.owner && !f.comm && !f.peers_connected;
   if (!one_device || !f.persistent_enabled || f.stamps || f.n == 0 || !one_point_per_thread(f.n, f.grid)) return 1;
   const uint32_t T = (uint32_t)((f.n + kPointsPerPass - 1) / kPointsPerPass);
@@ -69,11 +70,12 @@ inline uint32_t team_width(const AlignFacts& f, uint32_t* team_wgs) {
 }
 
 inline AlignPlan plan_align(const AlignFacts& f) {
-  if (f.robust) {
-    // The robust round has instantiations of the single-device launch and of the loop only: an upload never takes the
-    // fused launch (it uploads, then plans as a Resident call), a batch is k single aligns.
+  if (f.robust || f.prior) {
+    // The robust round and the pose prior have instantiations of the single-device launch and of the loop only: an
+    // upload never takes the fused launch (it uploads, then plans as a Resident call), a batch is k single aligns.
     AlignFacts g = f;
     g.robust = false;
+    g.prior = false;
     g.no_fused = true;
     g.k = 1;
     return plan_align(g);

@@ -285,6 +285,7 @@ int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* par
   a.prefetch_margin = (a.memo_points == 0 && a.stash_points == 0 && one_point_per_thread(ctx->n, grid)) ? ctx->prefetch_margin : 0.0;
   a.stamps = ctx->d_stamps;
   if (robust_on(ctx)) robust_args(ctx, &a);   // launch_persistent then takes the robust instantiation
+  if (ctx->prior_on) prior_args(ctx, &a);     // ... and the pose prior's
   a.world = multi ? (uint32_t)ctx->peer_world : 1u;
   a.rank = multi ? (uint32_t)ctx->peer_rank : 0u;
   a.mail = ctx->d_mail_table;
@@ -376,6 +377,9 @@ int align_ready(vgicp_ctx* ctx, const vgicp_params* params) {
   if (robust_on(ctx) && (ctx->comm != nullptr || ctx->peers_connected || ctx->owner != nullptr))
     return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the robust round (vgicp_hip_robust.h) is set on this context: it aligns on a "
                 "single device only, not with a communicator or connected peers");
+  if (ctx->prior_on && (ctx->comm != nullptr || ctx->peers_connected || ctx->owner != nullptr))
+    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "a pose prior (vgicp_hip_prior.h) is set on this context: it aligns on a "
+                "single device only, not with a communicator or connected peers");
   return ensure_log(ctx, params->max_iteration);
 }
 
@@ -446,6 +450,7 @@ int align_on_loop(vgicp_ctx* ctx, const double* guess, const vgicp_params* param
   if (large_table(ctx)) VG_RC(ensure_dense(ctx, &usable));
   IterArgs base = base_args(ctx);
   if (robust_on(ctx)) robust_args(ctx, &base);   // launch_iterate then takes the robust instantiation
+  if (ctx->prior_on) prior_args(ctx, &base);     // ... and launch_iterate / launch_close the pose prior's
   const uint32_t grid = iterate_grid(ctx);
   const bool use_comm = ctx->comm != nullptr;
   int total_launches = 0;

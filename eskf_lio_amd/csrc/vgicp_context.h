@@ -27,6 +27,7 @@
 #include "../../include/vgicp_hip_batch.h"
 #include "../../include/vgicp_hip_evaluate.h"
 #include "../../include/vgicp_hip_robust.h"
+#include "../../include/vgicp_hip_prior.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -280,6 +281,11 @@ struct CopyCrew {
 struct vgicp_multi;  // vgicp_multi.hip: the sub-contexts of an in-process multi-device context
 
 struct vgicp_ctx {
+  // FIRST, at offset 0 whatever follows: a mark and this build's sizeof(vgicp_ctx), written by the module that creates the
+  // context.  libvgicp_hip_prior.so writes fields of this struct from outside the module and refuses a context whose
+  // stamp is not its own build's (vgicp_prior.hip), so a pair from two builds is an error and not a corrupted context.
+  static constexpr uint64_t kLayoutMark = 0x7667637000000000ull;   // "vgcp" in the upper half
+  uint64_t layout = kLayoutMark | (uint64_t)sizeof(vgicp_ctx);
   uint64_t id = 0;                // creation number (never 0, never reused)
   int device = -1;
   vgicp_multi* multi = nullptr;   // this handle IS a multi-device context: every entry point forwards to vgicp_multi.hip
@@ -385,6 +391,10 @@ struct vgicp_ctx {
   int robust_kernel = 0;             // VGICP_OPTION_ROBUST_KERNEL
   int robust_scale_micro = 1000000;  // VGICP_OPTION_ROBUST_SCALE_MICRO: c = value / 1e6
   int robust_gate_micro = 0;         // VGICP_OPTION_GATE_MICRO: gate on d^2 = value / 1e6, 0 = none
+  // the pose prior (include/vgicp_hip_prior.h), as vgicp_set_pose_prior left it
+  bool prior_on = false;
+  double prior_pose[12] = {0};       // R0 column-major (9) then t0 (3)
+  double prior_info[21] = {0};       // lower triangle, row by row
   bool reference_order = false;      // VGICP_OPTION_REFERENCE_ORDER: prepared scans come in the reference's unordered_map order
   bool prep_with_deskew = false;
   double prep_voxel = 0.0;           // > 0: the resident scan was down-sampled on the device to one point per voxel of this size
@@ -518,6 +528,13 @@ inline void robust_args(const vgicp_ctx* ctx, Args* a) {
   a->robust_scale2 = c * c;
   a->robust_gate = (double)ctx->robust_gate_micro / 1000000.0;
 }
+// The pose prior as the kernels take it (the fields at the very end of IterArgs / PersistArgs).
+template <typename Args>
+inline void prior_args(const vgicp_ctx* ctx, Args* a) {
+  a->prior_on = 1u;
+  for (int k = 0; k < 12; ++k) a->prior_pose[k] = ctx->prior_pose[k];
+  for (int k = 0; k < 21; ++k) a->prior_info[k] = ctx->prior_info[k];
+}
 inline AlignFacts align_facts(const vgicp_ctx* ctx, const vgicp_params* params, AlignCall call, uint64_t n, size_t k = 1) {
   AlignFacts f = call_facts(call, params ? params->flags : 0u, params ? params->max_iteration : 0);
   f.n = n;
@@ -535,6 +552,7 @@ inline AlignFacts align_facts(const vgicp_ctx* ctx, const vgicp_params* params, 
   f.cooldown = ctx->persistent_cooldown;
   f.grid = ctx->persist_grid;
   f.robust = robust_on(ctx);
+  f.prior = ctx->prior_on;
   return f;
 }
 

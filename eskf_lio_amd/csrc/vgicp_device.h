@@ -93,6 +93,10 @@ struct IterArgs {
   uint32_t robust_kernel;   // VGICP_ROBUST_*
   double robust_scale2;     // c^2
   double robust_gate;       // gate on d^2; 0 = none
+  // the pose prior (include/vgicp_hip_prior.h); all zero = no prior (vgicp_accumulate, a group's loop: always)
+  uint32_t prior_on;
+  double prior_pose[12];    // R0 column-major (9) then t0 (3)
+  double prior_info[21];    // lower triangle of the information matrix, row by row, as normal_eq is laid out
 };
 
 // Arguments of the persistent single-launch align (single GPU): every round of the loop runs inside
@@ -166,6 +170,10 @@ struct PersistArgs {
   uint32_t robust_kernel;
   double robust_scale2;
   double robust_gate;
+  // the pose prior, as IterArgs has it; all zero = no prior (the fused and the team launch: always)
+  uint32_t prior_on;
+  double prior_pose[12];
+  double prior_info[21];
 };
 
 // The fused align (vgicp_align, one point per thread, one device): the persistent launch is enqueued BEFORE the copy

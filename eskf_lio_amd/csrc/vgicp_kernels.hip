@@ -391,7 +391,83 @@ __device__ __forceinline__ RoundHead prologue_fold(const IterArgs& a, PrologueSh
   return head;
 }
 
-template <int BLOCK>
+// The pose prior (include/vgicp_hip_prior.h): what the solver wave adds in front of the solve, one function for
+// prologue_solve and the persistent launch's solver section.  T: the pose the round's sums were taken at; totals (LDS):
+// the round's 27 data sums, which are NOT touched (they go to the log as they are).  Returns (LDS) the sums the round
+// solves with: A + G^T L G in the 21 lower-triangle slots, b + G^T L d in the 6 behind them, d and G being the chart
+// of vgicp_math.h's pose_prior_chart.  All 64 lanes of the wave call it; the lanes share the congruence instead of each
+// running it as straight-line code:
+//   every lane  d and G's lower right block (pose_prior_chart_blocks: uniform, ~150 operations); lane 0 puts d, G and L into LDS
+//   lanes 0-35  one entry of L G each, lanes 36-41 one entry of L d each
+//   lanes 0-20  one entry of the lower triangle of G^T (L G) each, lanes 21-26 one entry of G^T (L d) each
+// with a fixed order of the six products of every entry, so that every workgroup and both launches get the same bits.
+struct PriorShared {
+  double G[36];      // column-major
+  double LG[36];     // column-major
+  double d[6], Ld[6];
+  double info[21];
+  double solve[kSlots];
+};
+template <typename Args>
+__device__ __forceinline__ const double* prior_solve_totals(const Args& a, const Pose& T, const double* totals,
+                                                            uint32_t lane) {
+  __shared__ PriorShared ps;
+  Pose T0;
+  load_pose(a.prior_pose, T0);
+  double d[6], M[9];
+  pose_prior_chart_blocks(T0, T, d, M);
+  // G = [I, -[t]x; 0, M]: the zeros from 36 lanes, what is not zero from lane 0 (the same wave: LDS is in order within
+  // it), laid out by the function the host's chart uses
+  if (lane < 36) ps.G[lane] = 0.0;
+  if (lane == 0) {
+    pose_prior_chart_nonzero(T.t, M, ps.G);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ps.d[k] = d[k];
+  }
+  if (lane < 21) ps.info[lane] = a.prior_info[lane];   // one entry per lane, read from the dispatch packet's memory
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (lane < 42) {
+    const bool mat = lane < 36;
+    const uint32_t i = mat ? lane % 6u : lane - 36u, j = mat ? lane / 6u : 0u;   // entry (i, j) of L G, entry i of L d
+    const double* col = mat ? ps.G + 6u * j : ps.d;
+    double sum = 0.0;
+#pragma unroll
+    for (uint32_t k = 0; k < 6; ++k) {
+      const uint32_t hi = i > k ? i : k, lo = i > k ? k : i;
+      sum += ps.info[hi * (hi + 1u) / 2u + lo] * col[k];
+    }
+    if (mat) ps.LG[lane] = sum;
+    else ps.Ld[i] = sum;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (lane < kSlots) {
+    double sum = totals[lane];
+    if (lane < (uint32_t)kNormalEq) {
+      const bool mat = lane < 21u;
+      // lane = tri6(i, j): the row is the largest i with i (i + 1) / 2 <= lane
+      const uint32_t i = !mat ? lane - 21u : lane >= 15u ? 5u : lane >= 10u ? 4u : lane >= 6u ? 3u : lane >= 3u ? 2u : lane >= 1u ? 1u : 0u;
+      const uint32_t j = mat ? lane - i * (i + 1u) / 2u : 0u;
+      const double* left = ps.G + 6u * i;                   // column i of G = row i of G^T
+      const double* right = mat ? ps.LG + 6u * j : ps.Ld;
+      double add = 0.0;
+#pragma unroll
+      for (uint32_t k = 0; k < 6; ++k) add += left[k] * right[k];
+      sum += add;
+    }
+    ps.solve[lane] = sum;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return ps.solve;
+}
+
+// PRIOR: the round solves with the prior's terms on top of the data sums (prior_solve_totals); the log keeps the data sums.
+template <int BLOCK, bool PRIOR = false>
 __device__ __forceinline__ void prologue_solve(const IterArgs& a, PrologueShared<BLOCK>& sh,
                                                const Pose& old_total, uint32_t lane, int it,
                                                int max_it, double cos_thr, double tsq_thr) {
@@ -408,12 +484,14 @@ __device__ __forceinline__ void prologue_solve(const IterArgs& a, PrologueShared
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const double* solve = sh.totals;
+  if constexpr (PRIOR) solve = prior_solve_totals(a, old_total, sh.totals, lane);
   double A[21], g[6], xi[6];
 #pragma unroll
-  for (int k = 0; k < 21; ++k) A[k] = sh.totals[k];
+  for (int k = 0; k < 21; ++k) A[k] = solve[k];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) g[k] = -sh.totals[21 + k];
-  if (!ldlt6_solve_spd(A, g, xi)) ldlt6_solve_pivoted(sh.totals, sh.work, lane, xi);  // uniform branch
+  for (int k = 0; k < 6; ++k) g[k] = -solve[21 + k];
+  if (!ldlt6_solve_spd(A, g, xi)) ldlt6_solve_pivoted(solve, sh.work, lane, xi);  // uniform branch
   Pose step, next;
   se3_exp_device(xi, step);
   pose_compose(step, old_total, next);
@@ -611,7 +689,8 @@ constexpr uint32_t kMemoNone = 0xFFFFFFFEu;  // nothing looked up
 // beyond the caches' reach.  The arithmetic per match is unchanged, so the loop still returns the persistent launch's bits.
 // ROBUST: the weighted round of include/vgicp_hip_robust.h — an instantiation of its own, so that the plain one keeps its
 // code; nothing but accumulate_match's contribution differs.
-template <int BLOCK, bool ROBUST = false>
+// PRIOR: the pose prior of include/vgicp_hip_prior.h — instantiations of their own again; nothing but the solve differs.
+template <int BLOCK, bool ROBUST = false, bool PRIOR = false>
 __global__ __launch_bounds__(BLOCK) void iterate_kernel(IterArgs a) {
   constexpr int kWaves = BLOCK / 64;
   constexpr int kWorkers = BLOCK - 64;
@@ -659,7 +738,7 @@ __global__ __launch_bounds__(BLOCK) void iterate_kernel(IterArgs a) {
       have_payload = true;
     }
   } else if (solving) {
-    prologue_solve<BLOCK>(a, sh, head.total, lane, it, max_it, cos_thr, tsq_thr);
+    prologue_solve<BLOCK, PRIOR>(a, sh, head.total, lane, it, max_it, cos_thr, tsq_thr);
     if (a.stamps && blockIdx.x == 0 && tid == 0)
       atomicAdd((unsigned long long*)&a.stamps[6], (unsigned long long)(wall_clock64() - t_fold));
   }
@@ -752,7 +831,7 @@ __global__ __launch_bounds__(BLOCK) void iterate_kernel(IterArgs a) {
 
 // The launch after the last round: prologue only (fold the last rows, solve, publish the final
 // state), one workgroup.  A kernel of its own so per-kernel profiles of iterate_kernel hold rounds only.
-template <int BLOCK>
+template <int BLOCK, bool PRIOR = false>
 __global__ __launch_bounds__(BLOCK) void close_kernel(IterArgs a) {
   __shared__ PrologueShared<BLOCK> sh;
   int it, max_it;
@@ -760,7 +839,7 @@ __global__ __launch_bounds__(BLOCK) void close_kernel(IterArgs a) {
   const RoundHead head = prologue_fold<BLOCK>(a, sh, it, max_it, cos_thr, tsq_thr);
   if (head.stop || a.prev_rows == 0) return;
   __syncthreads();
-  if (threadIdx.x < 64) prologue_solve<BLOCK>(a, sh, head.total, threadIdx.x, it, max_it, cos_thr, tsq_thr);
+  if (threadIdx.x < 64) prologue_solve<BLOCK, PRIOR>(a, sh, head.total, threadIdx.x, it, max_it, cos_thr, tsq_thr);
 }
 
 // Scoring poses of the resident scan (vgicp_evaluate_resident, include/vgicp_hip_evaluate.h): what round 0 of the loop
@@ -1150,9 +1229,13 @@ struct TeamView {
 };
 // ROBUST: the weighted round (include/vgicp_hip_robust.h), single device, !STAMPS, !FUSED, !TEAM: accumulate_match's
 // contribution takes the weight, everything else is the plain body's.
-template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool FUSED = false, bool TEAM = false, bool ROBUST = false>
+// PRIOR: the pose prior (include/vgicp_hip_prior.h), the robust round's scope: the solver section solves with
+// prior_solve_totals' sums, everything else is the plain (or the robust) body's.
+template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool FUSED = false, bool TEAM = false, bool ROBUST = false,
+          bool PRIOR = false>
 __device__ __forceinline__ void persistent_body(const PersistArgs& a, const FusedUpload& up, const TeamView& tv = TeamView()) {
   static_assert(!ROBUST || (!MULTI && !STAMPS && !FUSED && !TEAM), "the robust round runs the single-device bodies only");
+  static_assert(!PRIOR || (!MULTI && !STAMPS && !FUSED && !TEAM), "the pose prior runs the single-device bodies only");
   static_assert(!FUSED || (!MULTI && !STAMPS && !MANY), "the fused upload serves the single-device one-point-per-thread body");
   static_assert(!TEAM || (!MULTI && !STAMPS && !MANY && !FUSED), "teams run the single-device one-point-per-thread body");
   static_assert(BLOCK / kSlots == kFolders, "the exchange reproduces the fold order of iterate_kernel<512>");
@@ -1474,14 +1557,16 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const double* solve = totals;   // PRIOR: the log's row (behind the barrier below) stays the data sums
+        if constexpr (PRIOR) solve = prior_solve_totals(a, total, totals, lane);
         double A[21], g[6], xi[6];
 #pragma unroll
-        for (int k = 0; k < 21; ++k) A[k] = totals[k];
+        for (int k = 0; k < 21; ++k) A[k] = solve[k];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) g[k] = -totals[21 + k];
+        for (int k = 0; k < 6; ++k) g[k] = -solve[21 + k];
         uint64_t f0 = 0, f1 = 0, f2 = 0;
         if (STAMPS) { f0 = pinned_clock(A); fine[0] += f0 - t_mark; }
-        if (!ldlt6_solve_spd(A, g, xi)) ldlt6_solve_pivoted(totals, work, lane, xi);  // uniform branch
+        if (!ldlt6_solve_spd(A, g, xi)) ldlt6_solve_pivoted(solve, work, lane, xi);  // uniform branch
         if (STAMPS) { f1 = pinned_clock(xi); fine[1] += f1 - f0; }
         Pose next, step;
         se3_exp_device(xi, step);
@@ -1596,17 +1681,17 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
 // after all, the workgroups run the one-point-per-thread body — the mapping, the sums and hence the bits of the launch
 // that a settled scan of that size gets (without the neighbour prefetch, which changes no result) — so the chain that
 // does not wait returns the bits of the one that does, whatever the sweep's raw size.
-template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false>
+template <int BLOCK, bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false, bool PRIOR = false>
 __global__ __launch_bounds__(BLOCK) void persistent_kernel(PersistArgs a) {
   const FusedUpload none{};
   if constexpr (MANY) {
     const uint32_t n_pts = a.n_dev ? (*a.n_dev < a.n ? *a.n_dev : a.n) : a.n;  // uniform
     if (n_pts <= gridDim.x * (uint32_t)(BLOCK - 64)) {
-      persistent_body<BLOCK, MULTI, STAMPS, false, false, false, ROBUST>(a, none);
+      persistent_body<BLOCK, MULTI, STAMPS, false, false, false, ROBUST, PRIOR>(a, none);
       return;
     }
   }
-  persistent_body<BLOCK, MULTI, STAMPS, MANY, false, false, ROBUST>(a, none);
+  persistent_body<BLOCK, MULTI, STAMPS, MANY, false, false, ROBUST, PRIOR>(a, none);
 }
 
 // The fused align: the upload's packing happens inside round 0 (a separate kernel, so that the production
@@ -2080,7 +2165,24 @@ inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((w
 
 }  // namespace
 
+namespace {
+template <bool ROBUST>
+hipError_t launch_iterate_prior(hipStream_t s, const IterArgs& args, uint32_t grid, int block) {
+  switch (block) {
+    case 256: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<256, ROBUST, true>), dim3(grid), dim3(256), 0, s, args); break;
+    case 512: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<512, ROBUST, true>), dim3(grid), dim3(512), 0, s, args); break;
+    case 1024: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<1024, ROBUST, true>), dim3(grid), dim3(1024), 0, s, args); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+}  // namespace
+
 hipError_t launch_iterate(hipStream_t s, const IterArgs& args, uint32_t grid, int block) {
+  if (args.prior_on != 0) {   // the pose prior: instantiations of their own, with and without the weights
+    return (args.robust_kernel != 0 || args.robust_gate > 0.0) ? launch_iterate_prior<true>(s, args, grid, block)
+                                                               : launch_iterate_prior<false>(s, args, grid, block);
+  }
   if (args.robust_kernel != 0 || args.robust_gate > 0.0) {   // the weighted round: instantiations of their own
     switch (block) {
       case 256: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<256, true>), dim3(grid), dim3(256), 0, s, args); break;
@@ -2157,15 +2259,15 @@ void persistent_exchange_image(uint32_t grid, unsigned long long* rows_words, un
 }
 
 namespace {
-template <bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false>
+template <bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false, bool PRIOR = false>
 hipError_t launch_persistent_as(hipStream_t s, const PersistArgs& args, uint32_t grid, size_t dyn, int device) {
   (void)device;
-  ++g_kernel_launches; hipLaunchKernelGGL((persistent_kernel<512, MULTI, STAMPS, MANY, ROBUST>), dim3(grid), dim3(512), dyn, s, args);
+  ++g_kernel_launches; hipLaunchKernelGGL((persistent_kernel<512, MULTI, STAMPS, MANY, ROBUST, PRIOR>), dim3(grid), dim3(512), dyn, s, args);
   return hipGetLastError();
 }
-template <bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false>
+template <bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false, bool PRIOR = false>
 hipError_t raise_lds_limit() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&persistent_kernel<512, MULTI, STAMPS, MANY, ROBUST>),
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&persistent_kernel<512, MULTI, STAMPS, MANY, ROBUST, PRIOR>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
 }
 }  // namespace
@@ -2187,6 +2289,10 @@ hipError_t persistent_prepare_device() {
   if (e == hipSuccess) e = raise_lds_limit<true, true, true>();
   if (e == hipSuccess) e = raise_lds_limit<false, false, false, true>();   // the robust round: single device, no stamps
   if (e == hipSuccess) e = raise_lds_limit<false, false, true, true>();
+  if (e == hipSuccess) e = raise_lds_limit<false, false, false, false, true>();  // the pose prior: likewise, plain and robust
+  if (e == hipSuccess) e = raise_lds_limit<false, false, true, false, true>();
+  if (e == hipSuccess) e = raise_lds_limit<false, false, false, true, true>();
+  if (e == hipSuccess) e = raise_lds_limit<false, false, true, true, true>();
   return e;
 }
 
@@ -2203,6 +2309,14 @@ hipError_t launch_persistent(hipStream_t s, const PersistArgs& args, uint32_t gr
   if (dyn > kPersistDynLds) return hipErrorInvalidValue;
   const bool multi = args.world > 1, stamps = args.stamps != nullptr;
   const bool many = (uint64_t)args.n > (uint64_t)grid * kPersistWorkers;
+  if (args.prior_on != 0) {   // the pose prior: one device, no stamps, with and without the weights
+    if (multi) return hipErrorInvalidValue;
+    if (args.robust_kernel != 0 || args.robust_gate > 0.0)
+      return many ? launch_persistent_as<false, false, true, true, true>(s, args, grid, dyn, device)
+                  : launch_persistent_as<false, false, false, true, true>(s, args, grid, dyn, device);
+    return many ? launch_persistent_as<false, false, true, false, true>(s, args, grid, dyn, device)
+                : launch_persistent_as<false, false, false, false, true>(s, args, grid, dyn, device);
+  }
   if (args.robust_kernel != 0 || args.robust_gate > 0.0) {   // the weighted round: one device, no stamps
     if (multi) return hipErrorInvalidValue;
     return many ? launch_persistent_as<false, false, true, true>(s, args, grid, dyn, device)
@@ -2246,9 +2360,11 @@ hipError_t launch_persistent_teams(hipStream_t s, const PersistArgs& args, const
 // Whether `grid` 512-thread workgroups of the persistent kernel with this much dynamic LDS can all be
 // resident at once on the current device (the in-kernel exchange requires it).
 hipError_t persistent_max_resident(uint32_t dyn_lds_bytes, int cu_count, uint32_t* max_grid) {
-  // the plain kernel with the most registers, and the robust round's (a body of its own: asked on its own)
-  const void* fns[2] = {reinterpret_cast<const void*>(&persistent_kernel<512, true, false, true>),
-                        reinterpret_cast<const void*>(&persistent_kernel<512, false, false, true, true>)};
+  // the plain kernel with the most registers, the robust round's and the pose prior's (bodies of their own: asked on
+  // their own)
+  const void* fns[3] = {reinterpret_cast<const void*>(&persistent_kernel<512, true, false, true>),
+                        reinterpret_cast<const void*>(&persistent_kernel<512, false, false, true, true>),
+                        reinterpret_cast<const void*>(&persistent_kernel<512, false, false, true, true, true>)};
   *max_grid = (uint32_t)cu_count;  // one workgroup per CU is what the design uses
   for (const void* fn : fns) {
     int per_cu = 0;
@@ -2265,6 +2381,15 @@ hipError_t persistent_max_resident(uint32_t dyn_lds_bytes, int cu_count, uint32_
 // The closing launch folds the last round's rows with the workgroup size of the body launches, so that
 // its sums are added in the same order as every other round's (and as the persistent launch adds them).
 hipError_t launch_close(hipStream_t s, const IterArgs& args, int block) {
+  if (args.prior_on != 0) {   // the last round's solve takes the pose prior as every other round's does
+    switch (block) {
+      case 256: ++g_kernel_launches; hipLaunchKernelGGL((close_kernel<256, true>), dim3(1), dim3(256), 0, s, args); break;
+      case 512: ++g_kernel_launches; hipLaunchKernelGGL((close_kernel<512, true>), dim3(1), dim3(512), 0, s, args); break;
+      case 1024: ++g_kernel_launches; hipLaunchKernelGGL((close_kernel<1024, true>), dim3(1), dim3(1024), 0, s, args); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (block) {
     case 256: ++g_kernel_launches; hipLaunchKernelGGL(close_kernel<256>, dim3(1), dim3(256), 0, s, args); break;
     case 512: ++g_kernel_launches; hipLaunchKernelGGL(close_kernel<512>, dim3(1), dim3(512), 0, s, args); break;

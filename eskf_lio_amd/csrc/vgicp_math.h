@@ -242,4 +242,153 @@ VG_HD bool converged(const Pose& step, double cosine_threshold, double translati
   return true;
 }
 
+// ---- the pose prior's chart (include/vgicp_hip_prior.h): one source for the kernels and vgicp_pose_prior_chart ----
+//
+// No library call but sqrt: the angle comes from half-angle steps and a Taylor series of this file's own.  On the device
+// every constant of a series goes through vg_const, which makes the compiler form it where it is used (a scalar register
+// pair): left alone, it hoists the constants of every polynomial out of the round loop into vector registers that live
+// through the whole persistent launch — the library's atan2, sin and cos brought 58 of them, all spilled to scratch.
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ double vg_const(double k) {
+  asm volatile("" : "+s"(k));
+  return k;
+}
+#else
+inline double vg_const(double k) { return k; }
+#endif
+
+// atan(u) for 0 <= u <= 1: two half-angle steps atan(u) = 2 atan(u / (1 + sqrt(1 + u^2))) bring the argument below
+// tan(pi/16) < 0.2, where the Taylor series sum (-1)^k w^(2k+1) / (2k + 1), k = 0 .. 12, is truncated below 1e-19.
+VG_HD double atan_unit(double u) {
+  const double w1 = u / (1.0 + sqrt(1.0 + u * u));
+  const double w = w1 / (1.0 + sqrt(1.0 + w1 * w1));
+  const double z = w * w;
+  double p = vg_const(1.0 / 25.0);
+  p = p * z - vg_const(1.0 / 23.0);
+  p = p * z + vg_const(1.0 / 21.0);
+  p = p * z - vg_const(1.0 / 19.0);
+  p = p * z + vg_const(1.0 / 17.0);
+  p = p * z - vg_const(1.0 / 15.0);
+  p = p * z + vg_const(1.0 / 13.0);
+  p = p * z - vg_const(1.0 / 11.0);
+  p = p * z + vg_const(1.0 / 9.0);
+  p = p * z - vg_const(1.0 / 7.0);
+  p = p * z + vg_const(1.0 / 5.0);
+  p = p * z - vg_const(1.0 / 3.0);
+  p = p * z + 1.0;
+  return 4.0 * (w * p);
+}
+
+// c(theta) of Jr^-1(phi) = I + 1/2 [phi]x + c [phi]x^2:
+//   c = 1/theta^2 - (1 + cos theta) / (2 theta sin theta) = (1 - (theta/2) cot(theta/2)) / theta^2
+// (the second form has no pole at theta = pi; cot_half comes from so3_log, which has sine and cosine at hand).  Up to
+// theta^2 = 0.25 — where se3_exp_device leaves its own series — the power series sum |B_2k| theta^(2k-2) / (2k)!,
+// k = 1 .. 8, in Horner form: the terms fall by theta^2 / (4 pi^2) each, so the truncation is below 1e-17 relative at the
+// switch-over, and the limit 1/12 is the value at 0.
+constexpr double kJrSeriesMax2 = 0.25;
+VG_HD double so3_jr_inv_coeff(double theta, double cot_half) {
+  const double n2 = theta * theta;
+  if (n2 > kJrSeriesMax2) return (1.0 - 0.5 * theta * cot_half) / n2;
+  double c = vg_const(3617.0 / 10670622842880000.0);
+  c = c * n2 + vg_const(1.0 / 74724249600.0);
+  c = c * n2 + vg_const(691.0 / 1307674368000.0);
+  c = c * n2 + vg_const(1.0 / 47900160.0);
+  c = c * n2 + vg_const(1.0 / 1209600.0);
+  c = c * n2 + vg_const(1.0 / 30240.0);
+  c = c * n2 + vg_const(1.0 / 720.0);
+  c = c * n2 + vg_const(1.0 / 12.0);
+  return c;
+}
+
+// Jr^-1(phi), column-major 3x3, theta = |phi| and cot(theta/2) as so3_log returns them: [phi]x^2 = phi phi^T - |phi|^2 I.
+VG_HD void so3_jr_inv(const double* phi, double theta, double cot_half, double* J) {
+  const double n2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
+  const double c = so3_jr_inv_coeff(theta, cot_half);
+  const double dg = 1.0 - c * n2;
+  J[0] = dg + c * phi[0] * phi[0]; J[4] = dg + c * phi[1] * phi[1]; J[8] = dg + c * phi[2] * phi[2];
+  const double xy = c * phi[0] * phi[1], xz = c * phi[0] * phi[2], yz = c * phi[1] * phi[2];
+  J[3] = xy - 0.5 * phi[2]; J[1] = xy + 0.5 * phi[2];
+  J[6] = xz + 0.5 * phi[1]; J[2] = xz - 0.5 * phi[1];
+  J[7] = yz - 0.5 * phi[0]; J[5] = yz + 0.5 * phi[0];
+}
+
+// The axis of a rotation M by an angle near pi from the symmetric part (M + M^T) / 2 = cos I + (1 - cos) a a^T: entry K
+// of a from the diagonal (the caller picks the largest), the two others from column K; the sign from v = sin(theta) a.
+template <int K>
+VG_HD void so3_log_near_pi(const double* M, double cosine, double theta, const double* v, double* phi) {
+  constexpr int I = (K + 1) % 3, J = (K + 2) % 3;
+  const double one_c = 1.0 - cosine;
+  const double ak2 = (M[K + 3 * K] - cosine) / one_c;
+  const double ak = sqrt(ak2 > 0.0 ? ak2 : 0.0);
+  double a[3];
+  a[K] = ak;
+  a[I] = 0.5 * (M[I + 3 * K] + M[K + 3 * I]) / (one_c * ak);
+  a[J] = 0.5 * (M[J + 3 * K] + M[K + 3 * J]) / (one_c * ak);
+  const double sign = (v[0] * a[0] + v[1] * a[1] + v[2] * a[2] < 0.0) ? -theta : theta;
+  phi[0] = sign * a[0]; phi[1] = sign * a[1]; phi[2] = sign * a[2];
+}
+
+// Log of a rotation matrix (column-major) as a rotation vector, |phi| <= pi; returns theta and leaves cot(theta/2) in
+// *cot_half (meaningless at theta = 0, where so3_jr_inv_coeff does not read it).  v = vee(M - M^T) / 2 = sin(theta) axis,
+// cosine = (trace - 1) / 2, theta = atan2(|v|, cosine) through tan(theta/2) = s / (r + c) on the cosine's side and
+// tan((pi - theta)/2) = s / (r - c) on the other, r = sqrt(s^2 + c^2): the argument of atan_unit is at most 1 either way.
+// phi = v theta / |v| away from pi, the symmetric part's axis close to it.
+VG_HD double so3_log(const double* M, double* phi, double* cot_half) {
+  const double v[3] = {0.5 * (M[5] - M[7]), 0.5 * (M[6] - M[2]), 0.5 * (M[1] - M[3])};
+  const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+  const double s = sqrt(s2);
+  const double cosine = 0.5 * (M[0] + M[4] + M[8] - 1.0);
+  const double r = sqrt(s2 + cosine * cosine);
+  const bool front = cosine >= 0.0;
+  const double u = s / (front ? r + cosine : r - cosine);
+  const double half = 2.0 * atan_unit(u);
+  const double theta = front ? half : vg_const(3.14159265358979323846) - half;
+  *cot_half = front ? 1.0 / u : u;
+  if (cosine > -0.9) {
+    const double f = s > 1.0e-150 ? theta / s : 1.0;
+    phi[0] = f * v[0]; phi[1] = f * v[1]; phi[2] = f * v[2];
+    return theta;
+  }
+  if (M[0] >= M[4] && M[0] >= M[8]) so3_log_near_pi<0>(M, cosine, theta, v, phi);
+  else if (M[4] >= M[8]) so3_log_near_pi<1>(M, cosine, theta, v, phi);
+  else so3_log_near_pi<2>(M, cosine, theta, v, phi);
+  return theta;
+}
+
+// The chart of the pose prior at pose T against the prior pose T0 (the ESKF's residual, reference
+// src/ErrorStateKF.cpp:132-135): d = [t - t0; Log(R0^T R)] and its Jacobian with respect to the round's increment
+// xi = (v, omega), T <- se3ToSE3(xi) T:  G = [I, -[t]x; 0, Jr^-1(phi) R^T].  M: the lower right 3x3 block, column-major.
+VG_HD void pose_prior_chart_blocks(const Pose& T0, const Pose& T, double* d, double* M) {
+  double R0tR[9], Rt[9], Jri[9];
+  for (int c = 0; c < 3; ++c)
+    for (int r = 0; r < 3; ++r) {
+      R0tR[r + 3 * c] = T0.R[3 * r] * T.R[3 * c] + T0.R[3 * r + 1] * T.R[3 * c + 1] + T0.R[3 * r + 2] * T.R[3 * c + 2];
+      Rt[r + 3 * c] = T.R[c + 3 * r];
+    }
+  for (int k = 0; k < 3; ++k) d[k] = T.t[k] - T0.t[k];
+  double cot_half;
+  const double theta = so3_log(R0tR, d + 3, &cot_half);
+  so3_jr_inv(d + 3, theta, cot_half, Jri);
+  mat3_mul(Jri, Rt, M);
+}
+// ... and G whole, column-major 6x6 (G[r + 6 c]).  pose_prior_chart_nonzero is the ONE place that lays G out, for the
+// host's chart and for the solver wave of the kernels: the 18 entries that are not zero, from the pose's translation and
+// M, into a G whose entries are zero already (the kernels zero it from 36 lanes and call this from one, with a pointer
+// into LDS; storing all 36 from that lane costs the persistent launch scratch).
+VG_HD void pose_prior_chart_nonzero(const double* t, const double* M, double* G) {
+  G[0] = 1.0; G[7] = 1.0; G[14] = 1.0;
+  // -[t]x in rows 0-2, columns 3-5
+  G[1 + 6 * 3] = -t[2]; G[2 + 6 * 3] = t[1];
+  G[0 + 6 * 4] = t[2];  G[2 + 6 * 4] = -t[0];
+  G[0 + 6 * 5] = -t[1]; G[1 + 6 * 5] = t[0];
+  for (int c = 0; c < 3; ++c)
+    for (int r = 0; r < 3; ++r) G[(3 + r) + 6 * (3 + c)] = M[r + 3 * c];
+}
+VG_HD void pose_prior_chart(const Pose& T0, const Pose& T, double* d, double* G) {
+  double M[9];
+  pose_prior_chart_blocks(T0, T, d, M);
+  for (int k = 0; k < 36; ++k) G[k] = 0.0;
+  pose_prior_chart_nonzero(T.t, M, G);
+}
+
 }  // namespace vgicp

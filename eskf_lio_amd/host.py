@@ -62,6 +62,8 @@ def load_library() -> C.CDLL:
     lib.host_icp_create_robust.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, C.c_char_p, C.c_double, C.c_double]
     lib.host_icp_set_robust.argtypes = [vp, C.c_int, C.c_double, C.c_double, dp]
     lib.host_icp_hypotheses_per_launch.argtypes = [vp]
+    lib.host_icp_align_with_prior.argtypes = [vp, sz, dp, dp, vp, dp, dp, dp, dp, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.host_icp_destroy.argtypes = [vp]
     lib.host_icp_align.argtypes = [vp, sz, dp, dp, vp, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_uint64), sz]
@@ -249,6 +251,26 @@ class ICP:
         self.correspondence_counts = counts[:it.value].copy()
         return capi.pose_from_abi(out)
 
+    def alignWithPrior(self, points, covs, localMap: LocalMap, guess, information) -> np.ndarray:
+        """ICP::alignWithPrior (vgicp_hip_prior.h): the MAP pose of the cloud given the pose `guess` with the 6 x 6
+        `information` in the filter's chart; posteriorInformation() then has the returned pose's information."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        cvs = np.ascontiguousarray(covs, dtype=np.float64).reshape(-1, 9)
+        g = capi.pose_to_abi(guess)
+        info = np.ascontiguousarray(np.asarray(information, dtype=np.float64).reshape(6, 6).T).reshape(36)
+        out, post = np.zeros(16), np.zeros(36)
+        it, conv, left = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(self._lib, self._lib.host_icp_align_with_prior(self._h, pts.shape[0], _dp(pts), _dp(cvs), localMap._h,
+                                                              _dp(g), _dp(info), _dp(out), _dp(post), C.byref(it),
+                                                              C.byref(conv), C.byref(left)))
+        self.iterations, self.converged = it.value, bool(conv.value)
+        self.prior_left_behind = bool(left.value)
+        self._posterior = post.reshape(6, 6).T.copy()
+        return capi.pose_from_abi(out)
+
+    def posteriorInformation(self) -> np.ndarray:
+        """ICP::posteriorInformation of the last alignWithPrior: G^-T A G^-1 + information, 6 x 6."""
+        return self._posterior.copy()
 
     def alignHypotheses(self, points, covs, localMap: LocalMap, guesses):
         """ICP::alignHypotheses on a cloud made from the arrays (one upload) -> [dict(pose, converged, iterations,

@@ -248,6 +248,28 @@ int host_icp_align(
     });
 }
 
+// icp->alignWithPrior(cloud, localMap, guess, information) (information: column-major 6 x 6), then
+// icp->posteriorInformation() into out_posterior (column-major 6 x 6); *has_prior: icp->hasPrior() afterwards.
+int host_icp_align_with_prior(
+  ICP * icp, size_t n, const double * points, const double * covs, const LocalMap * map,
+  const double guess[16], const double information[36], double out_pose[16], double out_posterior[36],
+  int32_t * iterations, int32_t * converged, int32_t * has_prior)
+{
+  return guarded(
+    [&] {
+      const PointCloud cloud = makeCloud(n, points, covs);
+      ESKF_LIO::Matrix6d info = ESKF_LIO::Matrix6d::Zero();
+      for (int k = 0; k < 36; ++k) {info.data()[k] = information[k];}
+      const Isometry3d T = icp->alignWithPrior(cloud, *map, ESKF_LIO::shim::poseFromData(guess), info);
+      std::memcpy(out_pose, ESKF_LIO::shim::poseData(T), 16 * sizeof(double));
+      const ESKF_LIO::Matrix6d post = icp->posteriorInformation();
+      for (int k = 0; k < 36; ++k) {out_posterior[k] = post.data()[k];}
+      if (iterations) {*iterations = icp->lastStats().iterations;}
+      if (converged) {*converged = icp->lastStats().converged ? 1 : 0;}
+      if (has_prior) {*has_prior = icp->hasPrior() ? 1 : 0;}
+    });
+}
+
 // icp->alignHypotheses(cloud, localMap, guesses) / icp->alignBest(...) on a cloud built from the arrays (not resident:
 // one upload).  out_poses k x 16, iterations / converged / final_corr k entries (each optional); with best != NULL the
 // call is alignBest: *best receives the chosen index and best_pose its pose.

@@ -401,7 +401,9 @@ DEFAULT_CONFIG = {                                          # config/hilti_confi
 class ErrorStateKF:
     """src/ErrorStateKF.cpp, include/ESKF_LIO/ErrorStateKF.hpp:15-53; `align` is ICP::align bound to a map."""
 
-    def __init__(self, config: dict, align):
+    def __init__(self, config: dict, align, align_with_prior=None):
+        """align_with_prior(points, covs, guess, information 6x6) -> (pose, posterior information 6x6 in the filter's
+        chart): needed only with kalman_filter.update.iterated (default off: the reference's update)."""
         imu = config["imu"]
         G = 9.81
         rate = float(imu["update_rate"])
@@ -432,6 +434,12 @@ class ErrorStateKF:
         self.G_ = np.eye(18)
         self.F_x_ = np.eye(18)
         self.align_ = align
+        # the YAML key kalman_filter.update.iterated (config["kalman_filter"] IS the file's `update` block); absent = off
+        self.iterated_ = bool(kf.get("iterated", False))
+        self.align_with_prior_ = align_with_prior
+        if self.iterated_ and align_with_prior is None:
+            raise ValueError("kalman_filter.update.iterated needs a backend with align_with_prior")
+        self.last_correction = None                         # (err 18, P+ 18x18 before the reset) of the last update
 
     def getStates(self):
         return self.states_
@@ -486,14 +494,32 @@ class ErrorStateKF:
         new = prev.copy()
         new.timestamp = end
         guess = prev.pose()
-        observation = self.align_(lidar.points, lidar.covariances, guess)
-        residual = np.zeros(6)
-        residual[:3] = observation[:3, 3] - guess[:3, 3]
-        residual[3:] = rotation_matrix_to_vector(guess[:3, :3].T @ observation[:3, :3])
-        S = self.H_ @ prev.P @ self.H_.T + self.V_
-        K = prev.P @ self.H_.T @ np.linalg.inv(S)
-        err = K @ residual
-        new.P = (np.eye(18) - K @ self.H_) @ prev.P
+        if self.iterated_:
+            # The iterated update (include/vgicp_hip_prior.h): the pose block of P enters every round of the align as the
+            # prior's information S^-1, S = H P H^T, so the returned pose T* is the MAP estimate.  With z* = d(T*) and
+            # Sigma the posterior covariance of the pose (the inverse of the data's information at T* in the filter's
+            # chart plus S^-1):  dx = P H^T S^-1 z*,  P+ = P - P H^T S^-1 (S - Sigma) S^-1 H P.  For a linear observation
+            # this is the Kalman update with V = the inverse of the data's information; the constant V_ plays no part.
+            S = self.H_ @ prev.P @ self.H_.T
+            S_inv = np.linalg.inv(S)
+            observation, posterior = self.align_with_prior_(lidar.points, lidar.covariances, guess, 0.5 * (S_inv + S_inv.T))
+            Sigma = np.linalg.inv(posterior)
+            residual = np.zeros(6)
+            residual[:3] = observation[:3, 3] - guess[:3, 3]
+            residual[3:] = rotation_matrix_to_vector(guess[:3, :3].T @ observation[:3, :3])
+            PHt = prev.P @ self.H_.T
+            err = PHt @ (S_inv @ residual)
+            new.P = prev.P - PHt @ S_inv @ (S - Sigma) @ S_inv @ PHt.T
+        else:
+            observation = self.align_(lidar.points, lidar.covariances, guess)
+            residual = np.zeros(6)
+            residual[:3] = observation[:3, 3] - guess[:3, 3]
+            residual[3:] = rotation_matrix_to_vector(guess[:3, :3].T @ observation[:3, :3])
+            S = self.H_ @ prev.P @ self.H_.T + self.V_
+            K = prev.P @ self.H_.T @ np.linalg.inv(S)
+            err = K @ residual
+            new.P = (np.eye(18) - K @ self.H_) @ prev.P
+        self.last_correction = (err.copy(), new.P.copy())
         # injectError (:166-174)
         new.position = new.position + err[0:3]
         new.velocity = new.velocity + err[3:6]
@@ -541,7 +567,7 @@ class Odometry:
 
     def __init__(self, config: dict, backend):
         self.backend = backend
-        self.filter = ErrorStateKF(config, backend.align)
+        self.filter = ErrorStateKF(config, backend.align, getattr(backend, "align_with_prior", None))
         self.initialized = False
         self.pending: List[LidarMeasurement] = []
         self.lidar: Optional[LidarMeasurement] = None
@@ -629,6 +655,7 @@ class GpuBackend:
                             gate=float(reg.get("gate", 0.0)))
         self.pre = host.CloudPreprocessor(config["cloud_preprocessor"]["voxel_size"], config["lidar_extrinsic"])
         self.iterations: List[int] = []
+        self.converged: List[bool] = []                     # of the aligns with a prior
 
     def preprocess(self, states, points, pointTime):
         if states is None:
@@ -639,6 +666,13 @@ class GpuBackend:
         T = self.icp.align(points, covs, self.map, guess)
         self.iterations.append(self.icp.iterations)
         return T
+
+    def align_with_prior(self, points, covs, guess, information):
+        """ICP::alignWithPrior + ICP::posteriorInformation (kalman_filter.update.iterated)."""
+        T = self.icp.alignWithPrior(points, covs, self.map, guess, information)
+        self.iterations.append(self.icp.iterations)
+        self.converged.append(self.icp.converged)
+        return T, self.icp.posteriorInformation()
 
     def update_map(self, points, covs, transform, initialize):
         self.map.updateLocalMap(points, covs, transform, initialize)
@@ -674,6 +708,7 @@ class DeviceBackend:
         self.voxel = config["cloud_preprocessor"]["voxel_size"]
         self.T_il = np.asarray(config["lidar_extrinsic"], dtype=np.float64)
         self.iterations: List[int] = []
+        self.converged: List[bool] = []                     # of the aligns with a prior
         self.kept: List[int] = []
 
     def preprocess(self, states, points, pointTime):
@@ -686,6 +721,22 @@ class DeviceBackend:
                                     self.reg["cosine_threshold"])
         self.iterations.append(r.iterations)
         return r.pose
+
+    def align_with_prior(self, points, covs, guess, information):
+        """The align with the prior (guess, information) and the posterior information in the filter's chart,
+        G^-T A G^-1 + information: A the data's information at the returned pose (vgicp_evaluate_resident), G the chart's
+        Jacobian there (vgicp_pose_prior_chart).  The prior is cleared again."""
+        from . import capi
+        self.ctx.set_pose_prior(guess, information)
+        try:
+            r = self.ctx.align_resident(guess, self.reg["max_iteration"], self.reg["translation_sq_threshold"],
+                                        self.reg["cosine_threshold"])
+        finally:
+            self.ctx.clear_pose_prior()
+        self.iterations.append(r.iterations)
+        self.converged.append(bool(r.converged))
+        return r.pose, capi.posterior_information(self.ctx.evaluate_resident([r.pose])[0].normal_eq, guess, r.pose,
+                                                  information)
 
     def update_map(self, points, covs, transform, initialize):
         if not initialize and self.prev is not None:

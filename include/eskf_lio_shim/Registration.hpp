@@ -18,6 +18,9 @@
 // setRobust / the optional keys registration.robust_kernel, robust_scale, gate: a Huber or Cauchy weight and a gate on the
 // squared Mahalanobis residual in every round (vgicp_hip_robust.h, which also says in which units).  Absent keys mean
 // the reference's plain least squares.
+// setPrior / clearPrior / alignWithPrior / posteriorInformation: a Gaussian prior on the pose in every round of the align
+// (vgicp_hip_prior.h) — the pose block of the filter's covariance, so that the pose returned is the MAP estimate and
+// ErrorStateKF::update can run as an iterated update (INTEGRATION.md has the patch).  No prior set: align() as ever.
 #ifndef ESKF_LIO_SHIM_REGISTRATION_HPP_
 #define ESKF_LIO_SHIM_REGISTRATION_HPP_
 
@@ -27,15 +30,43 @@
 #include <iostream>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "LocalMap.hpp"
 #include "../vgicp_hip_batch.h"
 #include "../vgicp_hip_evaluate.h"
 #include "../vgicp_hip_robust.h"
+#include "../vgicp_hip_prior.h"
+
+// referenced weakly, as LocalMap.hpp references the raw-point store's entry points: a program that links a stand-in of
+// the C ABI without them, or that does not link libvgicp_hip_prior.so beside libvgicp_hip.so, still links, and
+// ICP::setPrior then says so
+#pragma weak vgicp_set_pose_prior
+#pragma weak vgicp_pose_prior_chart
 
 namespace ESKF_LIO
 {
+
+// A 6 x 6 information matrix in the filter's chart [t - t0; Log(R0^T R)], column-major behind data().
+#if defined(ESKF_LIO_SHIM_NATIVE_TYPES)
+using Matrix6d = Eigen::Matrix<double, 6, 6>;
+#else
+struct Matrix6d
+{
+  double m[36];
+  static Matrix6d Zero()
+  {
+    Matrix6d z;
+    for (double & v : z.m) {v = 0.0;}
+    return z;
+  }
+  const double * data() const {return m;}
+  double * data() {return m;}
+  double & operator()(int r, int c) {return m[r + 6 * c];}
+  double operator()(int r, int c) const {return m[r + 6 * c];}
+};
+#endif
 
 // The keys ICP's YAML constructor reads (config/hilti_config.yaml:50-53).
 struct RegistrationConfig
@@ -129,10 +160,74 @@ public:
   double robustScale() const {return robustScaleMicro_ / 1000000.0;}   // as the library uses it
   double robustGate() const {return robustGateMicro_ / 1000000.0;}
 
+  // A Gaussian prior on the pose for every later align / alignHypotheses of this ICP (vgicp_hip_prior.h): the pose
+  // priorPose and a symmetric positive semi-definite information matrix in the chart [t - t0; Log(R0^T R)] (translation
+  // first) — the inverse of the pose block of the filter's P.  The library checks the values at the next align and
+  // refuses bad ones there (std::runtime_error with its text).  An all-zero information is no prior.
+  void setPrior(const Isometry3d & priorPose, const Matrix6d & information)
+  {
+    const double * p = shim::poseData(priorPose);
+    for (int k = 0; k < 16; ++k) {priorPose_[static_cast<size_t>(k)] = p[k];}
+    for (int k = 0; k < 36; ++k) {priorInformation_[static_cast<size_t>(k)] = information.data()[k];}
+    priorOn_ = true;
+  }
+  void clearPrior() {priorOn_ = false;}
+  bool hasPrior() const {return priorOn_;}
+
+  // setPrior(guess, priorInformation), align, clearPrior: the MAP pose of the cloud given the filter's pose `guess` with
+  // information priorInformation.  Leaves no prior behind, neither on this ICP nor on the map's context, and keeps what
+  // posteriorInformation() returns.
+  Isometry3d alignWithPrior(
+    const PointCloud & cloud, const LocalMap & localMap, const Isometry3d & guess, const Matrix6d & priorInformation)
+  {
+    setPrior(guess, priorInformation);
+    struct Clear
+    {
+      ICP * self;
+      vgicp_ctx * ctx;
+      ~Clear()
+      {
+        self->clearPrior();
+        if (vgicp_set_pose_prior) {(void)vgicp_set_pose_prior(ctx, nullptr, nullptr);}
+      }
+    } clear{this, localMap.context()};
+    const Isometry3d pose = align(cloud, localMap, guess);
+    // the data's information at the returned pose (the align left the cloud resident), carried from the chart of the
+    // normal equations into the filter's: G^-T A G^-1, plus the prior's
+    const std::vector<Evaluation> at = evaluateResidentScan(localMap.context(), {pose});
+    const std::array<double, 36> A = at[0].information();
+    double G[36], Ginv[36];
+    shim::check(localMap.context(), vgicp_pose_prior_chart(shim::poseData(guess), shim::poseData(pose), nullptr, G),
+      "vgicp_pose_prior_chart");
+    if (!invert6(G, Ginv)) {throw std::runtime_error("ICP::alignWithPrior: the chart's Jacobian is singular");}
+    double AG[36];
+    for (int r = 0; r < 6; ++r) {
+      for (int c = 0; c < 6; ++c) {
+        double v = 0.0;
+        for (int k = 0; k < 6; ++k) {v += A[static_cast<size_t>(r + 6 * k)] * Ginv[k + 6 * c];}
+        AG[r + 6 * c] = v;
+      }
+    }
+    for (int r = 0; r < 6; ++r) {
+      for (int c = 0; c < 6; ++c) {
+        double v = 0.0;
+        for (int k = 0; k < 6; ++k) {v += Ginv[k + 6 * r] * AG[k + 6 * c];}
+        posterior_.data()[r + 6 * c] = v + priorInformation.data()[r + 6 * c];
+      }
+    }
+    return pose;
+  }
+
+  // Of the last alignWithPrior: G^-T A G^-1 + priorInformation in the filter's chart — A the data's information at the
+  // returned pose (evaluate), G the chart's Jacobian there (vgicp_pose_prior_chart).  Its inverse is the covariance of
+  // the returned pose.
+  Matrix6d posteriorInformation() const {return posterior_;}
+
   Isometry3d align(const PointCloud & cloud, const LocalMap & localMap, const Isometry3d & guess)
   {
     vgicp_ctx * ctx = localMap.context();
     applyRobust(ctx);
+    applyPrior(ctx);
     const vgicp_params params = paramsOf();
     std::vector<uint64_t> counts(static_cast<size_t>(maxIteration_ > 0 ? maxIteration_ : 1), 0);
     vgicp_stats stats{};
@@ -223,6 +318,7 @@ public:
     }
     vgicp_ctx * ctx = localMap.context();
     applyRobust(ctx);
+    applyPrior(ctx);
     const vgicp_params params = paramsOf();
     lastUsedResidentScan_ = residentScanOrUpload(ctx, cloud, "alignHypotheses");
     shim::TraceScope tsCall(shim::Trace::AlignCall);
@@ -465,6 +561,52 @@ private:
     }
   }
 
+  // ... and THIS one's prior, set or cleared.  Without one a refusal is not an error (a multi-device context refuses the
+  // call and never has a prior; a stand-in of the C ABI may lack the entry point); with one, it is.
+  void applyPrior(vgicp_ctx * ctx) const
+  {
+    if (!vgicp_set_pose_prior) {
+      if (priorOn_) {throw std::runtime_error("ICP::setPrior: the linked vgicp module has no vgicp_set_pose_prior");}
+      return;
+    }
+    if (!priorOn_) {
+      (void)vgicp_set_pose_prior(ctx, nullptr, nullptr);
+      return;
+    }
+    shim::check(ctx, vgicp_set_pose_prior(ctx, priorPose_.data(), priorInformation_.data()), "vgicp_set_pose_prior");
+  }
+
+  // out = in^-1 for a column-major 6 x 6, Gauss-Jordan with partial pivoting; false for a singular matrix
+  static bool invert6(const double * in, double * out)
+  {
+    double a[6][12];
+    for (int r = 0; r < 6; ++r) {
+      for (int c = 0; c < 6; ++c) {
+        a[r][c] = in[r + 6 * c];
+        a[r][6 + c] = r == c ? 1.0 : 0.0;
+      }
+    }
+    for (int k = 0; k < 6; ++k) {
+      int p = k;
+      for (int r = k + 1; r < 6; ++r) {
+        if (std::fabs(a[r][k]) > std::fabs(a[p][k])) {p = r;}
+      }
+      if (!(std::fabs(a[p][k]) > 0.0)) {return false;}
+      for (int c = 0; c < 12; ++c) {std::swap(a[k][c], a[p][c]);}
+      const double inv = 1.0 / a[k][k];
+      for (int c = 0; c < 12; ++c) {a[k][c] *= inv;}
+      for (int r = 0; r < 6; ++r) {
+        if (r == k) {continue;}
+        const double f = a[r][k];
+        for (int c = 0; c < 12; ++c) {a[r][c] -= f * a[k][c];}
+      }
+    }
+    for (int r = 0; r < 6; ++r) {
+      for (int c = 0; c < 6; ++c) {out[r + 6 * c] = a[r][6 + c];}
+    }
+    return true;
+  }
+
   // vgicp_evaluate_resident on whatever scan is resident (1 <= poses.size() <= VGICP_EVAL_MAX)
   static std::vector<Evaluation> evaluateResidentScan(vgicp_ctx * ctx, const std::vector<Isometry3d> & poses)
   {
@@ -495,6 +637,10 @@ private:
   int robustKernel_ = VGICP_ROBUST_NONE;
   int robustScaleMicro_ = 1000000;
   int robustGateMicro_ = 0;
+  bool priorOn_ = false;
+  std::array<double, 16> priorPose_{};
+  std::array<double, 36> priorInformation_{};
+  Matrix6d posterior_ = Matrix6d::Zero();
   Stats lastStats_;
   bool lastUsedResidentScan_ = false;
   std::vector<uint64_t> fanCounts_;   // the last fan's per-round counts, hypothesis-major

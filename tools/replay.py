@@ -10,6 +10,8 @@ options: --out traj.tum   --device-map (keep the voxel grid on the GPU only)   -
          export is timed at the end)
          --robust-kernel none|huber|cauchy  --robust-scale C  --gate G (robust rounds, include/vgicp_hip_robust.h: in the
          library's regularised units, ~0.1; off by default)
+         --prior-update (kalman_filter.update.iterated: the filter's pose covariance enters every round of the align as a
+         prior, include/vgicp_hip_prior.h, and the update is the iterated one; off by default)
 The configuration is the reference's config/hilti_config.yaml as a dict (eskf_lio_amd/replay.py:DEFAULT_CONFIG);
 --config file.yaml overrides it with a file of the reference's own layout."""
 import argparse
@@ -70,6 +72,8 @@ def main():
     ap.add_argument("--robust-scale", type=float, default=None, help="its scale c (registration.robust_scale)")
     ap.add_argument("--gate", type=float, default=None,
                     help="gate on the squared Mahalanobis residual, 0 = none (registration.gate)")
+    ap.add_argument("--prior-update", action="store_true",
+                    help="the iterated filter update with the pose prior in every align (kalman_filter.update.iterated)")
     args = ap.parse_args()
     if args.raw_points_on_device and not args.resident:
         ap.error("--raw-points-on-device needs --resident")
@@ -81,6 +85,8 @@ def main():
                                 ("gate", args.gate)) if v is not None}
     if robust:
         cfg = dict(cfg, registration=dict(cfg["registration"], **robust))
+    if args.prior_update:
+        cfg = dict(cfg, kalman_filter=dict(cfg["kalman_filter"], iterated=True))
     truth = None
     if args.bag:
         events = replay.read_rosbag2(args.bag, imu_topic, lidar_topic)
