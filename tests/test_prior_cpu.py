@@ -10,12 +10,27 @@ import numpy as np
 import pytest
 
 import prior_reference as pr
+import solver_reference as sr
 from eskf_lio_amd import capi, replay
 from test_evaluate_cpu import declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-THETAS = (0.0, 1e-9, 1e-6, 1e-3, 1.0, 3.1)
+BACK = float(np.arccos(-0.9))                     # where so3_log hands over to so3_log_near_pi
+# both sides of cosine = 0 (front / back half of the angle) and of cosine = -0.9
+EDGE_THETAS = (0.5 * np.pi * (1 - 1e-12), 0.5 * np.pi * (1 + 1e-12), BACK * (1 - 1e-12), BACK * (1 + 1e-12))
+THETAS = (0.0, 1e-9, 1e-6, 1e-3, 1.0, 3.1) + EDGE_THETAS
 EPS = np.finfo(np.float64).eps
+# What Log costs at most, in place of the 1 / sin(theta) of the tolerances below: so3_log divides by sin(theta) only while
+# cosine > -0.9, where 1 / sin <= 1 / sqrt(1 - 0.81) = 2.294.  Beyond, so3_log_near_pi takes a_K = sqrt((M_KK - cos) /
+# (1 - cos)) of the largest diagonal entry, a_K^2 >= 1/3 and 1 - cos >= 1.9: the quotient carries at most 2 eps / 1.9, the
+# square root multiplies by 1 / (2 a_K) <= 0.87, and the two other entries divide a sum of two matrix entries by
+# (1 - cos) a_K >= 1.097 — every factor below 2.294, and none grows towards pi.
+LOG_COST_CAP = 1.0 / np.sqrt(1.0 - 0.81)
+
+
+def log_cost(theta):
+    s = np.sin(theta)
+    return min(1.0 / s, LOG_COST_CAP) if s > 0.0 else LOG_COST_CAP
 
 
 def random_pair(rng, theta):
@@ -155,6 +170,67 @@ def test_jacobian_equals_the_central_difference(theta):
             worst = max(worst, np.abs(column - G[:, k]).max() / S)
             assert np.abs(column - G[:, k]).max() <= tol, (theta, k)
     print(f"theta {theta}: worst |FD - G| / S {worst:.3e}")
+
+
+@pytest.mark.skipif(sr.unavailable_reason() is not None, reason=str(sr.unavailable_reason()))
+@pytest.mark.parametrize("theta", EDGE_THETAS + (3.1, np.pi - 1e-8))
+def test_chart_at_the_branch_edges_equals_extended_precision(theta):
+    """d and G at the angles where so3_log changes its formula, and 1e-8 below pi, against tests/solver_reference.py: Log
+    of the very fp64 matrices the library receives and Jr^-1 in extended precision (prior_reference's c(theta) cannot
+    serve next to pi: its closed form has the pole the header's second form avoids).  The tolerance formula of
+    test_chart_equals_the_numpy_restatement, 64 eps x (cost of Log) x S, the cost 1 / sin(theta) capped by what the
+    near-pi branch costs itself (LOG_COST_CAP above, with its derivation): at pi - 1e-8 that is 2.3 in place of 1e8.
+    The angle and the axis come back as they went in (observed: 0.014 of the tolerance at worst, at pi / 2)."""
+    rng = np.random.default_rng(int(theta * 1000) + 13)
+    worst = 0.0
+    for _ in range(50):
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        T0, T = random_pair(rng, 0.0)
+        unit = axis.astype(sr.LD)
+        unit /= np.sqrt(unit @ unit)
+        T[:3, :3] = np.asarray(T0[:3, :3].astype(sr.LD) @ sr.so3_exp(theta, unit), dtype=np.float64)
+        d, G = capi.pose_prior_chart(T0, T)
+        d_ref, G_ref = sr.chart(T0, T)
+        tol = 64 * EPS * log_cost(theta) * (1.0 + np.linalg.norm(T[:3, 3]) + theta)
+        diff = max(float(np.abs(d - d_ref).max()), float(np.abs(G - G_ref).max()))
+        worst = max(worst, diff / tol)
+        assert diff <= tol, (theta, diff, tol)
+        assert abs(np.linalg.norm(d[3:]) - theta) <= tol and np.abs(d[3:] - theta * axis).max() <= tol
+        Jr_inv = G[3:, 3:] @ T[:3, :3]
+        assert np.abs(Jr_inv @ d[3:] - d[3:]).max() <= tol
+    print(f"theta {theta}: worst difference / tolerance {worst:.3e}")
+
+
+@pytest.mark.skipif(sr.unavailable_reason() is not None, reason=str(sr.unavailable_reason()))
+@pytest.mark.parametrize("K", (0, 1, 2))
+def test_chart_at_exactly_pi(K):
+    """R0^T R = diag(1, -1, -1) and its two permutations, exactly: R0 a signed permutation matrix, so the product is
+    exact too.  The sine is zero and either sign of phi is the Log: Exp(phi) is compared with R0^T R, |phi| with pi, and G
+    with the extended-precision chart of the sign that came back.  Tolerance as above (cost LOG_COST_CAP); Exp(phi) is
+    off the matrix by pi - fl(pi) = 1.2e-16 on top of its own rounding."""
+    half_turn = -np.ones(3)
+    half_turn[K] = 1.0
+    for R0 in (np.eye(3), np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]]),
+               np.array([[0.0, 0.0, 1.0], [0.0, -1.0, 0.0], [1.0, 0.0, 0.0]])):
+        assert np.linalg.det(R0) == 1.0
+        T0, T = np.eye(4), np.eye(4)
+        T0[:3, :3], T[:3, :3] = R0, R0 @ np.diag(half_turn)
+        T0[:3, 3], T[:3, 3] = [0.5, -1.0, 2.0], [1.5, 0.25, -3.0]
+        assert np.array_equal(T0[:3, :3].T @ T[:3, :3], np.diag(half_turn))
+        d, G = capi.pose_prior_chart(T0, T)
+        phi = d[3:]
+        tol = 64 * EPS * LOG_COST_CAP * (1.0 + np.linalg.norm(T[:3, 3]) + np.pi)
+        assert np.array_equal(d[:3], T[:3, 3] - T0[:3, 3])
+        assert abs(abs(phi[K]) - np.pi) <= tol and np.abs(np.delete(phi, K)).max() <= tol, phi
+        angle = np.sqrt(phi.astype(sr.LD) @ phi.astype(sr.LD))
+        back = sr.so3_exp(angle, phi.astype(sr.LD) / angle)
+        assert np.abs(np.asarray(back, dtype=np.float64) - np.diag(half_turn)).max() <= tol
+        exact = np.zeros(3, dtype=sr.LD)
+        exact[K] = np.sign(phi[K]) * sr.PI                       # the Log of that sign, to extended precision
+        d_ref, G_ref = sr.chart(T0, T, exact)
+        assert float(np.abs(d - d_ref).max()) <= tol and float(np.abs(G - G_ref).max()) <= tol
+        assert np.array_equal(G[:3, :3], np.eye(3)) and not G[3:, :3].any()
 
 
 def test_series_switch_over_is_the_exponentials():
