@@ -626,14 +626,17 @@ __device__ __forceinline__ void accumulate_match(const double* R, const double (
   if constexpr (ROBUST) {
     // d^2 = e^T W e from W e, the weight from d^2; the count now, and W takes the weight as a factor BEFORE anything is
     // made of it: every one of the 27 sums below is linear in W, so each carries the factor w (nine products instead
-    // of 27, and w is dead before Q is live).  w = 1.0 leaves W's bits, w = 0 leaves +-0.
+    // of 27, and w is dead before Q is live).  w = 1.0 leaves W's bits.  A rejected correspondence (w = 0) gets W = +0
+    // by SELECTION, not by the product: its W may be NaN (a non-finite covariance entry fails the gate), and NaN x 0
+    // would put NaN into 27 sums of a round that does not count it.
     const double g0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
     const double g1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
     const double g2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
     const double w = robust_weight(robust, e0 * g0 + e1 * g1 + e2 * g2);
-    acc(v[kCountSlot], w > 0.0 ? 1.0 : 0.0);
+    const bool counted = w > 0.0;
+    acc(v[kCountSlot], counted ? 1.0 : 0.0);
 #pragma unroll
-    for (int k = 0; k < 9; ++k) W[k] = W[k] * w;
+    for (int k = 0; k < 9; ++k) W[k] = counted ? W[k] * w : 0.0;
   }
   // Q = [p]x W  (rows 3..5, columns 0..2 of J^T Sigma^-1 J)
   double Q[9];  // Q[r + 3c]

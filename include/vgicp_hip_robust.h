@@ -12,6 +12,8 @@
  *   - A correspondence is what it is without the mode: the exact-voxel lookup, unchanged.
  *   - e = R p + t - mu_voxel, W = (R C R^T + C_voxel)^-1 as the plain round forms them; d^2 = max(e^T W e, 0).
  *   - Gate g > 0: a correspondence with !(e^T W e <= g) has weight 0 and is NOT counted (a NaN residual is rejected).
+ *     A rejected correspondence adds +0 to every sum of the round, whatever its covariances hold: a scan point whose
+ *     covariance has a non-finite entry leaves a gated round's sums finite.
  *   - Huber, scale c:   w = 1 if d^2 <= c^2, else c / sqrt(d^2).
  *   - Cauchy, scale c:  w = 1 / (1 + d^2 / c^2).
  *   - The round solves (sum w J^T W J) xi = - sum w J^T W e.  The weights come from the pose the round starts with:
