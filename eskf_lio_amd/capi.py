@@ -55,6 +55,12 @@ EVAL_MAX = 64
 PRIOR_EXPORTS = ("vgicp_set_pose_prior", "vgicp_pose_prior_chart")
 PRIOR_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_prior.so")
 
+# every symbol include/vgicp_hip_points.h declares: likewise an entry point in a library of its own beside the module
+POINTS_EXPORTS = ("vgicp_points_resident",)
+POINTS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_points.so")
+POINT_QUANTILES_MAX = 16
+POINT_MATCHED, POINT_NEGATIVE, POINT_NOT_FINITE = 1, 2, 4
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -111,6 +117,17 @@ class Evaluation(C.Structure):
 
 class EvalStats(C.Structure):
     _fields_ = [("launches", C.c_int32), ("poses_per_launch", C.c_int32), ("seconds", C.c_double),
+                ("device_seconds", C.c_double)]
+
+
+class PointSummary(C.Structure):
+    """vgicp_point_summary (vgicp_hip_points.h), 168 bytes."""
+    _fields_ = [("points", C.c_uint64), ("matched", C.c_uint64), ("counted", C.c_uint64), ("negative", C.c_uint64),
+                ("not_finite", C.c_uint64), ("quantile", C.c_double * POINT_QUANTILES_MAX)]
+
+
+class PointStats(C.Structure):
+    _fields_ = [("launches", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double),
                 ("device_seconds", C.c_double)]
 
 
@@ -199,6 +216,13 @@ def load_library() -> C.CDLL:
         for name in PRIOR_EXPORTS:
             getattr(prior, name).restype = C.c_int
             setattr(lib, name, getattr(prior, name))
+    # the per-point report's library, likewise
+    if os.path.exists(POINTS_LIB_PATH):
+        points = C.CDLL(POINTS_LIB_PATH, mode=C.RTLD_GLOBAL)
+        points.vgicp_points_resident.argtypes = [vp, dp, sz, dp, dp, dp, C.POINTER(C.c_uint8), sz, dp,
+                                                 C.POINTER(PointSummary), C.POINTER(PointStats)]
+        points.vgicp_points_resident.restype = C.c_int
+        lib.vgicp_points_resident = points.vgicp_points_resident
     _lib = lib
     return lib
 
@@ -271,6 +295,25 @@ class PoseEvaluation:
     @property
     def JTr(self) -> np.ndarray:
         return expand_normal_eq(self.normal_eq)[1][0]
+
+
+@dataclass
+class PointReport:
+    """What points_resident returns: the per-point arrays that were asked for (else None), the counts, the quantiles in
+    the order they were asked, and how the call ran."""
+    points: int
+    matched: int
+    counted: int
+    negative: int
+    not_finite: int
+    quantiles: np.ndarray              # one order statistic of d^2 per requested q
+    d2: Optional[np.ndarray] = None    # raw e^T W e; +inf where the point has no voxel
+    sq_error: Optional[np.ndarray] = None
+    weight: Optional[np.ndarray] = None
+    status: Optional[np.ndarray] = None  # uint8: POINT_MATCHED | POINT_NEGATIVE | POINT_NOT_FINITE
+    launches: int = 0
+    seconds: float = 0.0
+    device_seconds: float = 0.0
 
 
 @dataclass
@@ -563,6 +606,34 @@ class Context:
                                       cost=float(out[h].cost), sq_error=float(out[h].sq_error),
                                       normal_eq=np.array(out[h].normal_eq[:], dtype=np.float64)))
         return res
+
+    def points_size(self) -> int:
+        """n of the resident scan (a pending preparation is settled): vgicp_scan_download's size query."""
+        n = C.c_size_t(0)
+        self._check(self._lib.vgicp_scan_download(self._h, 0, None, None, C.byref(n)))
+        return int(n.value)
+
+    def points_resident(self, pose, quantiles=(), d2=True, sq_error=True, weight=True, status=True) -> "PointReport":
+        """vgicp_points_resident (vgicp_hip_points.h): the resident scan at `pose`, point by point — raw d^2, |e|^2, the
+        weight under the context's robust options and the status flags, for the arrays asked — with the counts and the
+        order statistics of d^2 at `quantiles` (each in [0, 1], at most 16)."""
+        T = pose_to_abi(pose)
+        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        summary, st = PointSummary(), PointStats()
+        n = self.points_size() if (d2 or sq_error or weight or status) else 0
+        a_d2 = np.zeros(n) if d2 else None
+        a_sq = np.zeros(n) if sq_error else None
+        a_w = np.zeros(n) if weight else None
+        a_st = np.zeros(n, dtype=np.uint8) if status else None
+        self._check(self._lib.vgicp_points_resident(
+            self._h, _dp(T), n, _dp(a_d2) if d2 else None, _dp(a_sq) if sq_error else None, _dp(a_w) if weight else None,
+            a_st.ctypes.data_as(C.POINTER(C.c_uint8)) if status else None, qs.size, _dp(qs) if qs.size else None,
+            C.byref(summary), C.byref(st)))
+        return PointReport(points=int(summary.points), matched=int(summary.matched), counted=int(summary.counted),
+                           negative=int(summary.negative), not_finite=int(summary.not_finite),
+                           quantiles=np.array(summary.quantile[:qs.size], dtype=np.float64), d2=a_d2, sq_error=a_sq,
+                           weight=a_w, status=a_st, launches=st.launches, seconds=st.seconds,
+                           device_seconds=st.device_seconds)
 
     def align_batch_width(self) -> int:
         """vgicp_align_batch_width: hypotheses one launch takes for the scan that is resident now."""

@@ -31,6 +31,7 @@ std::atomic<uint64_t> g_context_ids{0};
 #include "vgicp_capi_registration.inl"
 #include "vgicp_capi_batch.inl"
 #include "vgicp_capi_evaluate.inl"
+#include "vgicp_capi_points.inl"
 #include "vgicp_capi_prepare.inl"
 #include "vgicp_capi_peers.inl"
 #include "vgicp_capi_multi_support.inl"

@@ -28,11 +28,13 @@
 #include "../../include/vgicp_hip_evaluate.h"
 #include "../../include/vgicp_hip_robust.h"
 #include "../../include/vgicp_hip_prior.h"
+#include "../../include/vgicp_hip_points.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
 #include "vgicp_prepare_plan.h"
 #include "vgicp_map_plan.h"
+#include "vgicp_points_plan.h"
 
 using namespace vgicp;
 
@@ -348,6 +350,10 @@ struct vgicp_ctx {
   // scoring poses (vgicp_hip_evaluate.h): storage of its own, made with the context
   DeviceBuf<double> d_eval_rows;       // kEvalRowBudget rows: [poses of a launch][rows per pose][kSlots]
   PinnedBuf<double> h_eval;            // pinned: VGICP_EVAL_MAX result rows of kSlots doubles, then VGICP_EVAL_MAX poses of 12; .dev() likewise
+  // the per-point report (vgicp_hip_points.h): storage of its own, made by the first call and grow-only
+  DeviceBuf<char> d_points;            // the planes, the keys, the sort's buffers and the counters, for points_capacity points
+  size_t points_capacity = 0;          // points (the scan capacity the buffer was sized from)
+  PinnedBuf<unsigned long long> h_points;  // pinned, kPointResultWords: the counts and the quantiles; .dev() likewise
   bool persistent_enabled = true;    // cleared by VGICP_PERSISTENT=0 or when a workgroup does not fit a CU
   double prefetch_margin = 0.015;    // see PersistArgs::prefetch_margin; VGICP_PREFETCH_MARGIN overrides (0 = off).  Round 6: 0.03 -> 0.015
                                      // once the workgroups that are no folders stopped polling early (C2: 0 7.18, 0.01 6.41, 0.015 6.34, 0.02 6.35, 0.03 6.52, 0.04 6.66 us per round)
@@ -614,6 +620,11 @@ int settle_context(vgicp_ctx* ctx);
 // that is not VGICP_OK
 int align_batch_sequential(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp_params* params, double* out_poses,
                            vgicp_batch_stats* stats, bool loop_only, int* first_bad);
+// vgicp_points_resident (include/vgicp_hip_points.h) behind its entry point in libvgicp_hip_points.so, which has made
+// the layout handshake: every other check, the settling, the launches, the delivery (vgicp_capi_points.inl).
+int points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, double* d2, double* sq_error, double* weight,
+                    uint8_t* status, size_t n_quantiles, const double* q, vgicp_point_summary* summary,
+                    vgicp_point_stats* stats);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

@@ -234,7 +234,46 @@ struct EvalArgs {
   uint32_t pad;
 };
 
+// The resident scan at a pose, point by point (vgicp_points_resident, include/vgicp_hip_points.h): one launch writes the
+// requested planes (any of them may be nullptr) and, when quantiles are wanted, a 64-bit sort key and the index per
+// point; a second, one wave, reads the counts, picks the ranks from the sorted keys and writes the result into
+// page-locked memory.  counters: 4 device words, zero before the first launch: matched, counted, negative, not finite.
+constexpr int kPointCounters = 4;
+constexpr int kPointQuantiles = 16;        // VGICP_POINT_QUANTILES_MAX
+constexpr int kPointResultWords = kPointCounters + kPointQuantiles;
+struct PointArgs {
+  const double* scan;  // SoA planes
+  uint64_t stride;
+  uint32_t n;
+  uint32_t mask;
+  const VoxelRecord* table;
+  double voxel_size;
+  double pose[12];           // R column-major (9), t (3)
+  const uint32_t* asym_dev;  // as IterArgs
+  uint32_t scan_seq;
+  uint32_t robust_kernel;    // as IterArgs: the context's robust settings (robust_args)
+  double robust_scale2;
+  double robust_gate;
+  double* d2;                // n each, or nullptr
+  double* sq_error;
+  double* weight;
+  uint8_t* status;
+  unsigned long long* keys;  // n keys and ...
+  uint32_t* idx;             // ... n indices for the sort, or both nullptr
+  uint32_t* counters;
+};
+struct PointPickArgs {
+  const unsigned long long* sorted;  // the n keys in ascending order (n_quantiles > 0)
+  const uint32_t* counters;
+  uint32_t n;
+  uint32_t n_quantiles;
+  double q[kPointQuantiles];
+  unsigned long long* out;   // page-locked, kPointResultWords: the four counts, then the quantiles' bit patterns
+};
+
 // ---- launchers (defined in vgicp_kernels.hip) ----
+hipError_t launch_point_terms(hipStream_t s, const PointArgs& args);
+hipError_t launch_point_pick(hipStream_t s, const PointPickArgs& args);
 // Rows of `poses` poses (grid: rows_per_pose x poses workgroups of 512 threads), and their fold into out[poses][kSlots]:
 // slots 0-26 the normal equations, 27 the count, 28 the cost, 29 the squared error.
 hipError_t launch_evaluate(hipStream_t s, const EvalArgs& args, uint32_t rows_per_pose, uint32_t poses);
@@ -418,6 +457,12 @@ hipError_t launch_prepare_tail(hipStream_t s, const PrepareArgs& a);
 // then stage the times unit by unit with the points instead of before the launch
 bool prepare_bounds_fused(uint32_t n, uint32_t states, bool ordered_states);
 uint64_t preprocess_cell_entries_for(uint32_t n);  // from the number of points alone (no host round trip)
+// The library's sort (vgicp_sort.h) of n (64-bit key, index) pairs for callers outside vgicp_preprocess.hip, where its
+// 64-bit instantiation lives: (keys_a, idx_a) hold the input and are overwritten, the result is left in (keys_b, idx_b);
+// split: sort_keys64_scratch_bytes(n) bytes.  Keys lie below ~0.  *launches (may be nullptr): kernels enqueued.
+size_t sort_keys64_scratch_bytes(uint32_t n);
+hipError_t launch_sort_keys64(hipStream_t s, unsigned long long* keys_a, uint32_t* idx_a, unsigned long long* keys_b,
+                              uint32_t* idx_b, void* split, uint32_t n, uint32_t* launches);
 // kernels enqueued by the launchers of this module since the counter was last reset (per host thread)
 extern thread_local uint64_t g_kernel_launches;
 hipError_t launch_transform_points(hipStream_t s, double* pts, uint32_t n, const double T16[16]);

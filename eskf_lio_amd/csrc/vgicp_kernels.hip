@@ -26,6 +26,7 @@
 //     alone (the first version's ticket + write-through + last-workgroup tail cost 13 us per round).
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
+#include "vgicp_points_plan.h"
 
 namespace vgicp {
 namespace {
@@ -958,6 +959,103 @@ __global__ __launch_bounds__(512) void evaluate_fold_kernel(const double* __rest
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) part[g] = fin[g][tid];
     out[(size_t)blockIdx.x * kSlots + tid] = tree_sum<kGroups>(part);
+  }
+}
+
+// The resident scan at a pose, point by point (vgicp_points_resident, include/vgicp_hip_points.h).  One point per
+// thread, 256 threads: the point's planes, ONE find_voxel probe, the payload, and the term as accumulate_match<..., ROBUST>
+// and evaluate_kernel form it (S = R C R^T + C_voxel by the same two loops, inverse3_cofactor, W e, then e . (W e)) —
+// without the 27 sums, so nothing is reduced but four counts.  The requested planes are written at the point's index:
+// every store of a wave is one coalesced access.  A point's values depend on nothing but the point, the pose and the
+// settings: not on which planes are asked, not on its neighbours.  Nothing waits for another workgroup.
+__global__ __launch_bounds__(256) void point_terms_kernel(PointArgs a) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool cov_sym = a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
+  const RobustSetting robust = robust_setting(a.robust_kernel, a.robust_scale2, a.robust_gate);
+  bool matched = false, counted = false, negative = false, not_finite = false;
+  if (i < a.n) {
+    double q[kScanPlanes];
+    load_point_sym(a.scan, a.stride, i, q, cov_sym);
+    double R[9], t[3], C[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { R[k] = a.pose[k]; C[k] = q[3 + k]; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = a.pose[9 + k];
+    const double inv_voxel = 1.0 / a.voxel_size;
+    double p[3];
+    transform_point(R, t, q[0], q[1], q[2], p);
+    const int32_t kx = voxel_coord_fast(p[0], a.voxel_size, inv_voxel);
+    const int32_t ky = voxel_coord_fast(p[1], a.voxel_size, inv_voxel);
+    const int32_t kz = voxel_coord_fast(p[2], a.voxel_size, inv_voxel);
+    const VoxelRecord* rec = find_voxel(a.table, a.mask, kx, ky, kz);
+    double raw = __builtin_inf(), sq = __builtin_inf(), w = 0.0;
+    if (rec != nullptr) {
+      matched = true;
+      double mu[3], S[9];
+      load_payload(rec, mu, S);
+      // S = R C R^T + C_voxel: accumulate_match's expressions
+      double RC[9];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+          RC[r + 3 * c] = R[r] * C[3 * c] + R[r + 3] * C[1 + 3 * c] + R[r + 6] * C[2 + 3 * c];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+          S[r + 3 * c] += RC[r] * R[c] + RC[r + 3] * R[c + 3] + RC[r + 6] * R[c + 6];
+      double W[9];
+      inverse3_cofactor(S, W);
+      const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
+      const double g0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
+      const double g1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
+      const double g2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
+      raw = e0 * g0 + e1 * g1 + e2 * g2;
+      sq = e0 * e0 + e1 * e1 + e2 * e2;
+      w = robust_weight(robust, raw);
+      counted = w > 0.0;
+      not_finite = !(fabs(raw) < __builtin_inf());
+      negative = !not_finite && raw < 0.0;
+    }
+    if (a.d2) a.d2[i] = raw;
+    if (a.sq_error) a.sq_error[i] = sq;
+    if (a.weight) a.weight[i] = w;
+    if (a.status) a.status[i] = (uint8_t)((matched ? 1u : 0u) | (negative ? 2u : 0u) | (not_finite ? 4u : 0u));
+    if (a.keys) {
+      a.keys[i] = matched && !not_finite ? point_key(raw) : kPointKeyUnranked;
+      a.idx[i] = i;
+    }
+  }
+  // one atomic per workgroup and counter, as insert_prepare_kernel counts
+  const int c_matched = __syncthreads_count(matched ? 1 : 0);
+  const int c_counted = __syncthreads_count(counted ? 1 : 0);
+  const int c_negative = __syncthreads_count(negative ? 1 : 0);
+  const int c_not_finite = __syncthreads_count(not_finite ? 1 : 0);
+  if (threadIdx.x == 0) {
+    if (c_matched) atomicAdd(&a.counters[0], (uint32_t)c_matched);
+    if (c_counted) atomicAdd(&a.counters[1], (uint32_t)c_counted);
+    if (c_negative) atomicAdd(&a.counters[2], (uint32_t)c_negative);
+    if (c_not_finite) atomicAdd(&a.counters[3], (uint32_t)c_not_finite);
+  }
+}
+
+// The pick: one wave.  m = matched - not finite is read here, on the device; lane j takes quantile j: its rank by
+// quantile_rank (vgicp_points_plan.h, the definition) and the sorted key there, whose pattern IS the value.  The ranked
+// points sort in front of the others, so a rank below m names one of them.  Counts and quantiles go straight into
+// page-locked memory.
+__global__ __launch_bounds__(64) void point_pick_kernel(PointPickArgs a) {
+  const uint32_t lane = threadIdx.x;
+  if (lane < (uint32_t)kPointCounters) a.out[lane] = a.counters[lane];
+  if (lane < a.n_quantiles && lane < (uint32_t)kPointQuantiles) {
+    const uint32_t matched = a.counters[0], not_finite = a.counters[3];
+    const uint64_t m = matched > not_finite ? matched - not_finite : 0u;
+    unsigned long long bits = 0x7FF8000000000000ull;   // NaN: nothing is ranked
+    if (m > 0) {
+      const uint64_t rank = quantile_rank(a.q[lane], m);
+      if (rank < a.n) bits = a.sorted[rank];
+    }
+    a.out[kPointCounters + lane] = bits;
   }
 }
 
@@ -2414,6 +2512,22 @@ hipError_t launch_evaluate(hipStream_t s, const EvalArgs& args, uint32_t rows_pe
 hipError_t launch_evaluate_fold(hipStream_t s, const double* rows, uint32_t rows_per_pose, uint32_t poses, double* out) {
   if (rows_per_pose < 1 || poses < 1 || (uint64_t)rows_per_pose * poses > (uint64_t)kEvalRowBudget) return hipErrorInvalidValue;
   ++g_kernel_launches; hipLaunchKernelGGL(evaluate_fold_kernel, dim3(poses), dim3(512), 0, s, rows, rows_per_pose, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_point_terms(hipStream_t s, const PointArgs& args) {
+  if (args.scan == nullptr || args.table == nullptr || args.counters == nullptr || (args.keys == nullptr) != (args.idx == nullptr))
+    return hipErrorInvalidValue;
+  if (args.n == 0) return hipSuccess;
+  ++g_kernel_launches; hipLaunchKernelGGL(point_terms_kernel, dim3((args.n + 255u) / 256u), dim3(256), 0, s, args);
+  return hipGetLastError();
+}
+
+hipError_t launch_point_pick(hipStream_t s, const PointPickArgs& args) {
+  if (args.counters == nullptr || args.out == nullptr || args.n_quantiles > (uint32_t)kPointQuantiles ||
+      (args.n_quantiles > 0 && args.n > 0 && args.sorted == nullptr))
+    return hipErrorInvalidValue;
+  ++g_kernel_launches; hipLaunchKernelGGL(point_pick_kernel, dim3(1), dim3(64), 0, s, args);
   return hipGetLastError();
 }
 

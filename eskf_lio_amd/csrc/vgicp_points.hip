@@ -1,0 +1,23 @@
+// vgicp_points.hip — libvgicp_hip_points.so: the entry point of include/vgicp_hip_points.h.
+// A library of its own because libvgicp_hip.so's exported vgicp_* names are pinned to the lists of the headers before
+// this one.  It holds the extern "C" entry only: the handshake with the module that made the context, then the forward
+// to vgicp_internal::points_resident (vgicp_capi_points.inl), which lives inside the module beside the kernels.  Built
+// from the same vgicp_context.h as the module (one Makefile, one rule set) and linked against it.
+#include "vgicp_context.h"
+
+extern "C" {
+
+int vgicp_points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, double* d2, double* sq_error,
+                          double* weight, uint8_t* status, size_t n_quantiles, const double* q,
+                          vgicp_point_summary* summary, vgicp_point_stats* stats) {
+  // rules 1 and 2 of the header's list (plan_points decides them from these two facts alone): nothing of the context is
+  // read or written unless its layout is this build's (the text goes where a failed vgicp_create's goes)
+  PointsFacts f;
+  f.ctx = ctx != nullptr;
+  f.same_build = ctx && ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx));
+  const PointsVerdict v = plan_points(f);
+  if (v.rule == 1) return v.status;
+  if (v.rule == 2) return fail(nullptr, v.status, v.text);
+  return vgicp_internal::points_resident(ctx, pose, capacity, d2, sq_error, weight, status, n_quantiles, q, summary, stats);
+}
+}  // extern "C"

@@ -1948,6 +1948,19 @@ hipError_t launch_prepare_tail(hipStream_t s, const PrepareArgs& a) {
   return hipGetLastError();
 }
 
+// The sort for callers in other translation units (vgicp_points_resident's keys): this file holds the one 64-bit
+// instantiation of vgicp_sort.h.
+size_t sort_keys64_scratch_bytes(uint32_t n) { return align256(sortk::split_bytes(n, sizeof(unsigned long long))); }
+
+hipError_t launch_sort_keys64(hipStream_t s, unsigned long long* keys_a, uint32_t* idx_a, unsigned long long* keys_b,
+                              uint32_t* idx_b, void* split, uint32_t n, uint32_t* launches) {
+  const hipError_t e = sortk::sort_pairs(keys_a, idx_a, keys_b, idx_b, split, n, s);
+  if (e != hipSuccess) return e;
+  g_kernel_launches += sortk::launches_for(n);
+  if (launches) *launches = sortk::launches_for(n);
+  return hipSuccess;
+}
+
 size_t deskew_scratch_words(uint32_t states) { return (size_t)states * (1 + kDeskewParts); }
 
 hipError_t launch_deskew(hipStream_t s, double* pts, uint32_t n, const double* point_time, const double* state_time,

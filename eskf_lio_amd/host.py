@@ -73,6 +73,10 @@ def load_library() -> C.CDLL:
     lib.host_icp_evaluate.argtypes = [vp, sz, dp, dp, vp, sz, dp, dp, i32p]
     lib.host_icp_align_best_by_score.argtypes = [vp, sz, dp, dp, vp, sz, dp, i32p, dp, i32p, i32p, dp]
     lib.host_frame_evaluate.argtypes = [vp, vp, vp, vp, sz, dp, C.c_int, dp, i32p]
+    u8p = C.POINTER(C.c_uint8)
+    lib.host_icp_point_report.argtypes = [vp, sz, dp, dp, vp, dp, sz, dp, C.c_int, sz, dp, dp, dp, u8p, u64p, dp, i32p]
+    lib.host_frame_point_report.argtypes = [vp, vp, vp, vp, dp, sz, dp, C.c_int, sz, dp, dp, dp, u8p, u64p, dp, i32p]
+    lib.host_icp_robust_scale_from_quantile.argtypes = [C.c_double, C.c_double, dp]
     lib.host_preprocessor_create.restype = vp
     lib.host_preprocessor_create.argtypes = [C.c_double, dp, C.c_int, C.c_int]
     lib.host_frame_begin.restype = vp
@@ -310,6 +314,27 @@ class ICP:
         self.used_resident = bool(res.value)
         return [_evaluation(row) for row in out]
 
+    def pointReport(self, points, covs, localMap: LocalMap, pose, quantiles=(), perPoint: bool = True):
+        """ICP::pointReport on a cloud made from the arrays (one upload) -> capi.PointReport."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        cvs = np.ascontiguousarray(covs, dtype=np.float64).reshape(-1, 9)
+        buf = _PointReportBuffers(pts.shape[0], quantiles, perPoint)
+        T = capi.pose_to_abi(pose)
+        res = C.c_int32(0)
+        _check(self._lib, self._lib.host_icp_point_report(self._h, pts.shape[0], _dp(pts), _dp(cvs), localMap._h, _dp(T),
+                                                          *buf.args(), C.byref(res)))
+        self.used_resident = bool(res.value)
+        return buf.report()
+
+    @staticmethod
+    def robustScaleFromQuantile(d2_quantile: float, factor: float = 1.0) -> float:
+        """ICP::robustScaleFromQuantile: factor * sqrt(d2_quantile); ValueError for what it refuses."""
+        lib = load_library()
+        out = np.zeros(1)
+        if lib.host_icp_robust_scale_from_quantile(float(d2_quantile), float(factor), _dp(out)) != 0:
+            raise ValueError(lib.host_last_error().decode())
+        return float(out[0])
+
     def alignBestByScore(self, points, covs, localMap: LocalMap, guesses) -> np.ndarray:
         """ICP::alignBestByScore -> the chosen pose; self.best is the chosen index, self.iterations / self.converged
         describe that hypothesis and self.evaluation is ICP::lastEvaluation()."""
@@ -323,6 +348,33 @@ class ICP:
         self.best, self.iterations, self.converged = int(best.value), int(it.value), bool(conv.value)
         self.evaluation = _evaluation(ev)
         return capi.pose_from_abi(pose)
+
+
+class _PointReportBuffers:
+    """The output arrays of host_icp_point_report / host_frame_point_report for a cloud of at most `capacity` points."""
+
+    def __init__(self, capacity: int, quantiles, per_point: bool):
+        self.q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        self.per_point, self.capacity = bool(per_point), int(capacity) if per_point else 0
+        self.d2, self.sq, self.w = (np.zeros(self.capacity) for _ in range(3))
+        self.status = np.zeros(self.capacity, dtype=np.uint8)
+        self.counts = np.zeros(5, dtype=np.uint64)
+        self.quantiles = np.zeros(max(self.q.size, 1))
+
+    def args(self):
+        give = self.per_point and self.capacity > 0
+        return (self.q.size, _dp(self.q) if self.q.size else None, 1 if self.per_point else 0, self.capacity,
+                _dp(self.d2) if give else None, _dp(self.sq) if give else None, _dp(self.w) if give else None,
+                self.status.ctypes.data_as(C.POINTER(C.c_uint8)) if give else None,
+                self.counts.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(self.quantiles))
+
+    def report(self) -> "capi.PointReport":
+        n = min(int(self.counts[0]), self.capacity)
+        cut = (lambda a: a[:n].copy()) if self.per_point else (lambda a: None)
+        return capi.PointReport(points=int(self.counts[0]), matched=int(self.counts[1]), counted=int(self.counts[2]),
+                                negative=int(self.counts[3]), not_finite=int(self.counts[4]),
+                                quantiles=self.quantiles[:self.q.size].copy(), d2=cut(self.d2), sq_error=cut(self.sq),
+                                weight=cut(self.w), status=cut(self.status))
 
 
 def _evaluation(row) -> "capi.PoseEvaluation":
@@ -429,6 +481,17 @@ class Frame:
         _check(self._lib, self._lib.host_frame_evaluate(self._h, preprocessor._h, icp._h, localMap._h, g.shape[0],
                                                         _dp(g), int(mutate), _dp(out), C.byref(res)))
         return [_evaluation(row) for row in out], bool(res.value)
+
+    def pointReport(self, preprocessor: "CloudPreprocessor", icp: "ICP", localMap: "LocalMap", pose, quantiles=(),
+                    perPoint: bool = True):
+        """process(states, meas), then ICP::pointReport on the prepared cloud (no map update)
+        -> (capi.PointReport, used_resident)."""
+        buf = _PointReportBuffers(self._pts.shape[0], quantiles, perPoint)
+        T = capi.pose_to_abi(pose)
+        res = C.c_int32(0)
+        _check(self._lib, self._lib.host_frame_point_report(self._h, preprocessor._h, icp._h, localMap._h, _dp(T),
+                                                            *buf.args(), C.byref(res)))
+        return buf.report(), bool(res.value)
 
     def hypotheses(self, preprocessor: "CloudPreprocessor", icp: "ICP", localMap: "LocalMap", guesses):
         """process(states, meas), then ICP::alignHypotheses on the cloud it left resident (no map update) ->

@@ -328,6 +328,43 @@ int host_icp_evaluate(
     });
 }
 
+// One ICP::PointReport into the caller's arrays: counts5 = points, matched, counted, negative, notFinite; quantiles as
+// asked; the per-point arrays (each optional, `capacity` entries) receive the report's, which the caller trims to points.
+static void packPointReport(
+  const ICP::PointReport & r, size_t capacity, double * d2, double * sq_error, double * weight, uint8_t * status,
+  uint64_t * counts5, double * quantiles)
+{
+  counts5[0] = r.points; counts5[1] = r.matched; counts5[2] = r.counted; counts5[3] = r.negative; counts5[4] = r.notFinite;
+  for (size_t j = 0; j < r.quantiles.size(); ++j) {quantiles[j] = r.quantiles[j];}
+  const size_t n = std::min(capacity, r.d2.size());
+  if (d2) {std::memcpy(d2, r.d2.data(), n * sizeof(double));}
+  if (sq_error) {std::memcpy(sq_error, r.squaredError.data(), n * sizeof(double));}
+  if (weight) {std::memcpy(weight, r.weight.data(), n * sizeof(double));}
+  if (status) {std::memcpy(status, r.status.data(), n);}
+}
+
+// icp->pointReport(cloud, localMap, pose, quantiles, per_point) on a cloud built from the arrays (not resident: one upload).
+int host_icp_point_report(
+  ICP * icp, size_t n, const double * points, const double * covs, const LocalMap * map, const double pose[16],
+  size_t nq, const double * q, int per_point, size_t capacity, double * d2, double * sq_error, double * weight,
+  uint8_t * status, uint64_t * counts5, double * quantiles, int32_t * used_resident)
+{
+  return guarded(
+    [&] {
+      const PointCloud cloud = makeCloud(n, points, covs);
+      const auto r = icp->pointReport(
+        cloud, *map, ESKF_LIO::shim::poseFromData(pose), std::vector<double>(q, q + nq), per_point != 0);
+      packPointReport(r, capacity, d2, sq_error, weight, status, counts5, quantiles);
+      if (used_resident) {*used_resident = icp->lastUsedResidentScan() ? 1 : 0;}
+    });
+}
+
+// ICP::robustScaleFromQuantile; a refusal is status 1 with the text in host_last_error
+int host_icp_robust_scale_from_quantile(double d2_quantile, double factor, double * out)
+{
+  return guarded([&] {*out = ICP::robustScaleFromQuantile(d2_quantile, factor);});
+}
+
 // icp->alignBestByScore(cloud, localMap, guesses): *best the chosen index, best_pose its pose, iterations / converged
 // of that hypothesis, evaluation (31 doubles) = icp->lastEvaluation().
 int host_icp_align_best_by_score(
@@ -507,6 +544,23 @@ int host_frame_evaluate(
       for (size_t h = 0; h < k; ++h) {g[h] = ESKF_LIO::shim::poseFromData(poses + 16 * h);}
       const auto all = icp->evaluate(*f->meas->cloud, *map, g);
       for (size_t h = 0; h < all.size(); ++h) {packEvaluation(all[h], out + 31 * h);}
+      if (used_resident) {*used_resident = icp->lastUsedResidentScan() ? 1 : 0;}
+    });
+}
+
+// process(states, meas), then icp->pointReport(*meas.cloud, localMap, pose, quantiles, per_point) on the cloud process()
+// just stamped (no map update): the report of the resident scan.  Outputs as host_icp_point_report.
+int host_frame_point_report(
+  HostFrame * f, const CloudPreprocessor * p, ICP * icp, LocalMap * map, const double pose[16], size_t nq,
+  const double * q, int per_point, size_t capacity, double * d2, double * sq_error, double * weight, uint8_t * status,
+  uint64_t * counts5, double * quantiles, int32_t * used_resident)
+{
+  return guarded(
+    [&] {
+      p->process(f->states, f->meas);
+      const auto r = icp->pointReport(
+        *f->meas->cloud, *map, ESKF_LIO::shim::poseFromData(pose), std::vector<double>(q, q + nq), per_point != 0);
+      packPointReport(r, capacity, d2, sq_error, weight, status, counts5, quantiles);
       if (used_resident) {*used_resident = icp->lastUsedResidentScan() ? 1 : 0;}
     });
 }

@@ -635,6 +635,17 @@ class Odometry:
         return self.trajectory
 
 
+ROBUST_SCALE_RANGE = (1e-6, (2 ** 31 - 1) / 1e6)         # VGICP_OPTION_ROBUST_SCALE_MICRO: 1 .. INT32_MAX millionths
+
+
+def robust_scale_from_quantile(d2_quantile: float) -> Optional[float]:
+    """registration.robust_scale_quantile: the scale c = sqrt(quantile of d^2), clamped to the option's range; None when
+    nothing was ranked (NaN): the scale then stays as it is."""
+    if not d2_quantile >= 0.0:
+        return None
+    return float(min(max(np.sqrt(d2_quantile), ROBUST_SCALE_RANGE[0]), ROBUST_SCALE_RANGE[1]))
+
+
 class GpuBackend:
     """The MI355X path behind the C++ mirror of the reference's classes (eskf_lio_amd/host.py)."""
 
@@ -656,19 +667,35 @@ class GpuBackend:
         self.pre = host.CloudPreprocessor(config["cloud_preprocessor"]["voxel_size"], config["lidar_extrinsic"])
         self.iterations: List[int] = []
         self.converged: List[bool] = []                     # of the aligns with a prior
+        # optional key (vgicp_hip_points.h): before each align the scale becomes sqrt(this quantile of d^2 at the guess)
+        self.scale_quantile = reg.get("robust_scale_quantile")
+        self.robust = (reg.get("robust_kernel") or "none", float(reg.get("gate", 0.0)))
+        self.scales: List[Tuple[float, float]] = []         # per align: (the quantile of d^2, the scale set)
 
     def preprocess(self, states, points, pointTime):
         if states is None:
             states = np.zeros((0, 8))
         return self.pre.process(states, points, pointTime)
 
+    def _scale_from_quantile(self, points, covs, guess):
+        if self.scale_quantile is None:
+            return
+        from . import capi
+        rep = self.icp.pointReport(points, covs, self.map, guess, [float(self.scale_quantile)], perPoint=False)
+        c = robust_scale_from_quantile(float(rep.quantiles[0]))
+        if c is not None:
+            _, c, _ = self.icp.setRobust(capi.ROBUST_KERNELS[self.robust[0]], c, self.robust[1])
+            self.scales.append((float(rep.quantiles[0]), c))
+
     def align(self, points, covs, guess):
+        self._scale_from_quantile(points, covs, guess)
         T = self.icp.align(points, covs, self.map, guess)
         self.iterations.append(self.icp.iterations)
         return T
 
     def align_with_prior(self, points, covs, guess, information):
         """ICP::alignWithPrior + ICP::posteriorInformation (kalman_filter.update.iterated)."""
+        self._scale_from_quantile(points, covs, guess)
         T = self.icp.alignWithPrior(points, covs, self.map, guess, information)
         self.iterations.append(self.icp.iterations)
         self.converged.append(self.icp.converged)
@@ -705,11 +732,25 @@ class DeviceBackend:
         if self.reg.get("robust_kernel") is not None or self.reg.get("gate"):   # optional keys (vgicp_hip_robust.h)
             self.ctx.set_robust(self.reg.get("robust_kernel") or "none", float(self.reg.get("robust_scale", 1.0)),
                                 float(self.reg.get("gate", 0.0)))
+        # optional key (vgicp_hip_points.h): before each align the scale becomes sqrt(this quantile of d^2 at the guess)
+        self.scale_quantile = self.reg.get("robust_scale_quantile")
+        self.scales: List[Tuple[float, float]] = []         # per align: (the quantile of d^2, the scale set)
         self.voxel = config["cloud_preprocessor"]["voxel_size"]
         self.T_il = np.asarray(config["lidar_extrinsic"], dtype=np.float64)
         self.iterations: List[int] = []
         self.converged: List[bool] = []                     # of the aligns with a prior
         self.kept: List[int] = []
+
+    def _scale_from_quantile(self, guess):
+        """The resident scan reported at the predicted pose; kernel and gate stay as configured."""
+        if self.scale_quantile is None:
+            return
+        rep = self.ctx.points_resident(guess, [float(self.scale_quantile)], d2=False, sq_error=False, weight=False,
+                                       status=False)
+        c = robust_scale_from_quantile(float(rep.quantiles[0]))
+        if c is not None:
+            _, c, _ = self.ctx.set_robust(self.reg.get("robust_kernel") or "none", c, float(self.reg.get("gate", 0.0)))
+            self.scales.append((float(rep.quantiles[0]), c))
 
     def preprocess(self, states, points, pointTime):
         kept, _ = self.ctx.scan_prepare(points, pointTime, states, self.T_il, self.voxel, 30)
@@ -717,6 +758,7 @@ class DeviceBackend:
         return None, None                                   # the prepared scan is on the device
 
     def align(self, points, covs, guess):
+        self._scale_from_quantile(guess)
         r = self.ctx.align_resident(guess, self.reg["max_iteration"], self.reg["translation_sq_threshold"],
                                     self.reg["cosine_threshold"])
         self.iterations.append(r.iterations)
@@ -727,6 +769,7 @@ class DeviceBackend:
         G^-T A G^-1 + information: A the data's information at the returned pose (vgicp_evaluate_resident), G the chart's
         Jacobian there (vgicp_pose_prior_chart).  The prior is cleared again."""
         from . import capi
+        self._scale_from_quantile(guess)
         self.ctx.set_pose_prior(guess, information)
         try:
             r = self.ctx.align_resident(guess, self.reg["max_iteration"], self.reg["translation_sq_threshold"],

@@ -21,6 +21,8 @@
 // setPrior / clearPrior / alignWithPrior / posteriorInformation: a Gaussian prior on the pose in every round of the align
 // (vgicp_hip_prior.h) — the pose block of the filter's covariance, so that the pose returned is the MAP estimate and
 // ErrorStateKF::update can run as an iterated update (INTEGRATION.md has the patch).  No prior set: align() as ever.
+// pointReport / robustScaleFromQuantile: a cloud at a pose, point by point (vgicp_hip_points.h) — matched or not, |e|^2,
+// d^2, the weight this ICP's robust settings give the point — and order statistics of d^2 to choose a scale or gate by.
 #ifndef ESKF_LIO_SHIM_REGISTRATION_HPP_
 #define ESKF_LIO_SHIM_REGISTRATION_HPP_
 
@@ -38,12 +40,15 @@
 #include "../vgicp_hip_evaluate.h"
 #include "../vgicp_hip_robust.h"
 #include "../vgicp_hip_prior.h"
+#include "../vgicp_hip_points.h"
 
 // referenced weakly, as LocalMap.hpp references the raw-point store's entry points: a program that links a stand-in of
 // the C ABI without them, or that does not link libvgicp_hip_prior.so beside libvgicp_hip.so, still links, and
 // ICP::setPrior then says so
 #pragma weak vgicp_set_pose_prior
 #pragma weak vgicp_pose_prior_chart
+// ... and libvgicp_hip_points.so's: ICP::pointReport says so
+#pragma weak vgicp_points_resident
 
 namespace ESKF_LIO
 {
@@ -441,6 +446,94 @@ public:
     lastUsedResidentScan_ = residentScanOrUpload(ctx, cloud, "evaluate");
     shim::TraceScope tsCall(shim::Trace::AlignCall);
     return evaluateResidentScan(ctx, poses);
+  }
+
+  // A cloud at a pose, point by point (one call of vgicp_points_resident).
+  struct PointReport
+  {
+    uint64_t points = 0;       // of the cloud
+    uint64_t matched = 0;      // points whose voxel is in the map at the pose: Evaluation::correspondences there
+    uint64_t counted = 0;      // points with weight > 0 under this ICP's robust settings: a robust round's count
+    uint64_t negative = 0;     // matched, raw d^2 < 0 (an indefinite covariance)
+    uint64_t notFinite = 0;    // matched, raw d^2 NaN or infinite
+    std::vector<double> quantiles;      // one order statistic of d^2 per requested quantile, NaN when nothing is ranked
+    // per point, in the cloud's order; empty when perPoint was false.  A point without a voxel: +infinity, +infinity, 0, 0
+    std::vector<double> d2;             // raw e^T W e, so that d2[i] <= g is "a round gated at g counts point i"
+    std::vector<double> squaredError;   // |e|^2
+    std::vector<double> weight;
+    std::vector<uint8_t> status;        // VGICP_POINT_MATCHED | VGICP_POINT_NEGATIVE | VGICP_POINT_NOT_FINITE
+  };
+
+  // Reports `cloud` at `pose`: the resident scan when the cloud still is what CloudPreprocessor::process left on the
+  // device (as evaluate decides it), else ONE upload of the cloud.  quantiles: each in [0, 1], at most
+  // VGICP_POINT_QUANTILES_MAX; order statistics of max(d^2, 0) over the matched points with a finite d^2, never
+  // interpolated.  The weights are those of this ICP's robust settings (setRobust), which are put on the context first.
+  // Changes neither the map nor what a later align returns.
+  PointReport pointReport(
+    const PointCloud & cloud, const LocalMap & localMap, const Isometry3d & pose,
+    const std::vector<double> & quantiles = {}, bool perPoint = true)
+  {
+    if (!vgicp_points_resident) {
+      throw std::runtime_error("ICP::pointReport: the linked vgicp module has no vgicp_points_resident (libvgicp_hip_points.so)");
+    }
+    if (quantiles.size() > static_cast<size_t>(VGICP_POINT_QUANTILES_MAX)) {
+      throw std::runtime_error("ICP::pointReport: more than VGICP_POINT_QUANTILES_MAX quantiles");
+    }
+    vgicp_ctx * ctx = localMap.context();
+    applyRobust(ctx);
+    lastUsedResidentScan_ = residentScanOrUpload(ctx, cloud, "pointReport");
+    shim::TraceScope tsCall(shim::Trace::AlignCall);
+    PointReport out;
+    vgicp_point_summary summary{};
+    const double * q = quantiles.empty() ? nullptr : quantiles.data();
+    if (perPoint) {
+      // arrays of the host cloud's size; the resident scan says when it is larger (a deferred host copy has not
+      // delivered the prepared cloud yet: rule 10 of the header sets summary.points) and the call is made once more
+      size_t n = cloud.points_.size();
+      for (int attempt = 0;; ++attempt) {
+        out.d2.resize(n);
+        out.squaredError.resize(n);
+        out.weight.resize(n);
+        out.status.resize(n);
+        summary.points = 0;
+        const int rc = vgicp_points_resident(
+          ctx, shim::poseData(pose), n, n ? out.d2.data() : nullptr, n ? out.squaredError.data() : nullptr,
+          n ? out.weight.data() : nullptr, n ? out.status.data() : nullptr, quantiles.size(), q, &summary, nullptr);
+        if (attempt == 0 && static_cast<size_t>(summary.points) > n && (rc == VGICP_ERR_BAD_ARGUMENT || n == 0)) {
+          n = static_cast<size_t>(summary.points);
+          continue;
+        }
+        shim::check(ctx, rc, "vgicp_points_resident");
+        break;
+      }
+      n = static_cast<size_t>(summary.points);
+      out.d2.resize(n);
+      out.squaredError.resize(n);
+      out.weight.resize(n);
+      out.status.resize(n);
+    } else {
+      shim::check(
+        ctx, vgicp_points_resident(ctx, shim::poseData(pose), 0, nullptr, nullptr, nullptr, nullptr, quantiles.size(), q,
+        &summary, nullptr), "vgicp_points_resident");
+    }
+    out.points = summary.points;
+    out.matched = summary.matched;
+    out.counted = summary.counted;
+    out.negative = summary.negative;
+    out.notFinite = summary.not_finite;
+    out.quantiles.assign(summary.quantile, summary.quantile + quantiles.size());
+    return out;
+  }
+
+  // A robust scale c from a quantile of d^2 (PointReport::quantiles): factor * sqrt(d2Quantile).  c is compared with d
+  // (c^2 with d^2), so the points below that quantile keep full weight under Huber when factor is 1.  A NaN or
+  // non-positive quantile or factor (nothing ranked, or every ranked d^2 zero) is refused.
+  static double robustScaleFromQuantile(double d2Quantile, double factor = 1.0)
+  {
+    if (!(d2Quantile > 0.0) || !(factor > 0.0) || !std::isfinite(d2Quantile) || !std::isfinite(factor)) {
+      throw std::invalid_argument("ICP::robustScaleFromQuantile: the quantile of d^2 and the factor must be positive and finite");
+    }
+    return factor * std::sqrt(d2Quantile);
   }
 
   // Which hypothesis of a fan to keep, by the score of its RETURNED pose: a converged one goes before one that is not;

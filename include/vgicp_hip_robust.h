@@ -27,6 +27,8 @@
  * synthetic scene of tests/test_robust.py at the true pose, d^2 of the points that belong to the map has median 0.0023
  * and 99th percentile 0.032; points displaced by 9 cm have median 0.088.  To pick values for real data, score a pose
  * with vgicp_evaluate_resident, declared in vgicp_hip_evaluate.h: cost / correspondences is the mean d^2 at that pose.
+ * For the distribution itself, vgicp_points_resident, declared in vgicp_hip_points.h, returns d^2 and the weight of every
+ * point of the resident scan at a pose, and order statistics of d^2 (a median, a 99th percentile) to set c and g by.
  *
  * SCOPE.  The mode applies to vgicp_align, vgicp_align_resident and vgicp_align_resident_batch on a single-device
  * context.  While it is on

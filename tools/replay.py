@@ -10,6 +10,8 @@ options: --out traj.tum   --device-map (keep the voxel grid on the GPU only)   -
          export is timed at the end)
          --robust-kernel none|huber|cauchy  --robust-scale C  --gate G (robust rounds, include/vgicp_hip_robust.h: in the
          library's regularised units, ~0.1; off by default)
+         --robust-scale-quantile Q (registration.robust_scale_quantile: before each frame's align the scan is reported at
+         the predicted pose, include/vgicp_hip_points.h, and the scale becomes sqrt(quantile Q of d^2); off by default)
          --prior-update (kalman_filter.update.iterated: the filter's pose covariance enters every round of the align as a
          prior, include/vgicp_hip_prior.h, and the update is the iterated one; off by default)
 The configuration is the reference's config/hilti_config.yaml as a dict (eskf_lio_amd/replay.py:DEFAULT_CONFIG);
@@ -72,6 +74,9 @@ def main():
     ap.add_argument("--robust-scale", type=float, default=None, help="its scale c (registration.robust_scale)")
     ap.add_argument("--gate", type=float, default=None,
                     help="gate on the squared Mahalanobis residual, 0 = none (registration.gate)")
+    ap.add_argument("--robust-scale-quantile", type=float, default=None,
+                    help="the scale follows this quantile of d^2 at each frame's predicted pose "
+                         "(registration.robust_scale_quantile)")
     ap.add_argument("--prior-update", action="store_true",
                     help="the iterated filter update with the pose prior in every align (kalman_filter.update.iterated)")
     args = ap.parse_args()
@@ -82,7 +87,8 @@ def main():
         cfg, imu_topic, lidar_topic = config_from_yaml(args.config)
     imu_topic, lidar_topic = args.imu_topic or imu_topic, args.lidar_topic or lidar_topic
     robust = {k: v for k, v in (("robust_kernel", args.robust_kernel), ("robust_scale", args.robust_scale),
-                                ("gate", args.gate)) if v is not None}
+                                ("gate", args.gate), ("robust_scale_quantile", args.robust_scale_quantile))
+              if v is not None}
     if robust:
         cfg = dict(cfg, registration=dict(cfg["registration"], **robust))
     if args.prior_update:
@@ -107,6 +113,10 @@ def main():
     replay.write_tum(args.out, traj)
     print(f"{len(traj)} poses -> {args.out}; Gauss-Newton rounds per frame: {odo.backend.iterations}")
     print(odo.report())
+    if backend.scales:
+        cs = [c for _, c in backend.scales]
+        print(f"robust scale from the {args.robust_scale_quantile} quantile of d^2 at each predicted pose: "
+              f"min {min(cs):.4f}, median {float(np.median(cs)):.4f}, max {max(cs):.4f}")
     if args.raw_points_on_device:
         t0 = time.perf_counter()
         keys, _ = backend.ctx.map_points_export()
