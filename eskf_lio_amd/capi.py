@@ -61,6 +61,10 @@ POINTS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_points.s
 POINT_QUANTILES_MAX = 16
 POINT_MATCHED, POINT_NEGATIVE, POINT_NOT_FINITE = 1, 2, 4
 
+# every symbol include/vgicp_hip_map_gated.h declares: likewise, three entry points in a library of their own
+MAP_GATED_EXPORTS = ("vgicp_map_insert_resident_gated", "vgicp_map_insert_resident_gated_async", "vgicp_map_gated_totals")
+MAP_GATED_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_gated.so")
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -128,6 +132,13 @@ class PointSummary(C.Structure):
 
 class PointStats(C.Structure):
     _fields_ = [("launches", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double),
+                ("device_seconds", C.c_double)]
+
+
+class GatedInsertStats(C.Structure):
+    """vgicp_gated_insert_stats (vgicp_hip_map_gated.h), 64 bytes."""
+    _fields_ = [("points", C.c_uint64), ("matched", C.c_uint64), ("refused", C.c_uint64), ("not_finite", C.c_uint64),
+                ("new_voxels", C.c_uint64), ("launches", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double),
                 ("device_seconds", C.c_double)]
 
 
@@ -223,6 +234,16 @@ def load_library() -> C.CDLL:
                                                  C.POINTER(PointSummary), C.POINTER(PointStats)]
         points.vgicp_points_resident.restype = C.c_int
         lib.vgicp_points_resident = points.vgicp_points_resident
+    # the gated map insertion's library, likewise
+    if os.path.exists(MAP_GATED_LIB_PATH):
+        gated = C.CDLL(MAP_GATED_LIB_PATH, mode=C.RTLD_GLOBAL)
+        gated.vgicp_map_insert_resident_gated.argtypes = [vp, dp, sz, C.c_double, sz, C.POINTER(C.c_uint8),
+                                                          C.POINTER(GatedInsertStats)]
+        gated.vgicp_map_insert_resident_gated_async.argtypes = [vp, dp, sz, C.c_double]
+        gated.vgicp_map_gated_totals.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        for name in MAP_GATED_EXPORTS:
+            getattr(gated, name).restype = C.c_int
+            setattr(lib, name, getattr(gated, name))
     _lib = lib
     return lib
 
@@ -817,6 +838,30 @@ class Context:
     def map_insert_resident_async(self, transform, max_points_per_voxel: int):
         T = pose_to_abi(transform)
         self._check(self._lib.vgicp_map_insert_resident_async(self._h, _dp(T), int(max_points_per_voxel)))
+
+    def map_insert_resident_gated(self, transform, max_points_per_voxel: int, gate: float, kept: bool = True):
+        """vgicp_map_insert_resident_gated (vgicp_hip_map_gated.h): insert the resident scan without the points that are
+        matched at `transform` and fail max(d^2, 0) <= gate.  Returns (kept, stats): a uint8 array, 1 kept and 0 refused
+        (None unless asked), and the call's GatedInsertStats."""
+        T = pose_to_abi(transform)
+        st = GatedInsertStats()
+        n = self.points_size() if kept else 0
+        a_kept = np.zeros(n, dtype=np.uint8) if kept else None
+        self._check(self._lib.vgicp_map_insert_resident_gated(
+            self._h, _dp(T), int(max_points_per_voxel), float(gate), n,
+            a_kept.ctypes.data_as(C.POINTER(C.c_uint8)) if kept else None, C.byref(st)))
+        return a_kept, st
+
+    def map_insert_resident_gated_async(self, transform, max_points_per_voxel: int, gate: float):
+        T = pose_to_abi(transform)
+        self._check(self._lib.vgicp_map_insert_resident_gated_async(self._h, _dp(T), int(max_points_per_voxel),
+                                                                    float(gate)))
+
+    def map_gated_totals(self):
+        """(points seen, points refused) by this context's gated insertions since the last map_reset."""
+        p, r = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vgicp_map_gated_totals(self._h, C.byref(p), C.byref(r)))
+        return int(p.value), int(r.value)
 
     def frame_stats(self, reset: bool = False) -> FrameStats:
         st = FrameStats()

@@ -58,7 +58,7 @@ int vgicp_internal::create_context(int device_id, uint32_t max_persist_grid, vgi
   VG_HIP(nullptr, ctx->stream.create());
   // the insertion's running totals (4 words) sit right behind the counter block: ONE copy after a preparation brings
   // both back, so a deferred insertion needs no copy of its own in the frame chain
-  // ... and behind those the raw-point log's words (kInsertWords: 4 + 4)
+  // ... and behind those the raw-point log's words (4 + 4) and a gated insertion's totals (kInsertWords: 4 + 4 + 4)
   VG_HIP(nullptr, ctx->d_counters.alloc((kCounterWords + kInsertWords) * sizeof(uint32_t)));
   VG_HIP(nullptr, ctx->h_counters.alloc(kCounterWords * sizeof(uint32_t)));
   VG_HIP(nullptr, ctx->h_prep.alloc((kCounterWords + kInsertWords) * sizeof(uint32_t)));

@@ -53,12 +53,28 @@ bool resident_lists_stay_short(const vgicp_ctx* ctx) {
 // staging area beside its upload, or nullptr: the staging area itself, made large enough here.  deferred: the counts go
 // to the running totals behind the counter block and nothing is waited for; settle() (or the next preparation's counter
 // copy) reads them.  Else the call returns with the map's new size known.
+// gate (the RESIDENT scan only, scratch nullptr): the insertion is a gated one (include/vgicp_hip_map_gated.h).  The
+// decision is launched here, behind whatever growth the table needed and in front of the first claim, as a launch of its
+// own; its keep plane lies behind the insertion's scratch in the staging area.
+struct GateCall {
+  double gate;
+  uint8_t* kept;            // the caller's array (synchronous entry), or nullptr
+  bool timed;               // ev_begin / ev_end around the launches
+};
 int insert_points(vgicp_ctx* ctx, const double* d_points, const double* d_covs, size_t n, const double transform[16],
-                  size_t max_points_per_voxel, void* scratch, bool short_lists, bool deferred, size_t* new_voxels) {
+                  size_t max_points_per_voxel, void* scratch, bool short_lists, bool deferred, size_t* new_voxels,
+                  const GateCall* gate = nullptr) {
   VG_RC(ensure_table(ctx, n));  // every point may open a voxel (grows / rehashes with a synchronisation when it has to)
   VG_RC(ensure_raw(ctx, n));    // ... and be kept (the log likewise)
   const size_t sb = map_insert_scratch_bytes((uint32_t)n);
-  if (!scratch) {
+  uint8_t* keep = nullptr;
+  if (gate) {
+    StageLayout lay;
+    const size_t o_scratch = lay.take(sb), o_keep = lay.take(n);
+    VG_RC(ensure_stage(ctx, lay.total));
+    scratch = stage_at<char>(ctx, o_scratch);
+    keep = stage_at<uint8_t>(ctx, o_keep);
+  } else if (!scratch) {
     VG_RC(ensure_stage(ctx, sb));
     scratch = ctx->d_stage;
   }
@@ -70,15 +86,49 @@ int insert_points(vgicp_ctx* ctx, const double* d_points, const double* d_covs, 
   } else {
     VG_RC(begin_map_update(ctx));
   }
+  if (gate) {
+    GateArgs g;
+    std::memset(&g, 0, sizeof g);
+    g.scan = ctx->d_scan;
+    g.stride = ctx->stride;
+    g.n = (uint32_t)n;
+    g.mask = (uint32_t)(ctx->slots - 1);
+    g.table = ctx->table;
+    g.voxel_size = ctx->voxel_size;
+    for (int k = 0; k < 12; ++k) g.pose[k] = pose12[k];
+    g.asym_dev = (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
+    g.scan_seq = ctx->scan_seq;
+    g.gate = gate->gate;
+    g.keep = keep;
+    g.counters = ctx->d_ins_counters + kGateWord;
+    if (gate->timed) VG_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
+    VG_HIP(ctx, launch_gate_decide(ctx->stream, g));
+  }
   VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size, d_points, d_covs,
                                 (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, scratch, sb,
-                                deferred ? ctx->d_ins_counters : ctx->d_counters, short_lists, raw_log(ctx)));
-  if (!deferred) return finish_insert(ctx, new_voxels);
+                                deferred ? ctx->d_ins_counters : ctx->d_counters, short_lists, raw_log(ctx), keep));
+  if (gate && gate->timed) VG_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
+  if (!deferred) {
+    // the synchronous gated entry: its counts and the keep plane ride on finish_insert's wait.  The insertion is enqueued
+    // by now, so a copy that cannot be enqueued must not keep finish_insert from taking the map's new size: it is
+    // reported behind it
+    int rc_gate = VGICP_OK;
+    if (gate) {
+      const hipError_t e = hipMemcpyAsync(ctx->h_ins_counters + kGateWord, ctx->d_ins_counters + kGateWord,
+                                          kGateCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+      if (e != hipSuccess) rc_gate = fail_hip(ctx, e, "hipMemcpyAsync(gate counters)");
+      arena_reset(ctx);
+      if (rc_gate == VGICP_OK && gate->kept) rc_gate = user_d2h(ctx, gate->kept, keep, n);
+    }
+    const int rc = finish_insert(ctx, new_voxels);
+    return rc != VGICP_OK ? rc : rc_gate;
+  }
   if (ctx->stage_events) { VG_HIP(ctx, hipEventRecord(ctx->ev_stage[5], ctx->stream)); ctx->ev_stage_set[5] = true; }
   ctx->insert_pending = true;
   ctx->ins_copy_enqueued = false;   // the next preparation's counter copy carries the totals (or settle() fetches them)
   ctx->insert_pending_upper = n;
   if (ctx->raw_on) ctx->raw_used_upper += n;
+  ctx->gate_pending = gate != nullptr;
   return VGICP_OK;
 }
 // what is still pending on the context (a prepared scan's size, an earlier frame's insertion) is settled by one synchronisation
@@ -97,6 +147,7 @@ int vgicp_map_reset(vgicp_ctx* ctx, double voxel_size, size_t capacity_hint) {
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->table.reset();
   ctx->slots = ctx->voxels = ctx->tombstones = 0;
+  ctx->gated_points = ctx->gated_refused = 0;
   ++ctx->map_version;
   ctx->voxel_size = voxel_size;
   ctx->raw_hint = capacity_hint;

@@ -110,8 +110,9 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
     if (staged->done) VG_HIP(ctx, hipEventRecord(staged->done, ctx->stream));
     VG_HIP(ctx, launch_prepare_tail(ctx->stream, a));
   }
-  // (+ the raw-point log's words when the map keeps raw points)
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_prep, ctx->d_counters, (kCounterWords + (ctx->raw_on ? kInsertWords : 4)) * sizeof(uint32_t),
+  // (+ the raw-point log's words when the map keeps raw points, + a pending gated insertion's)
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_prep, ctx->d_counters,
+                             (kCounterWords + (ctx->gate_pending ? kInsertWords : ctx->raw_on ? kInsertWordsRaw : 4)) * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, ctx->stream));
   if (ctx->insert_pending && !ctx->ins_copy_enqueued) {   // the deferred insertion's totals travel with this copy
     ctx->ins_copy_enqueued = true;
@@ -150,7 +151,7 @@ int resolve_prepare(vgicp_ctx* ctx, uint32_t* kept) {
 // A deferred insertion whose totals no copy has picked up yet (no preparation followed it): a copy of its own, now.
 int fetch_insert_totals(vgicp_ctx* ctx) {
   if (!ctx->insert_pending || ctx->ins_copy_enqueued) return VGICP_OK;
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_ins_counters, ctx->d_ins_counters, (ctx->raw_on ? 6 : 2) * sizeof(uint32_t),
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_ins_counters, ctx->d_ins_counters, (ctx->gate_pending ? kInsertWords : ctx->raw_on ? 6 : 2) * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, ctx->stream));
   ctx->ins_copy_enqueued = true;
   ctx->ins_from_prep = false;
@@ -168,6 +169,11 @@ int settle_insert(vgicp_ctx* ctx) {
   ctx->ins_seen[0] = totals[0];
   ctx->ins_seen[1] = totals[1];
   ctx->voxels += created;
+  if (ctx->gate_pending) {   // a gated insertion: what its decision refused (vgicp_map_gated_totals)
+    ctx->gate_pending = false;
+    ctx->gated_refused += (uint32_t)(totals[kGateWord + 1] - ctx->gate_seen[1]);
+    for (int k = 0; k < 3; ++k) ctx->gate_seen[k] = totals[kGateWord + k];
+  }
   if (failed) return fail(ctx, VGICP_ERR_TABLE_FULL, "voxel table probe sequence exhausted (deferred map insertion)");
   return raw_note(ctx, totals + 4);
 }

@@ -29,6 +29,7 @@
 #include "../../include/vgicp_hip_robust.h"
 #include "../../include/vgicp_hip_prior.h"
 #include "../../include/vgicp_hip_points.h"
+#include "../../include/vgicp_hip_map_gated.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -86,8 +87,12 @@ inline uint32_t next_nonzero(uint32_t& seq) {
 }
 
 // words behind the counter block (d_ins_counters): [0] [1] the deferred insertion's running totals, [2] [3] the
-// resident scan's symmetry verdicts, [4] [5] [6] the raw-point log (RawLog::ctr), [7] spare
-constexpr int kInsertWords = 8;
+// resident scan's symmetry verdicts, [4] [5] [6] the raw-point log (RawLog::ctr), [7] spare, [8] [9] [10] a gated insertion's
+// running totals (kGateCounters: matched, refused, not finite), [11] spare.  The copies that bring the block to the host
+// carry the first 2 / 4 / 6 / 8 words as before; all of them only while a gated insertion is pending
+constexpr int kInsertWords = 12;
+constexpr int kInsertWordsRaw = 8;    // up to the raw-point log's words
+constexpr int kGateWord = 8;
 constexpr int kDefaultChunk = 4;
 constexpr int kMaxChunksInFlight = 2;
 static_assert(kPlanTeamsMax == (uint32_t)kTeamsMax, "vgicp_align_plan.h plans with the team kernel's width");
@@ -463,6 +468,11 @@ struct vgicp_ctx {
   bool ins_copy_enqueued = false;    // some device-to-host copy behind the pending insertion carries its totals ...
   bool ins_from_prep = false;        // ... in the tail of h_prep (the next preparation's counter copy) rather than h_ins_counters
   uint64_t insert_pending_upper = 0;
+  // gated insertion (include/vgicp_hip_map_gated.h): the decision's running totals on the device (d_ins_counters +
+  // kGateWord), what the host has read of them, and the totals since vgicp_map_reset
+  uint32_t gate_seen[3] = {0, 0, 0};
+  bool gate_pending = false;         // the pending insertion is a gated one: its totals travel with the insertion's
+  uint64_t gated_points = 0, gated_refused = 0;
   // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
   // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
@@ -625,6 +635,12 @@ int align_batch_sequential(vgicp_ctx* ctx, size_t k, const double* guesses, cons
 int points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, double* d2, double* sq_error, double* weight,
                     uint8_t* status, size_t n_quantiles, const double* q, vgicp_point_summary* summary,
                     vgicp_point_stats* stats);
+// The entry points of include/vgicp_hip_map_gated.h behind libvgicp_hip_map_gated.so, which has made the handshake
+// (vgicp_capi_map_gated.inl).
+int map_insert_resident_gated(vgicp_ctx* ctx, const double transform[16], size_t max_points_per_voxel, double gate,
+                              size_t capacity, uint8_t* kept, vgicp_gated_insert_stats* stats);
+int map_insert_resident_gated_async(vgicp_ctx* ctx, const double transform[16], size_t max_points_per_voxel, double gate);
+int map_gated_totals(vgicp_ctx* ctx, uint64_t* points, uint64_t* refused);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

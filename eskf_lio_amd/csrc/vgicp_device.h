@@ -271,8 +271,31 @@ struct PointPickArgs {
   unsigned long long* out;   // page-locked, kPointResultWords: the four counts, then the quantiles' bit patterns
 };
 
+// The decision of a gated map insertion (vgicp_map_insert_resident_gated, include/vgicp_hip_map_gated.h): one launch
+// forms every point's term at the pose as point_terms_kernel forms it (ONE definition: point_term) and writes one keep
+// byte per point: 0 iff the point is matched and not max(raw, 0) <= gate (a NaN or infinite raw fails every gate, +inf
+// included).  Read-only on the table; the insertion that claims slots is a later launch.  counters: 3 device words that
+// only ever grow (running totals; the host remembers what it has read): matched, refused, not finite.
+constexpr int kGateCounters = 3;
+struct GateArgs {
+  const double* scan;  // SoA planes
+  uint64_t stride;
+  uint32_t n;
+  uint32_t mask;
+  const VoxelRecord* table;
+  double voxel_size;
+  double pose[12];           // R column-major (9), t (3)
+  const uint32_t* asym_dev;  // as IterArgs
+  uint32_t scan_seq;
+  uint32_t pad;
+  double gate;               // >= 0 or +inf
+  uint8_t* keep;             // n
+  uint32_t* counters;
+};
+
 // ---- launchers (defined in vgicp_kernels.hip) ----
 hipError_t launch_point_terms(hipStream_t s, const PointArgs& args);
+hipError_t launch_gate_decide(hipStream_t s, const GateArgs& args);
 hipError_t launch_point_pick(hipStream_t s, const PointPickArgs& args);
 // Rows of `poses` poses (grid: rows_per_pose x poses workgroups of 512 threads), and their fold into out[poses][kSlots]:
 // slots 0-26 the normal equations, 27 the count, 28 the cost, 29 the squared error.
@@ -489,11 +512,13 @@ struct RawLog {
   uint32_t capacity = 0;
   uint32_t* ctr = nullptr;
 };
+// keep (launch_map_insert): one byte per point, 0 = the point is not inserted (a gated insertion refused it: no probe, no
+// claim, not counted as lost), or nullptr: every point is.
 hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, double voxel_size,
                              const double* points_aos, const double* covs_aos, uint32_t n,
                              const double pose12[12], uint64_t max_points, void* scratch,
                              size_t scratch_bytes, uint32_t* counters, bool short_lists = false,
-                             const RawLog& raw = RawLog());
+                             const RawLog& raw = RawLog(), const uint8_t* keep = nullptr);
 // The log's live entries (slot FULL in `table`; with `claimed`, the rehash's old-slot -> new-slot words, those whose
 // old slot was carried over, renamed to the new slot) appended to dst; ctr[2] (zero before) counts them.  The source
 // holds *ctr[0] entries, at most `src_upper`; `slots`: of `table` (or of the old table that `claimed` covers).

@@ -962,6 +962,56 @@ __global__ __launch_bounds__(512) void evaluate_fold_kernel(const double* __rest
   }
 }
 
+// The term of point i, for point_terms_kernel and gate_decide_kernel (Args: PointArgs or GateArgs): the ONE definition.
+struct PointTerm {
+  double raw, sq;   // e^T W e and |e|^2; +infinity when the point's voxel is not in the map
+  bool matched;
+};
+template <class Args>
+__device__ __forceinline__ PointTerm point_term(const Args& a, uint32_t i, bool cov_sym) {
+  double q[kScanPlanes];
+  load_point_sym(a.scan, a.stride, i, q, cov_sym);
+  double R[9], t[3], C[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { R[k] = a.pose[k]; C[k] = q[3 + k]; }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) t[k] = a.pose[9 + k];
+  const double inv_voxel = 1.0 / a.voxel_size;
+  double p[3];
+  transform_point(R, t, q[0], q[1], q[2], p);
+  const int32_t kx = voxel_coord_fast(p[0], a.voxel_size, inv_voxel);
+  const int32_t ky = voxel_coord_fast(p[1], a.voxel_size, inv_voxel);
+  const int32_t kz = voxel_coord_fast(p[2], a.voxel_size, inv_voxel);
+  const VoxelRecord* rec = find_voxel(a.table, a.mask, kx, ky, kz);
+  PointTerm term{__builtin_inf(), __builtin_inf(), false};
+  if (rec != nullptr) {
+    term.matched = true;
+    double mu[3], S[9];
+    load_payload(rec, mu, S);
+    // S = R C R^T + C_voxel: accumulate_match's expressions
+    double RC[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+        RC[r + 3 * c] = R[r] * C[3 * c] + R[r + 3] * C[1 + 3 * c] + R[r + 6] * C[2 + 3 * c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+        S[r + 3 * c] += RC[r] * R[c] + RC[r + 3] * R[c + 3] + RC[r + 6] * R[c + 6];
+    double W[9];
+    inverse3_cofactor(S, W);
+    const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
+    const double g0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
+    const double g1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
+    const double g2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
+    term.raw = e0 * g0 + e1 * g1 + e2 * g2;
+    term.sq = e0 * e0 + e1 * e1 + e2 * e2;
+  }
+  return term;
+}
+
 // The resident scan at a pose, point by point (vgicp_points_resident, include/vgicp_hip_points.h).  One point per
 // thread, 256 threads: the point's planes, ONE find_voxel probe, the payload, and the term as accumulate_match<..., ROBUST>
 // and evaluate_kernel form it (S = R C R^T + C_voxel by the same two loops, inverse3_cofactor, W e, then e . (W e)) —
@@ -974,45 +1024,11 @@ __global__ __launch_bounds__(256) void point_terms_kernel(PointArgs a) {
   const RobustSetting robust = robust_setting(a.robust_kernel, a.robust_scale2, a.robust_gate);
   bool matched = false, counted = false, negative = false, not_finite = false;
   if (i < a.n) {
-    double q[kScanPlanes];
-    load_point_sym(a.scan, a.stride, i, q, cov_sym);
-    double R[9], t[3], C[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { R[k] = a.pose[k]; C[k] = q[3 + k]; }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = a.pose[9 + k];
-    const double inv_voxel = 1.0 / a.voxel_size;
-    double p[3];
-    transform_point(R, t, q[0], q[1], q[2], p);
-    const int32_t kx = voxel_coord_fast(p[0], a.voxel_size, inv_voxel);
-    const int32_t ky = voxel_coord_fast(p[1], a.voxel_size, inv_voxel);
-    const int32_t kz = voxel_coord_fast(p[2], a.voxel_size, inv_voxel);
-    const VoxelRecord* rec = find_voxel(a.table, a.mask, kx, ky, kz);
-    double raw = __builtin_inf(), sq = __builtin_inf(), w = 0.0;
-    if (rec != nullptr) {
+    const PointTerm term = point_term(a, i, cov_sym);
+    const double raw = term.raw, sq = term.sq;
+    double w = 0.0;
+    if (term.matched) {
       matched = true;
-      double mu[3], S[9];
-      load_payload(rec, mu, S);
-      // S = R C R^T + C_voxel: accumulate_match's expressions
-      double RC[9];
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-          RC[r + 3 * c] = R[r] * C[3 * c] + R[r + 3] * C[1 + 3 * c] + R[r + 6] * C[2 + 3 * c];
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-          S[r + 3 * c] += RC[r] * R[c] + RC[r + 3] * R[c + 3] + RC[r + 6] * R[c + 6];
-      double W[9];
-      inverse3_cofactor(S, W);
-      const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
-      const double g0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
-      const double g1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
-      const double g2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
-      raw = e0 * g0 + e1 * g1 + e2 * g2;
-      sq = e0 * e0 + e1 * e1 + e2 * e2;
       w = robust_weight(robust, raw);
       counted = w > 0.0;
       not_finite = !(fabs(raw) < __builtin_inf());
@@ -1037,6 +1053,33 @@ __global__ __launch_bounds__(256) void point_terms_kernel(PointArgs a) {
     if (c_counted) atomicAdd(&a.counters[1], (uint32_t)c_counted);
     if (c_negative) atomicAdd(&a.counters[2], (uint32_t)c_negative);
     if (c_not_finite) atomicAdd(&a.counters[3], (uint32_t)c_not_finite);
+  }
+}
+
+// The decision of a gated map insertion (GateArgs, vgicp_device.h): the same point, probe and term, and one keep byte.
+// A point is refused iff it is matched and not max(raw, 0) <= gate: a NaN or infinite raw fails the comparison at every
+// gate, a negative raw counts as 0, an unmatched point opens new ground and is kept.  Read-only on the table and
+// waiting on nothing: the claims of the insertion are a later launch, so no claim in flight is ever seen here.
+__global__ __launch_bounds__(256) void gate_decide_kernel(GateArgs a) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool cov_sym = a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
+  bool matched = false, refused = false, not_finite = false;
+  if (i < a.n) {
+    const PointTerm term = point_term(a, i, cov_sym);
+    matched = term.matched;
+    if (matched) {
+      not_finite = !(fabs(term.raw) < __builtin_inf());
+      refused = not_finite || !(fmax(term.raw, 0.0) <= a.gate);
+    }
+    a.keep[i] = refused ? (uint8_t)0 : (uint8_t)1;
+  }
+  const int c_matched = __syncthreads_count(matched ? 1 : 0);
+  const int c_refused = __syncthreads_count(refused ? 1 : 0);
+  const int c_not_finite = __syncthreads_count(not_finite ? 1 : 0);
+  if (threadIdx.x == 0) {
+    if (c_matched) atomicAdd(&a.counters[0], (uint32_t)c_matched);
+    if (c_refused) atomicAdd(&a.counters[1], (uint32_t)c_refused);
+    if (c_not_finite) atomicAdd(&a.counters[2], (uint32_t)c_not_finite);
   }
 }
 
@@ -2520,6 +2563,12 @@ hipError_t launch_point_terms(hipStream_t s, const PointArgs& args) {
     return hipErrorInvalidValue;
   if (args.n == 0) return hipSuccess;
   ++g_kernel_launches; hipLaunchKernelGGL(point_terms_kernel, dim3((args.n + 255u) / 256u), dim3(256), 0, s, args);
+  return hipGetLastError();
+}
+
+hipError_t launch_gate_decide(hipStream_t s, const GateArgs& args) {
+  if (args.n == 0) return hipSuccess;
+  ++g_kernel_launches; hipLaunchKernelGGL(gate_decide_kernel, dim3((args.n + 255u) / 256u), dim3(256), 0, s, args);
   return hipGetLastError();
 }
 

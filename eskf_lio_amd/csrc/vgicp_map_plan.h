@@ -81,7 +81,11 @@ enum class InsertEntry {
   Scan,            // vgicp_map_insert_scan: the scan comes from host buffers
   Resident,        // vgicp_map_insert_resident
   ResidentAsync,   // vgicp_map_insert_resident_async
-  Device           // vgicp_internal::map_insert_device: a multi-device context's replica, the scan is on its device
+  Device,          // vgicp_internal::map_insert_device: a multi-device context's replica, the scan is on its device
+  // include/vgicp_hip_map_gated.h: the resident entries' checks in the resident entries' order; what a gated entry
+  // refuses beyond them (transform entries, the gate, several devices, capacity) follows in plan_gate below
+  ResidentGated,       // vgicp_map_insert_resident_gated
+  ResidentGatedAsync   // vgicp_map_insert_resident_gated_async
 };
 struct InsertFacts {
   InsertEntry entry = InsertEntry::Scan;
@@ -102,7 +106,8 @@ struct InsertVerdict {
 inline InsertVerdict plan_insert(const InsertFacts& f) {
   const auto refuse = [](int status, const char* text) { return InsertVerdict{status, text, false}; };
   const InsertVerdict nothing{VGICP_OK, nullptr, true};
-  const bool resident = f.entry == InsertEntry::Resident || f.entry == InsertEntry::ResidentAsync;
+  const bool resident = f.entry == InsertEntry::Resident || f.entry == InsertEntry::ResidentAsync ||
+                        f.entry == InsertEntry::ResidentGated || f.entry == InsertEntry::ResidentGatedAsync;
   if (!f.has_table) return refuse(VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
   if (f.entry == InsertEntry::Scan && f.n == 0) return nothing;   // before it looks at a pointer
   if (resident && !f.scan_resident) return refuse(VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
@@ -114,6 +119,31 @@ inline InsertVerdict plan_insert(const InsertFacts& f) {
     return refuse(VGICP_ERR_BAD_ARGUMENT, "resident scan is a shard: use vgicp_map_insert_scan with the whole scan");
   if (!resident && f.n > 0x7FFFFFFFull) return refuse(VGICP_ERR_BAD_ARGUMENT, "scan too large");   // (the resident entries never had this check)
   return f.n == 0 ? nothing : InsertVerdict{};
+}
+
+// ---- what a gated insertion refuses once plan_insert has passed (include/vgicp_hip_map_gated.h, rules 4 to 7) ----
+struct GateFacts {
+  bool transform_finite = false;
+  double gate = 0.0;
+  bool several_devices = false;   // a multi-device, communicator or peer-connected context
+  bool kept_given = false;        // the synchronous entry, once settled: the caller's keep array ...
+  uint64_t capacity = 0;          // ... and its length
+  uint64_t n = 0;
+};
+struct GateVerdict {
+  int rule = 0;                   // 0: passed, else the header's number
+  int status = VGICP_OK;
+  const char* text = nullptr;
+};
+// finite and >= 0, or +inf
+inline bool gate_in_range(double gate) { return gate >= 0.0; }
+inline GateVerdict plan_gate(const GateFacts& f) {
+  if (!f.transform_finite) return GateVerdict{4, VGICP_ERR_BAD_ARGUMENT, "a transform entry is not finite"};
+  if (!gate_in_range(f.gate)) return GateVerdict{5, VGICP_ERR_BAD_ARGUMENT, "gate must be finite and >= 0, or +infinity"};
+  if (f.several_devices)
+    return GateVerdict{6, VGICP_ERR_BAD_ARGUMENT, "gated insertion works on a single-device context: the resident scan of a device is a shard here"};
+  if (f.kept_given && f.capacity < f.n) return GateVerdict{7, VGICP_ERR_BAD_ARGUMENT, "kept holds fewer than the scan's points"};
+  return GateVerdict{};
 }
 
 }  // namespace vgicp

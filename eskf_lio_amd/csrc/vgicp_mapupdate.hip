@@ -144,21 +144,26 @@ __device__ __forceinline__ uint32_t prepare_point(VoxelRecord* table, uint32_t m
 
 // LISTS: idx_of receives the point's `next` on its voxel's list (index + 1 of the point that headed the list before;
 // 0: this point found the list empty and is the voxel's leader) instead of the point's own index for the sort.
+// keep (may be nullptr): a point whose byte is 0 was refused by a gated insertion's decision (gate_decide_kernel, an
+// EARLIER launch): it probes nothing and claims nothing, is not "lost" (counters[1] stays "table full"), and takes
+// kNoSlot — behind every real slot in the sort, never the head of a segment — or, LISTS, stands on no list.
 template <bool LISTS>
 __global__ void insert_prepare_kernel(VoxelRecord* table, uint32_t mask, double voxel_size,
                                       const double* __restrict__ pts, const double* __restrict__ covs,
                                       uint32_t n, Pose12 pose, double* __restrict__ wpts,
                                       double* __restrict__ wcovs, uint32_t* __restrict__ slot_of,
-                                      uint32_t* __restrict__ idx_of, uint32_t* counters) {
+                                      uint32_t* __restrict__ idx_of, uint32_t* counters,
+                                      const uint8_t* __restrict__ keep) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   bool fresh = false, lost = false;
   if (i < n) {
-    const uint32_t found = prepare_point(table, mask, voxel_size, pts, covs, i, pose, wpts, wcovs, fresh);
-    lost = found == kNoSlot;
+    const bool refused = keep != nullptr && keep[i] == 0;
+    const uint32_t found = refused ? kNoSlot : prepare_point(table, mask, voxel_size, pts, covs, i, pose, wpts, wcovs, fresh);
+    lost = !refused && found == kNoSlot;
     slot_of[i] = found;
     if constexpr (LISTS) {
       uint32_t next = 0xFFFFFFFFu;  // on no list
-      if (!lost) next = atomicExch(reinterpret_cast<uint32_t*>(&table[found].reserved), i + 1u);
+      if (found != kNoSlot) next = atomicExch(reinterpret_cast<uint32_t*>(&table[found].reserved), i + 1u);
       idx_of[i] = next;
     } else {
       idx_of[i] = i;
@@ -484,7 +489,8 @@ size_t map_insert_scratch_bytes(uint32_t n) {
 hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, double voxel_size,
                              const double* points_aos, const double* covs_aos, uint32_t n,
                              const double pose12[12], uint64_t max_points, void* scratch,
-                             size_t scratch_bytes, uint32_t* counters, bool short_lists, const RawLog& raw) {
+                             size_t scratch_bytes, uint32_t* counters, bool short_lists, const RawLog& raw,
+                             const uint8_t* keep) {
   if (n == 0) return hipSuccess;
   if (scratch_bytes < map_insert_scratch_bytes(n)) return hipErrorInvalidValue;
   InsertScratch w = carve(scratch, n);
@@ -492,7 +498,8 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
   for (int k = 0; k < 12; ++k) pose.v[k] = pose12[k];
   if (short_lists) {
     ++g_kernel_launches; hipLaunchKernelGGL(insert_prepare_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table,
-                       mask, voxel_size, points_aos, covs_aos, n, pose, w.wpts, w.wcovs, w.slot_in, w.idx_in, counters);
+                       mask, voxel_size, points_aos, covs_aos, n, pose, w.wpts, w.wcovs, w.slot_in, w.idx_in, counters,
+                       keep);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (raw.entries) {
@@ -506,7 +513,7 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
   }
   ++g_kernel_launches; hipLaunchKernelGGL(insert_prepare_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, mask,
                      voxel_size, points_aos, covs_aos, n, pose, w.wpts, w.wcovs, w.slot_in, w.idx_in,
-                     counters);
+                     counters, keep);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // stable: equal slots keep ascending point index = scan order (the inputs are scratch from here on)

@@ -50,6 +50,10 @@ def load_library() -> C.CDLL:
     lib.host_localmap_drain.restype = sz
     lib.host_localmap_drain.argtypes = [vp]
     lib.host_localmap_update.argtypes = [vp, sz, dp, dp, dp, C.c_int]
+    lib.host_localmap_set_insert_gate.argtypes = [vp, C.c_double]
+    lib.host_localmap_insert_gate.restype = C.c_double
+    lib.host_localmap_insert_gate.argtypes = [vp]
+    lib.host_localmap_gated_totals.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.host_localmap_match.argtypes = [vp, sz, dp, dp, dp, dp, dp, dp, C.POINTER(sz)]
     lib.host_localmap_export.restype = sz
     lib.host_localmap_export.argtypes = [vp, sz, C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_uint64)]
@@ -157,6 +161,20 @@ class LocalMap:
     def savesRawPoints(self) -> bool:
         """True while save() writes every stored raw point, as the reference does."""
         return bool(self._lib.host_localmap_saves_raw_points(self._h))
+
+    def setInsertGate(self, gate: float):
+        """LocalMap::setInsertGate: 0 = off; > 0 keeps the points that fail max(d^2, 0) <= gate out of the map."""
+        if self._lib.host_localmap_set_insert_gate(self._h, float(gate)) != 0:
+            raise ValueError(self._lib.host_last_error().decode())
+
+    def insertGate(self) -> float:
+        return float(self._lib.host_localmap_insert_gate(self._h))
+
+    def gatedTotals(self):
+        """(points the gated insertions saw, points they refused, frames inserted whole while a gate was set)."""
+        out = (C.c_uint64 * 3)()
+        _check(self._lib, self._lib.host_localmap_gated_totals(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def drain(self) -> int:
         """Waits for the shadow grid's worker (LocalMap::grid()); the host grid's voxel count."""

@@ -107,6 +107,19 @@ int host_localmap_saves_raw_points(const LocalMap * map) {return map->savesRawPo
 // waits until the shadow grid's worker has filed every cloud handed to it (what LocalMap::grid() / save() do first);
 // returns the host grid's voxel count
 size_t host_localmap_drain(const LocalMap * map) {return map->grid().size();}
+// LocalMap::setInsertGate / insertGate / gatedTotals (include/vgicp_hip_map_gated.h); out: points, refused, plain frames
+int host_localmap_set_insert_gate(LocalMap * map, double gate) {return guarded([&] {map->setInsertGate(gate);});}
+double host_localmap_insert_gate(const LocalMap * map) {return map->insertGate();}
+int host_localmap_gated_totals(const LocalMap * map, uint64_t out[3])
+{
+  return guarded(
+    [&] {
+      const LocalMap::GatedTotals t = map->gatedTotals();
+      out[0] = t.points;
+      out[1] = t.refused;
+      out[2] = t.plainFrames;
+    });
+}
 
 // updateLocalMap(cloud, transform, initialize); the transformed cloud is written back to
 // points/covs, as the reference mutates the shared cloud in place (src/LocalMap.cpp:15).

@@ -567,6 +567,11 @@ class Odometry:
 
     def __init__(self, config: dict, backend):
         self.backend = backend
+        # optional key local_map.insert_gate (vgicp_hip_map_gated.h): only a backend that inserts the resident scan on the
+        # device can keep the gated points out of the map
+        if insert_gate_of(config) > 0.0 and not getattr(backend, "supports_insert_gate", False):
+            raise ValueError("local_map.insert_gate needs a backend that inserts the resident scan on the device "
+                             "(DeviceBackend, tools/replay.py --resident); this one inserts every point")
         self.filter = ErrorStateKF(config, backend.align, getattr(backend, "align_with_prior", None))
         self.initialized = False
         self.pending: List[LidarMeasurement] = []
@@ -646,11 +651,26 @@ def robust_scale_from_quantile(d2_quantile: float) -> Optional[float]:
     return float(min(max(np.sqrt(d2_quantile), ROBUST_SCALE_RANGE[0]), ROBUST_SCALE_RANGE[1]))
 
 
+def insert_gate_of(config: dict) -> float:
+    """local_map.insert_gate: 0 (absent) = off, else finite and > 0, or +inf, in the units of registration.gate."""
+    gate = float(config["local_map"].get("insert_gate", 0.0))
+    if not gate >= 0.0:
+        raise ValueError("local_map.insert_gate must be >= 0 (0: off) or +inf")
+    return gate
+
+
 class GpuBackend:
-    """The MI355X path behind the C++ mirror of the reference's classes (eskf_lio_amd/host.py)."""
+    """The MI355X path behind the C++ mirror of the reference's classes (eskf_lio_amd/host.py).  It hands the map a
+    fresh host cloud every frame (arrays in, arrays out), never the cloud process() stamped, so the map update is not the
+    resident insertion and local_map.insert_gate is refused here: the gate needs DeviceBackend (or the classes driven
+    frame by frame, host.Frame, where LocalMap::setInsertGate applies)."""
+    supports_insert_gate = False
 
     def __init__(self, config: dict, device_resident_map: bool = False):
         from . import host
+        if insert_gate_of(config) > 0.0:
+            raise ValueError("local_map.insert_gate needs a backend that inserts the resident scan on the device "
+                             "(DeviceBackend, tools/replay.py --resident); this one hands the map a host cloud every frame")
         lm = dict(config["local_map"])
         self.map = host.LocalMap(lm["voxel_size"], lm["max_num_points_per_voxel"],
                                  dict(translation_sq_threshold=lm["translation_sq_threshold"],
@@ -710,16 +730,22 @@ class DeviceBackend:
     -> vgicp_align_resident -> vgicp_map_insert_resident, straight on the C ABI (eskf_lio_amd/capi.py). Per
     frame the host sends 32 bytes per raw point and the IMU states, and receives the pose. The map is the
     device-resident voxel grid; the motion gate of LocalMap::needsMapUpdate (src/LocalMap.cpp:132-147) is a
-    few flops and stays on the host."""
+    few flops and stays on the host.  With local_map.insert_gate the insertion is vgicp_map_insert_resident_gated at the
+    frame's pose."""
+    supports_insert_gate = True
 
     def __init__(self, config: dict, device=0):
         """device: one ordinal, or a list of ordinals for ONE multi-device context (vgicp_create_multi)."""
         from . import capi
-        self.ctx = capi.Context(device)
         lm = config["local_map"]
+        if insert_gate_of(config) > 0.0 and isinstance(device, (list, tuple)):
+            raise ValueError("local_map.insert_gate needs a single-device context: the resident scan of a device is a shard "
+                             "in a multi-device one")
+        self.ctx = capi.Context(device)
         self.ctx.map_reset(lm["voxel_size"], 0)
         self.cap = int(lm["max_num_points_per_voxel"])
         self.gate = (lm["translation_sq_threshold"], lm["cosine_threshold"])
+        self.insert_gate = insert_gate_of(config)
         self.evict = (bool(lm["remove_distant_points"]), float(lm["distance_threshold"]), float(lm["removing_period"]))
         # the reference's period is wall-clock time (omp_get_wtime, src/LocalMap.cpp:60,70); a replay that has to be
         # repeatable counts map updates instead: local_map.remove_every_updates (10 s of sweeps at 10 Hz = 100)
@@ -788,7 +814,10 @@ class DeviceBackend:
             if not (cosine < self.gate[1] or float(moved[:3, 3] @ moved[:3, 3]) > self.gate[0]):
                 self.prev = transform.copy()
                 return
-        self.ctx.map_insert_resident(transform, self.cap)
+        if self.insert_gate > 0.0:
+            self.ctx.map_insert_resident_gated(transform, self.cap, self.insert_gate, kept=False)
+        else:
+            self.ctx.map_insert_resident(transform, self.cap)
         self.updates_since_evict += 1
         due = (self.updates_since_evict >= self.evict_every) if self.evict_every else \
             (time.perf_counter() - self.last_evict > self.evict[2])

@@ -38,6 +38,7 @@
 
 #include "../vgicp_hip.h"
 #include "../vgicp_hip_map_points.h"
+#include "../vgicp_hip_map_gated.h"
 
 // The raw-point store's entry points (vgicp_hip_map_points.h, and vgicp_set_option for its option) are referenced
 // weakly, so a program that links a stand-in of the C ABI without them (tests/native/shadow_stress.cpp) still links: a
@@ -47,6 +48,10 @@
 #pragma weak vgicp_map_points_size
 #pragma weak vgicp_map_points_export
 #pragma weak vgicp_set_option
+// ... and so are the gated insertion's (vgicp_hip_map_gated.h, in libvgicp_hip_map_gated.so beside the module): a program
+// that links without that library builds maps as before, and setInsertGate(g > 0) refuses.
+#pragma weak vgicp_map_insert_resident_gated_async
+#pragma weak vgicp_map_gated_totals
 #include "ShimTypes.hpp"
 #include "ShimSupport.hpp"
 #include "ResidentScan.hpp"
@@ -89,6 +94,10 @@ struct LocalMapConfig
   // shadow grid — no worker thread, no host copy of the prepared scan needed, and save() writes every raw point
   // whatever the host-copy mode.  YAML: local_map.raw_points_on_device (optional, default false).
   bool rawPointsOnDevice = false;
+  // > 0 (or +infinity): updateLocalMap keeps the points out of the map that are matched at the frame's pose and fail
+  // max(d^2, 0) <= insertGate (LocalMap::setInsertGate; include/vgicp_hip_map_gated.h has the rule and the units, which
+  // are ICP::robustScaleFromQuantile's).  0: off.  YAML: local_map.insert_gate (optional, default 0).
+  double insertGate = 0.0;
 };
 
 class LocalMap
@@ -171,6 +180,7 @@ public:
   {
     shim::check(ctx_, vgicp_map_reset(ctx_, voxelSize_, 0), "vgicp_map_reset");
     storeRawPointsOnDevice();
+    if (config.insertGate != 0.0) {setInsertGate(config.insertGate);}
   }
 
   ~LocalMap() {shadowStop();}
@@ -215,6 +225,7 @@ public:
     c.distanceThreshold = m["remove_distant_points"]["distance_threshold"].as<double>();
     c.removePeriod = m["remove_distant_points"]["removing_period"].as<double>();
     if (m["raw_points_on_device"].IsDefined()) {c.rawPointsOnDevice = m["raw_points_on_device"].as<bool>();}
+    if (m["insert_gate"].IsDefined()) {c.insertGate = m["insert_gate"].as<double>();}
     return c;
   }
 #endif
@@ -251,6 +262,7 @@ public:
     facts.moved = !initialize && hasPrevTransform_ && needsMapUpdate(transform);
     facts.evictionDue = shim::insertionDue(facts) && removeDistantPoints_ && now() - currentRemoveTime_ > removePeriod_;
     facts.soleOwner = cloud.use_count() == 1;
+    facts.gated = insertGate_ > 0.0;
     const Plan plan = shim::planUpdate(facts);
 
     if (plan.route != Plan::Route::ResidentScan) {
@@ -265,9 +277,16 @@ public:
       } else {
         if (plan.route == Plan::Route::ResidentScan) {
           shim::TraceScope tsInsert(shim::Trace::UpdateInsert);
-          shim::check(
-            ctx_, vgicp_map_insert_resident_async(ctx_, shim::poseData(transform), maxNumPointsPerVoxel_),
-            "vgicp_map_insert_resident_async");
+          if (plan.entry == Plan::Entry::Gated) {
+            shim::check(
+              ctx_, vgicp_map_insert_resident_gated_async(
+                ctx_, shim::poseData(transform), maxNumPointsPerVoxel_, insertGate_),
+              "vgicp_map_insert_resident_gated_async");
+          } else {
+            shim::check(
+              ctx_, vgicp_map_insert_resident_async(ctx_, shim::poseData(transform), maxNumPointsPerVoxel_),
+              "vgicp_map_insert_resident_async");
+          }
         } else if (!cloud->points_.empty()) {
           // the cloud is already in the world frame (transformed in place above, as the reference does)
           const Isometry3d identity = Isometry3d::Identity();
@@ -276,6 +295,7 @@ public:
               ctx_, cloud->points_.size(), cloud->points_.data()->data(), cloud->covariances_.data()->data(),
               shim::poseData(identity), maxNumPointsPerVoxel_, nullptr), "vgicp_map_insert_scan");
         }
+        if (plan.countPlain) {++plainFrames_;}
         if (plan.evict) {evictOnDevice(position);}
       }
       hasPrevTransform_ = true;
@@ -403,6 +423,54 @@ public:
   bool savesRawPoints() const {return !deviceResident_ || rawOnDevice_ || (keepRawPoints_ && shadowComplete_);}
   // the device map keeps the raw points (LocalMapConfig::rawPointsOnDevice)
   bool rawPointsOnDevice() const {return rawOnDevice_;}
+
+  // Gated insertion (include/vgicp_hip_map_gated.h): from the next updateLocalMap on, a frame whose cloud is still the
+  // resident scan is inserted without the points that are matched at its pose and fail max(d^2, 0) <= gate, on the
+  // device and enqueued only, as the plain insertion is.  gate: finite and >= 0, or +infinity, in the units of
+  // ICP::robustScaleFromQuantile; 0 switches the gate off, and the map then behaves exactly as without this call.
+  // A device-resident map only.  A map that keeps raw points for save() must read them from the device from here on
+  // (the shadow grid would file the refused points too): the store is switched on, which the module accepts while the map
+  // is empty — so set the gate before the first frame, or build the map with rawPointsOnDevice.
+  void setInsertGate(double gate)
+  {
+    if (!(gate >= 0.0)) {
+      throw std::invalid_argument("LocalMap::setInsertGate: the gate is finite and >= 0 (0: off), or +infinity");
+    }
+    if (gate > 0.0) {
+      if (!deviceResident_) {
+        throw std::invalid_argument("LocalMap::setInsertGate: only a device-resident map inserts the resident scan");
+      }
+      if (!(vgicp_map_insert_resident_gated_async && vgicp_map_gated_totals)) {
+        throw std::runtime_error("LocalMap::setInsertGate: the linked vgicp module has no gated insertion");
+      }
+      if (keepRawPoints_ && !rawOnDevice_) {
+        shadowDrain();
+        rawOnDevice_ = true;
+        try {
+          storeRawPointsOnDevice();
+        } catch (...) {
+          rawOnDevice_ = false;
+          throw;
+        }
+      }
+    }
+    insertGate_ = gate;
+  }
+  double insertGate() const {return insertGate_;}
+  struct GatedTotals
+  {
+    uint64_t points = 0, refused = 0;   // of the gated insertions since the map was made (vgicp_map_gated_totals: settles)
+    uint64_t plainFrames = 0;           // frames inserted whole while a gate was set: their cloud was no resident scan
+  };
+  GatedTotals gatedTotals() const
+  {
+    GatedTotals t;
+    t.plainFrames = plainFrames_;
+    if (vgicp_map_gated_totals) {
+      shim::check(ctx_, vgicp_map_gated_totals(ctx_, &t.points, &t.refused), "vgicp_map_gated_totals");
+    }
+    return t;
+  }
 
 private:
   static Key toKey(const Vector3i & v) {return Key{v(0), v(1), v(2)};}
@@ -652,6 +720,8 @@ private:
   bool keepRawPoints_ = false;
   bool rawOnDevice_ = false;         // the device map keeps the raw points: no shadow grid
   bool shadowComplete_ = true;       // every frame inserted on the device so far has also reached the shadow grid
+  double insertGate_ = 0.0;          // > 0: the resident route inserts through the gated entry (setInsertGate)
+  uint64_t plainFrames_ = 0;
   std::thread shadowThread_;
   mutable std::mutex shadowMutex_;
   mutable std::condition_variable shadowCv_, shadowIdle_;

@@ -19,6 +19,11 @@ struct UpdateFacts
   bool moved = false;         // needsMapUpdate(transform); asked only where it decides (insertionDue below)
   bool evictionDue = false;   // removeDistantPoints and the period is over; the clock is read only when insertionDue
   bool soleOwner = false;     // the caller moved its only pointer in (src/Odometry.cpp:86): nobody else can see the cloud
+  // LocalMap::setInsertGate(g > 0) on a device-resident map (include/vgicp_hip_map_gated.h).  false: every field of the
+  // plan is what it was before the gate existed.  A gated map that keeps raw points keeps them on the device
+  // (setInsertGate sees to rawOnDevice, or refuses), so a gated map never has a shadow grid to feed: the gate decides the
+  // entry and the count below, nothing else
+  bool gated = false;
 };
 
 struct UpdatePlan
@@ -33,6 +38,11 @@ struct UpdatePlan
   Transform transform = Transform::Here;
   HandOver handOver = HandOver::None;
   bool shadowComplete = true;   // every frame inserted on the device so far has also reached the shadow grid
+  // With a gate.  The resident-scan route inserts through vgicp_map_insert_resident_gated_async; a host cloud is no
+  // resident scan, so it is inserted whole and the frame is counted (LocalMap::gatedTotals().plainFrames).
+  enum class Entry {Plain, Gated};
+  Entry entry = Entry::Plain;
+  bool countPlain = false;
 };
 
 // reference: src/LocalMap.cpp:39 (with prevTransform_ initialised: the first update always inserts)
@@ -51,6 +61,9 @@ inline UpdatePlan planUpdate(const UpdateFacts & f)
   // resident route hands over every cloud whose host buffers are current (the worker moves a cloud nobody else can see
   // into the world frame even when nothing is inserted); a host cloud was transformed here already and goes over only
   // when it was inserted.
+  const bool gated = f.gated && f.deviceResident;   // (a host-authoritative map has no resident route: no gate)
+  p.entry = gated && p.route == Route::ResidentScan ? UpdatePlan::Entry::Gated : UpdatePlan::Entry::Plain;
+  p.countPlain = gated && p.route == Route::HostCloud && p.insert;
   const bool shadow = f.deviceResident && f.keepRawPoints && !f.rawOnDevice && f.shadowComplete;
   const bool wanted = p.route == Route::ResidentScan ? f.hostIsCurrent : p.route == Route::HostCloud && p.insert;
   // the worker reads the cloud later: it gets the caller's object only when nobody else can reach it, else a copy — a

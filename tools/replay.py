@@ -12,6 +12,8 @@ options: --out traj.tum   --device-map (keep the voxel grid on the GPU only)   -
          library's regularised units, ~0.1; off by default)
          --robust-scale-quantile Q (registration.robust_scale_quantile: before each frame's align the scan is reported at
          the predicted pose, include/vgicp_hip_points.h, and the scale becomes sqrt(quantile Q of d^2); off by default)
+         --insert-gate G (local_map.insert_gate, with --resident: points that are matched at the frame's
+         pose and fail max(d^2, 0) <= G are kept out of the map, include/vgicp_hip_map_gated.h; off by default)
          --prior-update (kalman_filter.update.iterated: the filter's pose covariance enters every round of the align as a
          prior, include/vgicp_hip_prior.h, and the update is the iterated one; off by default)
 The configuration is the reference's config/hilti_config.yaml as a dict (eskf_lio_amd/replay.py:DEFAULT_CONFIG);
@@ -77,6 +79,8 @@ def main():
     ap.add_argument("--robust-scale-quantile", type=float, default=None,
                     help="the scale follows this quantile of d^2 at each frame's predicted pose "
                          "(registration.robust_scale_quantile)")
+    ap.add_argument("--insert-gate", type=float, default=None,
+                    help="gate of the map insertion on d^2 at the frame's pose, 0 = none (local_map.insert_gate)")
     ap.add_argument("--prior-update", action="store_true",
                     help="the iterated filter update with the pose prior in every align (kalman_filter.update.iterated)")
     args = ap.parse_args()
@@ -91,6 +95,10 @@ def main():
               if v is not None}
     if robust:
         cfg = dict(cfg, registration=dict(cfg["registration"], **robust))
+    if args.insert_gate is not None:
+        if not args.resident:
+            ap.error("--insert-gate needs --resident")
+        cfg = dict(cfg, local_map=dict(cfg["local_map"], insert_gate=args.insert_gate))
     if args.prior_update:
         cfg = dict(cfg, kalman_filter=dict(cfg["kalman_filter"], iterated=True))
     truth = None
@@ -117,6 +125,9 @@ def main():
         cs = [c for _, c in backend.scales]
         print(f"robust scale from the {args.robust_scale_quantile} quantile of d^2 at each predicted pose: "
               f"min {min(cs):.4f}, median {float(np.median(cs)):.4f}, max {max(cs):.4f}")
+    if args.insert_gate:
+        points, refused = backend.ctx.map_gated_totals()
+        print(f"map insertion gated at d^2 <= {args.insert_gate}: {refused} of {points} points kept out of the map")
     if args.raw_points_on_device:
         t0 = time.perf_counter()
         keys, _ = backend.ctx.map_points_export()
