@@ -4,27 +4,23 @@
 // settle_after_launch), the report (report_align); then the two paths of a resident scan, align_persistent and
 // align_on_loop (RCCL all-reduce between launches with a communicator), behind run_align, which asks plan_align.
 namespace {
-uint32_t iterate_grid(const vgicp_ctx* ctx) {
-  const uint32_t block = (uint32_t)ctx->iter_block - 64;  // wave 0 of a workgroup solves, the rest own points
-  const uint32_t want = (ctx->n + block - 1) / block;
-  return std::min<uint32_t>(std::max<uint32_t>(want, 1), kMaxIterBlocks);
+// Workgroups of one round's launch over n points at this block size (also the rows per pose of an evaluation).
+uint32_t iterate_grid(uint32_t n, uint32_t block) {
+  const uint32_t workers = block - 64;  // wave 0 of a workgroup solves, the rest own points
+  return std::min<uint32_t>(std::max<uint32_t>((n + workers - 1) / workers, 1), kMaxIterBlocks);
 }
+uint32_t iterate_grid(const vgicp_ctx* ctx) { return iterate_grid(ctx->n, (uint32_t)ctx->iter_block); }
 
 IterArgs base_args(const vgicp_ctx* ctx) {
   IterArgs a;
   std::memset(&a, 0, sizeof a);
-  a.scan = ctx->d_scan;
-  a.stride = ctx->stride;
-  a.n = ctx->n;
-  a.mask = (uint32_t)(ctx->slots - 1);
-  a.table = ctx->table;
-  a.voxel_size = ctx->voxel_size;
+  static_cast<ResidentView&>(a) = resident_view(ctx);
   a.log = ctx->d_log_rows();
   a.stamps = ctx->d_stamps;
   a.memo = static_cast<int4*>(ctx->d_memo.get());
   a.memo_valid = 0;   // the caller knows which launch of the align this is
   a.scan_seq = ctx->scan_seq;
-  a.asym_dev = (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
+  a.asym_dev = symmetry_word(ctx);
   // the dense record copy (tables far beyond the caches' reach): used where it is current — the aligns that reach the
   // loop after a persistent launch has rebuilt it, or run_align's own ensure_dense
   a.dense = (ctx->d_dense && ctx->dense_version == ctx->map_version && ctx->slots >= ctx->dense_slots_threshold &&
@@ -239,12 +235,7 @@ bool trace_align() { static const bool on = std::getenv("VGICP_TRACE_ALIGN") != 
 void persistent_args_common(vgicp_ctx* ctx, const vgicp_params* params, PersistArgs* out) {
   PersistArgs& a = *out;
   std::memset(&a, 0, sizeof a);
-  a.scan = ctx->d_scan;
-  a.stride = ctx->stride;
-  a.n = ctx->n;                                        // a pending scan: the raw count, an upper bound
-  a.mask = (uint32_t)(ctx->slots - 1);
-  a.table = ctx->table;
-  a.voxel_size = ctx->voxel_size;
+  static_cast<ResidentView&>(a) = resident_view(ctx);   // n of a pending scan: the raw count, an upper bound
   a.seq = ++ctx->persist_seq == 0 ? ++ctx->persist_seq : ctx->persist_seq;  // never 0
   a.cosine_threshold = params->cosine_threshold;
   a.translation_sq_threshold = params->translation_sq_threshold;
@@ -259,8 +250,7 @@ int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* par
   PersistArgs& a = *out;
   persistent_args_common(ctx, params, &a);
   a.n_dev = ctx->scan_pending ? ctx->d_counters : nullptr;  // a pending scan's kept count is read from the device
-  // word 2 of that block: the symmetry verdict (developer A/B no_sym: always read all twelve planes)
-  a.asym_dev = (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
+  a.asym_dev = symmetry_word(ctx);
   a.scan_seq = ctx->scan_seq;
   if (wants_dense(ctx, ctx->n)) {
     bool usable = false;
@@ -284,8 +274,8 @@ int persistent_args(vgicp_ctx* ctx, const double* guess, const vgicp_params* par
   if (ctx->dev.no_memo) a.memo_points = 0;
   a.prefetch_margin = (a.memo_points == 0 && a.stash_points == 0 && one_point_per_thread(ctx->n, grid)) ? ctx->prefetch_margin : 0.0;
   a.stamps = ctx->d_stamps;
-  if (robust_on(ctx)) robust_args(ctx, &a);   // launch_persistent then takes the robust instantiation
-  if (ctx->prior_on) prior_args(ctx, &a);     // ... and the pose prior's
+  if (robust_on(ctx)) a.robust = robust_args(ctx);   // launch_persistent then takes the robust instantiation
+  if (ctx->prior_on) a.prior = prior_args(ctx);      // ... and the pose prior's
   a.world = multi ? (uint32_t)ctx->peer_world : 1u;
   a.rank = multi ? (uint32_t)ctx->peer_rank : 0u;
   a.mail = ctx->d_mail_table;
@@ -449,8 +439,8 @@ int align_on_loop(vgicp_ctx* ctx, const double* guess, const vgicp_params* param
   bool usable = false;
   if (large_table(ctx)) VG_RC(ensure_dense(ctx, &usable));
   IterArgs base = base_args(ctx);
-  if (robust_on(ctx)) robust_args(ctx, &base);   // launch_iterate then takes the robust instantiation
-  if (ctx->prior_on) prior_args(ctx, &base);     // ... and launch_iterate / launch_close the pose prior's
+  if (robust_on(ctx)) base.robust = robust_args(ctx);   // launch_iterate then takes the robust instantiation
+  if (ctx->prior_on) base.prior = prior_args(ctx);      // ... and launch_iterate / launch_close the pose prior's
   const uint32_t grid = iterate_grid(ctx);
   const bool use_comm = ctx->comm != nullptr;
   int total_launches = 0;

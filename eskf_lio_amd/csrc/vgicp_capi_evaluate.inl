@@ -1,14 +1,6 @@
 // vgicp_capi_evaluate.inl — part of vgicp_capi.hip.
 // vgicp_evaluate_resident (include/vgicp_hip_evaluate.h): argument checks, settling, the launch pairs with their one
 // synchronisation, the report.  Reads the context; writes only the evaluation's own storage (d_eval_rows, h_eval).
-namespace {
-// Workgroups per pose: the grid of the loop's 512-thread launch for this scan (iterate_grid with iter_block = 512).
-uint32_t evaluate_rows(uint32_t n) {
-  const uint32_t workers = 512 - 64;
-  return std::min<uint32_t>(std::max<uint32_t>((n + workers - 1) / workers, 1), kMaxIterBlocks);
-}
-}  // namespace
-
 extern "C" {
 
 int vgicp_evaluate_resident(vgicp_ctx* ctx, size_t k, const double* poses, vgicp_evaluation* out, vgicp_eval_stats* stats) {
@@ -29,21 +21,16 @@ int vgicp_evaluate_resident(vgicp_ctx* ctx, size_t k, const double* poses, vgicp
   VG_RC(settle(ctx));
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
 
-  const uint32_t rows = evaluate_rows(ctx->n);
+  const uint32_t rows = iterate_grid(ctx->n, 512);   // workgroups per pose: the grid of the loop's 512-thread launch
   const size_t per_launch = std::min<size_t>(VGICP_EVAL_MAX, (size_t)kEvalRowBudget / rows);
   double* h_poses = ctx->h_eval + (size_t)VGICP_EVAL_MAX * kSlots;
   for (size_t h = 0; h < k; ++h) pose_to_state(poses + 16 * h, h_poses + 12 * h);
   EvalArgs a;
   std::memset(&a, 0, sizeof a);
-  a.scan = ctx->d_scan;
-  a.stride = ctx->stride;
-  a.n = ctx->n;
-  a.mask = (uint32_t)(ctx->slots - 1);
-  a.table = ctx->table;
-  a.voxel_size = ctx->voxel_size;
+  static_cast<ResidentView&>(a) = resident_view(ctx);
   a.rows = ctx->d_eval_rows;
   a.scan_seq = ctx->scan_seq;
-  a.asym_dev = (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
+  a.asym_dev = symmetry_word(ctx);
   int launches = 0;
   VG_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
   for (size_t h0 = 0; h0 < k; h0 += per_launch) {

@@ -89,14 +89,9 @@ int insert_points(vgicp_ctx* ctx, const double* d_points, const double* d_covs, 
   if (gate) {
     GateArgs g;
     std::memset(&g, 0, sizeof g);
-    g.scan = ctx->d_scan;
-    g.stride = ctx->stride;
-    g.n = (uint32_t)n;
-    g.mask = (uint32_t)(ctx->slots - 1);
-    g.table = ctx->table;
-    g.voxel_size = ctx->voxel_size;
+    static_cast<ResidentView&>(g) = resident_view(ctx);   // a gated insertion is the resident scan's: n == ctx->n
     for (int k = 0; k < 12; ++k) g.pose[k] = pose12[k];
-    g.asym_dev = (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
+    g.asym_dev = symmetry_word(ctx);
     g.scan_seq = ctx->scan_seq;
     g.gate = gate->gate;
     g.keep = keep;

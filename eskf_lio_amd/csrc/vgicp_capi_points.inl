@@ -80,16 +80,14 @@ int points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, doub
 
   PointArgs a;
   std::memset(&a, 0, sizeof a);
-  a.scan = ctx->d_scan;
-  a.stride = ctx->stride;
-  a.n = n;
-  a.mask = (uint32_t)(ctx->slots - 1);
-  a.table = ctx->table;
-  a.voxel_size = ctx->voxel_size;
+  static_cast<ResidentView&>(a) = resident_view(ctx);   // settled: n is the resident scan's size
   pose_to_state(pose, a.pose);
-  a.asym_dev = (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
+  a.asym_dev = symmetry_word(ctx);
   a.scan_seq = ctx->scan_seq;
-  robust_args(ctx, &a);
+  const RobustArgs robust = robust_args(ctx);
+  a.robust_kernel = robust.kernel;
+  a.robust_scale2 = robust.scale2;
+  a.robust_gate = robust.gate;
   a.d2 = d2 ? points_at<double>(ctx, lay.d2) : nullptr;
   a.sq_error = sq_error ? points_at<double>(ctx, lay.sq_error) : nullptr;
   a.weight = weight ? points_at<double>(ctx, lay.weight) : nullptr;

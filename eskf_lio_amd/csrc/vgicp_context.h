@@ -536,20 +536,26 @@ inline AlignFacts call_facts(AlignCall call, uint32_t flags, int max_iteration) 
   return f;
 }
 inline bool robust_on(const vgicp_ctx* ctx) { return ctx->robust_kernel != 0 || ctx->robust_gate_micro != 0; }
-// The settings as the kernels take them (the three fields at the end of IterArgs / PersistArgs).
-template <typename Args>
-inline void robust_args(const vgicp_ctx* ctx, Args* a) {
-  const double c = (double)ctx->robust_scale_micro / 1000000.0;
-  a->robust_kernel = (uint32_t)ctx->robust_kernel;
-  a->robust_scale2 = c * c;
-  a->robust_gate = (double)ctx->robust_gate_micro / 1000000.0;
+// The resident scan and the voxel map as a launch sees them: the ONE place where an argument struct's view is filled.
+inline vgicp::ResidentView resident_view(const vgicp_ctx* ctx) {
+  return vgicp::ResidentView{ctx->d_scan, ctx->stride, ctx->n, (uint32_t)(ctx->slots - 1), ctx->table, ctx->voxel_size};
 }
-// The pose prior as the kernels take it (the fields at the very end of IterArgs / PersistArgs).
-template <typename Args>
-inline void prior_args(const vgicp_ctx* ctx, Args* a) {
-  a->prior_on = 1u;
-  for (int k = 0; k < 12; ++k) a->prior_pose[k] = ctx->prior_pose[k];
-  for (int k = 0; k < 21; ++k) a->prior_info[k] = ctx->prior_info[k];
+// What a launch's asym_dev is (with scan_seq = ctx->scan_seq): word 2 of the insertion's counter block, the symmetry
+// verdict of pack_scan_kernel, for a scan that went through it (developer A/B no_sym: always read all twelve planes).
+inline const uint32_t* symmetry_word(const vgicp_ctx* ctx) {
+  return (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
+}
+// The context's robust settings and its pose prior as the kernels take them.
+inline vgicp::RobustArgs robust_args(const vgicp_ctx* ctx) {
+  const double c = (double)ctx->robust_scale_micro / 1000000.0;
+  return vgicp::RobustArgs{(uint32_t)ctx->robust_kernel, c * c, (double)ctx->robust_gate_micro / 1000000.0};
+}
+inline vgicp::PriorArgs prior_args(const vgicp_ctx* ctx) {
+  vgicp::PriorArgs p;
+  p.on = 1u;
+  for (int k = 0; k < 12; ++k) p.pose[k] = ctx->prior_pose[k];
+  for (int k = 0; k < 21; ++k) p.info[k] = ctx->prior_info[k];
+  return p;
 }
 inline AlignFacts align_facts(const vgicp_ctx* ctx, const vgicp_params* params, AlignCall call, uint64_t n, size_t k = 1) {
   AlignFacts f = call_facts(call, params ? params->flags : 0u, params ? params->max_iteration : 0);

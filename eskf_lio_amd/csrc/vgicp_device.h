@@ -13,8 +13,10 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
+#include "vgicp_launch_plan.h"
 #include "vgicp_math.h"
 
 namespace vgicp {
@@ -65,13 +67,36 @@ constexpr uint32_t kOutcomeCommitted = 1;    // the loop ran to its end (several
 constexpr uint32_t kOutcomeAgreedAbort = 2;  // several GPUs: some rank gave up, every rank knows it
 constexpr uint32_t kOutcomeNoAgreement = 3;  // several GPUs: a peer's verdict never arrived
 
-struct IterArgs {
+// The resident scan and the voxel map as every launch over them sees them: the base of the five argument structs below
+// (resident_view(ctx), vgicp_context.h, fills it).  asym_dev / scan_seq stay fields of each struct, where they always
+// were: a kernel's scalar argument loads are grouped by offset, so no field of an argument struct may move (the
+// static_asserts behind each struct hold the offsets).
+#pragma GCC diagnostic push   // offsetof in a struct with a base: conditionally supported, and supported by both compilers
+#pragma GCC diagnostic ignored "-Winvalid-offsetof"
+struct ResidentView {
   const double* scan;  // SoA planes
   uint64_t stride;
-  uint32_t n;
-  uint32_t mask;  // slots - 1
+  uint32_t n;          // points of the scan
+  uint32_t mask;       // slots - 1
   const VoxelRecord* table;
   double voxel_size;
+};
+static_assert(sizeof(ResidentView) == 40, "the view is the first 40 bytes of every argument struct");
+// The robust round (include/vgicp_hip_robust.h) as the kernels take it (robust_args(ctx)); all zero = the plain round
+// (vgicp_accumulate, a group's loop, the fused and the team launch: always).
+struct RobustArgs {
+  uint32_t kernel;   // VGICP_ROBUST_*
+  double scale2;     // c^2
+  double gate;       // gate on d^2; 0 = none
+};
+// The pose prior (include/vgicp_hip_prior.h) as the kernels take it (prior_args(ctx)); all zero = no prior (likewise).
+struct PriorArgs {
+  uint32_t on;
+  double pose[12];   // R0 column-major (9) then t0 (3)
+  double info[21];   // lower triangle of the information matrix, row by row, as normal_eq is laid out
+};
+
+struct IterArgs : ResidentView {
   double* rows;        // [grid][kSlots]: partial rows this launch writes
   const double* prev;  // rows the previous launch wrote (or the all-reduced single row)
   uint32_t prev_rows;  // how many; 0 = first round, nothing to solve yet
@@ -89,15 +114,11 @@ struct IterArgs {
   uint32_t scan_seq;        // with asym_dev: *asym_dev != scan_seq = every covariance of the scan is bitwise symmetric
   const uint32_t* asym_dev; // (nine planes are read instead of twelve); nullptr = unknown, read all
   const VoxelRecord* dense; // dense copy of the FULL records (tables beyond the caches' reach), or nullptr
-  // the robust round (include/vgicp_hip_robust.h); all zero = the plain round (vgicp_accumulate, a group's loop: always)
-  uint32_t robust_kernel;   // VGICP_ROBUST_*
-  double robust_scale2;     // c^2
-  double robust_gate;       // gate on d^2; 0 = none
-  // the pose prior (include/vgicp_hip_prior.h); all zero = no prior (vgicp_accumulate, a group's loop: always)
-  uint32_t prior_on;
-  double prior_pose[12];    // R0 column-major (9) then t0 (3)
-  double prior_info[21];    // lower triangle of the information matrix, row by row, as normal_eq is laid out
+  RobustArgs robust;
+  PriorArgs prior;
 };
+static_assert(sizeof(IterArgs) == 424 && offsetof(IterArgs, rows) == 40 && offsetof(IterArgs, asym_dev) == 112 &&
+              offsetof(IterArgs, robust) == 128 && offsetof(IterArgs, prior) == 152, "IterArgs: no field may move");
 
 // Arguments of the persistent single-launch align (single GPU): every round of the loop runs inside
 // one kernel.  Workgroups exchange their partial rows through `rows` and `parts` (three buffers each, by
@@ -116,13 +137,7 @@ constexpr unsigned long long kRowUnset = ~0ull;             // a NaN pattern no 
 constexpr unsigned long long kRowNaN = 0x7FF8000000000000ull;  // what a computed NaN is published as
 constexpr size_t kMailRowWords = 3 * (size_t)kMaxRanks * kSlots;  // the rows of a mailbox
 constexpr size_t kMailWords = kMailRowWords + kSlots;          // + the verdict words (kMaxRanks used)
-struct PersistArgs {
-  const double* scan;  // SoA planes
-  uint64_t stride;
-  uint32_t n;          // points of the scan — an UPPER BOUND when n_dev is set (the launch plan is made from it)
-  uint32_t mask;
-  const VoxelRecord* table;
-  double voxel_size;
+struct PersistArgs : ResidentView {   // n: an UPPER BOUND when n_dev is set (the launch plan is made from it)
   double* rows;         // [3][kExchangeRows][kSlots]; kRowUnset where a workgroup publishes (between launches: all but the
                         // buffer of the last round, which the next launch's first round re-arms), else +0.0
   double* parts;        // [3][kFolders][kSlots], likewise
@@ -166,15 +181,11 @@ struct PersistArgs {
                            // voxel sizes to a face of its voxel has the neighbour behind that face looked up
                            // into LDS while the workers wait for the exchange
   uint64_t* stamps;
-  // the robust round, as IterArgs has it; all zero = the plain round (the fused and the team launch: always)
-  uint32_t robust_kernel;
-  double robust_scale2;
-  double robust_gate;
-  // the pose prior, as IterArgs has it; all zero = no prior (the fused and the team launch: always)
-  uint32_t prior_on;
-  double prior_pose[12];
-  double prior_info[21];
+  RobustArgs robust;
+  PriorArgs prior;
 };
+static_assert(sizeof(PersistArgs) == 576 && offsetof(PersistArgs, rows) == 40 && offsetof(PersistArgs, asym_dev) == 232 &&
+              offsetof(PersistArgs, robust) == 280 && offsetof(PersistArgs, prior) == 304, "PersistArgs: no field may move");
 
 // The fused align (vgicp_align, one point per thread, one device): the persistent launch is enqueued BEFORE the copy
 // threads stage the scan, and every workgroup reads its own 448 points out of the page-locked staging memory as the
@@ -220,19 +231,15 @@ constexpr size_t team_parts_words() { return 3 * (size_t)kTeamsMax * kFolders * 
 // Scoring poses of the resident scan (vgicp_evaluate_resident): launch (rows per pose) x (poses) workgroups write one
 // row each, a second launch folds every pose's rows into 32 doubles.  Row budget of one launch pair: kEvalRowBudget.
 constexpr int kEvalRowBudget = 4096;   // 1 MiB of rows: 16 poses of the largest geometry below 256 x 448 points, 8 of kMaxIterBlocks rows
-struct EvalArgs {
-  const double* scan;  // SoA planes
-  uint64_t stride;
-  uint32_t n;
-  uint32_t mask;
-  const VoxelRecord* table;
-  double voxel_size;
+struct EvalArgs : ResidentView {
   const double* poses;       // [poses][12], page-locked host memory as the device addresses it: R column-major (9), t (3)
   double* rows;              // [poses][rows per pose][kSlots]
   const uint32_t* asym_dev;  // as IterArgs
   uint32_t scan_seq;
   uint32_t pad;
 };
+static_assert(sizeof(EvalArgs) == 72 && offsetof(EvalArgs, poses) == 40 && offsetof(EvalArgs, asym_dev) == 56,
+              "EvalArgs: no field may move");
 
 // The resident scan at a pose, point by point (vgicp_points_resident, include/vgicp_hip_points.h): one launch writes the
 // requested planes (any of them may be nullptr) and, when quantiles are wanted, a 64-bit sort key and the index per
@@ -241,17 +248,11 @@ struct EvalArgs {
 constexpr int kPointCounters = 4;
 constexpr int kPointQuantiles = 16;        // VGICP_POINT_QUANTILES_MAX
 constexpr int kPointResultWords = kPointCounters + kPointQuantiles;
-struct PointArgs {
-  const double* scan;  // SoA planes
-  uint64_t stride;
-  uint32_t n;
-  uint32_t mask;
-  const VoxelRecord* table;
-  double voxel_size;
+struct PointArgs : ResidentView {
   double pose[12];           // R column-major (9), t (3)
   const uint32_t* asym_dev;  // as IterArgs
   uint32_t scan_seq;
-  uint32_t robust_kernel;    // as IterArgs: the context's robust settings (robust_args)
+  uint32_t robust_kernel;    // RobustArgs, flat: the offset is 4 mod 8, where a RobustArgs member cannot sit
   double robust_scale2;
   double robust_gate;
   double* d2;                // n each, or nullptr
@@ -262,6 +263,8 @@ struct PointArgs {
   uint32_t* idx;             // ... n indices for the sort, or both nullptr
   uint32_t* counters;
 };
+static_assert(sizeof(PointArgs) == 224 && offsetof(PointArgs, pose) == 40 && offsetof(PointArgs, asym_dev) == 136 &&
+              offsetof(PointArgs, robust_kernel) == 148, "PointArgs: no field may move");
 struct PointPickArgs {
   const unsigned long long* sorted;  // the n keys in ascending order (n_quantiles > 0)
   const uint32_t* counters;
@@ -277,13 +280,7 @@ struct PointPickArgs {
 // included).  Read-only on the table; the insertion that claims slots is a later launch.  counters: 3 device words that
 // only ever grow (running totals; the host remembers what it has read): matched, refused, not finite.
 constexpr int kGateCounters = 3;
-struct GateArgs {
-  const double* scan;  // SoA planes
-  uint64_t stride;
-  uint32_t n;
-  uint32_t mask;
-  const VoxelRecord* table;
-  double voxel_size;
+struct GateArgs : ResidentView {
   double pose[12];           // R column-major (9), t (3)
   const uint32_t* asym_dev;  // as IterArgs
   uint32_t scan_seq;
@@ -292,6 +289,9 @@ struct GateArgs {
   uint8_t* keep;             // n
   uint32_t* counters;
 };
+static_assert(sizeof(GateArgs) == 176 && offsetof(GateArgs, pose) == 40 && offsetof(GateArgs, asym_dev) == 136,
+              "GateArgs: no field may move");
+#pragma GCC diagnostic pop
 
 // ---- launchers (defined in vgicp_kernels.hip) ----
 hipError_t launch_point_terms(hipStream_t s, const PointArgs& args);
@@ -319,8 +319,7 @@ void persistent_exchange_image(uint32_t grid, unsigned long long* rows_words, un
 // current device: *max_grid = cu_count then, else 0 (the in-kernel exchange needs every workgroup resident).
 hipError_t persistent_prepare_device();  // once per context, on its device: every instantiation may use the whole CU's LDS
 hipError_t persistent_max_resident(uint32_t dyn_lds_bytes, int cu_count, uint32_t* max_grid);
-uint32_t persistent_dyn_lds_bytes(uint32_t memo_points, uint32_t stash_bytes);
-uint32_t persistent_max_dyn_lds_bytes();  // the most a launch plan ever asks for
+// persistent_dyn_lds_bytes, persistent_max_dyn_lds_bytes: vgicp_launch_plan.h
 // One VGICP round over the resident scan: prologue folds args.prev and advances the pose, body
 // accumulates this round's rows. block = 256 / 512 / 1024 threads per workgroup.
 hipError_t launch_iterate(hipStream_t s, const IterArgs& args, uint32_t grid, int block);

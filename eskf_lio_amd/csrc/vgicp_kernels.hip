@@ -24,12 +24,23 @@
 //     redundantly, in one fixed order — bit-reproducible) while its own scan loads are in flight, so
 //     the kernel boundary is the only grid-wide synchronisation and no workgroup runs a serial tail
 //     alone (the first version's ticket + write-through + last-workgroup tail cost 13 us per round).
+#include <array>
+#include <utility>
+
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
+#include "vgicp_launch_plan.h"
 #include "vgicp_points_plan.h"
 
 namespace vgicp {
 namespace {
+
+// Every covariance of the resident scan is bitwise symmetric (nine planes are read instead of twelve): the word that
+// pack_scan_kernel sets to the scan's sequence number when one is not still differs from it.  nullptr = unknown, read all.
+template <typename Args>
+__device__ __forceinline__ bool scan_cov_symmetric(const Args& a) {
+  return a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;
+}
 
 // The 96-byte payload {mean, covariance} as six 16-byte pieces that lie PIECES double2 apart: 1 in a record, the number
 // of worker threads in the plane-major neighbour-prefetch area of the persistent launch's LDS.
@@ -414,7 +425,7 @@ __device__ __forceinline__ const double* prior_solve_totals(const Args& a, const
                                                             uint32_t lane) {
   __shared__ PriorShared ps;
   Pose T0;
-  load_pose(a.prior_pose, T0);
+  load_pose(a.prior.pose, T0);
   double d[6], M[9];
   pose_prior_chart_blocks(T0, T, d, M);
   // G = [I, -[t]x; 0, M]: the zeros from 36 lanes, what is not zero from lane 0 (the same wave: LDS is in order within
@@ -425,7 +436,7 @@ __device__ __forceinline__ const double* prior_solve_totals(const Args& a, const
 #pragma unroll
     for (int k = 0; k < 6; ++k) ps.d[k] = d[k];
   }
-  if (lane < 21) ps.info[lane] = a.prior_info[lane];   // one entry per lane, read from the dispatch packet's memory
+  if (lane < 21) ps.info[lane] = a.prior.info[lane];   // one entry per lane, read from the dispatch packet's memory
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -707,11 +718,11 @@ __global__ __launch_bounds__(BLOCK) void iterate_kernel(IterArgs a) {
   const uint32_t stride_pts = gridDim.x * kWorkers;
   const double inv_voxel = 1.0 / a.voxel_size;
   const double same_margin = 0x1p-20 * a.voxel_size;  // same_voxel_coord
-  const bool cov_sym = a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
+  const bool cov_sym = scan_cov_symmetric(a);  // uniform
   const bool remembered = a.memo != nullptr && a.memo_valid != 0;           // uniform: an earlier launch of this align wrote the memos
   const VoxelRecord* pay_base = a.dense ? a.dense : a.table;                // uniform: where a remembered record's payload is read from
   RobustSetting robust;
-  if constexpr (ROBUST) robust = robust_setting(a.robust_kernel, a.robust_scale2, a.robust_gate);  // uniform
+  if constexpr (ROBUST) robust = robust_setting(a.robust.kernel, a.robust.scale2, a.robust.gate);  // uniform
   uint32_t i = worker ? blockIdx.x * kWorkers + (tid - 64) : a.n;
 
   double q[kScanPlanes];
@@ -863,7 +874,7 @@ __global__ __launch_bounds__(BLOCK) void evaluate_kernel(EvalArgs a) {
   const bool worker = wave != 0;
   const uint32_t stride_pts = gridDim.x * kWorkers;
   const double inv_voxel = 1.0 / a.voxel_size;
-  const bool cov_sym = a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
+  const bool cov_sym = scan_cov_symmetric(a);  // uniform
   uint32_t i = worker ? blockIdx.x * kWorkers + (tid - 64) : a.n;
 
   double q[kScanPlanes];
@@ -1020,7 +1031,7 @@ __device__ __forceinline__ PointTerm point_term(const Args& a, uint32_t i, bool 
 // settings: not on which planes are asked, not on its neighbours.  Nothing waits for another workgroup.
 __global__ __launch_bounds__(256) void point_terms_kernel(PointArgs a) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  const bool cov_sym = a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
+  const bool cov_sym = scan_cov_symmetric(a);  // uniform
   const RobustSetting robust = robust_setting(a.robust_kernel, a.robust_scale2, a.robust_gate);
   bool matched = false, counted = false, negative = false, not_finite = false;
   if (i < a.n) {
@@ -1062,7 +1073,7 @@ __global__ __launch_bounds__(256) void point_terms_kernel(PointArgs a) {
 // waiting on nothing: the claims of the insertion are a later launch, so no claim in flight is ever seen here.
 __global__ __launch_bounds__(256) void gate_decide_kernel(GateArgs a) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  const bool cov_sym = a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
+  const bool cov_sym = scan_cov_symmetric(a);  // uniform
   bool matched = false, refused = false, not_finite = false;
   if (i < a.n) {
     const PointTerm term = point_term(a, i, cov_sym);
@@ -1405,7 +1416,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // a.n bounds the count the device holds (a scan preparation that gave up must not send this launch out of range)
   const uint32_t n_pts = a.n_dev ? (*a.n_dev < a.n ? *a.n_dev : a.n) : a.n;  // uniform
-  const bool cov_sym = MANY && a.asym_dev != nullptr && *a.asym_dev != a.scan_seq;  // uniform
+  const bool cov_sym = MANY && scan_cov_symmetric(a);  // uniform
   const uint32_t grid = gridDim.x, blk = TEAM ? tv.vb : blockIdx.x;
   // MANY (the scan, or the upper bound the launch plan was made from, has more points than grid x 448): a thread owns
   // several points anyway, so wave 0 owns points as well and turns solver after the accumulate phase — 512 points
@@ -1452,7 +1463,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
   const double inv_voxel = 1.0 / a.voxel_size;
   const double same_margin = 0x1p-20 * a.voxel_size;  // same_voxel_coord
   RobustSetting robust;
-  if constexpr (ROBUST) robust = robust_setting(a.robust_kernel, a.robust_scale2, a.robust_gate);  // uniform
+  if constexpr (ROBUST) robust = robust_setting(a.robust.kernel, a.robust.scale2, a.robust.gate);  // uniform
 
   double q0[kScanPlanes];
 #pragma unroll
@@ -2309,50 +2320,41 @@ inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((w
 
 }  // namespace
 
+// ---- the round kernels' instantiations: one table of kernel pointers per list of vgicp_launch_plan.h, built from the
+// list itself, so that what exists, what has its LDS limit raised and what a plan can pick are one set ----
 namespace {
-template <bool ROBUST>
-hipError_t launch_iterate_prior(hipStream_t s, const IterArgs& args, uint32_t grid, int block) {
-  switch (block) {
-    case 256: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<256, ROBUST, true>), dim3(grid), dim3(256), 0, s, args); break;
-    case 512: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<512, ROBUST, true>), dim3(grid), dim3(512), 0, s, args); break;
-    case 1024: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<1024, ROBUST, true>), dim3(grid), dim3(1024), 0, s, args); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+using IterateFn = void (*)(IterArgs);
+using PersistentFn = void (*)(PersistArgs);
+template <size_t... I>
+constexpr std::array<IterateFn, sizeof...(I)> iterate_table(std::index_sequence<I...>) {
+  return {{&iterate_kernel<kIterateVariants[I].block, kIterateVariants[I].robust, kIterateVariants[I].prior>...}};
 }
+template <size_t... I>
+constexpr std::array<IterateFn, sizeof...(I)> close_table(std::index_sequence<I...>) {
+  return {{&close_kernel<kCloseVariants[I].block, kCloseVariants[I].prior>...}};
+}
+template <size_t... I>
+constexpr std::array<PersistentFn, sizeof...(I)> persistent_table(std::index_sequence<I...>) {
+  return {{&persistent_kernel<512, kPersistentVariants[I].multi, kPersistentVariants[I].stamps, kPersistentVariants[I].many,
+                              kPersistentVariants[I].robust, kPersistentVariants[I].prior>...}};
+}
+constexpr auto kIterateKernels = iterate_table(std::make_index_sequence<kIterateVariantCount>{});
+constexpr auto kCloseKernels = close_table(std::make_index_sequence<kCloseVariantCount>{});
+constexpr auto kPersistentKernels = persistent_table(std::make_index_sequence<kPersistentVariantCount>{});
 }  // namespace
 
 hipError_t launch_iterate(hipStream_t s, const IterArgs& args, uint32_t grid, int block) {
-  if (args.prior_on != 0) {   // the pose prior: instantiations of their own, with and without the weights
-    return (args.robust_kernel != 0 || args.robust_gate > 0.0) ? launch_iterate_prior<true>(s, args, grid, block)
-                                                               : launch_iterate_prior<false>(s, args, grid, block);
-  }
-  if (args.robust_kernel != 0 || args.robust_gate > 0.0) {   // the weighted round: instantiations of their own
-    switch (block) {
-      case 256: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<256, true>), dim3(grid), dim3(256), 0, s, args); break;
-      case 512: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<512, true>), dim3(grid), dim3(512), 0, s, args); break;
-      case 1024: ++g_kernel_launches; hipLaunchKernelGGL((iterate_kernel<1024, true>), dim3(grid), dim3(1024), 0, s, args); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  switch (block) {
-    case 256: ++g_kernel_launches; hipLaunchKernelGGL(iterate_kernel<256>, dim3(grid), dim3(256), 0, s, args); break;
-    case 512: ++g_kernel_launches; hipLaunchKernelGGL(iterate_kernel<512>, dim3(grid), dim3(512), 0, s, args); break;
-    case 1024: ++g_kernel_launches; hipLaunchKernelGGL(iterate_kernel<1024>, dim3(grid), dim3(1024), 0, s, args); break;
-    default: return hipErrorInvalidValue;
-  }
+  const int v = plan_iterate(block, args.robust.kernel, args.robust.gate, args.prior.on != 0);
+  if (v == kLaunchRefused) return hipErrorInvalidValue;
+  ++g_kernel_launches; hipLaunchKernelGGL(kIterateKernels[v], dim3(grid), dim3(block), 0, s, args);
   return hipGetLastError();
 }
 
 namespace {
-constexpr uint32_t kPersistWorkers = 512 - 64;
-constexpr uint32_t kPersistWide = 512;  // point-carrying threads when a thread owns several points (wave 0 included)
-constexpr uint32_t kMemoBytesPerPoint = kPersistWide * sizeof(int4);  // 8 192
-// dynamic LDS of the persistent launch: the CU's 160 KB minus the kernel's static use and a margin
-constexpr uint32_t kPersistDynLds = 150 * 1024;
+// kPersistWorkers, kPersistWide, kMemoBytesPerPoint, kPersistDynLds, kPrefetchBytes: vgicp_launch_plan.h
+static_assert(kMemoBytesPerPoint == kPersistWide * sizeof(int4) &&
+              kPrefetchBytes == kPersistWorkers * (sizeof(int4) + 6 * sizeof(double2)), "the plan's LDS sizes are the kernel's");
 constexpr uint32_t kMaxMemoPoints = 12;  // beyond that a thread's points are looked up every round
-constexpr uint32_t kPrefetchBytes = kPersistWorkers * (sizeof(int4) + 6 * sizeof(double2));  // 50 176
 constexpr uint32_t kFusedLoadBytes = kPersistWorkers * 18 * sizeof(double);  // fused_round0_load: 64 512
 }  // namespace
 
@@ -2376,11 +2378,6 @@ void persistent_lds_plan(uint32_t n, uint32_t grid, uint32_t* memo_points, uint3
   *stash_bytes = *stash_points ? budget - memo * kMemoBytesPerPoint : 0u;
 }
 
-uint32_t persistent_dyn_lds_bytes(uint32_t memo_points, uint32_t stash_bytes) {
-  return memo_points * kMemoBytesPerPoint + stash_bytes;
-}
-uint32_t persistent_max_dyn_lds_bytes() { return kPersistDynLds; }
-
 size_t persistent_rows_words() { return 3 * (size_t)kExchangeRows * kSlots; }
 size_t persistent_parts_words() { return 3 * (size_t)kFolders * kSlots; }
 
@@ -2402,20 +2399,6 @@ void persistent_exchange_image(uint32_t grid, unsigned long long* rows_words, un
   }
 }
 
-namespace {
-template <bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false, bool PRIOR = false>
-hipError_t launch_persistent_as(hipStream_t s, const PersistArgs& args, uint32_t grid, size_t dyn, int device) {
-  (void)device;
-  ++g_kernel_launches; hipLaunchKernelGGL((persistent_kernel<512, MULTI, STAMPS, MANY, ROBUST, PRIOR>), dim3(grid), dim3(512), dyn, s, args);
-  return hipGetLastError();
-}
-template <bool MULTI, bool STAMPS, bool MANY, bool ROBUST = false, bool PRIOR = false>
-hipError_t raise_lds_limit() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&persistent_kernel<512, MULTI, STAMPS, MANY, ROBUST, PRIOR>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
-}
-}  // namespace
-
 // LDS beyond the default 64 KB per workgroup has to be asked for, per device and per instantiation.  Done when a
 // context is created, NOT at the first launch: the launch path of a persistent kernel must not contain a runtime
 // call that may wait for the device — with several sub-contexts on one device another sub-context's launch is
@@ -2423,59 +2406,28 @@ hipError_t raise_lds_limit() {
 hipError_t persistent_prepare_device() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&persistent_fused_kernel<512>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
-  if (e == hipSuccess) e = raise_lds_limit<false, false, false>();
-  if (e == hipSuccess) e = raise_lds_limit<false, false, true>();
-  if (e == hipSuccess) e = raise_lds_limit<false, true, false>();
-  if (e == hipSuccess) e = raise_lds_limit<false, true, true>();
-  if (e == hipSuccess) e = raise_lds_limit<true, false, false>();
-  if (e == hipSuccess) e = raise_lds_limit<true, false, true>();
-  if (e == hipSuccess) e = raise_lds_limit<true, true, false>();
-  if (e == hipSuccess) e = raise_lds_limit<true, true, true>();
-  if (e == hipSuccess) e = raise_lds_limit<false, false, false, true>();   // the robust round: single device, no stamps
-  if (e == hipSuccess) e = raise_lds_limit<false, false, true, true>();
-  if (e == hipSuccess) e = raise_lds_limit<false, false, false, false, true>();  // the pose prior: likewise, plain and robust
-  if (e == hipSuccess) e = raise_lds_limit<false, false, true, false, true>();
-  if (e == hipSuccess) e = raise_lds_limit<false, false, false, true, true>();
-  if (e == hipSuccess) e = raise_lds_limit<false, false, true, true, true>();
+  for (PersistentFn fn : kPersistentKernels)
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
   return e;
 }
 
 hipError_t launch_persistent(hipStream_t s, const PersistArgs& args, uint32_t grid) {
-  int device = 0;
-  hipError_t e = hipGetDevice(&device);
-  if (e != hipSuccess) return e;
-  if (device < 0 || device >= 64) return hipErrorInvalidDevice;
-  size_t dyn = (size_t)args.memo_points * kMemoBytesPerPoint + (size_t)args.stash_bytes;
-  if (args.prefetch_margin > 0.0) {
-    if (dyn != 0) return hipErrorInvalidValue;  // the prefetch area shares the LDS of memo / stash
-    dyn = kPrefetchBytes;
-  }
-  if (dyn > kPersistDynLds) return hipErrorInvalidValue;
-  const bool multi = args.world > 1, stamps = args.stamps != nullptr;
-  const bool many = (uint64_t)args.n > (uint64_t)grid * kPersistWorkers;
-  if (args.prior_on != 0) {   // the pose prior: one device, no stamps, with and without the weights
-    if (multi) return hipErrorInvalidValue;
-    if (args.robust_kernel != 0 || args.robust_gate > 0.0)
-      return many ? launch_persistent_as<false, false, true, true, true>(s, args, grid, dyn, device)
-                  : launch_persistent_as<false, false, false, true, true>(s, args, grid, dyn, device);
-    return many ? launch_persistent_as<false, false, true, false, true>(s, args, grid, dyn, device)
-                : launch_persistent_as<false, false, false, false, true>(s, args, grid, dyn, device);
-  }
-  if (args.robust_kernel != 0 || args.robust_gate > 0.0) {   // the weighted round: one device, no stamps
-    if (multi) return hipErrorInvalidValue;
-    return many ? launch_persistent_as<false, false, true, true>(s, args, grid, dyn, device)
-                : launch_persistent_as<false, false, false, true>(s, args, grid, dyn, device);
-  }
-  if (many) {
-    if (multi) return stamps ? launch_persistent_as<true, true, true>(s, args, grid, dyn, device)
-                             : launch_persistent_as<true, false, true>(s, args, grid, dyn, device);
-    return stamps ? launch_persistent_as<false, true, true>(s, args, grid, dyn, device)
-                  : launch_persistent_as<false, false, true>(s, args, grid, dyn, device);
-  }
-  if (multi) return stamps ? launch_persistent_as<true, true, false>(s, args, grid, dyn, device)
-                           : launch_persistent_as<true, false, false>(s, args, grid, dyn, device);
-  return stamps ? launch_persistent_as<false, true, false>(s, args, grid, dyn, device)
-                : launch_persistent_as<false, false, false>(s, args, grid, dyn, device);
+  PersistentFacts f;
+  f.world = args.world;
+  f.stamps = args.stamps != nullptr;
+  f.n = args.n;
+  f.grid = grid;
+  f.memo_points = args.memo_points;
+  f.stash_bytes = args.stash_bytes;
+  f.prefetch_margin = args.prefetch_margin;
+  f.robust_kernel = args.robust.kernel;
+  f.robust_gate = args.robust.gate;
+  f.prior = args.prior.on != 0;
+  const PersistentPlan plan = plan_persistent(f);
+  if (plan.variant == kLaunchRefused) return hipErrorInvalidValue;
+  ++g_kernel_launches; hipLaunchKernelGGL(kPersistentKernels[plan.variant], dim3(grid), dim3(512), plan.dyn_lds, s, args);
+  return hipGetLastError();
 }
 
 hipError_t launch_persistent_fused(hipStream_t s, const PersistArgs& args, const FusedUpload& up, uint32_t grid) {
@@ -2506,11 +2458,12 @@ hipError_t launch_persistent_teams(hipStream_t s, const PersistArgs& args, const
 hipError_t persistent_max_resident(uint32_t dyn_lds_bytes, int cu_count, uint32_t* max_grid) {
   // the plain kernel with the most registers, the robust round's and the pose prior's (bodies of their own: asked on
   // their own)
-  const void* fns[3] = {reinterpret_cast<const void*>(&persistent_kernel<512, true, false, true>),
-                        reinterpret_cast<const void*>(&persistent_kernel<512, false, false, true, true>),
-                        reinterpret_cast<const void*>(&persistent_kernel<512, false, false, true, true, true>)};
+  constexpr int asked[3] = {find_persistent(true, false, true, false, false), find_persistent(false, false, true, true, false),
+                            find_persistent(false, false, true, true, true)};
+  static_assert(asked[0] >= 0 && asked[1] >= 0 && asked[2] >= 0, "the three instantiations are listed");
   *max_grid = (uint32_t)cu_count;  // one workgroup per CU is what the design uses
-  for (const void* fn : fns) {
+  for (const int v : asked) {
+    const void* fn = reinterpret_cast<const void*>(kPersistentKernels[v]);
     int per_cu = 0;
     // more than the default 64 KB of LDS per workgroup has to be asked for before the occupancy query can say yes
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistDynLds);
@@ -2525,21 +2478,9 @@ hipError_t persistent_max_resident(uint32_t dyn_lds_bytes, int cu_count, uint32_
 // The closing launch folds the last round's rows with the workgroup size of the body launches, so that
 // its sums are added in the same order as every other round's (and as the persistent launch adds them).
 hipError_t launch_close(hipStream_t s, const IterArgs& args, int block) {
-  if (args.prior_on != 0) {   // the last round's solve takes the pose prior as every other round's does
-    switch (block) {
-      case 256: ++g_kernel_launches; hipLaunchKernelGGL((close_kernel<256, true>), dim3(1), dim3(256), 0, s, args); break;
-      case 512: ++g_kernel_launches; hipLaunchKernelGGL((close_kernel<512, true>), dim3(1), dim3(512), 0, s, args); break;
-      case 1024: ++g_kernel_launches; hipLaunchKernelGGL((close_kernel<1024, true>), dim3(1), dim3(1024), 0, s, args); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  switch (block) {
-    case 256: ++g_kernel_launches; hipLaunchKernelGGL(close_kernel<256>, dim3(1), dim3(256), 0, s, args); break;
-    case 512: ++g_kernel_launches; hipLaunchKernelGGL(close_kernel<512>, dim3(1), dim3(512), 0, s, args); break;
-    case 1024: ++g_kernel_launches; hipLaunchKernelGGL(close_kernel<1024>, dim3(1), dim3(1024), 0, s, args); break;
-    default: return hipErrorInvalidValue;
-  }
+  const int v = plan_close(block, args.prior.on != 0);   // the last round's solve takes the pose prior as every other round's
+  if (v == kLaunchRefused) return hipErrorInvalidValue;
+  ++g_kernel_launches; hipLaunchKernelGGL(kCloseKernels[v], dim3(1), dim3(block), 0, s, args);
   return hipGetLastError();
 }
 

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 KERNEL_SOURCES = ("csrc/vgicp_kernels.hip", "csrc/vgicp_device.h", "csrc/vgicp_device_fn.h", "csrc/vgicp_math.h",
-                  "csrc/Makefile")
+                  "csrc/vgicp_launch_plan.h", "csrc/Makefile")
 
 
 def _sha(paths) -> str:
