@@ -26,6 +26,7 @@ std::atomic<uint64_t> g_context_ids{0};
 #include "vgicp_capi_memory.inl"
 #include "vgicp_capi_align.inl"
 #include "vgicp_capi_context.inl"
+#include "vgicp_capi_resident.inl"
 #include "vgicp_capi_map.inl"
 #include "vgicp_capi_upload.inl"
 #include "vgicp_capi_registration.inl"

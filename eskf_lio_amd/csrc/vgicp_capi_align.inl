@@ -19,8 +19,7 @@ IterArgs base_args(const vgicp_ctx* ctx) {
   a.stamps = ctx->d_stamps;
   a.memo = static_cast<int4*>(ctx->d_memo.get());
   a.memo_valid = 0;   // the caller knows which launch of the align this is
-  a.scan_seq = ctx->scan_seq;
-  a.asym_dev = symmetry_word(ctx);
+  set_symmetry(ctx, &a);
   // the dense record copy (tables far beyond the caches' reach): used where it is current — the aligns that reach the
   // loop after a persistent launch has rebuilt it, or run_align's own ensure_dense
   a.dense = (ctx->d_dense && ctx->dense_version == ctx->map_version && ctx->slots >= ctx->dense_slots_threshold &&

@@ -1,6 +1,7 @@
 // vgicp_capi_batch.inl — part of vgicp_capi.hip.
-// vgicp_align_resident_batch / vgicp_align_batch_width (include/vgicp_hip_batch.h): argument checks, settling, the
-// launches with their one synchronisation, and the k single aligns in a row.  Whether a batch runs as teams, and how
+// vgicp_align_resident_batch / vgicp_align_batch_width (include/vgicp_hip_batch.h): the plan (plan_batch,
+// vgicp_resident_plan.h), the call frame (vgicp_capi_resident.inl), the launches with their one synchronisation, and the k
+// single aligns in a row.  Whether a batch runs as teams, and how
 // wide: plan_align / team_width (vgicp_align_plan.h).
 namespace {
 AlignState* batch_state(const vgicp_ctx* ctx, size_t h) {
@@ -46,7 +47,7 @@ int run_batch_teams(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp
   }
   const size_t exchange_bytes = (team_rows_words() + team_parts_words()) * 8;
   int launches = 0;
-  VG_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
+  VG_RC(TimedSpan::begin(ctx));
   for (size_t h0 = 0; h0 < k; h0 += width, ++launches) {
     t.teams = (uint32_t)std::min<size_t>(width, k - h0);
     for (uint32_t h = 0; h < t.teams; ++h) pose_to_state(guesses + 16 * (h0 + h), t.pose0[h]);
@@ -57,10 +58,10 @@ int run_batch_teams(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp
     VG_HIP(ctx, hipMemsetAsync(ctx->d_batch_exchange, 0xFF, exchange_bytes, ctx->stream));
     VG_HIP(ctx, launch_persistent_teams(ctx->stream, a, t, ctx->persist_grid));
   }
-  VG_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
+  VG_RC(TimedSpan::end(ctx));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  VG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+  double device_seconds = 0.0;
+  VG_RC(TimedSpan::device_seconds(ctx, &device_seconds));
   ctx->persistent_launches += (uint64_t)launches;
   // accepted only if every team's echo is there and nobody gave up: the ONE abort word speaks for every hypothesis
   bool committed = true;
@@ -80,7 +81,7 @@ int run_batch_teams(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp
   if (stats) {
     stats->hypotheses_per_launch = (int32_t)std::min<size_t>(width, k);
     stats->launches = launches;
-    stats->device_seconds = ms * 1e-3;
+    stats->device_seconds = device_seconds;
   }
   return VGICP_OK;
 }
@@ -121,26 +122,23 @@ extern "C" {
 
 int vgicp_align_resident_batch(vgicp_ctx* ctx, size_t k, const double* guesses, const vgicp_params* params,
                                double* out_poses, vgicp_batch_stats* stats) {
-  if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (k < 1 || k > (size_t)VGICP_BATCH_MAX) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "k must be 1 .. VGICP_BATCH_MAX");
-  if (!guesses || !out_poses) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "NULL pose pointer");
-  VG_RC(check_params(ctx, params));
-  const double t0 = now_seconds();
+  BatchFacts f;
+  f.ctx = ctx != nullptr, f.k = k, f.guesses = guesses != nullptr, f.out_poses = out_poses != nullptr, f.params = params != nullptr;
+  if (params) f.max_iteration = params->max_iteration;
+  if (ctx) f.multi = ctx->multi != nullptr, f.at = resident_facts(ctx);
+  const ResidentVerdict v = plan_batch(f);
+  VG_RC(refuse(ctx, v));
+  const TimedSpan span;
   int first_bad = VGICP_OK;
-  int rc;
-  if (ctx->multi) {
+  int rc = VGICP_OK;
+  if (v.forward) {
     rc = vgicp_multi_api::align_resident_batch(ctx, k, guesses, params, out_poses, stats, &first_bad);
     if (rc != VGICP_OK) return rc;
-    if (stats) stats->seconds = now_seconds() - t0;
+    if (stats) stats->seconds = span.seconds();
     return (stats && stats->status) ? VGICP_OK : first_bad;
   }
-  VG_HIP(ctx, hipSetDevice(ctx->device));
-  if (!ctx->table) return fail(ctx, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first");
-  if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
-  // the team layout is made from the kept count: a pending scan (and a pending insertion with it) is settled first
-  rc = settle(ctx);
-  if (rc != VGICP_OK) return rc;
-  if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
+  VG_RC(settle_resident(ctx, &f.at));   // the team layout is made from the kept count
+  VG_RC(refuse(ctx, plan_batch(f)));
   const AlignPlan plan = plan_align(align_facts(ctx, params, AlignCall::Batch, ctx->n, k));
   bool ran = false;
   if (plan.width < 2) {
@@ -154,7 +152,7 @@ int vgicp_align_resident_batch(vgicp_ctx* ctx, size_t k, const double* guesses, 
       rc = vgicp_internal::align_batch_sequential(ctx, k, guesses, params, out_poses, stats, /*loop_only=*/true, &first_bad);
   }
   if (rc != VGICP_OK) return rc;
-  if (stats) stats->seconds = now_seconds() - t0;
+  if (stats) stats->seconds = span.seconds();
   return (stats && stats->status) ? VGICP_OK : first_bad;
 }
 
@@ -164,7 +162,7 @@ int vgicp_align_batch_width(vgicp_ctx* ctx, size_t* hypotheses_per_launch) {
   *hypotheses_per_launch = 1;
   if (ctx->multi) return vgicp_multi_api::align_batch_width(ctx, hypotheses_per_launch);
   VG_RC(settle(ctx));
-  if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident: call vgicp_scan_upload first");
+  if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, kNoScanText);
   uint32_t team_wgs = 0;
   *hypotheses_per_launch = team_width(align_facts(ctx, nullptr, AlignCall::Batch, ctx->n), &team_wgs);
   return VGICP_OK;

@@ -41,6 +41,9 @@ InsertVerdict insert_verdict(const vgicp_ctx* ctx, InsertEntry entry, bool point
   f.points_per_voxel = max_points_per_voxel;
   f.raw_on = ctx->raw_on;
   f.n = n;
+  // not several_devices(ctx) (vgicp_capi_resident.inl): what plan_insert refuses is a RANK's shard.  A sub-context of a
+  // multi-device context has peers too, but it answers for its group here (facts_of, vgicp_capi_map_gated.inl), which
+  // plan_gate then refuses in its own words; the multi-device handle itself never gets here
   f.shard_only = (ctx->comm || ctx->peers_connected) && !ctx->owner;
   return plan_insert(f);
 }
@@ -59,7 +62,7 @@ bool resident_lists_stay_short(const vgicp_ctx* ctx) {
 struct GateCall {
   double gate;
   uint8_t* kept;            // the caller's array (synchronous entry), or nullptr
-  bool timed;               // ev_begin / ev_end around the launches
+  bool timed;               // the entry's TimedSpan begins in front of the decision and ends behind the insertion
 };
 int insert_points(vgicp_ctx* ctx, const double* d_points, const double* d_covs, size_t n, const double transform[16],
                   size_t max_points_per_voxel, void* scratch, bool short_lists, bool deferred, size_t* new_voxels,
@@ -89,20 +92,17 @@ int insert_points(vgicp_ctx* ctx, const double* d_points, const double* d_covs, 
   if (gate) {
     GateArgs g;
     std::memset(&g, 0, sizeof g);
-    static_cast<ResidentView&>(g) = resident_view(ctx);   // a gated insertion is the resident scan's: n == ctx->n
-    for (int k = 0; k < 12; ++k) g.pose[k] = pose12[k];
-    g.asym_dev = symmetry_word(ctx);
-    g.scan_seq = ctx->scan_seq;
+    static_cast<PoseView&>(g) = pose_view(ctx, transform);   // a gated insertion is the resident scan's: n == ctx->n
     g.gate = gate->gate;
     g.keep = keep;
     g.counters = ctx->d_ins_counters + kGateWord;
-    if (gate->timed) VG_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
+    if (gate->timed) VG_RC(TimedSpan::begin(ctx));
     VG_HIP(ctx, launch_gate_decide(ctx->stream, g));
   }
   VG_HIP(ctx, launch_map_insert(ctx->stream, ctx->table, (uint32_t)(ctx->slots - 1), ctx->voxel_size, d_points, d_covs,
                                 (uint32_t)n, pose12, (uint64_t)max_points_per_voxel, scratch, sb,
                                 deferred ? ctx->d_ins_counters : ctx->d_counters, short_lists, raw_log(ctx), keep));
-  if (gate && gate->timed) VG_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
+  if (gate && gate->timed) VG_RC(TimedSpan::end(ctx));
   if (!deferred) {
     // the synchronous gated entry: its counts and the keep plane ride on finish_insert's wait.  The insertion is enqueued
     // by now, so a copy that cannot be enqueued must not keep finish_insert from taking the map's new size: it is

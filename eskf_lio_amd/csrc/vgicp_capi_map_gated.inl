@@ -3,13 +3,11 @@
 // libvgicp_hip_map_gated.so: the refusals (plan_insert's for the gated entries, then plan_gate: vgicp_map_plan.h), the
 // settling, and the call of insert_points (vgicp_capi_map.inl) with a GateCall — the one place an insertion is launched.
 namespace {
-bool several_devices(const vgicp_ctx* ctx) { return ctx->multi || ctx->owner || ctx->comm || ctx->peers_connected; }
 GateFacts gate_facts(const vgicp_ctx* ctx, const double* transform, double gate) {
   GateFacts f;
-  f.transform_finite = true;
-  for (int k = 0; k < 16; ++k) f.transform_finite = f.transform_finite && std::isfinite(transform[k]);
+  static_cast<ResidentFacts&>(f) = resident_facts(ctx);
+  f.transform_finite = first_not_finite(transform, 16) == 16;
   f.gate = gate;
-  f.several_devices = several_devices(ctx);
   return f;
 }
 // plan_insert's facts: a multi-device context keeps its map and scan in its sub-contexts, so the first of them answers
@@ -21,7 +19,7 @@ namespace vgicp_internal {
 int map_insert_resident_gated(vgicp_ctx* ctx, const double transform[16], size_t max_points_per_voxel, double gate,
                               size_t capacity, uint8_t* kept, vgicp_gated_insert_stats* stats) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  const double t0 = now_seconds();
+  const TimedSpan span;
   // as vgicp_map_insert_resident: what is pending is settled before anything is judged (a context of several devices
   // is refused below by what it is, not by what it has pending)
   if (!several_devices(ctx)) VG_RC(settle(ctx));
@@ -30,7 +28,6 @@ int map_insert_resident_gated(vgicp_ctx* ctx, const double transform[16], size_t
   GateFacts facts = gate_facts(ctx, transform, gate);
   facts.kept_given = kept != nullptr;
   facts.capacity = capacity;
-  facts.n = ctx->n;
   const GateVerdict g = plan_gate(facts);
   if (g.status != VGICP_OK) {
     if (g.rule == 7 && stats) stats->points = ctx->n;
@@ -41,7 +38,7 @@ int map_insert_resident_gated(vgicp_ctx* ctx, const double transform[16], size_t
   const uint64_t launches0 = g_kernel_launches;
   if (!v.nothing_to_do) {
     VG_HIP(ctx, hipSetDevice(ctx->device));
-    const GateCall call{gate, kept, true};
+    const GateCall call{gate, kept, /*timed=*/true};
     const int rc = insert_points(ctx, ctx->d_scan_aos, ctx->d_scan_aos + 3 * ctx->scan_capacity, n, transform, max_points_per_voxel,
                                  nullptr, resident_lists_stay_short(ctx), /*deferred=*/false, &new_voxels, &call);
     // the decision's counts came with the insertion's: read whatever the insertion's own verdict is
@@ -73,10 +70,9 @@ int map_insert_resident_gated(vgicp_ctx* ctx, const double transform[16], size_t
     stats->new_voxels = new_voxels;
     stats->launches = (int32_t)(g_kernel_launches - launches0);
     stats->reserved = 0;
-    float ms = 0.f;
-    if (!v.nothing_to_do) VG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
-    stats->device_seconds = ms * 1e-3;
-    stats->seconds = now_seconds() - t0;
+    stats->device_seconds = 0.0;   // nothing to do: no span was recorded
+    if (!v.nothing_to_do) VG_RC(span.device_seconds(ctx, &stats->device_seconds));
+    stats->seconds = span.seconds();
   }
   return VGICP_OK;
 }

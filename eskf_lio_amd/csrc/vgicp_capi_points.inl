@@ -1,7 +1,7 @@
 // vgicp_capi_points.inl — part of vgicp_capi.hip.
 // vgicp_points_resident (include/vgicp_hip_points.h) behind its entry point in libvgicp_hip_points.so: the refusals
-// (plan_points, vgicp_points_plan.h), settling, the launches with their one synchronisation, the delivery.  Reads the
-// context; writes only the report's own storage (d_points, h_points) and the arena.
+// (plan_points, vgicp_points_plan.h), the call frame (vgicp_capi_resident.inl), the launches with their one
+// synchronisation, the delivery.  Reads the context; writes only the report's own storage (d_points, h_points) and the arena.
 namespace {
 // ctx->d_points carved for `cap` points: the four planes, the sort's two (key, index) buffers and its splitters, the
 // counters.  Everything at a 256-byte boundary.
@@ -27,20 +27,16 @@ template <class T> T* points_at(const vgicp_ctx* ctx, size_t offset) { return re
 PointsFacts points_facts(const vgicp_ctx* ctx, const double* pose, size_t capacity, bool any_array, size_t n_quantiles,
                          const double* q, const vgicp_point_summary* summary) {
   PointsFacts f;
+  static_cast<ResidentFacts&>(f) = resident_facts(ctx);
   f.pose = pose != nullptr;
-  if (pose)
-    for (int k = 0; k < 16; ++k) f.pose_finite = f.pose_finite && std::isfinite(pose[k]);
+  f.pose_finite = !pose || first_not_finite(pose, 16) == 16;
   f.n_quantiles = n_quantiles;
   f.q = q != nullptr;
   f.summary = summary != nullptr;
   if (q && n_quantiles <= kPointQuantilesMax)
     for (size_t j = 0; j < n_quantiles; ++j) f.q_in_range = f.q_in_range && q[j] >= 0.0 && q[j] <= 1.0;
-  f.several_devices = ctx->multi || ctx->owner || ctx->comm || ctx->peers_connected;
-  f.has_map = ctx->table != nullptr;
-  f.scan_resident = ctx->scan_ready;
   f.any_array = any_array;
   f.capacity = capacity;
-  f.n = ctx->n;
   return f;
 }
 }  // namespace
@@ -50,17 +46,11 @@ int points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, doub
                     uint8_t* status, size_t n_quantiles, const double* q, vgicp_point_summary* summary,
                     vgicp_point_stats* stats) {
   if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  const bool any_array = d2 || sq_error || weight || status;
-  PointsFacts facts = points_facts(ctx, pose, capacity, any_array, n_quantiles, q, summary);
+  PointsFacts facts = points_facts(ctx, pose, capacity, d2 || sq_error || weight || status, n_quantiles, q, summary);
   PointsVerdict v = plan_points(facts);
   if (v.status != VGICP_OK) return fail(ctx, v.status, v.text);
-  const double t0 = now_seconds();
-  VG_HIP(ctx, hipSetDevice(ctx->device));
-  // the kept count, and with it the capacity check and the launch geometry: a pending scan (and a pending insertion
-  // with it) is settled first
-  VG_RC(settle(ctx));
-  facts = points_facts(ctx, pose, capacity, any_array, n_quantiles, q, summary);
-  facts.settled = true;
+  const TimedSpan span;
+  VG_RC(settle_resident(ctx, &facts));   // the capacity check and the launch geometry are made from the kept count
   v = plan_points(facts);
   if (v.status != VGICP_OK) {
     if (v.sets_points && summary) summary->points = ctx->n;
@@ -80,10 +70,7 @@ int points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, doub
 
   PointArgs a;
   std::memset(&a, 0, sizeof a);
-  static_cast<ResidentView&>(a) = resident_view(ctx);   // settled: n is the resident scan's size
-  pose_to_state(pose, a.pose);
-  a.asym_dev = symmetry_word(ctx);
-  a.scan_seq = ctx->scan_seq;
+  static_cast<PoseView&>(a) = pose_view(ctx, pose);   // settled: n is the resident scan's size
   const RobustArgs robust = robust_args(ctx);
   a.robust_kernel = robust.kernel;
   a.robust_scale2 = robust.scale2;
@@ -107,7 +94,7 @@ int points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, doub
   pick.out = ctx->h_points.dev();
 
   int launches = n ? 2 : 1;
-  VG_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
+  VG_RC(span.begin(ctx));
   VG_HIP(ctx, hipMemsetAsync(a.counters, 0, kPointCounters * sizeof(uint32_t), ctx->stream));
   VG_HIP(ctx, launch_point_terms(ctx->stream, a));
   if (ranks) {
@@ -117,7 +104,7 @@ int points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, doub
     launches += (int)sort_launches;
   }
   VG_HIP(ctx, launch_point_pick(ctx->stream, pick));
-  VG_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
+  VG_RC(span.end(ctx));
   // the arrays: through the arena, the runtime never sees the caller's pages
   arena_reset(ctx);
   if (n) {
@@ -138,12 +125,10 @@ int points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, doub
     for (size_t j = 0; j < n_quantiles; ++j) summary->quantile[j] = point_key_value(r[kPointCounters + j]);
   }
   if (stats) {
-    float ms = 0.f;
-    VG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+    VG_RC(span.device_seconds(ctx, &stats->device_seconds));
     stats->launches = launches;
     stats->reserved = 0;
-    stats->seconds = now_seconds() - t0;
-    stats->device_seconds = ms * 1e-3;
+    stats->seconds = span.seconds();
   }
   return VGICP_OK;
 }

@@ -34,6 +34,7 @@
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
 #include "vgicp_prepare_plan.h"
+#include "vgicp_resident_plan.h"
 #include "vgicp_map_plan.h"
 #include "vgicp_points_plan.h"
 
@@ -524,6 +525,10 @@ struct vgicp_ctx {
   int rank = 0;
 };
 
+// The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip): was
+// this context made by the build that reads it?  Reads the stamp only; each library refuses in its own words.
+inline bool same_build(const vgicp_ctx* ctx) { return ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx)); }
+
 // The facts plan_align (vgicp_align_plan.h) decides by, as this context and this call have them: the ONE place where a
 // single-device align's plan meets the context (a multi-device context fills its own: group_facts, vgicp_multi.hip).
 // n: the caller's count (AlignCall::Upload), else the resident scan's.
@@ -544,6 +549,10 @@ inline vgicp::ResidentView resident_view(const vgicp_ctx* ctx) {
 // verdict of pack_scan_kernel, for a scan that went through it (developer A/B no_sym: always read all twelve planes).
 inline const uint32_t* symmetry_word(const vgicp_ctx* ctx) {
   return (ctx->scan_sym_known && !ctx->dev.no_sym) ? ctx->d_ins_counters + 2 : nullptr;
+}
+template <class Args> void set_symmetry(const vgicp_ctx* ctx, Args* a) {   // the pair, wherever an argument struct keeps it
+  a->asym_dev = symmetry_word(ctx);
+  a->scan_seq = ctx->scan_seq;
 }
 // The context's robust settings and its pose prior as the kernels take them.
 inline vgicp::RobustArgs robust_args(const vgicp_ctx* ctx) {

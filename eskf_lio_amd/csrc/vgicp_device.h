@@ -68,9 +68,9 @@ constexpr uint32_t kOutcomeAgreedAbort = 2;  // several GPUs: some rank gave up,
 constexpr uint32_t kOutcomeNoAgreement = 3;  // several GPUs: a peer's verdict never arrived
 
 // The resident scan and the voxel map as every launch over them sees them: the base of the five argument structs below
-// (resident_view(ctx), vgicp_context.h, fills it).  asym_dev / scan_seq stay fields of each struct, where they always
-// were: a kernel's scalar argument loads are grouped by offset, so no field of an argument struct may move (the
-// static_asserts behind each struct hold the offsets).
+// (resident_view(ctx), vgicp_context.h, fills it).  asym_dev / scan_seq stay fields of each struct (of PoseView for the
+// two that share their first 148 bytes), where they always were: a kernel's scalar argument loads are grouped by
+// offset, so no field of an argument struct may move (the static_asserts behind each struct hold the offsets).
 #pragma GCC diagnostic push   // offsetof in a struct with a base: conditionally supported, and supported by both compilers
 #pragma GCC diagnostic ignored "-Winvalid-offsetof"
 struct ResidentView {
@@ -82,6 +82,15 @@ struct ResidentView {
   double voxel_size;
 };
 static_assert(sizeof(ResidentView) == 40, "the view is the first 40 bytes of every argument struct");
+// The view at a pose: the first 148 bytes of PointArgs and GateArgs, what point_term (vgicp_kernels.hip) reads
+// (pose_view(ctx, pose16), vgicp_capi_resident.inl, fills it).  A class with a base gives up its tail padding to the
+// class derived from it: the field behind scan_seq sits at 148, where it sat in the flat structs.
+struct PoseView : ResidentView {
+  double pose[12];           // R column-major (9), t (3)
+  const uint32_t* asym_dev;  // as IterArgs
+  uint32_t scan_seq;
+};
+static_assert(sizeof(PoseView) == 152 && offsetof(PoseView, pose) == 40, "PoseView: no field may move");
 // The robust round (include/vgicp_hip_robust.h) as the kernels take it (robust_args(ctx)); all zero = the plain round
 // (vgicp_accumulate, a group's loop, the fused and the team launch: always).
 struct RobustArgs {
@@ -248,11 +257,8 @@ static_assert(sizeof(EvalArgs) == 72 && offsetof(EvalArgs, poses) == 40 && offse
 constexpr int kPointCounters = 4;
 constexpr int kPointQuantiles = 16;        // VGICP_POINT_QUANTILES_MAX
 constexpr int kPointResultWords = kPointCounters + kPointQuantiles;
-struct PointArgs : ResidentView {
-  double pose[12];           // R column-major (9), t (3)
-  const uint32_t* asym_dev;  // as IterArgs
-  uint32_t scan_seq;
-  uint32_t robust_kernel;    // RobustArgs, flat: the offset is 4 mod 8, where a RobustArgs member cannot sit
+struct PointArgs : PoseView {
+  uint32_t robust_kernel;    // RobustArgs, flat: the offset is 4 mod 8 (the view's tail), where a RobustArgs member cannot sit
   double robust_scale2;
   double robust_gate;
   double* d2;                // n each, or nullptr
@@ -280,10 +286,7 @@ struct PointPickArgs {
 // included).  Read-only on the table; the insertion that claims slots is a later launch.  counters: 3 device words that
 // only ever grow (running totals; the host remembers what it has read): matched, refused, not finite.
 constexpr int kGateCounters = 3;
-struct GateArgs : ResidentView {
-  double pose[12];           // R column-major (9), t (3)
-  const uint32_t* asym_dev;  // as IterArgs
-  uint32_t scan_seq;
+struct GateArgs : PoseView {
   uint32_t pad;
   double gate;               // >= 0 or +inf
   uint8_t* keep;             // n

@@ -973,13 +973,12 @@ __global__ __launch_bounds__(512) void evaluate_fold_kernel(const double* __rest
   }
 }
 
-// The term of point i, for point_terms_kernel and gate_decide_kernel (Args: PointArgs or GateArgs): the ONE definition.
+// The term of point i, for point_terms_kernel and gate_decide_kernel (the view both argument structs begin with): the ONE definition.
 struct PointTerm {
   double raw, sq;   // e^T W e and |e|^2; +infinity when the point's voxel is not in the map
   bool matched;
 };
-template <class Args>
-__device__ __forceinline__ PointTerm point_term(const Args& a, uint32_t i, bool cov_sym) {
+__device__ __forceinline__ PointTerm point_term(const PoseView& a, uint32_t i, bool cov_sym) {
   double q[kScanPlanes];
   load_point_sym(a.scan, a.stride, i, q, cov_sym);
   double R[9], t[3], C[9];

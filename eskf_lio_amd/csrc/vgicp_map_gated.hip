@@ -9,15 +9,9 @@ namespace {
 // rules 1 and 2 of the header's list: nothing of the context is read or written unless its layout is this build's (the
 // text goes where a failed vgicp_create's goes).  *rc: the status to return when the handshake fails.
 bool handshake(const vgicp_ctx* ctx, int* rc) {
-  if (!ctx) {
-    *rc = VGICP_ERR_BAD_ARGUMENT;
-    return false;
-  }
-  if (ctx->layout != (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx))) {
-    *rc = fail(nullptr, VGICP_ERR_BAD_ARGUMENT, "context and libvgicp_hip_map_gated.so are not from one build of the module");
-    return false;
-  }
-  return true;
+  *rc = VGICP_ERR_BAD_ARGUMENT;
+  if (ctx && !same_build(ctx)) fail(nullptr, *rc, "context and libvgicp_hip_map_gated.so are not from one build of the module");
+  return ctx && same_build(ctx);
 }
 }  // namespace
 

@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "../../include/vgicp_hip.h"
+#include "vgicp_resident_plan.h"
 
 namespace vgicp {
 
@@ -122,13 +123,11 @@ inline InsertVerdict plan_insert(const InsertFacts& f) {
 }
 
 // ---- what a gated insertion refuses once plan_insert has passed (include/vgicp_hip_map_gated.h, rules 4 to 7) ----
-struct GateFacts {
+struct GateFacts : ResidentFacts {   // several_devices and n are asked here: plan_insert has asked for the map and the scan
   bool transform_finite = false;
   double gate = 0.0;
-  bool several_devices = false;   // a multi-device, communicator or peer-connected context
   bool kept_given = false;        // the synchronous entry, once settled: the caller's keep array ...
   uint64_t capacity = 0;          // ... and its length
-  uint64_t n = 0;
 };
 struct GateVerdict {
   int rule = 0;                   // 0: passed, else the header's number

@@ -14,7 +14,7 @@ int vgicp_points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity
   // read or written unless its layout is this build's (the text goes where a failed vgicp_create's goes)
   PointsFacts f;
   f.ctx = ctx != nullptr;
-  f.same_build = ctx && ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx));
+  f.same_build = ctx && same_build(ctx);
   const PointsVerdict v = plan_points(f);
   if (v.rule == 1) return v.status;
   if (v.rule == 2) return fail(nullptr, v.status, v.text);

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/vgicp_hip.h"
+#include "vgicp_resident_plan.h"
 
 #if defined(__HIPCC__)
 #define VGICP_POINTS_FN __host__ __device__ inline
@@ -20,7 +21,7 @@ constexpr uint64_t kPointQuantilesMax = 16;   // VGICP_POINT_QUANTILES_MAX
 
 // ---- what the call refuses.  Rules 1-9 are decided before anything is settled, rule 9 once more and rule 10 after
 // (`settled`): n is known only then ----
-struct PointsFacts {
+struct PointsFacts : ResidentFacts {   // several_devices, has_map, scan_resident, settled, n: as every call over the resident scan
   bool ctx = true;              // not NULL
   bool same_build = true;       // the context's layout stamp is this build's
   bool pose = true;             // not NULL
@@ -29,13 +30,8 @@ struct PointsFacts {
   bool q = true;                // not NULL
   bool summary = true;          // not NULL
   bool q_in_range = true;       // every q[j] in [0, 1] (a NaN is not)
-  bool several_devices = false; // a multi-device context, a communicator or a peer-connected context
-  bool has_map = true;
-  bool scan_resident = true;
-  bool settled = false;         // pending work has been settled: n is the resident scan's size
   bool any_array = false;       // one of d2 / sq_error / weight / status is given
   uint64_t capacity = 0;
-  uint64_t n = 0;
 };
 struct PointsVerdict {
   int status = VGICP_OK;
