@@ -349,6 +349,7 @@ constexpr uint32_t kArenaCompact = 1u;   // all of them bitwise symmetric: c00 c
 hipError_t launch_pack_arena(hipStream_t s, const void* arena_points, const void* arena_covs, uint32_t n,
                              const uint32_t* flags, bool wait, uint32_t seq, uint32_t spin_limit, double* aos_pts, double* aos_cov,
                              double* soa, uint64_t stride, uint32_t* asym);
+// ---- the voxel table's launchers (defined in vgicp_table.hip) ----
 hipError_t launch_table_clear(hipStream_t s, VoxelRecord* table, uint64_t slots);
 // Pack the FULL records of `table` into `dense` in slot order (128 bytes each) and leave every record's index there in
 // the upper half of its spare word.  block_counts: scratch of table_dense_blocks(slots) + 1 words.
@@ -490,6 +491,19 @@ hipError_t launch_sort_keys64(hipStream_t s, unsigned long long* keys_a, uint32_
                               uint32_t* idx_b, void* split, uint32_t n, uint32_t* launches);
 // kernels enqueued by the launchers of this module since the counter was last reset (per host thread)
 extern thread_local uint64_t g_kernel_launches;
+#ifdef __HIPCC__   // a host compiler that only reads the layouts (tests/native) has no launch syntax
+// How every launcher of the module enqueues a kernel: counted and launched in one statement (always inlined: no call
+// stands between a launcher and its launch, and the module exports no instantiation).  A launcher reads hipGetLastError()
+// once, at its end.  The sort adds launches_for(n) for its own launches: vgicp_sort.h is also built without the module.
+template <typename Kernel, typename... Args>
+static inline __attribute__((always_inline)) void counted_launch(Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes,
+                                                                hipStream_t s, const Args&... args) {
+  ++g_kernel_launches;
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
+}
+#endif
+// workgroups of `block` threads that cover `work` items
+inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((work + block - 1) / block); }
 hipError_t launch_transform_points(hipStream_t s, double* pts, uint32_t n, const double T16[16]);
 // CloudPreprocessor::deskew: ends = scratch of deskew_scratch_words(states) words (the first `states` are the
 // segment ends); poses = 12 doubles per state (R column-major, t); ordered_states: the host has checked that the

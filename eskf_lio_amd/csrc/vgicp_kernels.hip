@@ -10,9 +10,7 @@
 //                   ICP::computeTransform (:60-70)
 //   evaluate_kernel that round's body at several given poses at once, plus the objective and the squared error
 //                   (no counterpart in the reference: what Open3D's EvaluateRegistration is to its ICP)
-//   upsert/erase    the effect of LocalMap::updateLocalMap's insert and evict loops on the data the
-//                   path reads (src/LocalMap.cpp:47-72), mirrored from host-computed voxel values
-//   match kernels   LocalMap::correspondenceMatching with materialised output (src/LocalMap.cpp:78-112)
+// The voxel table's own kernels (clear, upsert, rehash, erase, match, dense copy) are vgicp_table.hip.
 //
 // Design notes (DESIGN.md has the numbers):
 //   * The scan is never written back: the TOTAL pose is applied to the original point in registers
@@ -572,6 +570,30 @@ __device__ __forceinline__ void inverse3_cofactor(const double (&S)[9], double (
   W[2] = c02 * id; W[5] = c12 * id; W[8] = c22 * id;
 }
 
+// The term of one correspondence, the ONE definition for the rounds (accumulate_match), the evaluation (evaluate_kernel)
+// and the per-point report and gate (point_term): S = R C R^T + C_voxel (S holds C_voxel on entry), W = S^-1, and the
+// raw squared Mahalanobis residual e^T W e for e = p - mu, formed as e . (W e).
+__device__ __forceinline__ void match_weight(const double* R, const double (&C)[9], double (&S)[9], double (&W)[9]) {
+  double RC[9];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+      RC[r + 3 * c] = R[r] * C[3 * c] + R[r + 3] * C[1 + 3 * c] + R[r + 6] * C[2 + 3 * c];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+      S[r + 3 * c] += RC[r] * R[c] + RC[r + 3] * R[c + 3] + RC[r + 6] * R[c + 6];
+  inverse3_cofactor(S, W);
+}
+__device__ __forceinline__ double mahalanobis(const double (&W)[9], double e0, double e1, double e2) {
+  const double g0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
+  const double g1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
+  const double g2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
+  return e0 * g0 + e1 * g1 + e2 * g2;
+}
+
 // The robust round (include/vgicp_hip_robust.h): the settings as a kernel holds them, made once per launch from the
 // three fields at the end of IterArgs / PersistArgs, and the weight of one correspondence from its squared Mahalanobis
 // residual raw = e^T W e.  d^2 = max(raw, 0); the gate is asked of raw itself, so a NaN residual is rejected.  Huber:
@@ -618,21 +640,8 @@ __device__ __forceinline__ void accumulate_match(const double* R, const double (
                                                  const double (&C)[9], const double (&mu)[3],
                                                  double (&S)[9], double (&v)[kSlots],
                                                  const RobustSetting& robust = RobustSetting()) {
-  // S = R C R^T + C_voxel
-  double RC[9];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      RC[r + 3 * c] = R[r] * C[3 * c] + R[r + 3] * C[1 + 3 * c] + R[r + 6] * C[2 + 3 * c];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      S[r + 3 * c] += RC[r] * R[c] + RC[r + 3] * R[c + 3] + RC[r + 6] * R[c + 6];
-
   double W[9];
-  inverse3_cofactor(S, W);
+  match_weight(R, C, S, W);
   auto acc = [](double& dst, double x) { if (FIRST) dst = x; else dst += x; };
   const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
   if constexpr (ROBUST) {
@@ -641,10 +650,7 @@ __device__ __forceinline__ void accumulate_match(const double* R, const double (
     // of 27, and w is dead before Q is live).  w = 1.0 leaves W's bits.  A rejected correspondence (w = 0) gets W = +0
     // by SELECTION, not by the product: its W may be NaN (a non-finite covariance entry fails the gate), and NaN x 0
     // would put NaN into 27 sums of a round that does not count it.
-    const double g0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
-    const double g1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
-    const double g2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
-    const double w = robust_weight(robust, e0 * g0 + e1 * g1 + e2 * g2);
+    const double w = robust_weight(robust, mahalanobis(W, e0, e1, e2));
     const bool counted = w > 0.0;
     acc(v[kCountSlot], counted ? 1.0 : 0.0);
 #pragma unroll
@@ -914,14 +920,12 @@ __global__ __launch_bounds__(BLOCK) void evaluate_kernel(EvalArgs a) {
       load_payload(rec, mu, S);
       if (first) accumulate_match<true>(R, p, C, mu, S, v);
       else accumulate_match<false>(R, p, C, mu, S, v);
-      // S now holds R C R^T + C_voxel; the same W beside the normal equations (the compiler keeps one copy)
+      // S now holds R C R^T + C_voxel: W again from it (the inverse match_weight ended with; the compiler merges the
+      // two), and the cost by mahalanobis, the definition the robust round and point_term use
       double W[9];
       inverse3_cofactor(S, W);
       const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
-      const double w0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
-      const double w1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
-      const double w2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
-      v[kCostSlot] += e0 * w0 + e1 * w1 + e2 * w2;
+      v[kCostSlot] += mahalanobis(W, e0, e1, e2);
       v[kSqErrorSlot] += e0 * e0 + e1 * e1 + e2 * e2;
     }
     first = false;
@@ -973,7 +977,9 @@ __global__ __launch_bounds__(512) void evaluate_fold_kernel(const double* __rest
   }
 }
 
-// The term of point i, for point_terms_kernel and gate_decide_kernel (the view both argument structs begin with): the ONE definition.
+// The term of point i, for point_terms_kernel and gate_decide_kernel (the view both argument structs begin with): the
+// point, ONE find_voxel probe, the payload, then match_weight and mahalanobis — the definition the rounds and the
+// evaluation call, so d^2 here is the evaluation's cost term and the robust round's raw residual.
 struct PointTerm {
   double raw, sq;   // e^T W e and |e|^2; +infinity when the point's voxel is not in the map
   bool matched;
@@ -998,34 +1004,19 @@ __device__ __forceinline__ PointTerm point_term(const PoseView& a, uint32_t i, b
     term.matched = true;
     double mu[3], S[9];
     load_payload(rec, mu, S);
-    // S = R C R^T + C_voxel: accumulate_match's expressions
-    double RC[9];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-        RC[r + 3 * c] = R[r] * C[3 * c] + R[r + 3] * C[1 + 3 * c] + R[r + 6] * C[2 + 3 * c];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-        S[r + 3 * c] += RC[r] * R[c] + RC[r + 3] * R[c + 3] + RC[r + 6] * R[c + 6];
     double W[9];
-    inverse3_cofactor(S, W);
+    match_weight(R, C, S, W);
     const double e0 = p[0] - mu[0], e1 = p[1] - mu[1], e2 = p[2] - mu[2];
-    const double g0 = W[0] * e0 + W[3] * e1 + W[6] * e2;
-    const double g1 = W[1] * e0 + W[4] * e1 + W[7] * e2;
-    const double g2 = W[2] * e0 + W[5] * e1 + W[8] * e2;
-    term.raw = e0 * g0 + e1 * g1 + e2 * g2;
+    term.raw = mahalanobis(W, e0, e1, e2);
     term.sq = e0 * e0 + e1 * e1 + e2 * e2;
   }
   return term;
 }
 
 // The resident scan at a pose, point by point (vgicp_points_resident, include/vgicp_hip_points.h).  One point per
-// thread, 256 threads: the point's planes, ONE find_voxel probe, the payload, and the term as accumulate_match<..., ROBUST>
-// and evaluate_kernel form it (S = R C R^T + C_voxel by the same two loops, inverse3_cofactor, W e, then e . (W e)) —
-// without the 27 sums, so nothing is reduced but four counts.  The requested planes are written at the point's index:
+// thread, 256 threads: the point's term by point_term (match_weight and mahalanobis, as accumulate_match<..., ROBUST>
+// and evaluate_kernel call them) — without the 27 sums, so nothing is reduced but four counts.  The requested planes are
+// written at the point's index:
 // every store of a wave is one coalesced access.  A point's values depend on nothing but the point, the pose and the
 // settings: not on which planes are asked, not on its neighbours.  Nothing waits for another workgroup.
 __global__ __launch_bounds__(256) void point_terms_kernel(PointArgs a) {
@@ -2046,277 +2037,6 @@ __global__ __launch_bounds__(kPackArenaBlock) void pack_arena_kernel(
   }
 }
 
-__global__ void table_clear_kernel(VoxelRecord* table, uint64_t slots) {
-  // 8 threads per record, 16 B each
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= slots * 8) return;
-  reinterpret_cast<int4*>(table)[g] = make_int4(0, 0, 0, 0);
-}
-
-// Batched upsert / rebuild in TWO launches, so that nothing inside a launch depends on what another workgroup of the
-// same launch wrote except the one state word that is claimed by compare-and-swap:
-//   claim   one thread per record: walk the probe sequence with ONE compare-and-swap per slot (EMPTY -> LOCKED).
-//           Won: the slot is this record's (fresh).  Lost to LOCKED: another key of this batch (keys are unique within
-//           a batch) — next slot.  Lost to FULL: a record from an earlier launch, its key is plain memory by now —
-//           mine (update in place) or next slot.  The slot index (and the fresh bit) goes to a scratch word per record.
-//   write   eight lanes per record, 16 bytes each (a record is one 128-byte line: {key, state} | mean + covariance =
-//           six 16-byte pieces | {count, spare}): plain coalesced stores, FULL included — the kernel boundary publishes.
-// One thread per record with a CAS, a release store and twelve scalar 8-byte stores into a random line measured 1.8 ms
-// per million voxels (profiles/r08_c2_kernel_stats.csv); eight lanes per record in ONE launch needs the key visible
-// before the state inside the launch: write-through key stores + wait cost 1.45 ms, a release fence per wave (it writes
-// the XCD's L2 back) 5.5 ms.
-// kClaimFresh / kClaimFailed: vgicp_device.h (the raw-point store reads the rehash's scratch words too)
-
-__device__ __forceinline__ uint32_t claim_slot(VoxelRecord* table, uint32_t mask, int32_t kx, int32_t ky, int32_t kz) {
-  uint32_t slot = voxel_hash(kx, ky, kz) & mask;
-  for (uint32_t probes = 0; probes <= mask; ++probes) {
-    VoxelRecord* rec = table + slot;
-    int32_t seen = SLOT_EMPTY;
-    if (__hip_atomic_compare_exchange_strong(&rec->state, &seen, SLOT_LOCKED, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT))
-      return slot | kClaimFresh;
-    if (seen == SLOT_FULL && rec->key[0] == kx && rec->key[1] == ky && rec->key[2] == kz) return slot;
-    slot = (slot + 1) & mask;
-  }
-  return kClaimFailed;
-}
-
-__global__ __launch_bounds__(256) void upsert_claim_kernel(VoxelRecord* table, uint32_t mask, uint32_t n,
-                                                           const int32_t* __restrict__ keys, uint32_t* __restrict__ claimed,
-                                                           uint32_t* counters) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t c = 0;
-  if (i < n) {
-    c = claim_slot(table, mask, keys[3 * (size_t)i], keys[3 * (size_t)i + 1], keys[3 * (size_t)i + 2]);
-    claimed[i] = c;
-  }
-  wave_count(&counters[0], i < n && c != kClaimFailed && (c & kClaimFresh) != 0);
-  wave_count(&counters[1], i < n && c == kClaimFailed);
-}
-
-__global__ __launch_bounds__(256) void upsert_write_kernel(VoxelRecord* table, uint32_t n, const uint32_t* __restrict__ claimed,
-                                                           const int32_t* __restrict__ keys, const double* __restrict__ means,
-                                                           const double* __restrict__ covs) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t i = t >> 3, sub = t & 7u;
-  if (i >= n) return;
-  const uint32_t c = claimed[i];
-  if (c == kClaimFailed) return;
-  const bool fresh = (c & kClaimFresh) != 0;
-  double2* line = reinterpret_cast<double2*>(table + (c & ~kClaimFresh));
-  if (sub == 0) {
-    if (fresh) reinterpret_cast<int4*>(line)[0] = make_int4(keys[3 * (size_t)i], keys[3 * (size_t)i + 1], keys[3 * (size_t)i + 2], SLOT_FULL);
-  } else if (sub == 7) {
-    // numPoints of a voxel mirrored from the host is not part of the batch: a new record starts at 1
-    if (fresh) reinterpret_cast<ulonglong2*>(line)[7] = make_ulonglong2(1ull, 0ull);
-  } else {
-    // piece `sub` of the payload: doubles 2 (sub - 1), 2 (sub - 1) + 1 of {mean[3], cov[9]}
-    const uint32_t p = 2u * (sub - 1u);
-    double2 piece;
-    piece.x = p < 3u ? means[3 * (size_t)i + p] : covs[9 * (size_t)i + (p - 3u)];
-    piece.y = p + 1u < 3u ? means[3 * (size_t)i + p + 1u] : covs[9 * (size_t)i + (p + 1u - 3u)];
-    line[sub] = piece;
-  }
-}
-
-// The rebuild into a larger table: one thread per OLD slot claims (the new table holds nothing else, every claim wins a
-// fresh slot), eight lanes per old slot then copy the 128-byte line.
-__global__ __launch_bounds__(256) void rehash_claim_kernel(const VoxelRecord* __restrict__ old_table, uint64_t old_slots,
-                                                           VoxelRecord* table, uint32_t mask, uint32_t* __restrict__ claimed,
-                                                           uint32_t* counters) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t c = 0;
-  bool full = false;
-  if (i < old_slots) {
-    const int4 head = *reinterpret_cast<const int4*>(old_table + i);
-    full = head.w == SLOT_FULL;
-    c = full ? claim_slot(table, mask, head.x, head.y, head.z) : kClaimFailed;
-    claimed[i] = c;
-  }
-  wave_count(&counters[0], full && c != kClaimFailed);
-  wave_count(&counters[1], full && c == kClaimFailed);
-}
-
-__global__ __launch_bounds__(256) void rehash_write_kernel(const VoxelRecord* __restrict__ old_table, uint64_t old_slots,
-                                                           VoxelRecord* table, const uint32_t* __restrict__ claimed) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t i = t >> 3;
-  const uint32_t sub = (uint32_t)(t & 7u);
-  if (i >= old_slots) return;
-  const uint32_t c = claimed[i];
-  if (c == kClaimFailed) return;
-  double2 piece = reinterpret_cast<const double2*>(old_table + i)[sub];
-  if (sub == 7) piece.y = 0.0;   // the spare word (per-voxel list head of an insertion) does not travel
-  reinterpret_cast<double2*>(table + (c & ~kClaimFresh))[sub] = piece;
-}
-
-__global__ void erase_kernel(VoxelRecord* table, uint32_t mask, uint32_t n,
-                             const int32_t* __restrict__ keys, uint32_t* counters) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int32_t kx = keys[3 * (size_t)i], ky = keys[3 * (size_t)i + 1], kz = keys[3 * (size_t)i + 2];
-  uint32_t slot = voxel_hash(kx, ky, kz) & mask;
-  bool erased = false;
-  for (uint32_t probes = 0; probes <= mask; ++probes) {
-    VoxelRecord* rec = table + slot;
-    const int32_t state = rec->state;
-    if (state == SLOT_EMPTY) break;
-    if (state == SLOT_FULL && rec->key[0] == kx && rec->key[1] == ky && rec->key[2] == kz) {
-      // duplicates in the batch race here: exactly one CAS wins and counts
-      int32_t expected = SLOT_FULL;
-      erased = __hip_atomic_compare_exchange_strong(&rec->state, &expected, SLOT_TOMB, __ATOMIC_RELAXED,
-                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }
-    slot = (slot + 1) & mask;
-  }
-  wave_count(&counters[0], erased);
-}
-
-__global__ void voxel_index_kernel(const double* __restrict__ pts, uint32_t n, double voxel_size,
-                                   int32_t* __restrict__ keys) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  // the division-free form the loop kernels use (exact, see voxel_coord_fast): this hook is how tests pin it
-  // ... and the persistent launch's shortcut "still in last round's voxel?" (same_voxel_coord): it may say no for
-  // the true key (the caller then makes the key), but a yes for any OTHER key would be a wrong correspondence — the
-  // hook poisons the key it returns in that case, so the same tests pin both functions.
-  const double inv_voxel = 1.0 / voxel_size;
-  const double same_margin = 0x1p-20 * voxel_size;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double x = pts[3 * (size_t)i + k];
-    int32_t key = voxel_coord_fast(x, voxel_size, inv_voxel);
-    bool wrong_yes = false;
-#pragma unroll
-    for (int d = 1; d <= 2; ++d) {
-      if (key <= INT32_MAX - d) wrong_yes = wrong_yes || same_voxel_coord(x, key + d, voxel_size, same_margin);
-      if (key >= INT32_MIN + d) wrong_yes = wrong_yes || same_voxel_coord(x, key - d, voxel_size, same_margin);
-    }
-    keys[3 * (size_t)i + k] = wrong_yes ? INT32_MIN : key;
-  }
-}
-
-// ---- correspondence materialisation: count per block, scan block counts, compact ----
-constexpr int kMatchBlock = 256;
-
-__device__ __forceinline__ const VoxelRecord* match_point(const double* pts, uint32_t i, uint32_t n,
-                                                          const VoxelRecord* table, uint32_t mask,
-                                                          double voxel_size) {
-  if (i >= n) return nullptr;
-  const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-  return find_voxel(table, mask, voxel_coord(x, voxel_size), voxel_coord(y, voxel_size),
-                    voxel_coord(z, voxel_size));
-}
-
-__global__ __launch_bounds__(kMatchBlock) void match_count_kernel(
-    const double* __restrict__ pts, uint32_t n, const VoxelRecord* __restrict__ table, uint32_t mask,
-    double voxel_size, uint32_t* __restrict__ block_counts) {
-  const uint32_t i = blockIdx.x * kMatchBlock + threadIdx.x;
-  const bool hit = match_point(pts, i, n, table, mask, voxel_size) != nullptr;
-  const int total = __syncthreads_count(hit ? 1 : 0);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = (uint32_t)total;
-}
-
-// Exclusive scan of block_counts in place by one workgroup; total -> *total_out.
-__global__ __launch_bounds__(1024) void match_scan_kernel(uint32_t* counts, uint32_t nb,
-                                                          uint32_t* total_out) {
-  __shared__ uint32_t wave_sum[16];
-  __shared__ uint32_t carry;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (uint32_t base = 0; base < nb; base += 1024) {
-    const uint32_t idx = base + tid;
-    const uint32_t val = idx < nb ? counts[idx] : 0u;
-    uint32_t incl = val;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, 64);
-      if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint32_t before = carry;
-    for (uint32_t w = 0; w < wave; ++w) before += wave_sum[w];
-    if (idx < nb) counts[idx] = before + incl - val;
-    __syncthreads();
-    if (tid == 1023) carry = before + incl;
-    __syncthreads();
-  }
-  if (tid == 0) *total_out = carry;
-}
-
-__global__ __launch_bounds__(kMatchBlock) void match_write_kernel(
-    const double* __restrict__ pts, const double* __restrict__ covs, uint32_t n,
-    const VoxelRecord* __restrict__ table, uint32_t mask, double voxel_size,
-    const uint32_t* __restrict__ block_offsets, double* __restrict__ src_points,
-    double* __restrict__ src_covs, double* __restrict__ map_points, double* __restrict__ map_covs,
-    uint64_t* __restrict__ src_index) {
-  __shared__ uint32_t wave_hits[kMatchBlock / 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t i = blockIdx.x * kMatchBlock + tid;
-  const VoxelRecord* rec = match_point(pts, i, n, table, mask, voxel_size);
-  const unsigned long long ballot = __ballot(rec != nullptr);
-  if (lane == 0) wave_hits[wave] = (uint32_t)__popcll(ballot);
-  __syncthreads();
-  if (rec == nullptr) return;
-  uint32_t pos = block_offsets[blockIdx.x] + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-  for (uint32_t w = 0; w < wave; ++w) pos += wave_hits[w];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    src_points[3 * (size_t)pos + k] = pts[3 * (size_t)i + k];
-    map_points[3 * (size_t)pos + k] = rec->mean[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    src_covs[9 * (size_t)pos + k] = covs[9 * (size_t)i + k];
-    map_covs[9 * (size_t)pos + k] = rec->cov[k];
-  }
-  if (src_index) src_index[pos] = i;
-}
-
-// ---- dense copy of the FULL records (count per block -> scan -> copy) ----
-constexpr int kDenseBlock = 256;
-__global__ __launch_bounds__(kDenseBlock) void dense_count_kernel(const VoxelRecord* __restrict__ table, uint64_t slots,
-                                                                  uint32_t* __restrict__ block_counts) {
-  const uint64_t i = (uint64_t)blockIdx.x * kDenseBlock + threadIdx.x;
-  const bool full = i < slots && table[i].state == SLOT_FULL;
-  const int total = __syncthreads_count(full ? 1 : 0);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = (uint32_t)total;
-}
-__global__ __launch_bounds__(kDenseBlock) void dense_write_kernel(VoxelRecord* table, uint64_t slots,
-                                                                  const uint32_t* __restrict__ block_offsets,
-                                                                  VoxelRecord* __restrict__ dense, uint64_t capacity) {
-  __shared__ uint32_t wave_hits[kDenseBlock / 64];
-  __shared__ uint32_t src[kDenseBlock];   // local slot numbers of the block's FULL records, in slot order
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint64_t i = (uint64_t)blockIdx.x * kDenseBlock + tid;
-  const bool full = i < slots && table[i].state == SLOT_FULL;
-  const unsigned long long ballot = __ballot(full);
-  if (lane == 0) wave_hits[wave] = (uint32_t)__popcll(ballot);
-  __syncthreads();
-  uint32_t rank = (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull)), total = 0;
-  for (uint32_t w = 0; w < kDenseBlock / 64; ++w) {
-    if (w < wave) rank += wave_hits[w];
-    total += wave_hits[w];
-  }
-  const uint32_t base = block_offsets[blockIdx.x];
-  if (full) {
-    src[rank] = tid;
-    reinterpret_cast<uint32_t*>(&table[i].reserved)[1] = base + rank;   // where this record's copy lives
-  }
-  __syncthreads();
-  // eight lanes per record, 16 bytes each: coalesced 128-byte lines both ways
-  // never beyond the allocation (the host sizes it for every record a pending insertion may still add; this is the belt)
-  for (uint32_t r = tid >> 3; r < total && (uint64_t)base + r < capacity; r += kDenseBlock / 8) {
-    const double2 piece = reinterpret_cast<const double2*>(table + ((uint64_t)blockIdx.x * kDenseBlock + src[r]))[tid & 7u];
-    reinterpret_cast<double2*>(dense + base + r)[tid & 7u] = piece;
-  }
-}
-
-inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((work + block - 1) / block); }
-
 }  // namespace
 
 // ---- the round kernels' instantiations: one table of kernel pointers per list of vgicp_launch_plan.h, built from the
@@ -2345,7 +2065,7 @@ constexpr auto kPersistentKernels = persistent_table(std::make_index_sequence<kP
 hipError_t launch_iterate(hipStream_t s, const IterArgs& args, uint32_t grid, int block) {
   const int v = plan_iterate(block, args.robust.kernel, args.robust.gate, args.prior.on != 0);
   if (v == kLaunchRefused) return hipErrorInvalidValue;
-  ++g_kernel_launches; hipLaunchKernelGGL(kIterateKernels[v], dim3(grid), dim3(block), 0, s, args);
+  counted_launch(kIterateKernels[v], dim3(grid), dim3(block), 0, s, args);
   return hipGetLastError();
 }
 
@@ -2425,7 +2145,7 @@ hipError_t launch_persistent(hipStream_t s, const PersistArgs& args, uint32_t gr
   f.prior = args.prior.on != 0;
   const PersistentPlan plan = plan_persistent(f);
   if (plan.variant == kLaunchRefused) return hipErrorInvalidValue;
-  ++g_kernel_launches; hipLaunchKernelGGL(kPersistentKernels[plan.variant], dim3(grid), dim3(512), plan.dyn_lds, s, args);
+  counted_launch(kPersistentKernels[plan.variant], dim3(grid), dim3(512), plan.dyn_lds, s, args);
   return hipGetLastError();
 }
 
@@ -2435,7 +2155,7 @@ hipError_t launch_persistent_fused(hipStream_t s, const PersistArgs& args, const
       (uint64_t)args.n > (uint64_t)grid * kPersistWorkers || up.unit < kPersistWorkers)
     return hipErrorInvalidValue;
   const size_t dyn = std::max<size_t>(args.prefetch_margin > 0.0 ? kPrefetchBytes : 0u, kFusedLoadBytes);
-  ++g_kernel_launches; hipLaunchKernelGGL(persistent_fused_kernel<512>, dim3(grid), dim3(512), dyn, s, args, up);
+  counted_launch(persistent_fused_kernel<512>, dim3(grid), dim3(512), dyn, s, args, up);
   return hipGetLastError();
 }
 
@@ -2448,7 +2168,7 @@ hipError_t launch_persistent_teams(hipStream_t s, const PersistArgs& args, const
       (uint64_t)teams.teams * kFolders * teams.folder_rows > (uint64_t)kTeamRowsMax || teams.abort_word == nullptr)
     return hipErrorInvalidValue;
   const size_t dyn = args.prefetch_margin > 0.0 ? kPrefetchBytes : 0u;
-  ++g_kernel_launches; hipLaunchKernelGGL(persistent_team_kernel<512>, dim3(grid), dim3(512), dyn, s, args, teams);
+  counted_launch(persistent_team_kernel<512>, dim3(grid), dim3(512), dyn, s, args, teams);
   return hipGetLastError();
 }
 
@@ -2479,7 +2199,7 @@ hipError_t persistent_max_resident(uint32_t dyn_lds_bytes, int cu_count, uint32_
 hipError_t launch_close(hipStream_t s, const IterArgs& args, int block) {
   const int v = plan_close(block, args.prior.on != 0);   // the last round's solve takes the pose prior as every other round's
   if (v == kLaunchRefused) return hipErrorInvalidValue;
-  ++g_kernel_launches; hipLaunchKernelGGL(kCloseKernels[v], dim3(1), dim3(block), 0, s, args);
+  counted_launch(kCloseKernels[v], dim3(1), dim3(block), 0, s, args);
   return hipGetLastError();
 }
 
@@ -2488,13 +2208,13 @@ hipError_t launch_evaluate(hipStream_t s, const EvalArgs& args, uint32_t rows_pe
   if (rows_per_pose < 1 || rows_per_pose > (uint32_t)kMaxIterBlocks || poses < 1 ||
       (uint64_t)rows_per_pose * poses > (uint64_t)kEvalRowBudget || args.poses == nullptr || args.rows == nullptr)
     return hipErrorInvalidValue;
-  ++g_kernel_launches; hipLaunchKernelGGL(evaluate_kernel<512>, dim3(rows_per_pose, poses), dim3(512), 0, s, args);
+  counted_launch(evaluate_kernel<512>, dim3(rows_per_pose, poses), dim3(512), 0, s, args);
   return hipGetLastError();
 }
 
 hipError_t launch_evaluate_fold(hipStream_t s, const double* rows, uint32_t rows_per_pose, uint32_t poses, double* out) {
   if (rows_per_pose < 1 || poses < 1 || (uint64_t)rows_per_pose * poses > (uint64_t)kEvalRowBudget) return hipErrorInvalidValue;
-  ++g_kernel_launches; hipLaunchKernelGGL(evaluate_fold_kernel, dim3(poses), dim3(512), 0, s, rows, rows_per_pose, out);
+  counted_launch(evaluate_fold_kernel, dim3(poses), dim3(512), 0, s, rows, rows_per_pose, out);
   return hipGetLastError();
 }
 
@@ -2502,13 +2222,13 @@ hipError_t launch_point_terms(hipStream_t s, const PointArgs& args) {
   if (args.scan == nullptr || args.table == nullptr || args.counters == nullptr || (args.keys == nullptr) != (args.idx == nullptr))
     return hipErrorInvalidValue;
   if (args.n == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(point_terms_kernel, dim3((args.n + 255u) / 256u), dim3(256), 0, s, args);
+  counted_launch(point_terms_kernel, dim3((args.n + 255u) / 256u), dim3(256), 0, s, args);
   return hipGetLastError();
 }
 
 hipError_t launch_gate_decide(hipStream_t s, const GateArgs& args) {
   if (args.n == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(gate_decide_kernel, dim3((args.n + 255u) / 256u), dim3(256), 0, s, args);
+  counted_launch(gate_decide_kernel, dim3((args.n + 255u) / 256u), dim3(256), 0, s, args);
   return hipGetLastError();
 }
 
@@ -2516,36 +2236,35 @@ hipError_t launch_point_pick(hipStream_t s, const PointPickArgs& args) {
   if (args.counters == nullptr || args.out == nullptr || args.n_quantiles > (uint32_t)kPointQuantiles ||
       (args.n_quantiles > 0 && args.n > 0 && args.sorted == nullptr))
     return hipErrorInvalidValue;
-  ++g_kernel_launches; hipLaunchKernelGGL(point_pick_kernel, dim3(1), dim3(64), 0, s, args);
+  counted_launch(point_pick_kernel, dim3(1), dim3(64), 0, s, args);
   return hipGetLastError();
 }
 
 hipError_t launch_solve_step(hipStream_t s, const double* packed27, double cosine_threshold,
                              double translation_sq_threshold, int force_pivoted, double* out20) {
-  ++g_kernel_launches; hipLaunchKernelGGL(solve_step_kernel, dim3(1), dim3(64), 0, s, packed27, cosine_threshold,
-                     translation_sq_threshold, force_pivoted, out20);
+  counted_launch(solve_step_kernel, dim3(1), dim3(64), 0, s, packed27, cosine_threshold, translation_sq_threshold, force_pivoted,
+                 out20);
   return hipGetLastError();
 }
 
 hipError_t launch_fold_rows(hipStream_t s, const double* rows, uint32_t nrows, const AlignState* state,
                             double* sums) {
-  ++g_kernel_launches; hipLaunchKernelGGL(fold_rows_kernel, dim3(1), dim3(1024), 0, s, rows, nrows, state, sums);
+  counted_launch(fold_rows_kernel, dim3(1), dim3(1024), 0, s, rows, nrows, state, sums);
   return hipGetLastError();
 }
 
 hipError_t launch_gather_scan(hipStream_t s, const uint32_t* perm, uint32_t m, const double* pts, const double* covs,
                               const unsigned long long* idx, double* out_pts, double* out_covs, unsigned long long* out_idx) {
   if (m == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(gather_scan_kernel, dim3(blocks_for(m, 256)), dim3(256), 0, s, perm, m, pts, covs, idx,
-                                          out_pts, out_covs, out_idx);
+  counted_launch(gather_scan_kernel, dim3(blocks_for(m, 256)), dim3(256), 0, s, perm, m, pts, covs, idx, out_pts, out_covs,
+                 out_idx);
   return hipGetLastError();
 }
 
 hipError_t launch_pack_scan(hipStream_t s, const double* points_aos, const double* covs_aos,
                             uint32_t n, double* soa, uint64_t stride, uint32_t* asym, uint32_t seq) {
   if (n == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(pack_scan_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, points_aos,
-                     covs_aos, n, soa, stride, asym, seq);
+  counted_launch(pack_scan_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, points_aos, covs_aos, n, soa, stride, asym, seq);
   return hipGetLastError();
 }
 
@@ -2557,77 +2276,9 @@ hipError_t launch_pack_arena(hipStream_t s, const void* arena_points, const void
   // few enough workgroups that the ones still waiting for their unit are a trickle of PCIe reads, enough of them that
   // 3 MB of loads are in flight; small LDS and 256 threads so that they find room beside other contexts' launches
   const uint32_t grid = std::min<uint32_t>(blocks_for(n, kPackArenaBlock), 128u);
-  ++g_kernel_launches; hipLaunchKernelGGL(pack_arena_kernel, dim3(grid), dim3(kPackArenaBlock), 0, s,
-                                          static_cast<const char*>(arena_points), static_cast<const char*>(arena_covs), n,
-                                          pack_arena_unit(), flags, wait ? 1u : 0u, seq, spin_limit, aos_pts, aos_cov, soa, stride, asym);
-  return hipGetLastError();
-}
-
-hipError_t launch_table_clear(hipStream_t s, VoxelRecord* table, uint64_t slots) {
-  ++g_kernel_launches; hipLaunchKernelGGL(table_clear_kernel, dim3(blocks_for(slots * 8, 256)), dim3(256), 0, s, table,
-                     slots);
-  return hipGetLastError();
-}
-
-uint32_t table_dense_blocks(uint64_t slots) { return blocks_for(slots, kDenseBlock); }
-
-hipError_t launch_table_dense(hipStream_t s, VoxelRecord* table, uint64_t slots, VoxelRecord* dense, uint64_t dense_capacity,
-                              uint32_t* block_counts) {
-  const uint32_t nb = table_dense_blocks(slots);
-  ++g_kernel_launches; hipLaunchKernelGGL(dense_count_kernel, dim3(nb), dim3(kDenseBlock), 0, s, table, slots, block_counts);
-  ++g_kernel_launches; hipLaunchKernelGGL(match_scan_kernel, dim3(1), dim3(1024), 0, s, block_counts, nb, block_counts + nb);
-  ++g_kernel_launches; hipLaunchKernelGGL(dense_write_kernel, dim3(nb), dim3(kDenseBlock), 0, s, table, slots, block_counts, dense, dense_capacity);
-  return hipGetLastError();
-}
-
-hipError_t launch_upsert(hipStream_t s, VoxelRecord* table, uint32_t mask, uint32_t n,
-                         const int32_t* keys, const double* means, const double* covs,
-                         uint32_t* counters, uint32_t* claimed) {
-  if (n == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(upsert_claim_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, mask, n, keys, claimed, counters);
-  ++g_kernel_launches; hipLaunchKernelGGL(upsert_write_kernel, dim3(blocks_for((uint64_t)n * 8, 256)), dim3(256), 0, s, table, n, claimed, keys,
-                     means, covs);
-  return hipGetLastError();
-}
-
-hipError_t launch_erase(hipStream_t s, VoxelRecord* table, uint32_t mask, uint32_t n,
-                        const int32_t* keys, uint32_t* counters) {
-  if (n == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(erase_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, mask, n, keys,
-                     counters);
-  return hipGetLastError();
-}
-
-hipError_t launch_rehash(hipStream_t s, const VoxelRecord* old_table, uint64_t old_slots,
-                         VoxelRecord* table, uint32_t mask, uint32_t* counters, uint32_t* claimed) {
-  ++g_kernel_launches; hipLaunchKernelGGL(rehash_claim_kernel, dim3(blocks_for(old_slots, 256)), dim3(256), 0, s, old_table,
-                     old_slots, table, mask, claimed, counters);
-  ++g_kernel_launches; hipLaunchKernelGGL(rehash_write_kernel, dim3(blocks_for(old_slots * 8, 256)), dim3(256), 0, s, old_table,
-                     old_slots, table, claimed);
-  return hipGetLastError();
-}
-
-hipError_t launch_voxel_index(hipStream_t s, const double* points_aos, uint32_t n, double voxel_size,
-                              int32_t* keys) {
-  if (n == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(voxel_index_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, points_aos, n,
-                     voxel_size, keys);
-  return hipGetLastError();
-}
-
-uint32_t match_blocks(uint32_t n) { return blocks_for(n, kMatchBlock); }
-
-hipError_t launch_match(hipStream_t s, const double* points_aos, const double* covs_aos, uint32_t n,
-                        const VoxelRecord* table, uint32_t mask, double voxel_size,
-                        uint32_t* block_counts, uint32_t* total, double* src_points,
-                        double* src_covs, double* map_points, double* map_covs, uint64_t* src_index) {
-  const uint32_t nb = match_blocks(n);
-  ++g_kernel_launches; hipLaunchKernelGGL(match_count_kernel, dim3(nb), dim3(kMatchBlock), 0, s, points_aos, n, table,
-                     mask, voxel_size, block_counts);
-  ++g_kernel_launches; hipLaunchKernelGGL(match_scan_kernel, dim3(1), dim3(1024), 0, s, block_counts, nb, total);
-  ++g_kernel_launches; hipLaunchKernelGGL(match_write_kernel, dim3(nb), dim3(kMatchBlock), 0, s, points_aos, covs_aos, n,
-                     table, mask, voxel_size, block_counts, src_points, src_covs, map_points,
-                     map_covs, src_index);
+  counted_launch(pack_arena_kernel, dim3(grid), dim3(kPackArenaBlock), 0, s, static_cast<const char*>(arena_points),
+                 static_cast<const char*>(arena_covs), n, pack_arena_unit(), flags, wait ? 1u : 0u, seq, spin_limit, aos_pts,
+                 aos_cov, soa, stride, asym);
   return hipGetLastError();
 }
 

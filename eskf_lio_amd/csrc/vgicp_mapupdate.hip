@@ -476,7 +476,6 @@ __global__ void raw_scatter_kernel(const RawPoint* __restrict__ log, uint32_t up
   }
 }
 
-inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((work + block - 1) / block); }
 
 }  // namespace
 
@@ -497,23 +496,21 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
   Pose12 pose;
   for (int k = 0; k < 12; ++k) pose.v[k] = pose12[k];
   if (short_lists) {
-    ++g_kernel_launches; hipLaunchKernelGGL(insert_prepare_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table,
-                       mask, voxel_size, points_aos, covs_aos, n, pose, w.wpts, w.wcovs, w.slot_in, w.idx_in, counters,
-                       keep);
+    counted_launch(insert_prepare_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, mask, voxel_size, points_aos,
+                   covs_aos, n, pose, w.wpts, w.wcovs, w.slot_in, w.idx_in, counters, keep);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (raw.entries) {
-      ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_list_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s,
-                         table, w.slot_in, w.idx_in, n, w.wpts, w.wcovs, max_points, raw);
+      counted_launch(insert_apply_list_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, w.slot_in, w.idx_in, n,
+                     w.wpts, w.wcovs, max_points, raw);
     } else {
-      ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_list_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s,
-                         table, w.slot_in, w.idx_in, n, w.wpts, w.wcovs, max_points, raw);
+      counted_launch(insert_apply_list_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, w.slot_in, w.idx_in, n,
+                     w.wpts, w.wcovs, max_points, raw);
     }
     return hipGetLastError();
   }
-  ++g_kernel_launches; hipLaunchKernelGGL(insert_prepare_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, mask,
-                     voxel_size, points_aos, covs_aos, n, pose, w.wpts, w.wcovs, w.slot_in, w.idx_in,
-                     counters, keep);
+  counted_launch(insert_prepare_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, mask, voxel_size, points_aos,
+                 covs_aos, n, pose, w.wpts, w.wcovs, w.slot_in, w.idx_in, counters, keep);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // stable: equal slots keep ascending point index = scan order (the inputs are scratch from here on)
@@ -521,27 +518,27 @@ hipError_t launch_map_insert(hipStream_t s, VoxelRecord* table, uint32_t mask, d
   if (e != hipSuccess) return e;
   g_kernel_launches += sortk::launches_for(n);
   if (raw.entries) {
-    ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table,
-                       w.slot_out, w.idx_out, n, w.wpts, w.wcovs, max_points, raw);
+    counted_launch(insert_apply_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, w.slot_out, w.idx_out, n, w.wpts,
+                   w.wcovs, max_points, raw);
   } else {
-    ++g_kernel_launches; hipLaunchKernelGGL(insert_apply_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table,
-                       w.slot_out, w.idx_out, n, w.wpts, w.wcovs, max_points, raw);
+    counted_launch(insert_apply_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, table, w.slot_out, w.idx_out, n, w.wpts,
+                   w.wcovs, max_points, raw);
   }
   return hipGetLastError();
 }
 
 hipError_t launch_map_evict(hipStream_t s, VoxelRecord* table, uint64_t slots, double voxel_size,
                             const double position[3], double distance, uint32_t* counters) {
-  ++g_kernel_launches; hipLaunchKernelGGL(evict_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots,
-                     voxel_size, position[0], position[1], position[2], distance, counters);
+  counted_launch(evict_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots, voxel_size, position[0], position[1],
+                 position[2], distance, counters);
   return hipGetLastError();
 }
 
 hipError_t launch_map_export(hipStream_t s, const VoxelRecord* table, uint64_t slots, uint32_t capacity,
                              int32_t* keys, double* means, double* covs, uint64_t* counts,
                              uint32_t* counters) {
-  ++g_kernel_launches; hipLaunchKernelGGL(export_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots,
-                     capacity, keys, means, covs, counts, counters);
+  counted_launch(export_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots, capacity, keys, means, covs, counts,
+                 counters);
   return hipGetLastError();
 }
 
@@ -549,14 +546,13 @@ hipError_t launch_raw_compact(hipStream_t s, const RawPoint* src, uint32_t src_u
                               const VoxelRecord* table, uint64_t slots, const uint32_t* claimed, RawPoint* dst,
                               uint32_t dst_capacity, uint32_t* dst_ctr) {
   if (src_upper == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(raw_compact_kernel, dim3(blocks_for(src_upper, 256)), dim3(256), 0, s, src,
-                     src_upper, ctr, table, slots, claimed, dst, dst_capacity, dst_ctr);
+  counted_launch(raw_compact_kernel, dim3(blocks_for(src_upper, 256)), dim3(256), 0, s, src, src_upper, ctr, table, slots,
+                 claimed, dst, dst_capacity, dst_ctr);
   return hipGetLastError();
 }
 
 hipError_t launch_raw_offsets(hipStream_t s, const VoxelRecord* table, uint64_t slots, uint32_t* offsets, uint32_t* total) {
-  ++g_kernel_launches; hipLaunchKernelGGL(raw_offsets_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots,
-                     offsets, total);
+  counted_launch(raw_offsets_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots, offsets, total);
   return hipGetLastError();
 }
 
@@ -564,8 +560,8 @@ hipError_t launch_raw_scatter(hipStream_t s, const RawPoint* log, uint32_t upper
                               const VoxelRecord* table, uint64_t slots, const uint32_t* offsets, uint32_t capacity,
                               int32_t* keys, double* points) {
   if (upper == 0) return hipSuccess;
-  ++g_kernel_launches; hipLaunchKernelGGL(raw_scatter_kernel, dim3(blocks_for(upper, 256)), dim3(256), 0, s, log, upper,
-                     ctr, table, slots, offsets, capacity, keys, points);
+  counted_launch(raw_scatter_kernel, dim3(blocks_for(upper, 256)), dim3(256), 0, s, log, upper, ctr, table, slots, offsets,
+                 capacity, keys, points);
   return hipGetLastError();
 }
 

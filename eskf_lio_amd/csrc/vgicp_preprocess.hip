@@ -1726,7 +1726,6 @@ __global__ void deskew_apply_kernel(double* __restrict__ pts, uint32_t n, const 
   pts[3 * (size_t)i + 2] = rz + T[11];
 }
 
-inline uint32_t blocks_for(uint64_t work, uint32_t block) { return (uint32_t)((work + block - 1) / block); }
 __host__ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 __host__ inline uint64_t pow2_at_least(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
 
@@ -1778,9 +1777,8 @@ hipError_t launch_fetch(hipStream_t s, const double* aos_pts, const double* aos_
                         uint32_t piece_bytes, unsigned long long* sums, unsigned long long* host_sums) {
   const size_t worst = (((size_t)n_cap * 24u + 255u) & ~size_t(255)) + (size_t)n_cap * 72u;
   const uint32_t grid = (uint32_t)std::min<size_t>(std::max<size_t>((worst + piece_bytes - 1) / piece_bytes, 1), 48);
-  ++g_kernel_launches;
-  hipLaunchKernelGGL(fetch_kernel, dim3(grid), dim3(kFetchBlock), 0, s, aos_pts, aos_cov, counters, epoch, n_cap, stage, flags,
-                     hdr_done, seq, piece_bytes, sums, host_sums);
+  counted_launch(fetch_kernel, dim3(grid), dim3(kFetchBlock), 0, s, aos_pts, aos_cov, counters, epoch, n_cap, stage, flags,
+                 hdr_done, seq, piece_bytes, sums, host_sums);
   return hipGetLastError();
 }
 
@@ -1860,15 +1858,12 @@ hipError_t launch_prepare_head(hipStream_t s, const PrepareArgs& a) {
       if (parts > kProloguePartsMax) parts = kProloguePartsMax;
       const uint32_t per_block = blocks_for(n, parts);
       uint32_t* part = a.ends + a.states;
-      hipLaunchKernelGGL(deskew_first_hit_kernel, dim3(parts), dim3(kFirstHitBlock), (size_t)a.states * 12, s, a.point_time, n,
-                         a.state_time, a.states, per_block, part);
-      ++g_kernel_launches;
+      counted_launch(deskew_first_hit_kernel, dim3(parts), dim3(kFirstHitBlock), (size_t)a.states * 12, s, a.point_time, n,
+                     a.state_time, a.states, per_block, part);
       pa.parts = parts;
       pa.part = part;
     } else {
-      hipLaunchKernelGGL(deskew_bounds_kernel, dim3(1), dim3(kBoundsBlock), 0, s, a.point_time, n, a.state_time, a.states,
-                         a.ends);
-      ++g_kernel_launches;
+      counted_launch(deskew_bounds_kernel, dim3(1), dim3(kBoundsBlock), 0, s, a.point_time, n, a.state_time, a.states, a.ends);
       pa.parts = 0;
     }
   }
@@ -1887,9 +1882,8 @@ hipError_t launch_prepare_head(hipStream_t s, const PrepareArgs& a) {
   pa.src_spin = a.src_spin;
   pa.src_step = a.src_step;
   for (int c = 0; c < 3; ++c) pa.src_off[c] = a.src_off[c];
-  hipLaunchKernelGGL(sweep_prologue_kernel, dim3(blocks_for(n, 256)), dim3(256),
-                     (size_t)a.states * (fused ? sizeof(double) : sizeof(uint32_t)), s, pa);
-  ++g_kernel_launches;
+  counted_launch(sweep_prologue_kernel, dim3(blocks_for(n, 256)), dim3(256),
+                 (size_t)a.states * (fused ? sizeof(double) : sizeof(uint32_t)), s, pa);
   if (a.ev_after_prologue) {
     const hipError_t ee = hipEventRecord(a.ev_after_prologue, s);
     if (ee != hipSuccess) return ee;
@@ -1922,29 +1916,28 @@ hipError_t launch_prepare_tail(hipStream_t s, const PrepareArgs& a) {
   uint32_t* q_light = reinterpret_cast<uint32_t*>(codes_in);
   const uint32_t keep_blocks = (scan_tiles + 3u) / 4u, split_blocks = blocks_for(n, kSplitBlock);
   if (items == (uint32_t)kScanItemsSmall) {
-    hipLaunchKernelGGL(run_scan_kernel<kScanItemsSmall>, dim3(scan_tiles + cell_blocks_x * kLevels), dim3(kScanThreads), 0, s, a.pts,
-                       codes_out, idx_out, n, spts, queries, keep_i, a.counters, tiles_a, a.epoch, scan_tiles, table, mask,
-                       cell_blocks_x, a.host_kept);
-    hipLaunchKernelGGL(keep_and_split_kernel<kScanItemsSmall>, dim3(keep_blocks + split_blocks), dim3(kSplitBlock), 0, s, keep_i, n,
-                       rank_i, a.counters, tiles_b, a.epoch, scan_tiles, keep_blocks, spts, a.voxel_size, table, mask, queries, q_heavy,
-                       q_light);
+    counted_launch(run_scan_kernel<kScanItemsSmall>, dim3(scan_tiles + cell_blocks_x * kLevels), dim3(kScanThreads), 0, s, a.pts,
+                   codes_out, idx_out, n, spts, queries, keep_i, a.counters, tiles_a, a.epoch, scan_tiles, table, mask,
+                   cell_blocks_x, a.host_kept);
+    counted_launch(keep_and_split_kernel<kScanItemsSmall>, dim3(keep_blocks + split_blocks), dim3(kSplitBlock), 0, s, keep_i, n,
+                   rank_i, a.counters, tiles_b, a.epoch, scan_tiles, keep_blocks, spts, a.voxel_size, table, mask, queries,
+                   q_heavy, q_light);
   } else {
-    hipLaunchKernelGGL(run_scan_kernel<kScanItemsLarge>, dim3(scan_tiles + cell_blocks_x * kLevels), dim3(kScanThreads), 0, s, a.pts,
-                       codes_out, idx_out, n, spts, queries, keep_i, a.counters, tiles_a, a.epoch, scan_tiles, table, mask,
-                       cell_blocks_x, a.host_kept);
-    hipLaunchKernelGGL(keep_and_split_kernel<kScanItemsLarge>, dim3(keep_blocks + split_blocks), dim3(kSplitBlock), 0, s, keep_i, n,
-                       rank_i, a.counters, tiles_b, a.epoch, scan_tiles, keep_blocks, spts, a.voxel_size, table, mask, queries, q_heavy,
-                       q_light);
+    counted_launch(run_scan_kernel<kScanItemsLarge>, dim3(scan_tiles + cell_blocks_x * kLevels), dim3(kScanThreads), 0, s, a.pts,
+                   codes_out, idx_out, n, spts, queries, keep_i, a.counters, tiles_a, a.epoch, scan_tiles, table, mask,
+                   cell_blocks_x, a.host_kept);
+    counted_launch(keep_and_split_kernel<kScanItemsLarge>, dim3(keep_blocks + split_blocks), dim3(kSplitBlock), 0, s, keep_i, n,
+                   rank_i, a.counters, tiles_b, a.epoch, scan_tiles, keep_blocks, spts, a.voxel_size, table, mask, queries,
+                   q_heavy, q_light);
   }
   // ---- octree cells of all levels, the exact search (one wave per kept point; the grid covers every raw point,
   //      the waves beyond the kept count leave at once), covariances ----
-  hipLaunchKernelGGL(knn_search_kernel, dim3(8 * (blocks_for((n + 7) / 8, kSearchBlock / 64) + 2)), dim3(kSearchBlock), 0, s, spts,
-                     idx_out, n, a.voxel_size, a.knn, table, mask, q_heavy, q_light, rank_i, a.epoch, nbr, a.out_pts, a.out_idx, a.soa,
-                     a.soa_stride, a.counters, a.debug);
+  counted_launch(knn_search_kernel, dim3(8 * (blocks_for((n + 7) / 8, kSearchBlock / 64) + 2)), dim3(kSearchBlock), 0, s, spts,
+                 idx_out, n, a.voxel_size, a.knn, table, mask, q_heavy, q_light, rank_i, a.epoch, nbr, a.out_pts, a.out_idx,
+                 a.soa, a.soa_stride, a.counters, a.debug);
   const int found = a.knn < (int)n ? a.knn : (int)n;
-  hipLaunchKernelGGL(cov_kernel, dim3(blocks_for(n, kCovBlock)), dim3(kCovBlock), 0, s, a.pts, nbr, found, a.out_covs, a.soa,
-                     a.soa_stride, a.counters, a.epoch);
-  g_kernel_launches += 4;
+  counted_launch(cov_kernel, dim3(blocks_for(n, kCovBlock)), dim3(kCovBlock), 0, s, a.pts, nbr, found, a.out_covs, a.soa,
+                 a.soa_stride, a.counters, a.epoch);
   return hipGetLastError();
 }
 
@@ -1971,16 +1964,13 @@ hipError_t launch_deskew(hipStream_t s, double* pts, uint32_t n, const double* p
     if (parts > kDeskewParts) parts = kDeskewParts;
     const uint32_t per_block = blocks_for(n, parts);
     uint32_t* part = ends + states;
-    hipLaunchKernelGGL(deskew_first_hit_kernel, dim3(parts), dim3(kFirstHitBlock), (size_t)states * 12, s, point_time, n,
-                       state_time, states, per_block, part);
-    hipLaunchKernelGGL(deskew_merge_kernel, dim3(1), dim3(1024), (size_t)states * 4, s, part, parts, states, ends);
-    g_kernel_launches += 2;
+    counted_launch(deskew_first_hit_kernel, dim3(parts), dim3(kFirstHitBlock), (size_t)states * 12, s, point_time, n, state_time,
+                   states, per_block, part);
+    counted_launch(deskew_merge_kernel, dim3(1), dim3(1024), (size_t)states * 4, s, part, parts, states, ends);
   } else {
-    hipLaunchKernelGGL(deskew_bounds_kernel, dim3(1), dim3(kBoundsBlock), 0, s, point_time, n, state_time, states, ends);
-    ++g_kernel_launches;
+    counted_launch(deskew_bounds_kernel, dim3(1), dim3(kBoundsBlock), 0, s, point_time, n, state_time, states, ends);
   }
-  hipLaunchKernelGGL(deskew_apply_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, pts, n, ends, states, poses);
-  ++g_kernel_launches;
+  counted_launch(deskew_apply_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, pts, n, ends, states, poses);
   return hipGetLastError();
 }
 

@@ -8,7 +8,7 @@ import hashlib
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-KERNEL_SOURCES = ("csrc/vgicp_kernels.hip", "csrc/vgicp_device.h", "csrc/vgicp_device_fn.h", "csrc/vgicp_math.h",
+KERNEL_SOURCES = ("csrc/vgicp_kernels.hip", "csrc/vgicp_table.hip", "csrc/vgicp_device.h", "csrc/vgicp_device_fn.h", "csrc/vgicp_math.h",
                   "csrc/vgicp_launch_plan.h", "csrc/Makefile")
 
 

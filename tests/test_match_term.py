@@ -1,5 +1,6 @@
 """One correspondence's term on the device over its domain: accumulate_match, inverse3_cofactor, rcp_newton and
-robust_weight of eskf_lio_amd/csrc/vgicp_kernels.hip and the cost / squared-error slots of evaluate_kernel, against
+robust_weight of eskf_lio_amd/csrc/vgicp_kernels.hip, the cost / squared-error slots of evaluate_kernel and the per-point
+report's point_term (match_weight and mahalanobis are the term's one definition, called by all three), against
 tests/match_term_reference.py (60-digit arithmetic; the bound is derived there), which tests/test_match_term_cpu.py holds
 against the oracle and shows to have teeth.
 
@@ -96,6 +97,37 @@ def test_the_plain_term_over_its_domain(gpu_ctx, swept):
     for axis, r in by_axis.items():
         print(f"axis {axis}: J^T W J {r[0]:.3f}, J^T W e {r[1]:.3f}, cost {r[2]:.3f}, |e|^2 {r[3]:.3f}")
     assert negative >= 12 and len(worst) == len(groups)
+    assert gpu_ctx.counter(COUNTER_FALLBACKS) == 0
+
+
+# ---- the per-point report's term ---------------------------------------------------------------------------------------
+def test_the_per_point_report_forms_the_same_term(gpu_ctx, swept):
+    """The third user of the term: for every case of every group, points_resident at the case's pose (no quantiles) reports
+    the one point MATCHED with d2[0] == the cost and sq_error[0] == the squared error of evaluate_resident at that pose —
+    with ==: the evaluation's row is one term added to +0.0 — and weight 1.0 at the default robust options.  Where the
+    reference's raw residual is negative the report's is too, with POINT_NEGATIVE set.  465 cases, 12 of them negative,
+    on an MI355X."""
+    from eskf_lio_amd import capi
+    vmap, groups, refs = swept
+    load_map(gpu_ctx, SweepMap(vmap))
+    checked, negative = 0, 0
+    for g in groups:
+        upload(gpu_ctx, g)
+        rows = evaluate_rows(gpu_ctx, [c.pose for c in g.cases])
+        for k, (c, (_, values)) in enumerate(zip(g.cases, rows)):
+            what = (g.name, c.label)
+            rep = gpu_ctx.points_resident(c.pose)
+            assert rep.points == 1 and rep.matched == 1, what
+            assert rep.status[0] & capi.POINT_MATCHED, (what, rep.status[0])
+            assert rep.d2[0] == values[27], (what, rep.d2[0], values[27])
+            assert rep.sq_error[0] == values[28], (what, rep.sq_error[0], values[28])
+            assert rep.weight[0] == 1.0, (what, rep.weight[0])
+            if refs[(g.name, k)].raw < 0:
+                assert rep.d2[0] < 0.0 and rep.status[0] & capi.POINT_NEGATIVE, (what, rep.d2[0], rep.status[0])
+                negative += 1
+            checked += 1
+    print(f"{checked} cases, {negative} with a negative raw residual: the report's term equals the evaluation's")
+    assert negative >= 12 and checked == sum(len(g.cases) for g in groups)
     assert gpu_ctx.counter(COUNTER_FALLBACKS) == 0
 
 
