@@ -65,6 +65,11 @@ POINT_MATCHED, POINT_NEGATIVE, POINT_NOT_FINITE = 1, 2, 4
 MAP_GATED_EXPORTS = ("vgicp_map_insert_resident_gated", "vgicp_map_insert_resident_gated_async", "vgicp_map_gated_totals")
 MAP_GATED_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_gated.so")
 
+# every symbol include/vgicp_hip_map_carve.h declares: likewise, three entry points in a library of their own
+MAP_CARVE_EXPORTS = ("vgicp_map_carve_resident", "vgicp_map_carve_resident_async", "vgicp_map_carve_totals")
+MAP_CARVE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_carve.so")
+CARVE_MAX_STEPS = 4096
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -140,6 +145,25 @@ class GatedInsertStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("matched", C.c_uint64), ("refused", C.c_uint64), ("not_finite", C.c_uint64),
                 ("new_voxels", C.c_uint64), ("launches", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double),
                 ("device_seconds", C.c_double)]
+
+
+class CarveParams(C.Structure):
+    """vgicp_carve_params (vgicp_hip_map_carve.h), 48 bytes."""
+    _fields_ = [("origin", C.c_double * 3), ("margin", C.c_double), ("max_range", C.c_double),
+                ("min_hits", C.c_uint32), ("stride", C.c_uint32)]
+
+
+class CarveStats(C.Structure):
+    """vgicp_carve_stats (vgicp_hip_map_carve.h), 64 bytes."""
+    _fields_ = [("rays", C.c_uint64), ("visits", C.c_uint64), ("touched", C.c_uint64), ("shielded", C.c_uint64),
+                ("removed", C.c_uint64), ("launches", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double),
+                ("device_seconds", C.c_double)]
+
+
+def carve_params(margin: float = 0.0, max_range: float = 80.0, min_hits: int = 1, stride: int = 1,
+                 origin=(0.0, 0.0, 0.0)) -> CarveParams:
+    return CarveParams((C.c_double * 3)(*[float(v) for v in origin]), float(margin), float(max_range), int(min_hits),
+                       int(stride))
 
 
 _lib: Optional[C.CDLL] = None
@@ -244,6 +268,15 @@ def load_library() -> C.CDLL:
         for name in MAP_GATED_EXPORTS:
             getattr(gated, name).restype = C.c_int
             setattr(lib, name, getattr(gated, name))
+    # free-space carving's library, likewise
+    if os.path.exists(MAP_CARVE_LIB_PATH):
+        carve = C.CDLL(MAP_CARVE_LIB_PATH, mode=C.RTLD_GLOBAL)
+        carve.vgicp_map_carve_resident.argtypes = [vp, dp, C.POINTER(CarveParams), sz, ip, C.POINTER(sz), C.POINTER(CarveStats)]
+        carve.vgicp_map_carve_resident_async.argtypes = [vp, dp, C.POINTER(CarveParams)]
+        carve.vgicp_map_carve_totals.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        for name in MAP_CARVE_EXPORTS:
+            getattr(carve, name).restype = C.c_int
+            setattr(lib, name, getattr(carve, name))
     _lib = lib
     return lib
 
@@ -862,6 +895,32 @@ class Context:
         p, r = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.vgicp_map_gated_totals(self._h, C.byref(p), C.byref(r)))
         return int(p.value), int(r.value)
+
+    def map_carve_resident(self, transform, params, keys: bool = True):
+        """vgicp_map_carve_resident (vgicp_hip_map_carve.h): remove the voxels the resident scan sees through at
+        `transform`.  params: a CarveParams or what carve_params() takes as keywords.  Returns (removed keys as int32
+        (m, 3) in unspecified order, or None unless asked; the call's CarveStats)."""
+        T = pose_to_abi(transform)
+        p = params if isinstance(params, CarveParams) else carve_params(**params)
+        st = CarveStats()
+        room = self.map_size()[0] if keys else 0
+        a_keys = np.zeros((room, 3), dtype=np.int32) if keys else None
+        removed = C.c_size_t(0)
+        self._check(self._lib.vgicp_map_carve_resident(
+            self._h, _dp(T), C.byref(p), room, a_keys.ctypes.data_as(C.POINTER(C.c_int32)) if room else None,
+            C.byref(removed), C.byref(st)))
+        return (a_keys[:removed.value].copy() if keys else None), st
+
+    def map_carve_resident_async(self, transform, params):
+        T = pose_to_abi(transform)
+        p = params if isinstance(params, CarveParams) else carve_params(**params)
+        self._check(self._lib.vgicp_map_carve_resident_async(self._h, _dp(T), C.byref(p)))
+
+    def map_carve_totals(self):
+        """(rays cast, voxels removed) by this context's carving calls since the last map_reset."""
+        r, m = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vgicp_map_carve_totals(self._h, C.byref(r), C.byref(m)))
+        return int(r.value), int(m.value)
 
     def frame_stats(self, reset: bool = False) -> FrameStats:
         st = FrameStats()

@@ -35,5 +35,6 @@ std::atomic<uint64_t> g_context_ids{0};
 #include "vgicp_capi_points.inl"
 #include "vgicp_capi_prepare.inl"
 #include "vgicp_capi_map_gated.inl"
+#include "vgicp_capi_map_carve.inl"
 #include "vgicp_capi_peers.inl"
 #include "vgicp_capi_multi_support.inl"

@@ -143,6 +143,7 @@ int vgicp_map_reset(vgicp_ctx* ctx, double voxel_size, size_t capacity_hint) {
   ctx->table.reset();
   ctx->slots = ctx->voxels = ctx->tombstones = 0;
   ctx->gated_points = ctx->gated_refused = 0;
+  ctx->carve_rays = ctx->carve_removed = 0;
   ++ctx->map_version;
   ctx->voxel_size = voxel_size;
   ctx->raw_hint = capacity_hint;

@@ -320,6 +320,11 @@ int ensure_raw(vgicp_ctx* ctx, uint64_t n) {
 int reserve_dense(vgicp_ctx* ctx);
 // Room for `incoming` new voxels: when plan_table_growth (vgicp_map_plan.h) says so, a table of the size it says.
 int ensure_table(vgicp_ctx* ctx, uint64_t incoming) {
+  // a growing table leaves its tombstones behind: a deferred carve's are counted first (voxels + tombstones, the sum
+  // the plan is made from, is the same before and after)
+  if (ctx->carve_pending && plan_table_growth(ctx->table != nullptr, ctx->slots, ctx->voxels, ctx->tombstones,
+                                              ctx->insert_pending_upper, incoming).grow)
+    VG_RC(settle(ctx));
   const TableGrowth plan = plan_table_growth(ctx->table != nullptr, ctx->slots, ctx->voxels, ctx->tombstones,
                                              ctx->insert_pending_upper, incoming);
   if (!plan.grow) return VGICP_OK;

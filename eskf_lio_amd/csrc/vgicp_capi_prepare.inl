@@ -110,11 +110,11 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
     if (staged->done) VG_HIP(ctx, hipEventRecord(staged->done, ctx->stream));
     VG_HIP(ctx, launch_prepare_tail(ctx->stream, a));
   }
-  // (+ the raw-point log's words when the map keeps raw points, + a pending gated insertion's)
+  // (+ the raw-point log's words when the map keeps raw points, + a pending gated insertion's or carve's)
   VG_HIP(ctx, hipMemcpyAsync(ctx->h_prep, ctx->d_counters,
-                             (kCounterWords + (ctx->gate_pending ? kInsertWords : ctx->raw_on ? kInsertWordsRaw : 4)) * sizeof(uint32_t),
+                             (kCounterWords + ((ctx->gate_pending || ctx->carve_pending) ? kInsertWords : ctx->raw_on ? kInsertWordsRaw : 4)) * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, ctx->stream));
-  if (ctx->insert_pending && !ctx->ins_copy_enqueued) {   // the deferred insertion's totals travel with this copy
+  if ((ctx->insert_pending || ctx->carve_pending) && !ctx->ins_copy_enqueued) {   // the deferred insertion's (carve's) totals travel with this copy
     ctx->ins_copy_enqueued = true;
     ctx->ins_from_prep = true;
   }
@@ -150,8 +150,8 @@ int resolve_prepare(vgicp_ctx* ctx, uint32_t* kept) {
 
 // A deferred insertion whose totals no copy has picked up yet (no preparation followed it): a copy of its own, now.
 int fetch_insert_totals(vgicp_ctx* ctx) {
-  if (!ctx->insert_pending || ctx->ins_copy_enqueued) return VGICP_OK;
-  VG_HIP(ctx, hipMemcpyAsync(ctx->h_ins_counters, ctx->d_ins_counters, (ctx->gate_pending ? kInsertWords : ctx->raw_on ? 6 : 2) * sizeof(uint32_t),
+  if (!(ctx->insert_pending || ctx->carve_pending) || ctx->ins_copy_enqueued) return VGICP_OK;
+  VG_HIP(ctx, hipMemcpyAsync(ctx->h_ins_counters, ctx->d_ins_counters, ((ctx->gate_pending || ctx->carve_pending) ? kInsertWords : ctx->raw_on ? 6 : 2) * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, ctx->stream));
   ctx->ins_copy_enqueued = true;
   ctx->ins_from_prep = false;
@@ -160,10 +160,21 @@ int fetch_insert_totals(vgicp_ctx* ctx) {
 
 // The deferred map insertion's counts (running totals), once the stream has been synchronised.
 int settle_insert(vgicp_ctx* ctx) {
+  if (!ctx->insert_pending && !ctx->carve_pending) return VGICP_OK;
+  const uint32_t* totals = ctx->ins_from_prep ? ctx->h_prep + kCounterWords : ctx->h_ins_counters;
+  if (ctx->carve_pending) {   // a deferred carve (vgicp_map_carve_resident_async): finish_removal's arithmetic on what it removed
+    ctx->carve_pending = false;
+    const uint32_t rays = totals[kCarveRaysWord] - ctx->carve_seen[0], removed = totals[kCarveRemovedWord] - ctx->carve_seen[1];
+    ctx->carve_seen[0] = totals[kCarveRaysWord];
+    ctx->carve_seen[1] = totals[kCarveRemovedWord];
+    ctx->voxels -= removed;
+    ctx->tombstones += removed;
+    ctx->carve_rays += rays;
+    ctx->carve_removed += removed;
+  }
   if (!ctx->insert_pending) return VGICP_OK;
   ctx->insert_pending = false;
   ctx->insert_pending_upper = 0;
-  const uint32_t* totals = ctx->ins_from_prep ? ctx->h_prep + kCounterWords : ctx->h_ins_counters;
   const uint32_t created = totals[0] - ctx->ins_seen[0];
   const uint32_t failed = totals[1] - ctx->ins_seen[1];
   ctx->ins_seen[0] = totals[0];
@@ -196,7 +207,7 @@ int settle_scan(vgicp_ctx* ctx) {
 // Everything deferred is brought up to date (one synchronisation if anything is pending): entry points that read
 // or change what a pending operation still owns call this first.
 int settle(vgicp_ctx* ctx) {
-  if (!ctx->scan_pending && !ctx->insert_pending) return VGICP_OK;
+  if (!ctx->scan_pending && !ctx->insert_pending && !ctx->carve_pending) return VGICP_OK;
   VG_HIP(ctx, hipSetDevice(ctx->device));
   VG_RC(fetch_insert_totals(ctx));
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));

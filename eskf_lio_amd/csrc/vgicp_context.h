@@ -30,6 +30,7 @@
 #include "../../include/vgicp_hip_prior.h"
 #include "../../include/vgicp_hip_points.h"
 #include "../../include/vgicp_hip_map_gated.h"
+#include "../../include/vgicp_hip_map_carve.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -88,12 +89,15 @@ inline uint32_t next_nonzero(uint32_t& seq) {
 }
 
 // words behind the counter block (d_ins_counters): [0] [1] the deferred insertion's running totals, [2] [3] the
-// resident scan's symmetry verdicts, [4] [5] [6] the raw-point log (RawLog::ctr), [7] spare, [8] [9] [10] a gated insertion's
-// running totals (kGateCounters: matched, refused, not finite), [11] spare.  The copies that bring the block to the host
-// carry the first 2 / 4 / 6 / 8 words as before; all of them only while a gated insertion is pending
+// resident scan's symmetry verdicts, [4] [5] [6] the raw-point log (RawLog::ctr), [7] a deferred carve's rays, [8] [9] [10] a
+// gated insertion's running totals (kGateCounters: matched, refused, not finite), [11] a deferred carve's removed voxels
+// (include/vgicp_hip_map_carve.h).  The copies that bring the block to the host carry the first 2 / 4 / 6 / 8 words as
+// before; all of them only while a gated insertion or a carve is pending
 constexpr int kInsertWords = 12;
 constexpr int kInsertWordsRaw = 8;    // up to the raw-point log's words
 constexpr int kGateWord = 8;
+constexpr int kCarveRaysWord = 7;
+constexpr int kCarveRemovedWord = 11;
 constexpr int kDefaultChunk = 4;
 constexpr int kMaxChunksInFlight = 2;
 static_assert(kPlanTeamsMax == (uint32_t)kTeamsMax, "vgicp_align_plan.h plans with the team kernel's width");
@@ -474,6 +478,16 @@ struct vgicp_ctx {
   uint32_t gate_seen[3] = {0, 0, 0};
   bool gate_pending = false;         // the pending insertion is a gated one: its totals travel with the insertion's
   uint64_t gated_points = 0, gated_refused = 0;
+  // free-space carving (include/vgicp_hip_map_carve.h).  A deferred carve's counts are running totals on the device
+  // (d_ins_counters + kCarveRaysWord / kCarveRemovedWord); the synchronisation that settles reads them with the
+  // insertion's and applies voxels -= removed, tombstones += removed.  A removal leaves voxels + tombstones, the sum
+  // plan_table_growth plans with, as it is: a pending carve needs no upper bound in the growth plan (unlike
+  // insert_pending_upper), and by itself it makes no deferred call wait
+  bool carve_pending = false;
+  uint32_t carve_seen[2] = {0, 0};   // rays, removed: what the host has read of the running totals
+  uint64_t carve_rays = 0, carve_removed = 0;   // since vgicp_map_reset
+  PinnedBuf<int32_t> h_carve_keys;   // pinned, grow-only: the synchronous call's key list on its way to the caller
+  size_t carve_keys_capacity = 0;    // voxels
   // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
   // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
@@ -525,7 +539,7 @@ struct vgicp_ctx {
   int rank = 0;
 };
 
-// The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip): was
+// The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip, vgicp_map_carve.hip): was
 // this context made by the build that reads it?  Reads the stamp only; each library refuses in its own words.
 inline bool same_build(const vgicp_ctx* ctx) { return ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx)); }
 
@@ -656,6 +670,11 @@ int map_insert_resident_gated(vgicp_ctx* ctx, const double transform[16], size_t
                               size_t capacity, uint8_t* kept, vgicp_gated_insert_stats* stats);
 int map_insert_resident_gated_async(vgicp_ctx* ctx, const double transform[16], size_t max_points_per_voxel, double gate);
 int map_gated_totals(vgicp_ctx* ctx, uint64_t* points, uint64_t* refused);
+// The entry points of include/vgicp_hip_map_carve.h behind libvgicp_hip_map_carve.so, likewise (vgicp_capi_map_carve.inl).
+int map_carve_resident(vgicp_ctx* ctx, const double transform[16], const vgicp_carve_params* params, size_t capacity,
+                       int32_t* removed_keys, size_t* removed, vgicp_carve_stats* stats);
+int map_carve_resident_async(vgicp_ctx* ctx, const double transform[16], const vgicp_carve_params* params);
+int map_carve_totals(vgicp_ctx* ctx, uint64_t* rays, uint64_t* removed);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

@@ -554,6 +554,30 @@ hipError_t launch_raw_scatter(hipStream_t s, const RawPoint* log, uint32_t upper
 // Erase every voxel whose centre is farther than `distance` from `position`; counters[0] += erased.
 hipError_t launch_map_evict(hipStream_t s, VoxelRecord* table, uint64_t slots, double voxel_size,
                             const double position[3], double distance, uint32_t* counters);
+// Free-space carving (include/vgicp_hip_map_carve.h has the rule): two launches.  MARK, one lane per point of the scan
+// (AoS, as the insertion reads it): the shield lookup, and the point's ray through the table if it casts one; hits and the
+// shield bit go into the LOW half of the record's spare word (kCarveShield | hits: the insertion's list head, zero
+// between insertions; the upper half is the dense copy's index and is left alone).  SWEEP, one lane per slot: decide,
+// write SLOT_TOMB, put the low half back to 0.  Any of the counter pointers may be nullptr; every word only grows.
+constexpr uint32_t kCarveShield = 0x80000000u;
+struct CarveArgs {
+  VoxelRecord* table;
+  uint64_t slots;              // a power of two
+  double voxel_size;
+  const double* points_aos;    // n x 3
+  uint32_t n;
+  uint32_t stride, min_hits;
+  double pose[12];             // R column-major (9), t (3)
+  double origin[3], margin, max_range;
+  uint32_t* rays;              // mark
+  unsigned long long* visits;  // mark
+  uint32_t* touched;           // sweep: FULL voxels with >= 1 hit
+  uint32_t* shielded;          // sweep: ... of which shielded
+  uint32_t* removed;           // sweep; also the length of keys
+  int32_t* keys;               // sweep: the removed voxels' keys, 3 each, or nullptr
+  uint32_t keys_capacity;      // voxels
+};
+hipError_t launch_map_carve(hipStream_t s, const CarveArgs& args);
 // Append every FULL record to the output arrays (unordered); counters[0] = records written.
 hipError_t launch_map_export(hipStream_t s, const VoxelRecord* table, uint64_t slots, uint32_t capacity,
                              int32_t* keys, double* means, double* covs, uint64_t* counts,

@@ -145,4 +145,28 @@ inline GateVerdict plan_gate(const GateFacts& f) {
   return GateVerdict{};
 }
 
+// ---- what a carving call refuses (include/vgicp_hip_map_carve.h, rules 3 to 9; 1 and 2 are the side library's
+// handshake).  The two entries refuse alike: nothing here depends on the scan's size ----
+struct CarveFacts : ResidentFacts {   // has_map, scan_resident, several_devices
+  bool pointers = false;          // transform and params are there
+  bool entries_finite = false;    // all 16 of the transform and the 3 of the origin
+  double margin = 0.0, max_range = 0.0, voxel_size = 0.0;
+  uint32_t min_hits = 0, stride = 0;
+};
+using CarveVerdict = GateVerdict;
+constexpr double kCarveMaxSteps = 4096.0;   // VGICP_CARVE_MAX_STEPS: a ray's walk is bounded by 3 (this + 1) + 3 steps
+inline CarveVerdict plan_carve(const CarveFacts& f) {
+  if (!f.has_map) return CarveVerdict{3, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first"};
+  if (!f.scan_resident) return CarveVerdict{3, VGICP_ERR_NOT_READY, kNoScanText};
+  if (!f.pointers) return CarveVerdict{4, VGICP_ERR_BAD_ARGUMENT, "NULL pointer"};
+  if (!f.entries_finite) return CarveVerdict{5, VGICP_ERR_BAD_ARGUMENT, "a transform or origin entry is not finite"};
+  if (!(f.margin >= 0.0) || std::isinf(f.margin)) return CarveVerdict{6, VGICP_ERR_BAD_ARGUMENT, "margin must be finite and >= 0"};
+  if (!(f.max_range > 0.0) || std::isinf(f.max_range) || !(f.max_range / f.voxel_size <= kCarveMaxSteps))
+    return CarveVerdict{7, VGICP_ERR_BAD_ARGUMENT, "max_range must be finite, > 0 and at most 4096 voxel sizes"};
+  if (f.min_hits == 0 || f.stride == 0) return CarveVerdict{8, VGICP_ERR_BAD_ARGUMENT, "min_hits and stride must be >= 1"};
+  if (f.several_devices)
+    return CarveVerdict{9, VGICP_ERR_BAD_ARGUMENT, "carving works on a single-device context: the resident scan of a device is a shard here"};
+  return CarveVerdict{};
+}
+
 }  // namespace vgicp

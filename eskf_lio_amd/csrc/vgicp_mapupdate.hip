@@ -31,6 +31,11 @@
 // export can place every point without ordering the log.  The log is never written past its capacity: the host keeps
 // an upper bound of what is appended (every point of an insertion may be accepted) and grows the log before it could
 // fill; should an append not fit anyway, ctr[1] is set, nothing is written and the call fails.
+//
+// Free-space carving (include/vgicp_hip_map_carve.h) takes voxels back: carve_mark_kernel walks a ray per point through
+// the table and leaves hits and a shield bit in the low half of the records' spare word (the list head above, zero
+// between insertions), carve_sweep_kernel turns the voxels enough rays crossed into tombstones as evict_kernel does and
+// clears the marks.  Two launches, nothing in them waits.
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
 #include "vgicp_sort.h"
@@ -404,6 +409,140 @@ __global__ void evict_kernel(VoxelRecord* table, uint64_t slots, double voxel_si
   if (threadIdx.x == 0 && gone) atomicAdd(&counters[0], (uint32_t)gone);
 }
 
+// ---- free-space carving (include/vgicp_hip_map_carve.h states the rule operation by operation; this restates it) ----
+// floor(x / h) per axis, the insertion's key (voxel_coord); false unless all three lie within +-2^30 (NaN fails)
+__device__ __forceinline__ bool carve_key(const double* x, double h, int32_t* k) {
+#pragma clang fp contract(off)
+  bool defined = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double q = floor(x[a] / h);
+    const bool in = fabs(q) <= 0x1p30;
+    defined = defined && in;
+    k[a] = in ? (int32_t)q : 0;
+  }
+  return defined;
+}
+// The voxel with this key, if it is FULL, takes `mark` into the low half of its spare word (no value comes back).  The
+// probe is find_voxel's: one 16-byte access per slot (key + state), linear, stops at EMPTY, skips TOMB and other keys.
+__device__ __forceinline__ void carve_mark(VoxelRecord* table, uint32_t mask, int32_t kx, int32_t ky, int32_t kz, bool shield) {
+  const VoxelRecord* rec = find_voxel(table, mask, kx, ky, kz);
+  if (!rec) return;
+  uint32_t* word = reinterpret_cast<uint32_t*>(&const_cast<VoxelRecord*>(rec)->reserved);
+  if (!shield) {
+    atomicAdd(word, 1u);
+  } else if (!(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kCarveShield)) {
+    atomicOr(word, kCarveShield);   // (a scan puts many points into one voxel: most find the bit set)
+  }
+}
+// the parameter at which the ray leaves voxel k along one axis
+__device__ __forceinline__ double carve_boundary(int32_t k, double d, double o, double h) {
+#pragma clang fp contract(off)
+  if (d == 0.0) return __builtin_inf();
+  return ((double)(k + (d > 0.0 ? 1 : 0)) * h - o) / d;
+}
+
+__global__ void __launch_bounds__(kBlock) carve_mark_kernel(CarveArgs a) {
+#pragma clang fp contract(off)
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t mask = (uint32_t)(a.slots - 1);
+  const double h = a.voxel_size;
+  bool ray = false;
+  uint32_t visits = 0;
+  if (i < a.n) {
+    double e[3];
+    int32_t k[3];
+    transform_point(a.pose, a.pose + 9, a.points_aos[3 * (size_t)i], a.points_aos[3 * (size_t)i + 1], a.points_aos[3 * (size_t)i + 2], e);
+    if (carve_key(e, h, k)) carve_mark(a.table, mask, k[0], k[1], k[2], /*shield=*/true);
+    if (i % a.stride == 0u) {
+      double o[3];
+      transform_point(a.pose, a.pose + 9, a.origin[0], a.origin[1], a.origin[2], o);
+      const double dx = e[0] - o[0], dy = e[1] - o[1], dz = e[2] - o[2];
+      const double len = sqrt((dx * dx + dy * dy) + dz * dz);
+      const double shorter = len - a.margin;
+      const double t_stop = (shorter < a.max_range ? shorter : a.max_range) / len;
+      const bool finite = isfinite(dx) && isfinite(dy) && isfinite(dz);
+      if (t_stop > 0.0 && finite && carve_key(o, h, k)) {
+        ray = true;
+        // the walk's hard bound: what vgicp_map_plan.h lets through keeps the ceiling at kCarveMaxSteps + 1
+        double cells = ceil((t_stop * len) / h);
+        if (!(cells <= 4097.0)) cells = 4097.0;
+        const uint32_t max_steps = 3u * (uint32_t)cells + 3u;
+        int32_t kx = k[0], ky = k[1], kz = k[2];
+        const int32_t sx = dx > 0.0 ? 1 : -1, sy = dy > 0.0 ? 1 : -1, sz = dz > 0.0 ? 1 : -1;
+        double tx = carve_boundary(kx, dx, o[0], h), ty = carve_boundary(ky, dy, o[1], h), tz = carve_boundary(kz, dz, o[2], h);
+        carve_mark(a.table, mask, kx, ky, kz, false);
+        visits = 1;
+        for (uint32_t step = 0; step < max_steps; ++step) {
+          if (tx <= ty && tx <= tz) {
+            if (!(tx < t_stop)) break;
+            kx += sx;
+            tx = carve_boundary(kx, dx, o[0], h);
+          } else if (ty <= tz) {
+            if (!(ty < t_stop)) break;
+            ky += sy;
+            ty = carve_boundary(ky, dy, o[1], h);
+          } else {
+            if (!(tz < t_stop)) break;
+            kz += sz;
+            tz = carve_boundary(kz, dz, o[2], h);
+          }
+          carve_mark(a.table, mask, kx, ky, kz, false);
+          ++visits;
+        }
+      }
+    }
+  }
+  // one atomic per workgroup and counter
+  const int cast = __syncthreads_count(ray ? 1 : 0);
+  __shared__ unsigned long long wave_visits[kBlock / 64];
+  unsigned long long sum = visits;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, (unsigned int)d, 64);
+  if ((threadIdx.x & 63u) == 0u) wave_visits[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBlock / 64; ++w) total += wave_visits[w];
+    if (a.rays && cast) atomicAdd(a.rays, (uint32_t)cast);
+    if (a.visits && total) atomicAdd(a.visits, total);
+  }
+}
+
+// One lane per slot, as evict_kernel: a slot whose marks are not zero is decided and its marks cleared.
+__global__ void __launch_bounds__(kBlock) carve_sweep_kernel(CarveArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool touched = false, shielded = false, gone = false;
+  VoxelRecord* rec = a.table + (i < a.slots ? i : 0);
+  if (i < a.slots) {
+    uint32_t* word = reinterpret_cast<uint32_t*>(&rec->reserved);
+    const uint32_t marks = *word;
+    if (marks != 0u) {
+      *word = 0u;
+      if (rec->state == SLOT_FULL) {   // (marks land on FULL records only)
+        const uint32_t hits = marks & ~kCarveShield;
+        touched = hits >= 1u;
+        shielded = touched && (marks & kCarveShield) != 0u;
+        gone = hits >= a.min_hits && (marks & kCarveShield) == 0u;
+        if (gone) rec->state = SLOT_TOMB;
+      }
+    }
+  }
+  const int n_touched = __syncthreads_count(touched ? 1 : 0);
+  const int n_shielded = __syncthreads_count(shielded ? 1 : 0);
+  if (threadIdx.x == 0) {
+    if (a.touched && n_touched) atomicAdd(a.touched, (uint32_t)n_touched);
+    if (a.shielded && n_shielded) atomicAdd(a.shielded, (uint32_t)n_shielded);
+  }
+  // the count and, when a key list is wanted, every removed voxel's place in it: one atomic per workgroup
+  const uint32_t pos = block_reserve(a.removed, gone ? 1u : 0u);
+  if (gone && a.keys && pos < a.keys_capacity) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.keys[3 * (size_t)pos + k] = rec->key[k];
+  }
+}
+
 __global__ void export_kernel(const VoxelRecord* __restrict__ table, uint64_t slots, uint32_t capacity,
                               int32_t* __restrict__ keys, double* __restrict__ means,
                               double* __restrict__ covs, uint64_t* __restrict__ counts,
@@ -531,6 +670,14 @@ hipError_t launch_map_evict(hipStream_t s, VoxelRecord* table, uint64_t slots, d
                             const double position[3], double distance, uint32_t* counters) {
   counted_launch(evict_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots, voxel_size, position[0], position[1],
                  position[2], distance, counters);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_carve(hipStream_t s, const CarveArgs& args) {
+  if (!args.removed || args.slots == 0 || (args.slots & (args.slots - 1)) != 0) return hipErrorInvalidValue;
+  if (args.n == 0) return hipSuccess;   // no point: no mark, and nothing for the sweep to find
+  counted_launch(carve_mark_kernel, dim3(blocks_for(args.n, kBlock)), dim3(kBlock), 0, s, args);
+  counted_launch(carve_sweep_kernel, dim3(blocks_for(args.slots, kBlock)), dim3(kBlock), 0, s, args);
   return hipGetLastError();
 }
 

@@ -54,6 +54,10 @@ def load_library() -> C.CDLL:
     lib.host_localmap_insert_gate.restype = C.c_double
     lib.host_localmap_insert_gate.argtypes = [vp]
     lib.host_localmap_gated_totals.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.host_localmap_set_carve.argtypes = [vp, C.c_double, C.c_double, C.c_uint32, C.c_uint32, dp]
+    lib.host_localmap_clear_carve.restype = None
+    lib.host_localmap_clear_carve.argtypes = [vp]
+    lib.host_localmap_carve_totals.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.host_localmap_match.argtypes = [vp, sz, dp, dp, dp, dp, dp, dp, C.POINTER(sz)]
     lib.host_localmap_export.restype = sz
     lib.host_localmap_export.argtypes = [vp, sz, C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_uint64)]
@@ -175,6 +179,25 @@ class LocalMap:
         out = (C.c_uint64 * 3)()
         _check(self._lib, self._lib.host_localmap_gated_totals(self._h, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def setCarve(self, margin: float = 0.0, max_range: float = 80.0, min_hits: int = 1, stride: int = 1,
+                 origin=(0.0, 0.0, 0.0)):
+        """LocalMap::setCarve (vgicp_hip_map_carve.h): every update on the resident scan first removes the voxels that
+        scan sees through.  origin: the sensor's origin in the prepared scan's frame (the extrinsic's translation)."""
+        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        if not (0 <= int(min_hits) < 2 ** 32 and 0 <= int(stride) < 2 ** 32):
+            raise ValueError("LocalMap::setCarve: min_hits and stride are 32-bit counts")
+        if self._lib.host_localmap_set_carve(self._h, float(margin), float(max_range), int(min_hits), int(stride), _dp(o)) != 0:
+            raise ValueError(self._lib.host_last_error().decode())
+
+    def clearCarve(self):
+        self._lib.host_localmap_clear_carve(self._h)
+
+    def carveTotals(self):
+        """(rays cast, voxels removed) by this map's carving since it was made."""
+        out = (C.c_uint64 * 2)()
+        _check(self._lib, self._lib.host_localmap_carve_totals(self._h, out))
+        return int(out[0]), int(out[1])
 
     def drain(self) -> int:
         """Waits for the shadow grid's worker (LocalMap::grid()); the host grid's voxel count."""

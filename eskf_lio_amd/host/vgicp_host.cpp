@@ -121,6 +121,27 @@ int host_localmap_gated_totals(const LocalMap * map, uint64_t out[3])
     });
 }
 
+// LocalMap::setCarve / clearCarve / carveTotals (include/vgicp_hip_map_carve.h); out: rays, removed
+int host_localmap_set_carve(
+  LocalMap * map, double margin, double max_range, uint32_t min_hits, uint32_t stride, const double origin[3])
+{
+  return guarded(
+    [&] {
+      const vgicp_carve_params p = {{origin[0], origin[1], origin[2]}, margin, max_range, min_hits, stride};
+      map->setCarve(p);
+    });
+}
+void host_localmap_clear_carve(LocalMap * map) {map->clearCarve();}
+int host_localmap_carve_totals(const LocalMap * map, uint64_t out[2])
+{
+  return guarded(
+    [&] {
+      const LocalMap::CarveTotals t = map->carveTotals();
+      out[0] = t.rays;
+      out[1] = t.removed;
+    });
+}
+
 // updateLocalMap(cloud, transform, initialize); the transformed cloud is written back to
 // points/covs, as the reference mutates the shared cloud in place (src/LocalMap.cpp:15).
 int host_localmap_update(

@@ -572,6 +572,10 @@ class Odometry:
         if insert_gate_of(config) > 0.0 and not getattr(backend, "supports_insert_gate", False):
             raise ValueError("local_map.insert_gate needs a backend that inserts the resident scan on the device "
                              "(DeviceBackend, tools/replay.py --resident); this one inserts every point")
+        # optional key local_map.carve (vgicp_hip_map_carve.h): likewise, the rays are the resident scan's
+        if carve_of(config) is not None and not getattr(backend, "supports_carve", False):
+            raise ValueError("local_map.carve needs a backend that keeps the scan and the map on the device "
+                             "(DeviceBackend, tools/replay.py --resident)")
         self.filter = ErrorStateKF(config, backend.align, getattr(backend, "align_with_prior", None))
         self.initialized = False
         self.pending: List[LidarMeasurement] = []
@@ -659,6 +663,29 @@ def insert_gate_of(config: dict) -> float:
     return gate
 
 
+def carve_of(config: dict):
+    """local_map.carve: absent = off (None), else the parameters of vgicp_map_carve_resident as a dict: max_range
+    (required, finite and > 0), margin (0), min_hits (1), stride (1), origin (None: the sensor's origin in the prepared
+    scan's frame, i.e. the extrinsic translation)."""
+    c = config["local_map"].get("carve")
+    if c is None:
+        return None
+    unknown = set(c) - {"margin", "max_range", "min_hits", "stride", "origin"}
+    if unknown or "max_range" not in c:
+        raise ValueError(f"local_map.carve takes max_range (required), margin, min_hits, stride, origin; got {sorted(c)}")
+    out = dict(margin=float(c.get("margin", 0.0)), max_range=float(c["max_range"]), min_hits=int(c.get("min_hits", 1)),
+               stride=int(c.get("stride", 1)), origin=None if c.get("origin") is None else tuple(float(v) for v in c["origin"]))
+    if not (np.isfinite(out["max_range"]) and out["max_range"] > 0.0):
+        raise ValueError("local_map.carve.max_range must be finite and > 0")
+    if not (np.isfinite(out["margin"]) and out["margin"] >= 0.0):
+        raise ValueError("local_map.carve.margin must be finite and >= 0")
+    if out["min_hits"] < 1 or out["stride"] < 1:
+        raise ValueError("local_map.carve.min_hits and local_map.carve.stride must be >= 1")
+    if out["origin"] is not None and (len(out["origin"]) != 3 or not np.all(np.isfinite(out["origin"]))):
+        raise ValueError("local_map.carve.origin must be three finite numbers")
+    return out
+
+
 class GpuBackend:
     """The MI355X path behind the C++ mirror of the reference's classes (eskf_lio_amd/host.py).  It hands the map a
     fresh host cloud every frame (arrays in, arrays out), never the cloud process() stamped, so the map update is not the
@@ -731,8 +758,10 @@ class DeviceBackend:
     frame the host sends 32 bytes per raw point and the IMU states, and receives the pose. The map is the
     device-resident voxel grid; the motion gate of LocalMap::needsMapUpdate (src/LocalMap.cpp:132-147) is a
     few flops and stays on the host.  With local_map.insert_gate the insertion is vgicp_map_insert_resident_gated at the
-    frame's pose."""
+    frame's pose.  With local_map.carve every map update first carves the map with the frame's scan at the frame's pose
+    (vgicp_map_carve_resident_async), then inserts."""
     supports_insert_gate = True
+    supports_carve = True
 
     def __init__(self, config: dict, device=0):
         """device: one ordinal, or a list of ordinals for ONE multi-device context (vgicp_create_multi)."""
@@ -741,6 +770,12 @@ class DeviceBackend:
         if insert_gate_of(config) > 0.0 and isinstance(device, (list, tuple)):
             raise ValueError("local_map.insert_gate needs a single-device context: the resident scan of a device is a shard "
                              "in a multi-device one")
+        self.carve = carve_of(config)
+        if self.carve is not None and isinstance(device, (list, tuple)):
+            raise ValueError("local_map.carve needs a single-device context: the resident scan of a device is a shard "
+                             "in a multi-device one")
+        if self.carve is not None and self.carve["origin"] is None:
+            self.carve["origin"] = tuple(float(v) for v in np.asarray(config["lidar_extrinsic"], dtype=np.float64)[:3, 3])
         self.ctx = capi.Context(device)
         self.ctx.map_reset(lm["voxel_size"], 0)
         self.cap = int(lm["max_num_points_per_voxel"])
@@ -814,6 +849,8 @@ class DeviceBackend:
             if not (cosine < self.gate[1] or float(moved[:3, 3] @ moved[:3, 3]) > self.gate[0]):
                 self.prev = transform.copy()
                 return
+        if self.carve is not None and not initialize:
+            self.ctx.map_carve_resident_async(transform, self.carve)
         if self.insert_gate > 0.0:
             self.ctx.map_insert_resident_gated(transform, self.cap, self.insert_gate, kept=False)
         else:

@@ -39,6 +39,7 @@
 #include "../vgicp_hip.h"
 #include "../vgicp_hip_map_points.h"
 #include "../vgicp_hip_map_gated.h"
+#include "../vgicp_hip_map_carve.h"
 
 // The raw-point store's entry points (vgicp_hip_map_points.h, and vgicp_set_option for its option) are referenced
 // weakly, so a program that links a stand-in of the C ABI without them (tests/native/shadow_stress.cpp) still links: a
@@ -52,6 +53,9 @@
 // that links without that library builds maps as before, and setInsertGate(g > 0) refuses.
 #pragma weak vgicp_map_insert_resident_gated_async
 #pragma weak vgicp_map_gated_totals
+// ... and free-space carving's (vgicp_hip_map_carve.h, in libvgicp_hip_map_carve.so): without that library setCarve refuses.
+#pragma weak vgicp_map_carve_resident_async
+#pragma weak vgicp_map_carve_totals
 #include "ShimTypes.hpp"
 #include "ShimSupport.hpp"
 #include "ResidentScan.hpp"
@@ -98,6 +102,11 @@ struct LocalMapConfig
   // max(d^2, 0) <= insertGate (LocalMap::setInsertGate; include/vgicp_hip_map_gated.h has the rule and the units, which
   // are ICP::robustScaleFromQuantile's).  0: off.  YAML: local_map.insert_gate (optional, default 0).
   double insertGate = 0.0;
+  // carve: every updateLocalMap whose cloud is still the resident scan first removes the voxels that scan sees through
+  // (LocalMap::setCarve; include/vgicp_hip_map_carve.h has the rule).  YAML: local_map.carve.{margin, max_range,
+  // min_hits, stride, origin} (optional; carving is off unless local_map.carve is there, and max_range is required then).
+  bool carve = false;
+  vgicp_carve_params carveParams = {{0.0, 0.0, 0.0}, 0.0, 0.0, 1, 1};
 };
 
 class LocalMap
@@ -181,6 +190,7 @@ public:
     shim::check(ctx_, vgicp_map_reset(ctx_, voxelSize_, 0), "vgicp_map_reset");
     storeRawPointsOnDevice();
     if (config.insertGate != 0.0) {setInsertGate(config.insertGate);}
+    if (config.carve) {setCarve(config.carveParams);}
   }
 
   ~LocalMap() {shadowStop();}
@@ -226,6 +236,19 @@ public:
     c.removePeriod = m["remove_distant_points"]["removing_period"].as<double>();
     if (m["raw_points_on_device"].IsDefined()) {c.rawPointsOnDevice = m["raw_points_on_device"].as<bool>();}
     if (m["insert_gate"].IsDefined()) {c.insertGate = m["insert_gate"].as<double>();}
+    if (m["carve"].IsDefined()) {
+      const auto & k = m["carve"];
+      c.carve = true;
+      c.carveParams.max_range = k["max_range"].as<double>();
+      if (k["margin"].IsDefined()) {c.carveParams.margin = k["margin"].as<double>();}
+      if (k["min_hits"].IsDefined()) {c.carveParams.min_hits = k["min_hits"].as<uint32_t>();}
+      if (k["stride"].IsDefined()) {c.carveParams.stride = k["stride"].as<uint32_t>();}
+      if (k["origin"].IsDefined()) {
+        const std::vector<double> origin = k["origin"].as<std::vector<double>>();
+        if (origin.size() != 3) {throw std::invalid_argument("local_map.carve.origin: three numbers");}
+        for (int a = 0; a < 3; ++a) {c.carveParams.origin[a] = origin[a];}
+      }
+    }
     return c;
   }
 #endif
@@ -263,6 +286,7 @@ public:
     facts.evictionDue = shim::insertionDue(facts) && removeDistantPoints_ && now() - currentRemoveTime_ > removePeriod_;
     facts.soleOwner = cloud.use_count() == 1;
     facts.gated = insertGate_ > 0.0;
+    facts.carve = carve_;
     const Plan plan = shim::planUpdate(facts);
 
     if (plan.route != Plan::Route::ResidentScan) {
@@ -277,6 +301,11 @@ public:
       } else {
         if (plan.route == Plan::Route::ResidentScan) {
           shim::TraceScope tsInsert(shim::Trace::UpdateInsert);
+          if (plan.carve) {
+            shim::check(
+              ctx_, vgicp_map_carve_resident_async(ctx_, shim::poseData(transform), &carveParams_),
+              "vgicp_map_carve_resident_async");
+          }
           if (plan.entry == Plan::Entry::Gated) {
             shim::check(
               ctx_, vgicp_map_insert_resident_gated_async(
@@ -468,6 +497,56 @@ public:
     t.plainFrames = plainFrames_;
     if (vgicp_map_gated_totals) {
       shim::check(ctx_, vgicp_map_gated_totals(ctx_, &t.points, &t.refused), "vgicp_map_gated_totals");
+    }
+    return t;
+  }
+
+  // Free-space carving (include/vgicp_hip_map_carve.h): from the next updateLocalMap on, a frame whose cloud is still the
+  // resident scan first removes from the map the voxels that at least min_hits of its rays cross and that hold none of
+  // its returns — at the frame's pose, on the device, enqueued only — and is inserted then.  params.origin is the
+  // sensor's origin in the prepared scan's frame: the translation of the extrinsic the preparation applied.
+  // A device-resident map only; its raw points move to the device as for setInsertGate (set it before the first frame).
+  void setCarve(const vgicp_carve_params & params)
+  {
+    const bool finite = std::isfinite(params.origin[0]) && std::isfinite(params.origin[1]) && std::isfinite(params.origin[2]);
+    if (!finite || !(params.margin >= 0.0) || std::isinf(params.margin) || !(params.max_range > 0.0) ||
+      std::isinf(params.max_range) || !(params.max_range / voxelSize_ <= VGICP_CARVE_MAX_STEPS) || params.min_hits == 0 ||
+      params.stride == 0)
+    {
+      throw std::invalid_argument(
+              "LocalMap::setCarve: origin finite, margin finite and >= 0, max_range finite, > 0 and at most "
+              "VGICP_CARVE_MAX_STEPS voxel sizes, min_hits and stride >= 1");
+    }
+    if (!deviceResident_) {
+      throw std::invalid_argument("LocalMap::setCarve: only a device-resident map holds the resident scan's rays");
+    }
+    if (!(vgicp_map_carve_resident_async && vgicp_map_carve_totals)) {
+      throw std::runtime_error("LocalMap::setCarve: the linked vgicp module has no free-space carving");
+    }
+    if (keepRawPoints_ && !rawOnDevice_) {
+      shadowDrain();
+      rawOnDevice_ = true;
+      try {
+        storeRawPointsOnDevice();
+      } catch (...) {
+        rawOnDevice_ = false;
+        throw;
+      }
+    }
+    carveParams_ = params;
+    carve_ = true;
+  }
+  void clearCarve() {carve_ = false;}
+  bool carving() const {return carve_;}
+  struct CarveTotals
+  {
+    uint64_t rays = 0, removed = 0;   // since the map was made (vgicp_map_carve_totals: settles)
+  };
+  CarveTotals carveTotals() const
+  {
+    CarveTotals t;
+    if (vgicp_map_carve_totals) {
+      shim::check(ctx_, vgicp_map_carve_totals(ctx_, &t.rays, &t.removed), "vgicp_map_carve_totals");
     }
     return t;
   }
@@ -722,6 +801,8 @@ private:
   bool shadowComplete_ = true;       // every frame inserted on the device so far has also reached the shadow grid
   double insertGate_ = 0.0;          // > 0: the resident route inserts through the gated entry (setInsertGate)
   uint64_t plainFrames_ = 0;
+  bool carve_ = false;               // the resident route carves before it inserts (setCarve)
+  vgicp_carve_params carveParams_ = {{0.0, 0.0, 0.0}, 0.0, 0.0, 1, 1};
   std::thread shadowThread_;
   mutable std::mutex shadowMutex_;
   mutable std::condition_variable shadowCv_, shadowIdle_;

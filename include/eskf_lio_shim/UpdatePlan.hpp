@@ -24,6 +24,10 @@ struct UpdateFacts
   // (setInsertGate sees to rawOnDevice, or refuses), so a gated map never has a shadow grid to feed: the gate decides the
   // entry and the count below, nothing else
   bool gated = false;
+  // LocalMap::setCarve on a device-resident map (include/vgicp_hip_map_carve.h).  false: every field of the plan is what
+  // it is without it.  Like a gated map, a carving map that keeps raw points keeps them on the device (setCarve sees to
+  // rawOnDevice, or refuses): the shadow grid is never fed a map it cannot follow
+  bool carve = false;
 };
 
 struct UpdatePlan
@@ -43,6 +47,10 @@ struct UpdatePlan
   enum class Entry {Plain, Gated};
   Entry entry = Entry::Plain;
   bool countPlain = false;
+  // With setCarve.  The resident-scan route carves the map with the scan it is about to insert, at the frame's pose and
+  // BEFORE the insertion (vgicp_map_carve_resident_async: enqueued only).  A host cloud is no resident scan, so it casts no
+  // rays; the host-authoritative map is never carved.
+  bool carve = false;
 };
 
 // reference: src/LocalMap.cpp:39 (with prevTransform_ initialised: the first update always inserts)
@@ -64,6 +72,7 @@ inline UpdatePlan planUpdate(const UpdateFacts & f)
   const bool gated = f.gated && f.deviceResident;   // (a host-authoritative map has no resident route: no gate)
   p.entry = gated && p.route == Route::ResidentScan ? UpdatePlan::Entry::Gated : UpdatePlan::Entry::Plain;
   p.countPlain = gated && p.route == Route::HostCloud && p.insert;
+  p.carve = f.carve && f.deviceResident && p.route == Route::ResidentScan && p.insert;
   const bool shadow = f.deviceResident && f.keepRawPoints && !f.rawOnDevice && f.shadowComplete;
   const bool wanted = p.route == Route::ResidentScan ? f.hostIsCurrent : p.route == Route::HostCloud && p.insert;
   // the worker reads the cloud later: it gets the caller's object only when nobody else can reach it, else a copy — a

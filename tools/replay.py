@@ -14,6 +14,9 @@ options: --out traj.tum   --device-map (keep the voxel grid on the GPU only)   -
          the predicted pose, include/vgicp_hip_points.h, and the scale becomes sqrt(quantile Q of d^2); off by default)
          --insert-gate G (local_map.insert_gate, with --resident: points that are matched at the frame's
          pose and fail max(d^2, 0) <= G are kept out of the map, include/vgicp_hip_map_gated.h; off by default)
+         --carve-range R [--carve-margin M --carve-min-hits H --carve-stride S] (local_map.carve, with --resident: before
+         every map update the voxels that at least H of the scan's rays cross within R metres, stopping M metres short of
+         their returns, and that hold no return of the scan, are removed, include/vgicp_hip_map_carve.h; off by default)
          --prior-update (kalman_filter.update.iterated: the filter's pose covariance enters every round of the align as a
          prior, include/vgicp_hip_prior.h, and the update is the iterated one; off by default)
 The configuration is the reference's config/hilti_config.yaml as a dict (eskf_lio_amd/replay.py:DEFAULT_CONFIG);
@@ -56,7 +59,18 @@ def config_from_yaml(path):
     return cfg, imu["topic_name"], y["sensors"]["lidar"]["topic_name"]
 
 
-def main():
+def carve_config(cfg, args):
+    """The configuration with local_map.carve from the --carve-* flags (the same object when none is given)."""
+    given = {k: v for k, v in (("max_range", args.carve_range), ("margin", args.carve_margin), ("min_hits", args.carve_min_hits),
+                               ("stride", args.carve_stride)) if v is not None}
+    if not given:
+        return cfg
+    if "max_range" not in given:
+        raise ValueError("--carve-margin, --carve-min-hits and --carve-stride need --carve-range")
+    return dict(cfg, local_map=dict(cfg["local_map"], carve=given))
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bag")
     ap.add_argument("--synthetic", type=int, default=0, help="number of synthetic LiDAR frames")
@@ -83,9 +97,26 @@ def main():
                     help="gate of the map insertion on d^2 at the frame's pose, 0 = none (local_map.insert_gate)")
     ap.add_argument("--prior-update", action="store_true",
                     help="the iterated filter update with the pose prior in every align (kalman_filter.update.iterated)")
-    args = ap.parse_args()
+    ap.add_argument("--carve-range", type=float, default=None,
+                    help="free-space carving before every map update: metres a ray is followed (local_map.carve.max_range)")
+    ap.add_argument("--carve-margin", type=float, default=None, help="metres a ray stops short of its return (local_map.carve.margin)")
+    ap.add_argument("--carve-min-hits", type=int, default=None, help="rays that must cross a voxel (local_map.carve.min_hits)")
+    ap.add_argument("--carve-stride", type=int, default=None, help="every S-th point casts a ray (local_map.carve.stride)")
+    args = ap.parse_args(argv)
     if args.raw_points_on_device and not args.resident:
         ap.error("--raw-points-on-device needs --resident")
+    if any(v is not None for v in (args.carve_range, args.carve_margin, args.carve_min_hits, args.carve_stride)):
+        if not args.resident:
+            ap.error("--carve-* needs --resident")
+        if args.carve_range is None:
+            ap.error("--carve-margin, --carve-min-hits and --carve-stride need --carve-range")
+    args.parser = ap
+    return args
+
+
+def main():
+    args = parse_args()
+    ap = args.parser
     cfg, imu_topic, lidar_topic = replay.DEFAULT_CONFIG, replay.IMU_TOPIC, replay.LIDAR_TOPIC
     if args.config:
         cfg, imu_topic, lidar_topic = config_from_yaml(args.config)
@@ -101,6 +132,7 @@ def main():
         cfg = dict(cfg, local_map=dict(cfg["local_map"], insert_gate=args.insert_gate))
     if args.prior_update:
         cfg = dict(cfg, kalman_filter=dict(cfg["kalman_filter"], iterated=True))
+    cfg = carve_config(cfg, args)
     truth = None
     if args.bag:
         events = replay.read_rosbag2(args.bag, imu_topic, lidar_topic)
@@ -128,6 +160,9 @@ def main():
     if args.insert_gate:
         points, refused = backend.ctx.map_gated_totals()
         print(f"map insertion gated at d^2 <= {args.insert_gate}: {refused} of {points} points kept out of the map")
+    if args.carve_range is not None:
+        rays, removed = backend.ctx.map_carve_totals()
+        print(f"free-space carving within {args.carve_range} m: {removed} voxels removed by {rays} rays")
     if args.raw_points_on_device:
         t0 = time.perf_counter()
         keys, _ = backend.ctx.map_points_export()
