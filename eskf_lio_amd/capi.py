@@ -70,6 +70,13 @@ MAP_CARVE_EXPORTS = ("vgicp_map_carve_resident", "vgicp_map_carve_resident_async
 MAP_CARVE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_carve.so")
 CARVE_MAX_STEPS = 4096
 
+# every symbol include/vgicp_hip_map_rays.h declares: likewise, one entry point in a library of its own
+MAP_RAYS_EXPORTS = ("vgicp_rays_resident",)
+MAP_RAYS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_rays.so")
+RAYS_MAX_POSES = 64
+RAY_NO_RAY, RAY_OPEN, RAY_OWN, RAY_BEHIND, RAY_CONFIRMED, RAY_BLOCKED, RAY_NEAR = range(7)
+RAY_CLASS_NAMES = ("no_ray", "open", "own", "behind", "confirmed", "blocked", "near")
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -164,6 +171,50 @@ def carve_params(margin: float = 0.0, max_range: float = 80.0, min_hits: int = 1
                  origin=(0.0, 0.0, 0.0)) -> CarveParams:
     return CarveParams((C.c_double * 3)(*[float(v) for v in origin]), float(margin), float(max_range), int(min_hits),
                        int(stride))
+
+
+class RayParams(C.Structure):
+    """vgicp_ray_params (vgicp_hip_map_rays.h), 56 bytes."""
+    _fields_ = [("origin", C.c_double * 3), ("margin", C.c_double), ("beyond", C.c_double), ("max_range", C.c_double),
+                ("stride", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RayOutputs(C.Structure):
+    """vgicp_ray_outputs (vgicp_hip_map_rays.h), 32 bytes: each plane optional."""
+    _fields_ = [("status", C.POINTER(C.c_uint8)), ("range", C.POINTER(C.c_double)), ("hit_key", C.POINTER(C.c_int32)),
+                ("steps", C.POINTER(C.c_uint32))]
+
+
+class RayCounts(C.Structure):
+    """vgicp_ray_counts (vgicp_hip_map_rays.h), 80 bytes."""
+    _fields_ = [("rays", C.c_uint64), ("visits", C.c_uint64), ("by_class", C.c_uint64 * 8)]
+
+
+class RayStats(C.Structure):
+    """vgicp_ray_stats (vgicp_hip_map_rays.h), 24 bytes."""
+    _fields_ = [("launches", C.c_int32), ("groups", C.c_int32), ("seconds", C.c_double), ("device_seconds", C.c_double)]
+
+
+def ray_params(margin: float = 0.0, beyond: float = 0.0, max_range: float = 80.0, stride: int = 1,
+               origin=(0.0, 0.0, 0.0)) -> RayParams:
+    return RayParams((C.c_double * 3)(*[float(v) for v in origin]), float(margin), float(beyond), float(max_range),
+                     int(stride), 0)
+
+
+@dataclass
+class RayReport:
+    """What Context.rays_resident returns.  counts: one dict per pose (rays, visits, by_class: a list of 8).  The planes
+    (a single pose with per_point=True, else None): status uint8 (n), range float64 (n; NaN with no hit), hit_key int32
+    (n, 3; INT32_MIN with no hit), steps uint32 (n)."""
+    counts: list
+    status: Optional[np.ndarray]
+    range: Optional[np.ndarray]
+    hit_key: Optional[np.ndarray]
+    steps: Optional[np.ndarray]
+    launches: int
+    groups: int
+    seconds: float
+    device_seconds: float
 
 
 _lib: Optional[C.CDLL] = None
@@ -277,6 +328,13 @@ def load_library() -> C.CDLL:
         for name in MAP_CARVE_EXPORTS:
             getattr(carve, name).restype = C.c_int
             setattr(lib, name, getattr(carve, name))
+    # the ray report's library, likewise
+    if os.path.exists(MAP_RAYS_LIB_PATH):
+        rays = C.CDLL(MAP_RAYS_LIB_PATH, mode=C.RTLD_GLOBAL)
+        rays.vgicp_rays_resident.argtypes = [vp, dp, sz, C.POINTER(RayParams), C.POINTER(RayOutputs), C.POINTER(RayCounts),
+                                             C.POINTER(RayStats)]
+        rays.vgicp_rays_resident.restype = C.c_int
+        lib.vgicp_rays_resident = rays.vgicp_rays_resident
     _lib = lib
     return lib
 
@@ -921,6 +979,30 @@ class Context:
         r, m = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.vgicp_map_carve_totals(self._h, C.byref(r), C.byref(m)))
         return int(r.value), int(m.value)
+
+    def rays_resident(self, poses, params, per_point: bool = True) -> "RayReport":
+        """vgicp_rays_resident (vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at `poses`
+        (one 4x4 pose or k of them), read-only.  params: a RayParams or what ray_params() takes as keywords.  The planes
+        come with a single pose and per_point=True."""
+        ps = np.asarray(poses, dtype=np.float64)
+        ps = ps.reshape(1, 4, 4) if ps.ndim == 2 else ps
+        k = len(ps)
+        g = np.ascontiguousarray(np.stack([pose_to_abi(T) for T in ps]).reshape(k, 16)) if k else np.zeros((0, 16))
+        p = params if isinstance(params, RayParams) else ray_params(**params)
+        planes = per_point and k == 1
+        n = self.points_size() if planes else 0
+        status = np.zeros(n, dtype=np.uint8) if planes else None
+        rng = np.zeros(n) if planes else None
+        keys = np.zeros((n, 3), dtype=np.int32) if planes else None
+        steps = np.zeros(n, dtype=np.uint32) if planes else None
+        out = RayOutputs(status.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(rng), keys.ctypes.data_as(C.POINTER(C.c_int32)),
+                         steps.ctypes.data_as(C.POINTER(C.c_uint32))) if planes else None
+        counts = (RayCounts * max(k, 1))()
+        st = RayStats()
+        self._check(self._lib.vgicp_rays_resident(self._h, _dp(g), k, C.byref(p), C.byref(out) if planes else None, counts,
+                                                  C.byref(st)))
+        return RayReport([dict(rays=int(c.rays), visits=int(c.visits), by_class=[int(v) for v in c.by_class]) for c in counts[:k]],
+                         status, rng, keys, steps, st.launches, st.groups, st.seconds, st.device_seconds)
 
     def frame_stats(self, reset: bool = False) -> FrameStats:
         st = FrameStats()

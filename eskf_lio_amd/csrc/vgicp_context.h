@@ -31,6 +31,7 @@
 #include "../../include/vgicp_hip_points.h"
 #include "../../include/vgicp_hip_map_gated.h"
 #include "../../include/vgicp_hip_map_carve.h"
+#include "../../include/vgicp_hip_map_rays.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -488,6 +489,11 @@ struct vgicp_ctx {
   uint64_t carve_rays = 0, carve_removed = 0;   // since vgicp_map_reset
   PinnedBuf<int32_t> h_carve_keys;   // pinned, grow-only: the synchronous call's key list on its way to the caller
   size_t carve_keys_capacity = 0;    // voxels
+  // the ray report (include/vgicp_hip_map_rays.h): read-only, so what it confirms lives beside the table
+  DeviceBuf<uint32_t> d_ray_bits;    // one bit per slot and pose of a group (ray_group_poses, vgicp_map_plan.h); made by the
+                                     // first call, anew only when the table's slot count has changed
+  uint64_t ray_bits_slots = 0;       // the slot count d_ray_bits was sized for
+  PinnedBuf<char> h_rays;            // pinned, grow-only: the poses on their way in, the counts and the planes on their way out
   // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
   // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
@@ -539,7 +545,7 @@ struct vgicp_ctx {
   int rank = 0;
 };
 
-// The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip, vgicp_map_carve.hip): was
+// The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip, vgicp_map_carve.hip, vgicp_map_rays.hip): was
 // this context made by the build that reads it?  Reads the stamp only; each library refuses in its own words.
 inline bool same_build(const vgicp_ctx* ctx) { return ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx)); }
 
@@ -675,6 +681,9 @@ int map_carve_resident(vgicp_ctx* ctx, const double transform[16], const vgicp_c
                        int32_t* removed_keys, size_t* removed, vgicp_carve_stats* stats);
 int map_carve_resident_async(vgicp_ctx* ctx, const double transform[16], const vgicp_carve_params* params);
 int map_carve_totals(vgicp_ctx* ctx, uint64_t* rays, uint64_t* removed);
+// The entry point of include/vgicp_hip_map_rays.h behind libvgicp_hip_map_rays.so, likewise (vgicp_capi_map_rays.inl).
+int rays_resident(vgicp_ctx* ctx, const double* poses, size_t n_poses, const vgicp_ray_params* params,
+                  const vgicp_ray_outputs* per_point, vgicp_ray_counts* counts, vgicp_ray_stats* stats);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

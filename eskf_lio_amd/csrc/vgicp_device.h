@@ -578,6 +578,28 @@ struct CarveArgs {
   uint32_t keys_capacity;      // voxels
 };
 hipError_t launch_map_carve(hipStream_t s, const CarveArgs& args);
+// The ray report (include/vgicp_hip_map_rays.h has the rule): two launches per group of poses, each one lane per point
+// and pose (grid.y = the group's poses).  CONFIRM: the lookup of the point's own voxel, whose slot's bit goes into the
+// pose's bitmap (zero before).  WALK: the point's ray through the table up to the first FULL voxel, its class from the
+// bitmap, the planes (single pose) and the counts.  The table is only read.
+constexpr uint32_t kRayCountWords = 10;   // per pose, 64-bit: rays, visits, by_class[8] (vgicp_ray_counts)
+struct RayArgs {
+  const VoxelRecord* table;
+  uint64_t slots;              // a power of two
+  double voxel_size;
+  const double* points_aos;    // n x 3
+  uint32_t n, stride;
+  const double* poses;         // device: 12 per pose of the group (R column-major, t)
+  uint32_t n_poses;            // of the group
+  double origin[3], margin, beyond, max_range;
+  uint32_t* bits;              // slots / 32 words per pose of the group
+  unsigned long long* counts;  // kRayCountWords per pose of the group; every word only grows
+  uint8_t* status;             // the planes: nullptr, or n entries (n_poses == 1)
+  double* range;
+  int32_t* hit_key;
+  uint32_t* steps;
+};
+hipError_t launch_map_rays(hipStream_t s, const RayArgs& args);
 // Append every FULL record to the output arrays (unordered); counters[0] = records written.
 hipError_t launch_map_export(hipStream_t s, const VoxelRecord* table, uint64_t slots, uint32_t capacity,
                              int32_t* keys, double* means, double* covs, uint64_t* counts,

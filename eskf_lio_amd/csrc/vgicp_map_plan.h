@@ -169,4 +169,43 @@ inline CarveVerdict plan_carve(const CarveFacts& f) {
   return CarveVerdict{};
 }
 
+// ---- what the ray report refuses (include/vgicp_hip_map_rays.h, rules 3 to 11; 1 and 2 are the side library's
+// handshake), and how its poses go in groups ----
+struct RayFacts : ResidentFacts {   // has_map, scan_resident, several_devices
+  bool pointers = false;          // poses and params are there
+  uint64_t n_poses = 0;
+  bool entries_finite = false;    // all 16 of every pose and the 3 of the origin
+  double margin = 0.0, beyond = 0.0, max_range = 0.0, voxel_size = 0.0;
+  uint32_t stride = 0, reserved = 0;
+  bool per_point = false;         // a per-point plane is asked for
+};
+using RayVerdict = GateVerdict;
+constexpr uint64_t kRayMaxPoses = 64;                 // VGICP_RAYS_MAX_POSES
+constexpr uint64_t kRayBitmapBudget = 16ull << 20;    // bytes of confirmation bitmaps one group of poses may take
+inline RayVerdict plan_rays(const RayFacts& f) {
+  if (!f.has_map) return RayVerdict{3, VGICP_ERR_NOT_READY, "no voxel map: call vgicp_map_reset first"};
+  if (!f.scan_resident) return RayVerdict{3, VGICP_ERR_NOT_READY, kNoScanText};
+  if (!f.pointers || f.n_poses == 0 || f.n_poses > kRayMaxPoses)
+    return RayVerdict{4, VGICP_ERR_BAD_ARGUMENT, "poses and params must not be NULL, n_poses 1 .. VGICP_RAYS_MAX_POSES"};
+  if (!f.entries_finite) return RayVerdict{5, VGICP_ERR_BAD_ARGUMENT, "a pose or origin entry is not finite"};
+  if (!(f.margin >= 0.0) || std::isinf(f.margin)) return RayVerdict{6, VGICP_ERR_BAD_ARGUMENT, "margin must be finite and >= 0"};
+  if (!(f.beyond >= 0.0) || std::isinf(f.beyond)) return RayVerdict{7, VGICP_ERR_BAD_ARGUMENT, "beyond must be finite and >= 0"};
+  if (!(f.max_range > 0.0) || std::isinf(f.max_range) || !(f.max_range / f.voxel_size <= kCarveMaxSteps))
+    return RayVerdict{8, VGICP_ERR_BAD_ARGUMENT, "max_range must be finite, > 0 and at most 4096 voxel sizes"};
+  if (f.stride == 0 || f.reserved != 0) return RayVerdict{9, VGICP_ERR_BAD_ARGUMENT, "stride must be >= 1 and reserved 0"};
+  if (f.per_point && f.n_poses != 1) return RayVerdict{10, VGICP_ERR_BAD_ARGUMENT, "per-point outputs are for a single pose"};
+  if (f.several_devices)
+    return RayVerdict{11, VGICP_ERR_BAD_ARGUMENT, "the ray report works on a single-device context: the resident scan of a device is a shard here"};
+  return RayVerdict{};
+}
+// one bit per slot and pose (slots: a power of two >= kMinSlots, so whole 32-bit words); the poses one group holds
+inline uint64_t ray_bitmap_bytes(uint64_t slots) { return slots / 8; }
+inline uint64_t ray_group_poses(uint64_t slots) {
+  return std::max<uint64_t>(1, std::min<uint64_t>(kRayMaxPoses, kRayBitmapBudget / std::max<uint64_t>(1, ray_bitmap_bytes(slots))));
+}
+inline uint64_t ray_groups(uint64_t slots, uint64_t n_poses) {
+  const uint64_t per = ray_group_poses(slots);
+  return (n_poses + per - 1) / per;
+}
+
 }  // namespace vgicp

@@ -36,6 +36,10 @@
 // the table and leaves hits and a shield bit in the low half of the records' spare word (the list head above, zero
 // between insertions), carve_sweep_kernel turns the voxels enough rays crossed into tombstones as evict_kernel does and
 // clears the marks.  Two launches, nothing in them waits.
+//
+// The ray report (include/vgicp_hip_map_rays.h) is the read-only query made of the same step: rays_confirm_kernel sets a
+// bit per slot that holds a return (a bitmap beside the table, not the spare word), rays_walk_kernel walks every ray up
+// to its first FULL voxel and classes it, for several poses in one grid.
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
 #include "vgicp_sort.h"
@@ -543,6 +547,130 @@ __global__ void __launch_bounds__(kBlock) carve_sweep_kernel(CarveArgs a) {
   }
 }
 
+// ---- the ray report (include/vgicp_hip_map_rays.h states the rule operation by operation; this restates it).  The key,
+// the boundary, the transform and the probe are carving's above: one definition of the step serves both ----
+// CONFIRM: one lane per point and pose.  The slot of the point's own voxel, if FULL, gets its bit in the pose's bitmap
+// (test before set, as carve_mark does for the shield: a scan puts many points into one voxel).
+__global__ void __launch_bounds__(kBlock) rays_confirm_kernel(RayArgs a) {
+#pragma clang fp contract(off)
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const double* pose = a.poses + 12 * (size_t)blockIdx.y;
+  uint32_t* bits = a.bits + (size_t)blockIdx.y * (size_t)(a.slots >> 5);
+  double e[3];
+  int32_t k[3];
+  transform_point(pose, pose + 9, a.points_aos[3 * (size_t)i], a.points_aos[3 * (size_t)i + 1], a.points_aos[3 * (size_t)i + 2], e);
+  if (!carve_key(e, a.voxel_size, k)) return;
+  const VoxelRecord* rec = find_voxel(a.table, (uint32_t)(a.slots - 1), k[0], k[1], k[2]);
+  if (!rec) return;
+  const uint64_t slot = (uint64_t)(rec - a.table);
+  uint32_t* word = bits + (slot >> 5);
+  const uint32_t bit = 1u << (slot & 31u);
+  if (!(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(word, bit);
+}
+
+// WALK: one lane per point and pose.  The ray's walk up to the first FULL voxel, the class, the planes, the counts.
+__global__ void __launch_bounds__(kBlock) rays_walk_kernel(RayArgs a) {
+#pragma clang fp contract(off)
+  __shared__ uint32_t by_class[8];
+  __shared__ unsigned long long wave_visits[kBlock / 64];
+  if (threadIdx.x < 8u) by_class[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t mask = (uint32_t)(a.slots - 1);
+  const double h = a.voxel_size;
+  const double* pose = a.poses + 12 * (size_t)blockIdx.y;
+  const uint32_t* bits = a.bits + (size_t)blockIdx.y * (size_t)(a.slots >> 5);
+  bool ray = false;
+  uint32_t visits = 0;
+  if (i < a.n) {
+    uint32_t cls = 0u;   // NO_RAY
+    const VoxelRecord* hit = nullptr;
+    double t_in = 0.0, len = 0.0;
+    int32_t kx = 0, ky = 0, kz = 0;
+    double e[3];
+    if (i % a.stride == 0u) {
+      double o[3];
+      int32_t k[3];
+      transform_point(pose, pose + 9, a.points_aos[3 * (size_t)i], a.points_aos[3 * (size_t)i + 1], a.points_aos[3 * (size_t)i + 2], e);
+      transform_point(pose, pose + 9, a.origin[0], a.origin[1], a.origin[2], o);
+      const double dx = e[0] - o[0], dy = e[1] - o[1], dz = e[2] - o[2];
+      len = sqrt((dx * dx + dy * dy) + dz * dz);
+      const double longer = len + a.beyond;
+      const double t_end = (longer < a.max_range ? longer : a.max_range) / len;
+      const double t_front = (len - a.margin) / len;
+      const bool finite = isfinite(dx) && isfinite(dy) && isfinite(dz);
+      if (len > 0.0 && t_end > 0.0 && finite && carve_key(o, h, k)) {
+        ray = true;
+        // the walk's hard bound, carving's: what vgicp_map_plan.h lets through keeps the ceiling at kCarveMaxSteps + 1
+        double cells = ceil((t_end * len) / h);
+        if (!(cells <= 4097.0)) cells = 4097.0;
+        const uint32_t max_steps = 3u * (uint32_t)cells + 3u;
+        kx = k[0]; ky = k[1]; kz = k[2];
+        const int32_t sx = dx > 0.0 ? 1 : -1, sy = dy > 0.0 ? 1 : -1, sz = dz > 0.0 ? 1 : -1;
+        double tx = carve_boundary(kx, dx, o[0], h), ty = carve_boundary(ky, dy, o[1], h), tz = carve_boundary(kz, dz, o[2], h);
+        hit = find_voxel(a.table, mask, kx, ky, kz);
+        visits = 1;
+        for (uint32_t step = 0; step < max_steps && !hit; ++step) {
+          if (tx <= ty && tx <= tz) {
+            if (!(tx < t_end)) break;
+            t_in = tx;
+            kx += sx;
+            tx = carve_boundary(kx, dx, o[0], h);
+          } else if (ty <= tz) {
+            if (!(ty < t_end)) break;
+            t_in = ty;
+            ky += sy;
+            ty = carve_boundary(ky, dy, o[1], h);
+          } else {
+            if (!(tz < t_end)) break;
+            t_in = tz;
+            kz += sz;
+            tz = carve_boundary(kz, dz, o[2], h);
+          }
+          hit = find_voxel(a.table, mask, kx, ky, kz);
+          ++visits;
+        }
+        // the class, in the header's order
+        if (!hit) {
+          cls = 1u;   // OPEN
+        } else {
+          int32_t ke[3];
+          const bool own = carve_key(e, h, ke) && ke[0] == kx && ke[1] == ky && ke[2] == kz;
+          const uint64_t slot = (uint64_t)(hit - a.table);
+          const bool confirmed = (bits[slot >> 5] >> (slot & 31u)) & 1u;
+          cls = own ? 2u : t_in >= 1.0 ? 3u : confirmed ? 4u : t_in < t_front ? 5u : 6u;
+        }
+      }
+    }
+    atomicAdd(&by_class[cls], 1u);
+    if (a.status) a.status[i] = (uint8_t)cls;
+    if (a.range) a.range[i] = hit ? t_in * len : __longlong_as_double(0x7FF8000000000000ll);
+    if (a.hit_key) {
+      a.hit_key[3 * (size_t)i] = hit ? kx : INT32_MIN;
+      a.hit_key[3 * (size_t)i + 1] = hit ? ky : INT32_MIN;
+      a.hit_key[3 * (size_t)i + 2] = hit ? kz : INT32_MIN;
+    }
+    if (a.steps) a.steps[i] = visits;
+  }
+  // at most one global atomic per workgroup and counter
+  const int cast = __syncthreads_count(ray ? 1 : 0);   // (also the barrier behind the histogram's adds)
+  unsigned long long sum = visits;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, (unsigned int)d, 64);
+  if ((threadIdx.x & 63u) == 0u) wave_visits[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  unsigned long long* counts = a.counts + (size_t)kRayCountWords * blockIdx.y;
+  if (threadIdx.x == 0) {
+    unsigned long long total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBlock / 64; ++w) total += wave_visits[w];
+    if (cast) atomicAdd(counts, (unsigned long long)cast);
+    if (total) atomicAdd(counts + 1, total);
+  }
+  if (threadIdx.x < 8u && by_class[threadIdx.x]) atomicAdd(counts + 2 + threadIdx.x, (unsigned long long)by_class[threadIdx.x]);
+}
+
 __global__ void export_kernel(const VoxelRecord* __restrict__ table, uint64_t slots, uint32_t capacity,
                               int32_t* __restrict__ keys, double* __restrict__ means,
                               double* __restrict__ covs, uint64_t* __restrict__ counts,
@@ -678,6 +806,18 @@ hipError_t launch_map_carve(hipStream_t s, const CarveArgs& args) {
   if (args.n == 0) return hipSuccess;   // no point: no mark, and nothing for the sweep to find
   counted_launch(carve_mark_kernel, dim3(blocks_for(args.n, kBlock)), dim3(kBlock), 0, s, args);
   counted_launch(carve_sweep_kernel, dim3(blocks_for(args.slots, kBlock)), dim3(kBlock), 0, s, args);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_rays(hipStream_t s, const RayArgs& args) {
+  if (!args.table || !args.bits || !args.counts || !args.poses || args.slots < 32 || (args.slots & (args.slots - 1)) != 0)
+    return hipErrorInvalidValue;
+  if (args.n_poses == 0 || args.n_poses > 65535u || args.stride == 0) return hipErrorInvalidValue;
+  if (args.n_poses != 1 && (args.status || args.range || args.hit_key || args.steps)) return hipErrorInvalidValue;
+  if (args.n == 0) return hipSuccess;
+  const dim3 grid(blocks_for(args.n, kBlock), args.n_poses);
+  counted_launch(rays_confirm_kernel, grid, dim3(kBlock), 0, s, args);
+  counted_launch(rays_walk_kernel, grid, dim3(kBlock), 0, s, args);
   return hipGetLastError();
 }
 

@@ -58,6 +58,10 @@ def load_library() -> C.CDLL:
     lib.host_localmap_clear_carve.restype = None
     lib.host_localmap_clear_carve.argtypes = [vp]
     lib.host_localmap_carve_totals.argtypes = [vp, C.POINTER(C.c_uint64)]
+    u64p = C.POINTER(C.c_uint64)
+    lib.host_localmap_ray_report.argtypes = [vp, dp, dp, C.c_uint32, sz, C.POINTER(C.c_uint8), dp, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_uint32), u64p, C.POINTER(sz), C.POINTER(C.c_int)]
+    lib.host_localmap_ray_counts.argtypes = [vp, sz, dp, dp, C.c_uint32, u64p, C.POINTER(C.c_int)]
     lib.host_localmap_match.argtypes = [vp, sz, dp, dp, dp, dp, dp, dp, C.POINTER(sz)]
     lib.host_localmap_export.restype = sz
     lib.host_localmap_export.argtypes = [vp, sz, C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_uint64)]
@@ -198,6 +202,48 @@ class LocalMap:
         out = (C.c_uint64 * 2)()
         _check(self._lib, self._lib.host_localmap_carve_totals(self._h, out))
         return int(out[0]), int(out[1])
+
+    @staticmethod
+    def _ray_params(margin, beyond, max_range, origin):
+        return np.ascontiguousarray([*[float(v) for v in origin], float(margin), float(beyond), float(max_range)], dtype=np.float64)
+
+    @staticmethod
+    def _ray_counts(words):
+        return dict(rays=int(words[0]), visits=int(words[1]), by_class=[int(v) for v in words[2:10]])
+
+    def rayReport(self, transform, margin: float = 0.0, beyond: float = 0.0, max_range: float = 80.0, stride: int = 1,
+                  origin=(0.0, 0.0, 0.0)):
+        """LocalMap::rayReport (vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at
+        `transform`, read-only.  None where the map or the scan is not on the device; else a dict of status, range,
+        hit_key, steps and counts."""
+        T = capi.pose_to_abi(transform)
+        p = self._ray_params(margin, beyond, max_range, origin)
+        n, available, counts = C.c_size_t(0), C.c_int(0), (C.c_uint64 * 10)()
+        # the size first, then the planes
+        _check(self._lib, self._lib.host_localmap_ray_report(self._h, _dp(T), _dp(p), int(stride), 0, None, None, None, None,
+                                                             counts, C.byref(n), C.byref(available)))
+        if not available.value:
+            return None
+        m = n.value
+        status, rng = np.zeros(m, dtype=np.uint8), np.zeros(m)
+        keys, steps = np.zeros((m, 3), dtype=np.int32), np.zeros(m, dtype=np.uint32)
+        _check(self._lib, self._lib.host_localmap_ray_report(
+            self._h, _dp(T), _dp(p), int(stride), m, status.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(rng),
+            keys.ctypes.data_as(C.POINTER(C.c_int32)), steps.ctypes.data_as(C.POINTER(C.c_uint32)), counts, C.byref(n),
+            C.byref(available)))
+        if not available.value or n.value != m:
+            return None
+        return dict(status=status, range=rng, hit_key=keys, steps=steps, counts=self._ray_counts(counts))
+
+    def rayCounts(self, transforms, margin: float = 0.0, beyond: float = 0.0, max_range: float = 80.0, stride: int = 1,
+                  origin=(0.0, 0.0, 0.0)):
+        """LocalMap::rayCounts: the counts alone at several poses (at most 64); None where not available."""
+        Ts = np.ascontiguousarray(np.stack([capi.pose_to_abi(T) for T in transforms]).reshape(-1, 16))
+        p = self._ray_params(margin, beyond, max_range, origin)
+        available, counts = C.c_int(0), (C.c_uint64 * (10 * len(Ts)))()
+        _check(self._lib, self._lib.host_localmap_ray_counts(self._h, len(Ts), _dp(Ts), _dp(p), int(stride), counts,
+                                                             C.byref(available)))
+        return [self._ray_counts(counts[10 * k:10 * k + 10]) for k in range(len(Ts))] if available.value else None
 
     def drain(self) -> int:
         """Waits for the shadow grid's worker (LocalMap::grid()); the host grid's voxel count."""

@@ -142,6 +142,49 @@ int host_localmap_carve_totals(const LocalMap * map, uint64_t out[2])
     });
 }
 
+// LocalMap::rayReport / rayCounts (include/vgicp_hip_map_rays.h).  params: origin (3), margin, beyond, max_range.
+// *available = 0: the map or the scan is not on the device, nothing is written.  ray_report: capacity points of room in
+// every plane (NULL: not wanted), *n the report's points; counts: rays, visits, by_class[8] per transform.
+int host_localmap_ray_report(
+  const LocalMap * map, const double transform[16], const double params[6], uint32_t stride, size_t capacity,
+  uint8_t * status, double * range, int32_t * hit_key, uint32_t * steps, uint64_t counts[10], size_t * n, int * available)
+{
+  return guarded(
+    [&] {
+      const vgicp_ray_params p = {{params[0], params[1], params[2]}, params[3], params[4], params[5], stride, 0};
+      const LocalMap::RayReport r = map->rayReport(ESKF_LIO::shim::poseFromData(transform), p);
+      *available = r.available ? 1 : 0;
+      *n = r.status.size();
+      if (!r.available) {return;}
+      const size_t m = std::min(capacity, r.status.size());
+      if (status && m) {std::memcpy(status, r.status.data(), m);}
+      if (range && m) {std::memcpy(range, r.range.data(), m * sizeof(double));}
+      if (hit_key && m) {std::memcpy(hit_key, r.hitKey.data(), m * 3 * sizeof(int32_t));}
+      if (steps && m) {std::memcpy(steps, r.steps.data(), m * sizeof(uint32_t));}
+      counts[0] = r.counts.rays;
+      counts[1] = r.counts.visits;
+      for (int k = 0; k < 8; ++k) {counts[2 + k] = r.counts.byClass[k];}
+    });
+}
+int host_localmap_ray_counts(
+  const LocalMap * map, size_t k, const double * transforms, const double params[6], uint32_t stride, uint64_t * counts,
+  int * available)
+{
+  return guarded(
+    [&] {
+      const vgicp_ray_params p = {{params[0], params[1], params[2]}, params[3], params[4], params[5], stride, 0};
+      std::vector<Isometry3d> T(k);
+      for (size_t h = 0; h < k; ++h) {T[h] = ESKF_LIO::shim::poseFromData(transforms + 16 * h);}
+      const LocalMap::RayCountsList r = map->rayCounts(T, p);
+      *available = r.available ? 1 : 0;
+      for (size_t h = 0; h < r.counts.size(); ++h) {
+        counts[10 * h] = r.counts[h].rays;
+        counts[10 * h + 1] = r.counts[h].visits;
+        for (int c = 0; c < 8; ++c) {counts[10 * h + 2 + c] = r.counts[h].byClass[c];}
+      }
+    });
+}
+
 // updateLocalMap(cloud, transform, initialize); the transformed cloud is written back to
 // points/covs, as the reference mutates the shared cloud in place (src/LocalMap.cpp:15).
 int host_localmap_update(

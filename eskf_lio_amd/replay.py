@@ -759,7 +759,8 @@ class DeviceBackend:
     device-resident voxel grid; the motion gate of LocalMap::needsMapUpdate (src/LocalMap.cpp:132-147) is a
     few flops and stays on the host.  With local_map.insert_gate the insertion is vgicp_map_insert_resident_gated at the
     frame's pose.  With local_map.carve every map update first carves the map with the frame's scan at the frame's pose
-    (vgicp_map_carve_resident_async), then inserts."""
+    (vgicp_map_carve_resident_async), then inserts.  set_ray_report(...) adds the read-only ray report
+    (vgicp_rays_resident) at every aligned pose, before the map update; its class totals add up in ray_totals."""
     supports_insert_gate = True
     supports_carve = True
 
@@ -801,6 +802,24 @@ class DeviceBackend:
         self.iterations: List[int] = []
         self.converged: List[bool] = []                     # of the aligns with a prior
         self.kept: List[int] = []
+        self.ray_params = None                              # set_ray_report
+        self.ray_totals = dict(frames=0, rays=0, visits=0, by_class=[0] * 8)
+
+    def set_ray_report(self, max_range: float, margin: float = 0.0, beyond: float = 0.0, stride: int = 1, origin=None):
+        """From the next frame on: the ray report (vgicp_hip_map_rays.h) of the frame's scan at its aligned pose, before
+        the map update; counts only.  origin: the sensor's origin in the prepared scan's frame, by default the extrinsic's
+        translation."""
+        from . import capi
+        if origin is None:
+            origin = tuple(float(v) for v in self.T_il[:3, 3])
+        self.ray_params = capi.ray_params(margin=margin, beyond=beyond, max_range=max_range, stride=stride, origin=origin)
+
+    def _ray_report(self, transform):
+        c = self.ctx.rays_resident(transform, self.ray_params, per_point=False).counts[0]
+        self.ray_totals["frames"] += 1
+        self.ray_totals["rays"] += c["rays"]
+        self.ray_totals["visits"] += c["visits"]
+        self.ray_totals["by_class"] = [a + b for a, b in zip(self.ray_totals["by_class"], c["by_class"])]
 
     def _scale_from_quantile(self, guess):
         """The resident scan reported at the predicted pose; kernel and gate stay as configured."""
@@ -843,6 +862,8 @@ class DeviceBackend:
                                                   information)
 
     def update_map(self, points, covs, transform, initialize):
+        if self.ray_params is not None and self.prev is not None:   # (the first frame is not aligned: its map is empty)
+            self._ray_report(transform)
         if not initialize and self.prev is not None:
             moved = np.linalg.inv(self.prev) @ transform
             cosine = 0.5 * (np.trace(moved[:3, :3]) - 1.0)

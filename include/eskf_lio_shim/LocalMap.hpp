@@ -40,6 +40,7 @@
 #include "../vgicp_hip_map_points.h"
 #include "../vgicp_hip_map_gated.h"
 #include "../vgicp_hip_map_carve.h"
+#include "../vgicp_hip_map_rays.h"
 
 // The raw-point store's entry points (vgicp_hip_map_points.h, and vgicp_set_option for its option) are referenced
 // weakly, so a program that links a stand-in of the C ABI without them (tests/native/shadow_stress.cpp) still links: a
@@ -56,6 +57,9 @@
 // ... and free-space carving's (vgicp_hip_map_carve.h, in libvgicp_hip_map_carve.so): without that library setCarve refuses.
 #pragma weak vgicp_map_carve_resident_async
 #pragma weak vgicp_map_carve_totals
+// ... and the ray report's (vgicp_hip_map_rays.h, in libvgicp_hip_map_rays.so): without that library rayReport and rayCounts
+// say available == false.
+#pragma weak vgicp_rays_resident
 #include "ShimTypes.hpp"
 #include "ShimSupport.hpp"
 #include "ResidentScan.hpp"
@@ -551,7 +555,76 @@ public:
     return t;
   }
 
+  // The ray report (include/vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at a pose,
+  // read-only — which returns appeared in front of the map's surface (VGICP_RAY_BEHIND), which rays the map blocks
+  // (VGICP_RAY_BLOCKED: what carving would see through), per point and counted.  Like ICP::pointReport and carveTotals a
+  // query beside the drop-in calls: none of them changes its route.  available == false, and nothing thrown, where the
+  // map or the scan is not on the device (a host-authoritative map, no resident scan, a module without the library).
+  using RayParams = vgicp_ray_params;
+  struct RayCounts
+  {
+    uint64_t rays = 0, visits = 0;
+    uint64_t byClass[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [VGICP_RAY_NO_RAY] .. [VGICP_RAY_NEAR]
+  };
+  struct RayReport
+  {
+    bool available = false;
+    std::vector<uint8_t> status;      // VGICP_RAY_*, one per point of the resident scan
+    std::vector<double> range;        // metres to the hit; NaN with none
+    std::vector<int32_t> hitKey;      // 3 per point; INT32_MIN with none
+    std::vector<uint32_t> steps;      // voxels visited
+    RayCounts counts;
+  };
+  struct RayCountsList
+  {
+    bool available = false;
+    std::vector<RayCounts> counts;    // one per transform
+  };
+  RayReport rayReport(const Isometry3d & transform, const RayParams & params) const
+  {
+    RayReport r;
+    if (!deviceResident_ || !vgicp_rays_resident) {return r;}
+    size_t n = 0;
+    if (vgicp_scan_download(ctx_, 0, nullptr, nullptr, &n) != VGICP_OK) {return r;}   // size query: no resident scan
+    r.status.resize(n);
+    r.range.resize(n);
+    r.hitKey.resize(3 * n);
+    r.steps.resize(n);
+    const vgicp_ray_outputs out = {r.status.data(), r.range.data(), r.hitKey.data(), r.steps.data()};
+    vgicp_ray_counts c;
+    const int rc = vgicp_rays_resident(ctx_, shim::poseData(transform), 1, &params, &out, &c, nullptr);
+    if (rc == VGICP_ERR_NOT_READY) {return RayReport();}
+    shim::check(ctx_, rc, "vgicp_rays_resident");
+    r.counts = toRayCounts(c);
+    r.available = true;
+    return r;
+  }
+  RayCountsList rayCounts(const std::vector<Isometry3d> & transforms, const RayParams & params) const
+  {
+    RayCountsList r;
+    if (!deviceResident_ || !vgicp_rays_resident || transforms.empty()) {return r;}
+    std::vector<double> poses(16 * transforms.size());
+    for (size_t k = 0; k < transforms.size(); ++k) {
+      std::memcpy(poses.data() + 16 * k, shim::poseData(transforms[k]), 16 * sizeof(double));
+    }
+    std::vector<vgicp_ray_counts> c(transforms.size());
+    const int rc = vgicp_rays_resident(ctx_, poses.data(), transforms.size(), &params, nullptr, c.data(), nullptr);
+    if (rc == VGICP_ERR_NOT_READY) {return r;}
+    shim::check(ctx_, rc, "vgicp_rays_resident");
+    for (const auto & v : c) {r.counts.push_back(toRayCounts(v));}
+    r.available = true;
+    return r;
+  }
+
 private:
+  static RayCounts toRayCounts(const vgicp_ray_counts & c)
+  {
+    RayCounts out;
+    out.rays = c.rays;
+    out.visits = c.visits;
+    for (int k = 0; k < 8; ++k) {out.byClass[k] = c.by_class[k];}
+    return out;
+  }
   static Key toKey(const Vector3i & v) {return Key{v(0), v(1), v(2)};}
   // the context may have served another map before (shim::defaultContext is shared, and a caller may switch the option
   // through the C ABI): the option is set to THIS map's config every time.  The map is empty here (just reset), which is

@@ -17,6 +17,9 @@ options: --out traj.tum   --device-map (keep the voxel grid on the GPU only)   -
          --carve-range R [--carve-margin M --carve-min-hits H --carve-stride S] (local_map.carve, with --resident: before
          every map update the voxels that at least H of the scan's rays cross within R metres, stopping M metres short of
          their returns, and that hold no return of the scan, are removed, include/vgicp_hip_map_carve.h; off by default)
+         --ray-report RANGE [--ray-margin M --ray-beyond B --ray-stride S] (with --resident: the read-only ray report of
+         every frame's scan at its aligned pose, before the map update, include/vgicp_hip_map_rays.h: the first map voxel
+         on every ray within RANGE metres and B metres behind the return; the class totals of the run are printed)
          --prior-update (kalman_filter.update.iterated: the filter's pose covariance enters every round of the align as a
          prior, include/vgicp_hip_prior.h, and the update is the iterated one; off by default)
 The configuration is the reference's config/hilti_config.yaml as a dict (eskf_lio_amd/replay.py:DEFAULT_CONFIG);
@@ -70,6 +73,22 @@ def carve_config(cfg, args):
     return dict(cfg, local_map=dict(cfg["local_map"], carve=given))
 
 
+def ray_report_params(args):
+    """What DeviceBackend.set_ray_report takes, from the --ray-* flags; None without --ray-report."""
+    if args.ray_report is None:
+        return None
+    return dict(max_range=args.ray_report, margin=args.ray_margin or 0.0, beyond=args.ray_beyond or 0.0,
+                stride=args.ray_stride or 1)
+
+
+def ray_report_line(totals, params):
+    names = capi.RAY_CLASS_NAMES
+    classes = ", ".join(f"{names[c]} {totals['by_class'][c]}" for c in range(len(names)))
+    return (f"ray report within {params['max_range']} m (margin {params['margin']}, beyond {params['beyond']}, stride "
+            f"{params['stride']}) at {totals['frames']} aligned poses: {totals['rays']} rays, {totals['visits']} voxels visited; "
+            f"{classes}")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bag")
@@ -102,7 +121,17 @@ def parse_args(argv=None):
     ap.add_argument("--carve-margin", type=float, default=None, help="metres a ray stops short of its return (local_map.carve.margin)")
     ap.add_argument("--carve-min-hits", type=int, default=None, help="rays that must cross a voxel (local_map.carve.min_hits)")
     ap.add_argument("--carve-stride", type=int, default=None, help="every S-th point casts a ray (local_map.carve.stride)")
+    ap.add_argument("--ray-report", type=float, default=None, metavar="RANGE",
+                    help="the ray report at every aligned pose before the map update: metres a ray is followed (vgicp_hip_map_rays.h)")
+    ap.add_argument("--ray-margin", type=float, default=None, help="metres in front of a return within which a hit is near, not blocked")
+    ap.add_argument("--ray-beyond", type=float, default=None, help="metres a ray is followed behind its return")
+    ap.add_argument("--ray-stride", type=int, default=None, help="every S-th point casts a ray")
     args = ap.parse_args(argv)
+    if any(v is not None for v in (args.ray_report, args.ray_margin, args.ray_beyond, args.ray_stride)):
+        if not args.resident:
+            ap.error("--ray-* needs --resident")
+        if args.ray_report is None:
+            ap.error("--ray-margin, --ray-beyond and --ray-stride need --ray-report")
     if args.raw_points_on_device and not args.resident:
         ap.error("--raw-points-on-device needs --resident")
     if any(v is not None for v in (args.carve_range, args.carve_margin, args.carve_min_hits, args.carve_stride)):
@@ -114,8 +143,9 @@ def parse_args(argv=None):
     return args
 
 
-def main():
-    args = parse_args()
+def main(argv=None):
+    """Runs the replay; returns its summary: poses, and with --ray-report the class totals of the run (ray_report)."""
+    args = parse_args(argv)
     ap = args.parser
     cfg, imu_topic, lidar_topic = replay.DEFAULT_CONFIG, replay.IMU_TOPIC, replay.LIDAR_TOPIC
     if args.config:
@@ -148,8 +178,12 @@ def main():
     backend = replay.DeviceBackend(cfg) if args.resident else replay.GpuBackend(cfg, device_resident_map=args.device_map)
     if args.raw_points_on_device:
         backend.ctx.set_option(capi.OPTION_MAP_RAW_POINTS, 1)   # the map is empty here, as the option wants
+    ray_params = ray_report_params(args)
+    if ray_params is not None:
+        backend.set_ray_report(**ray_params)
     odo = replay.Odometry(cfg, backend)
     traj = odo.run(events)
+    summary = dict(poses=len(traj), ray_report=None)
     replay.write_tum(args.out, traj)
     print(f"{len(traj)} poses -> {args.out}; Gauss-Newton rounds per frame: {odo.backend.iterations}")
     print(odo.report())
@@ -163,6 +197,9 @@ def main():
     if args.carve_range is not None:
         rays, removed = backend.ctx.map_carve_totals()
         print(f"free-space carving within {args.carve_range} m: {removed} voxels removed by {rays} rays")
+    if ray_params is not None:
+        summary["ray_report"] = dict(backend.ray_totals, classes=dict(zip(capi.RAY_CLASS_NAMES, backend.ray_totals["by_class"])))
+        print(ray_report_line(backend.ray_totals, ray_params))
     if args.raw_points_on_device:
         t0 = time.perf_counter()
         keys, _ = backend.ctx.map_points_export()
@@ -171,6 +208,7 @@ def main():
     if truth is not None:
         err = [np.linalg.norm(T[:3, 3] - G[:3, 3]) for (_, T), (_, G) in zip(traj, truth)]
         print(f"synthetic stream: position error against the generating motion, max {max(err):.4f} m")
+    return summary
 
 
 if __name__ == "__main__":
