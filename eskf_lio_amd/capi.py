@@ -77,6 +77,13 @@ RAYS_MAX_POSES = 64
 RAY_NO_RAY, RAY_OPEN, RAY_OWN, RAY_BEHIND, RAY_CONFIRMED, RAY_BLOCKED, RAY_NEAR = range(7)
 RAY_CLASS_NAMES = ("no_ray", "open", "own", "behind", "confirmed", "blocked", "near")
 
+# every symbol include/vgicp_hip_search_report.h declares: likewise, one entry point (a test hook) in a library of its own
+SEARCH_REPORT_EXPORTS = ("vgicp_prepare_search_report",)
+SEARCH_REPORT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_search_report.so")
+# the fourteen paths of the neighbour search, in the order of the struct's fields (and of the kernel's bits)
+SEARCH_PATHS = ("home", "crowded", "no_own_cell", "window_is_k", "whole_scan", "clipped", "open2", "open1", "leaf",
+                "finest", "compacted", "spilled", "waited", "reranked")
+
 
 class VgicpError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -108,6 +115,21 @@ ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2
 ROBUST_EXPORTS = ()
 ROBUST_KERNELS = {"none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY}
 COUNTER_UPLOAD_SLOW = 6
+
+
+class SearchReport(C.Structure):
+    """vgicp_search_report (vgicp_hip_search_report.h), 96 bytes."""
+    _fields_ = [(name, C.c_uint32) for name in
+                ("kept", "n_heavy", "n_light", "cells", "spilled_or_swept", "batches_total", "batches_max", "cells_total",
+                 "cells_max", "above_voxel") + SEARCH_PATHS]
+
+    def paths(self) -> dict:
+        return {name: int(getattr(self, name)) for name in SEARCH_PATHS}
+
+    def line(self) -> str:
+        """One line for a log: the start lists, then every path with the queries that took it."""
+        return (f"kept {self.kept} heavy {self.n_heavy} light {self.n_light} cells {self.cells} | "
+                + " ".join(f"{k} {v}" for k, v in self.paths().items()))
 
 
 class Stats(C.Structure):
@@ -335,6 +357,12 @@ def load_library() -> C.CDLL:
                                              C.POINTER(RayStats)]
         rays.vgicp_rays_resident.restype = C.c_int
         lib.vgicp_rays_resident = rays.vgicp_rays_resident
+    # the neighbour search's path report, likewise
+    if os.path.exists(SEARCH_REPORT_LIB_PATH):
+        report = C.CDLL(SEARCH_REPORT_LIB_PATH, mode=C.RTLD_GLOBAL)
+        report.vgicp_prepare_search_report.argtypes = [vp, C.POINTER(SearchReport)]
+        report.vgicp_prepare_search_report.restype = C.c_int
+        lib.vgicp_prepare_search_report = report.vgicp_prepare_search_report
     _lib = lib
     return lib
 
@@ -793,6 +821,17 @@ class Context:
         self._check(self._lib.vgicp_voxel_index(self._h, points.shape[0], _dp(points),
                                                 keys.ctypes.data_as(C.POINTER(C.c_int32))))
         return keys
+
+    def search_report(self, start_lists_only: bool = False) -> "SearchReport":
+        """vgicp_prepare_search_report (vgicp_hip_search_report.h): the paths the neighbour search of the last settled
+        preparation took, from a context created under VGICP_DEBUG_PREP.  Any other context is refused
+        (ERR_BAD_ARGUMENT) unless start_lists_only: then kept, n_heavy and n_light, which every context has, are
+        returned and the rest is zero.  ERR_NOT_READY before any preparation has been settled."""
+        r = SearchReport()
+        rc = self._lib.vgicp_prepare_search_report(self._h, C.byref(r))
+        if not (start_lists_only and rc == ERR_BAD_ARGUMENT and "VGICP_DEBUG_PREP" in self.last_error()):
+            self._check(rc)
+        return r
 
     def preprocess(self, points, voxel_size: float, knn: int = 30):
         """CloudPreprocessor::voxelDownsampleAndEstimateCovariances (CloudPreprocessor.cpp:76-127) on the

@@ -43,7 +43,10 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
   int rc = ensure_cells(ctx, preprocess_cell_bytes(entries));
   if (rc != VGICP_OK) return rc;
   const int debug = ctx->dev.debug_prep;
-  if (debug) VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 72 * sizeof(uint32_t), ctx->stream));
+  if (debug) {
+    VG_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 72 * sizeof(uint32_t), ctx->stream));
+    VG_HIP(ctx, hipMemsetAsync(ctx->d_counters + kPathWord0, 0, kPathCount * sizeof(uint32_t), ctx->stream));
+  }
   next_nonzero(ctx->prep_epoch);
   PrepareArgs a;
   std::memset(&a, 0, sizeof a);
@@ -125,11 +128,13 @@ int enqueue_prepare(vgicp_ctx* ctx, double* d_pts, size_t n, double voxel_size, 
 int resolve_prepare(vgicp_ctx* ctx, uint32_t* kept) {
   const uint32_t* h = ctx->h_prep;
   *kept = 0;
+  ctx->prep_settled = false;
   if (h[kScanTimeout] == ctx->prep_epoch)
     return fail(ctx, VGICP_ERR_HIP, "a device-wide scan of the scan preparation gave up waiting for a tile");
   if (h[kBeyondGrid] == ctx->prep_epoch)
     return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "a point lies beyond the search grid (more than 2^17 voxel sizes from the origin)");
   *kept = h[0];
+  ctx->prep_settled = true;
   ctx->prep_indefinite = h[kIndefiniteCounter];
   ctx->prep_deskewed = (int64_t)h[kDeskewedCounter];
   if (ctx->dev.debug_prep) {
@@ -988,3 +993,34 @@ int vgicp_scan_download(vgicp_ctx* ctx, size_t capacity, double* points, double*
   return VGICP_OK;
 }
 }  // extern "C"
+
+// vgicp_prepare_search_report (include/vgicp_hip_search_report.h) behind its entry point in
+// libvgicp_hip_search_report.so, which has made the layout handshake: the counter block as the last settled preparation
+// left it in h_prep.  The path counts are words kPathWord0.. in the order of the struct's last fourteen fields.
+namespace vgicp_internal {
+int prepare_search_report(vgicp_ctx* ctx, vgicp_search_report* report) {
+  if (!report) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "report is NULL");
+  std::memset(report, 0, sizeof *report);
+  if (several_devices(ctx)) return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the search report reads a single-device context");
+  VG_RC(settle(ctx));
+  if (!ctx->prep_settled) return fail(ctx, VGICP_ERR_NOT_READY, "no scan preparation has been settled: call vgicp_preprocess or vgicp_scan_prepare first");
+  const uint32_t* h = ctx->h_prep;
+  report->kept = h[0];
+  report->n_heavy = h[kHeavyQueries];
+  report->n_light = h[kLightQueries];
+  if (!ctx->dev.debug_prep)
+    return fail(ctx, VGICP_ERR_BAD_ARGUMENT, "the context was created without VGICP_DEBUG_PREP: its searches count no paths");
+  report->cells = h[1];
+  report->spilled_or_swept = h[2];
+  report->batches_total = h[3];
+  report->batches_max = h[4];
+  report->cells_total = h[5];
+  report->cells_max = h[6];
+  report->above_voxel = h[7];
+  static_assert(offsetof(vgicp_search_report, reranked) - offsetof(vgicp_search_report, home) == (kPathCount - 1) * sizeof(uint32_t),
+                "one field per path, in the order of the kPath* bits");
+  uint32_t* paths = &report->home;
+  for (int k = 0; k < kPathCount; ++k) paths[k] = h[kPathWord0 + k];
+  return VGICP_OK;
+}
+}  // namespace vgicp_internal

@@ -16,6 +16,7 @@
 #include <mutex>
 #include <thread>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +33,7 @@
 #include "../../include/vgicp_hip_map_gated.h"
 #include "../../include/vgicp_hip_map_carve.h"
 #include "../../include/vgicp_hip_map_rays.h"
+#include "../../include/vgicp_hip_search_report.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -375,6 +377,7 @@ struct vgicp_ctx {
   uint64_t upload_bytes = 0;
   double upload_seconds = 0.0;
   uint64_t prep_indefinite = 0;      // kept points of the last scan preparation with an indefinite covariance
+  bool prep_settled = false;         // h_prep holds the counter block of a preparation that resolve_prepare accepted
   // developer / test switches of the environment, read ONCE when the context is created (never inside a call)
   struct DevSwitches {
     bool no_sym = false, no_stash = false, no_memo = false, verbose = false, insert_sort = false;
@@ -545,7 +548,8 @@ struct vgicp_ctx {
   int rank = 0;
 };
 
-// The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip, vgicp_map_carve.hip, vgicp_map_rays.hip): was
+// The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip, vgicp_map_carve.hip, vgicp_map_rays.hip,
+// vgicp_search_report.hip): was
 // this context made by the build that reads it?  Reads the stamp only; each library refuses in its own words.
 inline bool same_build(const vgicp_ctx* ctx) { return ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx)); }
 
@@ -684,6 +688,8 @@ int map_carve_totals(vgicp_ctx* ctx, uint64_t* rays, uint64_t* removed);
 // The entry point of include/vgicp_hip_map_rays.h behind libvgicp_hip_map_rays.so, likewise (vgicp_capi_map_rays.inl).
 int rays_resident(vgicp_ctx* ctx, const double* poses, size_t n_poses, const vgicp_ray_params* params,
                   const vgicp_ray_outputs* per_point, vgicp_ray_counts* counts, vgicp_ray_stats* stats);
+// The entry point of include/vgicp_hip_search_report.h behind libvgicp_hip_search_report.so, likewise (vgicp_capi_prepare.inl).
+int prepare_search_report(vgicp_ctx* ctx, vgicp_search_report* report);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

@@ -391,6 +391,7 @@ size_t map_insert_scratch_bytes(uint32_t n);
 //   [76], [77] tile tickets of the two single-launch scans
 //   [78], [79] queries of the neighbour search that start first (sparse neighbourhood) / after them
 //   [80] workgroup ticket of the prologue (zero between launches: the workgroup that draws the last one clears it)
+//   [81..94] developer counts: queries of the neighbour search that took each of its paths (kPath* below)
 constexpr int kCounterWords = 96;
 constexpr int kIndefiniteCounter = 72;
 constexpr int kBeyondGrid = 73;
@@ -401,6 +402,26 @@ constexpr int kTicketB = 77;
 constexpr int kHeavyQueries = 78;
 constexpr int kLightQueries = 79;
 constexpr int kTicketP = 80;
+// The paths of knn_search_kernel (vgicp_preprocess.hip): every query keeps a mask of the ones it took, and a context
+// created with VGICP_DEBUG_PREP adds 1 to word kPathWord0 + bit for every bit set -- the number of queries that took
+// the path (vgicp_prepare_search_report, include/vgicp_hip_search_report.h, in this order).
+constexpr int kPathWord0 = 81;
+constexpr int kPathCount = 14;
+constexpr uint32_t kPathHome = 1u << 0;        // the query's own cell is its first candidates (has_home)
+constexpr uint32_t kPathCrowded = 1u << 1;     // an own cell holds K points but more than kHomePoints
+constexpr uint32_t kPathNoOwnCell = 1u << 2;   // no own cell on any level holds K points
+constexpr uint32_t kPathWindowIsK = 1u << 3;   // the opening window holds exactly K entries: bound from their maximum
+constexpr uint32_t kPathWholeScan = 1u << 4;   // no level's 27-cell block covers the ball: every point of the scan
+constexpr uint32_t kPathClipped = 1u << 5;     // the 27-cell block reaches over the grid's edge
+constexpr uint32_t kPathOpen2 = 1u << 6;       // a cell opened two levels down
+constexpr uint32_t kPathOpen1 = 1u << 7;       // a level-1 cell opened one level down
+constexpr uint32_t kPathLeaf = 1u << 8;        // a cell above the finest level measured
+constexpr uint32_t kPathFinest = 1u << 9;      // a finest cell measured
+constexpr uint32_t kPathCompacted = 1u << 10;  // the pool of waiting cells compacted
+constexpr uint32_t kPathSpilled = 1u << 11;    // no room in the pool even so: the cell measured instead of opened
+constexpr uint32_t kPathWaited = 1u << 12;     // candidates of a batch waited for room in the buffer
+constexpr uint32_t kPathReranked = 1u << 13;   // more than 56 entries survived the select: all-pairs ranking
+static_assert(kPathWord0 + kPathCount <= kCounterWords, "the path counts lie inside the counter block");
 // the prologue finds the deskew's segments itself (no launch for the bounds) for ordered state queues up to this many
 // states (8 bytes of LDS each) and sweeps up to this many workgroups of 256 points (a look-back slot each)
 constexpr uint32_t kFusedBoundsStatesMax = 4096;

@@ -922,6 +922,7 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
 
   uint32_t batches = 0, pops = 0, spills = 0;
+  uint32_t paths = 0;   // wave-uniform: the kPath* bits of the routes this query took (vgicp_device.h), reported under debug
 
   // squared distance to sorted point j and, from the same record, its original index
   auto dist2 = [&](uint32_t j, uint32_t& id) {
@@ -952,6 +953,7 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
   // (not when it is crowded -- thousands of returns in one finest cell next to the sensor: measuring all of them in
   // sorted order costs more insertions than the best-first search needs; 64: 270 us, 128 / 256: 250 us, no cap: 308 us)
   const bool has_home = enough != 0 && home_end - home_start <= kHomePoints;
+  paths |= has_home ? kPathHome : (enough != 0 ? kPathCrowded : kPathNoOwnCell);
 
   // The candidates start from up to 64 consecutive points of the sorted order around the query (inside home when there
   // is one): real points and usually near ones. The search skips the points it has measured here when it meets them
@@ -1001,6 +1003,7 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
     }
     kth = top >= 0x7F800000u ? INFINITY : (double)__builtin_bit_cast(float, top);
     if (cnt > 56u) {
+      paths |= kPathReranked;
       // hardly any room left (dozens of points within a 2^-12 band of the K-th distance): keep exactly the K nearest by
       // (distance, index) — all pairs, the one place besides the end where the order is made
       uint32_t rank = 0;
@@ -1033,6 +1036,7 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
     cnt = W;
     if (cnt > (uint32_t)K) tighten();
     else if (cnt == (uint32_t)K) {   // exactly K points in reach so far: their largest distance is the bound
+      paths |= kPathWindowIsK;
       double mx = (uint32_t)lane < cnt ? ld : 0.0;
       for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
       kth = uniform_f64(mx);
@@ -1050,12 +1054,15 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
       const uint32_t ahead = (uint32_t)__builtin_popcountll(todo & lanes_below);
       const bool now = pass && ahead < room;
       if (now) { cdv[cnt + ahead] = d; civ[cnt + ahead] = id; }
-      cnt += (uint32_t)__builtin_popcountll(__ballot(now));
+      const unsigned long long placed = __ballot(now);
+      cnt += (uint32_t)__builtin_popcountll(placed);
+      const bool left_waiting = (todo & ~placed) != 0ull;
+      if (left_waiting) paths |= kPathWaited;
       // ... but not after every batch: a select costs ~35 vector instructions, a candidate that slips in under a stale
       // bound ~2.  The bound is tightened when the buffer holds kKnnTightenAt entries, or when candidates of this
       // batch are still waiting for room (A/B on the 60 000-point frame sweep: after every batch 100.4 us; at 40 / 48 /
       // 56 / 64 entries 95.8 / 96.6 / 95.1 / 96.3; at 40 with 16 instead of 20 bits of the key: 94.7)
-      if (cnt > (uint32_t)K && (cnt >= kKnnTightenAt || (todo & ~__ballot(now)) != 0ull)) {
+      if (cnt > (uint32_t)K && (cnt >= kKnnTightenAt || left_waiting)) {
         wave_sync();   // (the lanes' mirror of the buffer is brought up to date only where somebody reads it)
         if ((uint32_t)lane < cnt) { ld = cdv[lane]; li = civ[lane]; }
         tighten();
@@ -1103,6 +1110,7 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
   int waiting = 0;
   // drop the waiting cells that the k-th distance has overtaken since they were pushed
   auto compact = [&]() {
+    paths |= kPathCompacted;
     const double limit = fmin(bound, kth);
     int kept = 0;
     for (int base = 0; base < waiting; base += 64) {
@@ -1145,12 +1153,17 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
     const unsigned long long covers = __ballot((lane < kLevels) & (bound <= r * r));
     level = covers ? __builtin_ctzll(covers) : kLevels;
   }
+  if (level == kLevels) paths |= kPathWholeScan;
   if (level < kLevels) {
     {
       const int top = kCoordMax >> level;
       const int x = (int)(cx >> level) + lane % 3 - 1, y = (int)(cy >> level) + (lane / 3) % 3 - 1,
                 z = (int)(cz >> level) + lane / 9 - 1;
       bool want = lane < 27 && x >= 0 && y >= 0 && z >= 0 && x <= top && y <= top && z <= top;
+      {  // (a block coordinate at 0 or at top: the lanes beyond it have dropped their cells -- decided on the scalar unit)
+        const int bx = (int)(cx >> level), by = (int)(cy >> level), bz = (int)(cz >> level);
+        if (bx == 0 || by == 0 || bz == 0 || bx == top || by == top || bz == top) paths |= kPathClipped;
+      }
       // Morton codes of the 27 cells without spreading any bits: the block's centre is the query's code shifted
       // (scalar), a step of +-1 along an axis is an increment / decrement of that axis' dilated digits (scalar
       // too), and every lane picks one of three per axis
@@ -1252,11 +1265,14 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
         if (waiting + incoming > kPool) {  // no room even so: measure this cell's points instead (still exact)
           measure = true;
           ++spills;
+          paths |= kPathSpilled;
         } else {
+          paths |= step == 2 ? kPathOpen2 : kPathOpen1;
           push(want, d2, cell_key(cm, l - step), cs, ce);
         }
       }
       if (measure) {
+        paths |= l > 0 ? kPathLeaf : kPathFinest;
         for (uint32_t base = start; base < end; base += 64u) {
           const uint32_t j = base + (uint32_t)lane;
           const bool valid = j < end;
@@ -1304,6 +1320,7 @@ __global__ __launch_bounds__(kSearchBlock) void knn_search_kernel(
       atomicAdd(&counters[5], pops);
       atomicMax(&counters[6], pops);
       if (level > kFineShift) atomicAdd(&counters[7], 1u);
+      for (uint32_t left = paths; left; left &= left - 1u) atomicAdd(&counters[kPathWord0 + __builtin_ctz(left)], 1u);
       if (debug >= 2) {  // developer histograms: cells taken, and wall time of this query (100 MHz clock)
         atomicAdd(&counters[8 + (pops / 8u < 31u ? pops / 8u : 31u)], 1u);
         const uint32_t us8 = (uint32_t)((wall_clock64() - t_begin) / 800u);
