@@ -77,6 +77,12 @@ RAYS_MAX_POSES = 64
 RAY_NO_RAY, RAY_OPEN, RAY_OWN, RAY_BEHIND, RAY_CONFIRMED, RAY_BLOCKED, RAY_NEAR = range(7)
 RAY_CLASS_NAMES = ("no_ray", "open", "own", "behind", "confirmed", "blocked", "near")
 
+# every symbol include/vgicp_hip_map_levels.h declares: likewise, four entry points in a library of their own
+MAP_LEVELS_EXPORTS = ("vgicp_map_levels_build", "vgicp_map_level_size", "vgicp_map_level_export", "vgicp_align_resident_levels")
+MAP_LEVELS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_levels.so")
+LEVELS_MAX = 4
+LEVEL_STAGES_MAX = 8
+
 # every symbol include/vgicp_hip_search_report.h declares: likewise, one entry point (a test hook) in a library of its own
 SEARCH_REPORT_EXPORTS = ("vgicp_prepare_search_report",)
 SEARCH_REPORT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_search_report.so")
@@ -193,6 +199,23 @@ def carve_params(margin: float = 0.0, max_range: float = 80.0, min_hits: int = 1
                  origin=(0.0, 0.0, 0.0)) -> CarveParams:
     return CarveParams((C.c_double * 3)(*[float(v) for v in origin]), float(margin), float(max_range), int(min_hits),
                        int(stride))
+
+
+class LevelsStats(C.Structure):
+    """vgicp_levels_stats (vgicp_hip_map_levels.h), 104 bytes."""
+    _fields_ = [("voxels", C.c_uint64 * (LEVELS_MAX + 1)), ("slots", C.c_uint64 * (LEVELS_MAX + 1)), ("levels", C.c_int32),
+                ("launches", C.c_int32), ("seconds", C.c_double), ("device_seconds", C.c_double)]
+
+
+@dataclass
+class LevelsBuild:
+    """What Context.map_levels_build returns: voxels and slots per level ([0]: the map), and how the call ran."""
+    voxels: list
+    slots: list
+    levels: int
+    launches: int
+    seconds: float
+    device_seconds: float
 
 
 class RayParams(C.Structure):
@@ -357,6 +380,16 @@ def load_library() -> C.CDLL:
                                              C.POINTER(RayStats)]
         rays.vgicp_rays_resident.restype = C.c_int
         lib.vgicp_rays_resident = rays.vgicp_rays_resident
+    # the map levels' library, likewise
+    if os.path.exists(MAP_LEVELS_LIB_PATH):
+        levels = C.CDLL(MAP_LEVELS_LIB_PATH, mode=C.RTLD_GLOBAL)
+        levels.vgicp_map_levels_build.argtypes = [vp, C.c_int, C.POINTER(LevelsStats)]
+        levels.vgicp_map_level_size.argtypes = [vp, C.c_int, C.POINTER(sz), C.POINTER(sz), dp]
+        levels.vgicp_map_level_export.argtypes = [vp, C.c_int, sz, ip, dp, dp, C.POINTER(C.c_uint64), C.POINTER(sz)]
+        levels.vgicp_align_resident_levels.argtypes = [vp, dp, sz, ip, C.POINTER(Params), dp, C.POINTER(Stats)]
+        for name in MAP_LEVELS_EXPORTS:
+            getattr(levels, name).restype = C.c_int
+            setattr(lib, name, getattr(levels, name))
     # the neighbour search's path report, likewise
     if os.path.exists(SEARCH_REPORT_LIB_PATH):
         report = C.CDLL(SEARCH_REPORT_LIB_PATH, mode=C.RTLD_GLOBAL)
@@ -1018,6 +1051,68 @@ class Context:
         r, m = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.vgicp_map_carve_totals(self._h, C.byref(r), C.byref(m)))
         return int(r.value), int(m.value)
+
+    # -- the map's coarser levels (vgicp_hip_map_levels.h) --
+    def map_levels_build(self, levels: int) -> "LevelsBuild":
+        """vgicp_map_levels_build: ask for `levels` levels (0 .. LEVELS_MAX; 0 releases them) and bring them up to date."""
+        st = LevelsStats()
+        self._check(self._lib.vgicp_map_levels_build(self._h, int(levels), C.byref(st)))
+        return LevelsBuild(list(st.voxels), list(st.slots), st.levels, st.launches, st.seconds, st.device_seconds)
+
+    def map_level_size(self, level: int):
+        """(voxels, table slots, voxel size) of a level; level 0 is the map."""
+        v, s, h = C.c_size_t(), C.c_size_t(), C.c_double()
+        self._check(self._lib.vgicp_map_level_size(self._h, int(level), C.byref(v), C.byref(s), C.byref(h)))
+        return v.value, s.value, h.value
+
+    def map_level_export(self, level: int):
+        """(keys, means, covs, counts) of every voxel of a level, sorted by key as map_export sorts."""
+        n = self.map_level_size(level)[0]
+        keys = np.zeros((n, 3), dtype=np.int32)
+        means, covs = np.zeros((n, 3)), np.zeros((n, 9))
+        counts = np.zeros(n, dtype=np.uint64)
+        w = C.c_size_t()
+        self._check(self._lib.vgicp_map_level_export(self._h, int(level), n, keys.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     _dp(means), _dp(covs), counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                     C.byref(w)))
+        assert w.value == n, (w.value, n)
+        order = np.lexsort(keys.T)
+        return keys[order], means[order], covs[order], counts[order]
+
+    def align_resident_levels(self, guess, schedule, params, allow_degenerate: bool = False):
+        """vgicp_align_resident_levels: the resident scan in stages.  schedule: the level of every stage; params: per
+        stage a dict with max_iteration, translation_sq_threshold, cosine_threshold and optionally chunk_iterations and
+        flags (or one dict for all stages).  Returns (pose 4x4, [AlignResult per stage])."""
+        schedule = [int(l) for l in schedule]
+        k = len(schedule)
+        per = [params] * k if isinstance(params, dict) else list(params)
+        if len(per) != k:
+            raise ValueError("schedule / params disagree in length")
+        ps = (Params * max(k, 1))(*[Params(int(p["max_iteration"]), int(p.get("chunk_iterations", 0)),
+                                           float(p["translation_sq_threshold"]), float(p["cosine_threshold"]),
+                                           int(p.get("flags", 0)), 0) for p in per])
+        caps = [max(int(p["max_iteration"]), 1) for p in per]
+        counts = [np.zeros(c, dtype=np.uint64) for c in caps]
+        neqs = [np.zeros((c, 27)) for c in caps]
+        kms = [np.zeros(c + 1, dtype=np.float32) for c in caps]
+        sts = (Stats * max(k, 1))()
+        for i in range(k):
+            sts[i].corr_count = counts[i].ctypes.data_as(C.POINTER(C.c_uint64))
+            sts[i].normal_eq = _dp(neqs[i])
+            sts[i].kernel_ms = kms[i].ctypes.data_as(C.POINTER(C.c_float))
+        lv = (C.c_int32 * max(k, 1))(*schedule)
+        g = pose_to_abi(guess)
+        out = np.zeros(16)
+        rc = self._lib.vgicp_align_resident_levels(self._h, _dp(g), k, lv, ps, _dp(out), sts)
+        self._check(rc, (ERR_DEGENERATE,) if allow_degenerate else ())
+        stages = []
+        for i in range(k):
+            st, it = sts[i], sts[i].iterations
+            stages.append(AlignResult(pose=None, iterations=it, converged=bool(st.converged), world_size=st.world_size,
+                                      launches=st.launches, seconds=st.seconds, device_seconds=st.device_seconds,
+                                      corr_count=counts[i][:it].copy(), normal_eq=neqs[i][:it].copy(), status=rc,
+                                      message=self.last_error() if rc else ""))
+        return pose_from_abi(out), stages
 
     def rays_resident(self, poses, params, per_point: bool = True) -> "RayReport":
         """vgicp_rays_resident (vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at `poses`

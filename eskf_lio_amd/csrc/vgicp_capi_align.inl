@@ -23,7 +23,7 @@ IterArgs base_args(const vgicp_ctx* ctx) {
   // the dense record copy (tables far beyond the caches' reach): used where it is current — the aligns that reach the
   // loop after a persistent launch has rebuilt it, or run_align's own ensure_dense
   a.dense = (ctx->d_dense && ctx->dense_version == ctx->map_version && ctx->slots >= ctx->dense_slots_threshold &&
-             ctx->dense_slots_threshold != 0) ? ctx->d_dense : nullptr;
+             ctx->dense_slots_threshold != 0 && ctx->view_level == 0) ? ctx->d_dense : nullptr;   // a level never uses it
   return a;
 }
 
@@ -122,6 +122,7 @@ int reset_persistent_exchange(vgicp_ctx* ctx) {
 // measured 6.7 ns per random 128-byte line and CU out of a 5-10 GB table against 5.4 ns out of 2.5 GB, and a cliff for
 // more lines in flight above 4 GB.  Smaller tables (C2: 512 MB) never use it.  VGICP_DENSE_SLOTS (read when the context is created) overrides the threshold, 0 = never.
 bool large_table(const vgicp_ctx* ctx) {
+  if (ctx->view_level != 0) return false;   // a stage of vgicp_align_resident_levels: the dense copy is the map's, not a level's
   return ctx->table && ctx->dense_slots_threshold != 0 && ctx->slots >= ctx->dense_slots_threshold && ctx->voxels > 0;
 }
 bool wants_dense(const vgicp_ctx* ctx, uint32_t n_upper) { return large_table(ctx) && !one_point_per_thread(n_upper, ctx->persist_grid); }

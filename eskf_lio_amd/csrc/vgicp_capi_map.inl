@@ -142,6 +142,7 @@ int vgicp_map_reset(vgicp_ctx* ctx, double voxel_size, size_t capacity_hint) {
   VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->table.reset();
   ctx->slots = ctx->voxels = ctx->tombstones = 0;
+  for (auto& l : ctx->level) l = vgicp_ctx::MapLevel{};   // the levels empty with the map; levels_requested stays
   ctx->gated_points = ctx->gated_refused = 0;
   ctx->carve_rays = ctx->carve_removed = 0;
   ++ctx->map_version;

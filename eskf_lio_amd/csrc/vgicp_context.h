@@ -34,6 +34,7 @@
 #include "../../include/vgicp_hip_map_carve.h"
 #include "../../include/vgicp_hip_map_rays.h"
 #include "../../include/vgicp_hip_search_report.h"
+#include "../../include/vgicp_hip_map_levels.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -41,6 +42,7 @@
 #include "vgicp_resident_plan.h"
 #include "vgicp_map_plan.h"
 #include "vgicp_points_plan.h"
+#include "vgicp_levels_plan.h"
 
 using namespace vgicp;
 
@@ -497,6 +499,21 @@ struct vgicp_ctx {
                                      // first call, anew only when the table's slot count has changed
   uint64_t ray_bits_slots = 0;       // the slot count d_ray_bits was sized for
   PinnedBuf<char> h_rays;            // pinned, grow-only: the poses on their way in, the counts and the planes on their way out
+  // the map's coarser levels (include/vgicp_hip_map_levels.h): nothing of this is allocated while levels_requested == 0.
+  // level[l - 1] is level l: an open-addressing table like the map's, never with a dense copy; version: the map_version
+  // it was built at (0: never, or emptied), checked by every call that reads a level (ensure_levels, as ensure_dense)
+  struct MapLevel {
+    DeviceBuf<VoxelRecord> table;
+    uint64_t slots = 0;
+    uint64_t voxels = 0;             // known once level_counts_pending is false
+    uint64_t version = 0;
+  };
+  int levels_requested = 0;
+  MapLevel level[VGICP_LEVELS_MAX];
+  DeviceBuf<uint32_t> d_level_counts;    // per level {voxels, probe sequences exhausted}
+  PinnedBuf<uint32_t> h_level_counts;    // pinned: the same, copied behind every rebuild
+  bool level_counts_pending = false;     // that copy is enqueued and nobody has waited for it yet
+  int view_level = 0;                    // != 0 only inside a stage of vgicp_align_resident_levels: resident_view() is that level's
   // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
   // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
@@ -549,7 +566,7 @@ struct vgicp_ctx {
 };
 
 // The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip, vgicp_map_carve.hip, vgicp_map_rays.hip,
-// vgicp_search_report.hip): was
+// vgicp_search_report.hip, vgicp_map_levels.hip): was
 // this context made by the build that reads it?  Reads the stamp only; each library refuses in its own words.
 inline bool same_build(const vgicp_ctx* ctx) { return ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx)); }
 
@@ -567,6 +584,11 @@ inline AlignFacts call_facts(AlignCall call, uint32_t flags, int max_iteration) 
 inline bool robust_on(const vgicp_ctx* ctx) { return ctx->robust_kernel != 0 || ctx->robust_gate_micro != 0; }
 // The resident scan and the voxel map as a launch sees them: the ONE place where an argument struct's view is filled.
 inline vgicp::ResidentView resident_view(const vgicp_ctx* ctx) {
+  if (ctx->view_level != 0) {   // a stage of vgicp_align_resident_levels: the level is just another (table, mask, voxel_size)
+    const vgicp_ctx::MapLevel& l = ctx->level[ctx->view_level - 1];
+    return vgicp::ResidentView{ctx->d_scan, ctx->stride, ctx->n, (uint32_t)(l.slots - 1), l.table,
+                               level_voxel_size(ctx->voxel_size, ctx->view_level)};
+  }
   return vgicp::ResidentView{ctx->d_scan, ctx->stride, ctx->n, (uint32_t)(ctx->slots - 1), ctx->table, ctx->voxel_size};
 }
 // What a launch's asym_dev is (with scan_seq = ctx->scan_seq): word 2 of the insertion's counter block, the symmetry
@@ -690,6 +712,13 @@ int rays_resident(vgicp_ctx* ctx, const double* poses, size_t n_poses, const vgi
                   const vgicp_ray_outputs* per_point, vgicp_ray_counts* counts, vgicp_ray_stats* stats);
 // The entry point of include/vgicp_hip_search_report.h behind libvgicp_hip_search_report.so, likewise (vgicp_capi_prepare.inl).
 int prepare_search_report(vgicp_ctx* ctx, vgicp_search_report* report);
+// The entry points of include/vgicp_hip_map_levels.h behind libvgicp_hip_map_levels.so, likewise (vgicp_capi_map_levels.inl).
+int map_levels_build(vgicp_ctx* ctx, int levels, vgicp_levels_stats* stats);
+int map_level_size(vgicp_ctx* ctx, int level, size_t* voxels, size_t* table_slots, double* voxel_size);
+int map_level_export(vgicp_ctx* ctx, int level, size_t capacity, int32_t* keys, double* means, double* covs, uint64_t* counts,
+                     size_t* written);
+int align_resident_levels(vgicp_ctx* ctx, const double guess[16], size_t stages, const int32_t* levels, const vgicp_params* params,
+                          double out_pose[16], vgicp_stats* stats);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

@@ -375,6 +375,12 @@ hipError_t launch_match(hipStream_t s, const double* points_aos, const double* c
                         uint32_t* block_counts, uint32_t* total, double* src_points,
                         double* src_covs, double* map_points, double* map_covs, uint64_t* src_index);
 uint32_t match_blocks(uint32_t n);
+// ---- vgicp_levels.hip: a coarser level of the map (include/vgicp_hip_map_levels.h) ----
+// Level l in `coarse` (coarse_slots all EMPTY before, a power of two, at least twice the finer level's voxels) from level
+// l-1 in `fine`: the CLAIM launch (one thread per finer slot) and the FILL launch (eight lanes per slot of the level).
+// counters[0] += voxels of the level, counters[1] += probe sequences exhausted.
+hipError_t launch_level_build(hipStream_t s, const VoxelRecord* fine, uint64_t fine_slots, VoxelRecord* coarse,
+                              uint64_t coarse_slots, uint32_t* counters);
 
 // ---- vgicp_mapupdate.hip: LocalMap::updateLocalMap's insert / evict loops on the device ----
 // Scratch the insertion needs for n points (bytes), and the insertion itself: transform, find-or-claim

@@ -104,5 +104,22 @@ __device__ __forceinline__ const VoxelRecord* find_voxel(const VoxelRecord* tabl
   return nullptr;
 }
 
+// The claim of the table's two-launch writes (vgicp_table.hip has the scheme): walk the probe sequence with ONE
+// compare-and-swap per slot (EMPTY -> LOCKED).  -> the slot with kClaimFresh set when it was won, the slot alone when an
+// earlier launch left this key there, or kClaimFailed.  The keys that claim within ONE launch must be unique.
+__device__ __forceinline__ uint32_t claim_slot(VoxelRecord* table, uint32_t mask, int32_t kx, int32_t ky, int32_t kz) {
+  uint32_t slot = voxel_hash(kx, ky, kz) & mask;
+  for (uint32_t probes = 0; probes <= mask; ++probes) {
+    VoxelRecord* rec = table + slot;
+    int32_t seen = SLOT_EMPTY;
+    if (__hip_atomic_compare_exchange_strong(&rec->state, &seen, SLOT_LOCKED, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT))
+      return slot | kClaimFresh;
+    if (seen == SLOT_FULL && rec->key[0] == kx && rec->key[1] == ky && rec->key[2] == kz) return slot;
+    slot = (slot + 1) & mask;
+  }
+  return kClaimFailed;
+}
+
 }  // namespace
 }  // namespace vgicp

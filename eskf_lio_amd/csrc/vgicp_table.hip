@@ -33,19 +33,7 @@ __global__ void table_clear_kernel(VoxelRecord* table, uint64_t slots) {
 // the XCD's L2 back) 5.5 ms.
 // kClaimFresh / kClaimFailed: vgicp_device.h (the raw-point store reads the rehash's scratch words too)
 
-__device__ __forceinline__ uint32_t claim_slot(VoxelRecord* table, uint32_t mask, int32_t kx, int32_t ky, int32_t kz) {
-  uint32_t slot = voxel_hash(kx, ky, kz) & mask;
-  for (uint32_t probes = 0; probes <= mask; ++probes) {
-    VoxelRecord* rec = table + slot;
-    int32_t seen = SLOT_EMPTY;
-    if (__hip_atomic_compare_exchange_strong(&rec->state, &seen, SLOT_LOCKED, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT))
-      return slot | kClaimFresh;
-    if (seen == SLOT_FULL && rec->key[0] == kx && rec->key[1] == ky && rec->key[2] == kz) return slot;
-    slot = (slot + 1) & mask;
-  }
-  return kClaimFailed;
-}
+// claim_slot: vgicp_device_fn.h (the map levels' claim launch, vgicp_levels.hip, walks the same way)
 
 __global__ __launch_bounds__(256) void upsert_claim_kernel(VoxelRecord* table, uint32_t mask, uint32_t n,
                                                            const int32_t* __restrict__ keys, uint32_t* __restrict__ claimed,

@@ -567,6 +567,10 @@ class Odometry:
 
     def __init__(self, config: dict, backend):
         self.backend = backend
+        # optional key registration.coarse_to_fine (vgicp_hip_map_levels.h): the levels live beside the device's map
+        if coarse_to_fine_of(config) is not None and not getattr(backend, "supports_coarse_to_fine", False):
+            raise ValueError("registration.coarse_to_fine needs a backend that keeps the scan and the map on the device "
+                             "(DeviceBackend, tools/replay.py --resident)")
         # optional key local_map.insert_gate (vgicp_hip_map_gated.h): only a backend that inserts the resident scan on the
         # device can keep the gated points out of the map
         if insert_gate_of(config) > 0.0 and not getattr(backend, "supports_insert_gate", False):
@@ -686,6 +690,29 @@ def carve_of(config: dict):
     return out
 
 
+def coarse_to_fine_of(config: dict):
+    """registration.coarse_to_fine: absent = off (None), else (levels, coarse): the level of every stage (each 0 .. 4, at
+    most 8 stages, e.g. [3, 2, 1, 0]) and what every stage but the last stops by — max_iteration (30),
+    translation_sq_threshold (1e-4), cosine_threshold (0.999); the last stage takes the registration's own values."""
+    c = config["registration"].get("coarse_to_fine")
+    if c is None:
+        return None
+    unknown = set(c) - {"levels", "coarse"}
+    if unknown or "levels" not in c:
+        raise ValueError(f"registration.coarse_to_fine takes levels (required) and coarse; got {sorted(c)}")
+    levels = [int(l) for l in c["levels"]]
+    if not 1 <= len(levels) <= 8 or any(l < 0 or l > 4 for l in levels):
+        raise ValueError("registration.coarse_to_fine.levels: 1 .. 8 stages, each level 0 .. 4")
+    k = dict(c.get("coarse") or {})
+    if set(k) - {"max_iteration", "translation_sq_threshold", "cosine_threshold"}:
+        raise ValueError(f"registration.coarse_to_fine.coarse takes max_iteration, translation_sq_threshold, cosine_threshold; got {sorted(k)}")
+    coarse = dict(max_iteration=int(k.get("max_iteration", 30)), translation_sq_threshold=float(k.get("translation_sq_threshold", 1e-4)),
+                  cosine_threshold=float(k.get("cosine_threshold", 0.999)))
+    if coarse["max_iteration"] < 0:
+        raise ValueError("registration.coarse_to_fine.coarse.max_iteration must be >= 0")
+    return levels, coarse
+
+
 class GpuBackend:
     """The MI355X path behind the C++ mirror of the reference's classes (eskf_lio_amd/host.py).  It hands the map a
     fresh host cloud every frame (arrays in, arrays out), never the cloud process() stamped, so the map update is not the
@@ -763,6 +790,7 @@ class DeviceBackend:
     (vgicp_rays_resident) at every aligned pose, before the map update; its class totals add up in ray_totals."""
     supports_insert_gate = True
     supports_carve = True
+    supports_coarse_to_fine = True
 
     def __init__(self, config: dict, device=0):
         """device: one ordinal, or a list of ordinals for ONE multi-device context (vgicp_create_multi)."""
@@ -777,8 +805,15 @@ class DeviceBackend:
                              "in a multi-device one")
         if self.carve is not None and self.carve["origin"] is None:
             self.carve["origin"] = tuple(float(v) for v in np.asarray(config["lidar_extrinsic"], dtype=np.float64)[:3, 3])
+        self.coarse_to_fine = coarse_to_fine_of(config)
+        if self.coarse_to_fine is not None and isinstance(device, (list, tuple)):
+            raise ValueError("registration.coarse_to_fine needs a single-device context: the resident scan of a device is a "
+                             "shard in a multi-device one")
         self.ctx = capi.Context(device)
         self.ctx.map_reset(lm["voxel_size"], 0)
+        self.stage_iterations: List[List[int]] = []         # per align in stages: the rounds of every stage
+        if self.coarse_to_fine is not None:
+            self.ctx.map_levels_build(max(self.coarse_to_fine[0]))   # the count; the levels follow the map lazily
         self.cap = int(lm["max_num_points_per_voxel"])
         self.gate = (lm["translation_sq_threshold"], lm["cosine_threshold"])
         self.insert_gate = insert_gate_of(config)
@@ -837,12 +872,24 @@ class DeviceBackend:
         self.kept.append(kept)
         return None, None                                   # the prepared scan is on the device
 
+    def _align(self, guess):
+        """vgicp_align_resident, or with registration.coarse_to_fine vgicp_align_resident_levels: every stage but the last
+        with the coarse thresholds, the last with the registration's own -> (pose, the last stage's result)."""
+        fine = dict(max_iteration=self.reg["max_iteration"], translation_sq_threshold=self.reg["translation_sq_threshold"],
+                    cosine_threshold=self.reg["cosine_threshold"])
+        if self.coarse_to_fine is None:
+            r = self.ctx.align_resident(guess, fine["max_iteration"], fine["translation_sq_threshold"], fine["cosine_threshold"])
+            return r.pose, r
+        levels, coarse = self.coarse_to_fine
+        pose, stages = self.ctx.align_resident_levels(guess, levels, [coarse] * (len(levels) - 1) + [fine])
+        self.stage_iterations.append([s.iterations for s in stages])
+        return pose, stages[-1]
+
     def align(self, points, covs, guess):
         self._scale_from_quantile(guess)
-        r = self.ctx.align_resident(guess, self.reg["max_iteration"], self.reg["translation_sq_threshold"],
-                                    self.reg["cosine_threshold"])
+        pose, r = self._align(guess)
         self.iterations.append(r.iterations)
-        return r.pose
+        return pose
 
     def align_with_prior(self, points, covs, guess, information):
         """The align with the prior (guess, information) and the posterior information in the filter's chart,
@@ -852,14 +899,12 @@ class DeviceBackend:
         self._scale_from_quantile(guess)
         self.ctx.set_pose_prior(guess, information)
         try:
-            r = self.ctx.align_resident(guess, self.reg["max_iteration"], self.reg["translation_sq_threshold"],
-                                        self.reg["cosine_threshold"])
+            pose, r = self._align(guess)
         finally:
             self.ctx.clear_pose_prior()
         self.iterations.append(r.iterations)
         self.converged.append(bool(r.converged))
-        return r.pose, capi.posterior_information(self.ctx.evaluate_resident([r.pose])[0].normal_eq, guess, r.pose,
-                                                  information)
+        return pose, capi.posterior_information(self.ctx.evaluate_resident([pose])[0].normal_eq, guess, pose, information)
 
     def update_map(self, points, covs, transform, initialize):
         if self.ray_params is not None and self.prev is not None:   # (the first frame is not aligned: its map is empty)

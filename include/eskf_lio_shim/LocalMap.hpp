@@ -41,6 +41,7 @@
 #include "../vgicp_hip_map_gated.h"
 #include "../vgicp_hip_map_carve.h"
 #include "../vgicp_hip_map_rays.h"
+#include "../vgicp_hip_map_levels.h"
 
 // The raw-point store's entry points (vgicp_hip_map_points.h, and vgicp_set_option for its option) are referenced
 // weakly, so a program that links a stand-in of the C ABI without them (tests/native/shadow_stress.cpp) still links: a
@@ -60,6 +61,8 @@
 // ... and the ray report's (vgicp_hip_map_rays.h, in libvgicp_hip_map_rays.so): without that library rayReport and rayCounts
 // say available == false.
 #pragma weak vgicp_rays_resident
+// ... and the map levels' (vgicp_hip_map_levels.h, in libvgicp_hip_map_levels.so): without that library setLevels(n > 0) refuses.
+#pragma weak vgicp_map_levels_build
 #include "ShimTypes.hpp"
 #include "ShimSupport.hpp"
 #include "ResidentScan.hpp"
@@ -111,6 +114,10 @@ struct LocalMapConfig
   // min_hits, stride, origin} (optional; carving is off unless local_map.carve is there, and max_range is required then).
   bool carve = false;
   vgicp_carve_params carveParams = {{0.0, 0.0, 0.0}, 0.0, 0.0, 1, 1};
+  // > 0: the device keeps the map again at 2, 4, .. 2^levels times the voxel size (LocalMap::setLevels;
+  // include/vgicp_hip_map_levels.h has the rule), for ICP::alignCoarseToFine.  YAML: the largest level of
+  // registration.coarse_to_fine.levels (optional; no levels unless it is there).
+  int levels = 0;
 };
 
 class LocalMap
@@ -195,6 +202,7 @@ public:
     storeRawPointsOnDevice();
     if (config.insertGate != 0.0) {setInsertGate(config.insertGate);}
     if (config.carve) {setCarve(config.carveParams);}
+    if (config.levels != 0) {setLevels(config.levels);}
   }
 
   ~LocalMap() {shadowStop();}
@@ -251,6 +259,17 @@ public:
         const std::vector<double> origin = k["origin"].as<std::vector<double>>();
         if (origin.size() != 3) {throw std::invalid_argument("local_map.carve.origin: three numbers");}
         for (int a = 0; a < 3; ++a) {c.carveParams.origin[a] = origin[a];}
+      }
+    }
+    // the schedule is the registration's (ICP reads it); the map keeps the levels it names
+    if (config["registration"].IsDefined() && config["registration"]["coarse_to_fine"].IsDefined() &&
+      config["registration"]["coarse_to_fine"]["levels"].IsDefined())
+    {
+      for (const int l : config["registration"]["coarse_to_fine"]["levels"].as<std::vector<int>>()) {
+        if (l < 0 || l > VGICP_LEVELS_MAX) {
+          throw std::invalid_argument("registration.coarse_to_fine.levels: each 0 .. VGICP_LEVELS_MAX");
+        }
+        c.levels = std::max(c.levels, l);
       }
     }
     return c;
@@ -554,6 +573,24 @@ public:
     }
     return t;
   }
+
+  // The map's coarser levels (include/vgicp_hip_map_levels.h): from now on the device keeps the map again at 2, 4, ..
+  // 2^levels times its voxel size and brings the levels up to date whenever ICP::alignCoarseToFine reads them after the
+  // map has changed (two launches per level, nothing when the map did not change).  0 releases them.  None of the
+  // drop-in calls changes its route.
+  void setLevels(int levels)
+  {
+    if (levels < 0 || levels > VGICP_LEVELS_MAX) {
+      throw std::invalid_argument("LocalMap::setLevels: levels must be 0 .. VGICP_LEVELS_MAX");
+    }
+    if (!vgicp_map_levels_build) {
+      if (levels == 0) {return;}
+      throw std::runtime_error("LocalMap::setLevels: the linked vgicp module has no map levels (libvgicp_hip_map_levels.so)");
+    }
+    shim::check(ctx_, vgicp_map_levels_build(ctx_, levels, nullptr), "vgicp_map_levels_build");
+    levels_ = levels;
+  }
+  int levels() const {return levels_;}
 
   // The ray report (include/vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at a pose,
   // read-only — which returns appeared in front of the map's surface (VGICP_RAY_BEHIND), which rays the map blocks
@@ -875,6 +912,7 @@ private:
   double insertGate_ = 0.0;          // > 0: the resident route inserts through the gated entry (setInsertGate)
   uint64_t plainFrames_ = 0;
   bool carve_ = false;               // the resident route carves before it inserts (setCarve)
+  int levels_ = 0;                   // coarser levels the device keeps of this map (setLevels)
   vgicp_carve_params carveParams_ = {{0.0, 0.0, 0.0}, 0.0, 0.0, 1, 1};
   std::thread shadowThread_;
   mutable std::mutex shadowMutex_;

@@ -21,6 +21,9 @@
 // setPrior / clearPrior / alignWithPrior / posteriorInformation: a Gaussian prior on the pose in every round of the align
 // (vgicp_hip_prior.h) — the pose block of the filter's covariance, so that the pose returned is the MAP estimate and
 // ErrorStateKF::update can run as an iterated update (INTEGRATION.md has the patch).  No prior set: align() as ever.
+// alignCoarseToFine / the optional keys registration.coarse_to_fine.{levels, coarse}: the cloud registered in stages against
+// the map's coarser levels (vgicp_hip_map_levels.h; LocalMap::setLevels keeps them), each stage from the pose of the one
+// before it — converges from guesses several voxels off, where align() settles in a neighbouring voxel.
 // pointReport / robustScaleFromQuantile: a cloud at a pose, point by point (vgicp_hip_points.h) — matched or not, |e|^2,
 // d^2, the weight this ICP's robust settings give the point — and order statistics of d^2 to choose a scale or gate by.
 #ifndef ESKF_LIO_SHIM_REGISTRATION_HPP_
@@ -41,6 +44,7 @@
 #include "../vgicp_hip_robust.h"
 #include "../vgicp_hip_prior.h"
 #include "../vgicp_hip_points.h"
+#include "../vgicp_hip_map_levels.h"
 
 // referenced weakly, as LocalMap.hpp references the raw-point store's entry points: a program that links a stand-in of
 // the C ABI without them, or that does not link libvgicp_hip_prior.so beside libvgicp_hip.so, still links, and
@@ -49,6 +53,8 @@
 #pragma weak vgicp_pose_prior_chart
 // ... and libvgicp_hip_points.so's: ICP::pointReport says so
 #pragma weak vgicp_points_resident
+// ... and libvgicp_hip_map_levels.so's: ICP::alignCoarseToFine says so
+#pragma weak vgicp_align_resident_levels
 
 namespace ESKF_LIO
 {
@@ -84,6 +90,13 @@ struct RegistrationConfig
   int robustKernel = VGICP_ROBUST_NONE;
   double robustScale = 1.0;   // c, in the library's regularised units (~0.1, not ~3)
   double robustGate = 0.0;    // gate on d^2; 0 = none
+  // coarse to fine (vgicp_hip_map_levels.h; not in the reference's file): registration.coarse_to_fine.levels, the level of
+  // every stage, e.g. [3, 2, 1, 0], and registration.coarse_to_fine.coarse.{max_iteration, translation_sq_threshold,
+  // cosine_threshold} for every stage but the last, which takes the three values above
+  std::vector<int> coarseToFineLevels;
+  int coarseMaxIteration = 30;
+  double coarseTranslationSquaredThreshold = 1.0e-4;
+  double coarseCosineThreshold = 0.999;
 
   // registration.robust_kernel: none | huber | cauchy
   static int robustKernelFromName(const std::string & name)
@@ -119,6 +132,9 @@ public:
     , chunkIterations_(config.chunkIterations)
   {
     setRobust(config.robustKernel, config.robustScale, config.robustGate);
+    setCoarseToFine(
+      config.coarseToFineLevels, config.coarseMaxIteration, config.coarseTranslationSquaredThreshold,
+      config.coarseCosineThreshold);
   }
 
 #if defined(ESKF_LIO_SHIM_HAVE_YAML)
@@ -136,8 +152,108 @@ public:
     if (reg["robust_scale"].IsDefined()) {c.robustScale = reg["robust_scale"].as<double>();}
     if (reg["gate"].IsDefined()) {c.robustGate = reg["gate"].as<double>();}
     setRobust(c.robustKernel, c.robustScale, c.robustGate);
+    if (reg["coarse_to_fine"].IsDefined()) {
+      const YAML::Node ctf = reg["coarse_to_fine"];
+      if (ctf["levels"].IsDefined()) {c.coarseToFineLevels = ctf["levels"].as<std::vector<int>>();}
+      const YAML::Node coarse = ctf["coarse"];
+      if (coarse.IsDefined()) {
+        if (coarse["max_iteration"].IsDefined()) {c.coarseMaxIteration = coarse["max_iteration"].as<int>();}
+        if (coarse["translation_sq_threshold"].IsDefined()) {
+          c.coarseTranslationSquaredThreshold = coarse["translation_sq_threshold"].as<double>();
+        }
+        if (coarse["cosine_threshold"].IsDefined()) {c.coarseCosineThreshold = coarse["cosine_threshold"].as<double>();}
+      }
+      setCoarseToFine(
+        c.coarseToFineLevels, c.coarseMaxIteration, c.coarseTranslationSquaredThreshold, c.coarseCosineThreshold);
+    }
   }
 #endif
+
+  // The schedule alignCoarseToFine(cloud, map, guess) walks and what every stage but the last stops by (the last stage
+  // takes this ICP's own three values, as align() does).  Throws std::invalid_argument for anything the library would
+  // refuse, and changes nothing then.  An empty schedule: alignCoarseToFine without one is align().
+  void setCoarseToFine(
+    const std::vector<int> & levels, int coarseMaxIteration = 30, double coarseTranslationSquaredThreshold = 1.0e-4,
+    double coarseCosineThreshold = 0.999)
+  {
+    checkSchedule(levels);
+    if (coarseMaxIteration < 0) {throw std::invalid_argument("ICP::setCoarseToFine: coarse max_iteration < 0");}
+    schedule_ = levels;
+    coarseMaxIteration_ = coarseMaxIteration;
+    coarseTranslationSquaredThreshold_ = coarseTranslationSquaredThreshold;
+    coarseCosineThreshold_ = coarseCosineThreshold;
+  }
+  const std::vector<int> & coarseToFineLevels() const {return schedule_;}
+
+  // One stage of the last alignCoarseToFine.
+  struct StageStats
+  {
+    int level = 0;
+    Stats stats;
+  };
+
+  // Registers `cloud` in stages (vgicp_align_resident_levels): stage i against level schedule[i] of the map, from the pose
+  // stage i - 1 returned (stage 0: from guess); every stage but the last with the coarse thresholds, the last with this
+  // ICP's own.  The map must keep the levels the schedule names (LocalMap::setLevels; the YAML constructors of both classes
+  // read the same key).  The cloud is the resident scan when it still is what CloudPreprocessor::process left on the
+  // device (as alignHypotheses decides it), else ONE upload of it.  Robust settings and prior apply to every stage.
+  // lastStats() describes the last stage, lastStages() all of them.
+  Isometry3d alignCoarseToFine(
+    const PointCloud & cloud, const LocalMap & localMap, const Isometry3d & guess, const std::vector<int> & schedule)
+  {
+    checkSchedule(schedule);
+    if (schedule.empty()) {throw std::invalid_argument("ICP::alignCoarseToFine: the schedule is empty");}
+    if (!vgicp_align_resident_levels) {
+      throw std::runtime_error(
+              "ICP::alignCoarseToFine: the linked vgicp module has no vgicp_align_resident_levels (libvgicp_hip_map_levels.so)");
+    }
+    vgicp_ctx * ctx = localMap.context();
+    applyRobust(ctx);
+    applyPrior(ctx);
+    lastUsedResidentScan_ = residentScanOrUpload(ctx, cloud, "alignCoarseToFine");
+    shim::TraceScope tsCall(shim::Trace::AlignCall);
+    const size_t stages = schedule.size();
+    std::vector<int32_t> levels(schedule.begin(), schedule.end());
+    std::vector<vgicp_params> params(stages, paramsOf());
+    for (size_t i = 0; i + 1 < stages; ++i) {
+      params[i].max_iteration = coarseMaxIteration_;
+      params[i].translation_sq_threshold = coarseTranslationSquaredThreshold_;
+      params[i].cosine_threshold = coarseCosineThreshold_;
+    }
+    std::vector<std::vector<uint64_t>> counts(stages);
+    std::vector<vgicp_stats> stats(stages);
+    for (size_t i = 0; i < stages; ++i) {
+      counts[i].assign(static_cast<size_t>(params[i].max_iteration > 0 ? params[i].max_iteration : 1), 0);
+      stats[i] = vgicp_stats{};
+      stats[i].corr_count = counts[i].data();
+    }
+    double pose[16];
+    const int rc = vgicp_align_resident_levels(
+      ctx, shim::poseData(guess), stages, levels.data(), params.data(), pose, stats.data());
+    shim::check(ctx, rc, "vgicp_align_resident_levels");
+    lastStages_.assign(stages, StageStats{});
+    for (size_t i = 0; i < stages; ++i) {
+      StageStats & s = lastStages_[i];
+      s.level = schedule[i];
+      s.stats.iterations = stats[i].iterations;
+      s.stats.converged = stats[i].converged != 0;
+      s.stats.seconds = stats[i].seconds;
+      s.stats.deviceSeconds = stats[i].device_seconds;
+      counts[i].resize(static_cast<size_t>(stats[i].iterations));
+      s.stats.correspondenceCounts = counts[i];
+    }
+    lastStats_ = lastStages_.back().stats;
+    if (!lastStats_.converged) {
+      std::cout << "ICP not converged!\n";
+    }
+    return shim::poseFromData(pose);
+  }
+  // ... with the schedule this ICP was given (setCoarseToFine, registration.coarse_to_fine.levels); none: align()
+  Isometry3d alignCoarseToFine(const PointCloud & cloud, const LocalMap & localMap, const Isometry3d & guess)
+  {
+    return schedule_.empty() ? align(cloud, localMap, guess) : alignCoarseToFine(cloud, localMap, guess, schedule_);
+  }
+  const std::vector<StageStats> & lastStages() const {return lastStages_;}          // of the last alignCoarseToFine()
 
   // The robust round of every later align / alignHypotheses of this ICP (vgicp_hip_robust.h): kind = VGICP_ROBUST_NONE,
   // _HUBER or _CAUCHY, its scale c, and the gate on the squared Mahalanobis residual (0 = none), in the library's
@@ -604,6 +720,18 @@ private:
     return params;
   }
 
+  static void checkSchedule(const std::vector<int> & levels)
+  {
+    if (levels.size() > static_cast<size_t>(VGICP_LEVEL_STAGES_MAX)) {
+      throw std::invalid_argument("ICP: a coarse-to-fine schedule has at most VGICP_LEVEL_STAGES_MAX stages");
+    }
+    for (const int l : levels) {
+      if (l < 0 || l > VGICP_LEVELS_MAX) {
+        throw std::invalid_argument("ICP: every level of a coarse-to-fine schedule must be 0 .. VGICP_LEVELS_MAX");
+      }
+    }
+  }
+
   // the size of a cloud that is about to go up as it is: one covariance per point, or `method` throws
   static size_t pointsWithCovariances(const PointCloud & cloud, const char * method)
   {
@@ -730,6 +858,11 @@ private:
   int robustKernel_ = VGICP_ROBUST_NONE;
   int robustScaleMicro_ = 1000000;
   int robustGateMicro_ = 0;
+  std::vector<int> schedule_;          // of alignCoarseToFine(cloud, map, guess); empty: none
+  int coarseMaxIteration_ = 30;
+  double coarseTranslationSquaredThreshold_ = 1.0e-4;
+  double coarseCosineThreshold_ = 0.999;
+  std::vector<StageStats> lastStages_;
   bool priorOn_ = false;
   std::array<double, 16> priorPose_{};
   std::array<double, 36> priorInformation_{};

@@ -20,6 +20,9 @@ options: --out traj.tum   --device-map (keep the voxel grid on the GPU only)   -
          --ray-report RANGE [--ray-margin M --ray-beyond B --ray-stride S] (with --resident: the read-only ray report of
          every frame's scan at its aligned pose, before the map update, include/vgicp_hip_map_rays.h: the first map voxel
          on every ray within RANGE metres and B metres behind the return; the class totals of the run are printed)
+         --levels 3,2,1,0 [--coarse-max-iteration N --coarse-translation-sq-threshold T --coarse-cosine-threshold C]
+         (registration.coarse_to_fine, with --resident: every frame's align runs in stages against the map's coarser
+         levels, include/vgicp_hip_map_levels.h, every stage but the last with the coarse thresholds; off by default)
          --prior-update (kalman_filter.update.iterated: the filter's pose covariance enters every round of the align as a
          prior, include/vgicp_hip_prior.h, and the update is the iterated one; off by default)
 The configuration is the reference's config/hilti_config.yaml as a dict (eskf_lio_amd/replay.py:DEFAULT_CONFIG);
@@ -73,6 +76,20 @@ def carve_config(cfg, args):
     return dict(cfg, local_map=dict(cfg["local_map"], carve=given))
 
 
+def coarse_to_fine_config(cfg, args):
+    """The configuration with registration.coarse_to_fine from --levels / --coarse-* (the same object when none is given)."""
+    coarse = {k: v for k, v in (("max_iteration", args.coarse_max_iteration),
+                                ("translation_sq_threshold", args.coarse_translation_sq_threshold),
+                                ("cosine_threshold", args.coarse_cosine_threshold)) if v is not None}
+    if args.levels is None:
+        if coarse:
+            raise ValueError("--coarse-* needs --levels")
+        return cfg
+    levels = [int(l) for l in args.levels.split(",")]
+    ctf = dict(levels=levels, coarse=coarse) if coarse else dict(levels=levels)
+    return dict(cfg, registration=dict(cfg["registration"], coarse_to_fine=ctf))
+
+
 def ray_report_params(args):
     """What DeviceBackend.set_ray_report takes, from the --ray-* flags; None without --ray-report."""
     if args.ray_report is None:
@@ -121,6 +138,14 @@ def parse_args(argv=None):
     ap.add_argument("--carve-margin", type=float, default=None, help="metres a ray stops short of its return (local_map.carve.margin)")
     ap.add_argument("--carve-min-hits", type=int, default=None, help="rays that must cross a voxel (local_map.carve.min_hits)")
     ap.add_argument("--carve-stride", type=int, default=None, help="every S-th point casts a ray (local_map.carve.stride)")
+    ap.add_argument("--levels", default=None, metavar="L,L,..",
+                    help="the level of every stage of each frame's align, e.g. 3,2,1,0 (registration.coarse_to_fine.levels)")
+    ap.add_argument("--coarse-max-iteration", type=int, default=None,
+                    help="rounds of every stage but the last (registration.coarse_to_fine.coarse.max_iteration, default 30)")
+    ap.add_argument("--coarse-translation-sq-threshold", type=float, default=None,
+                    help="... its translation threshold (registration.coarse_to_fine.coarse.translation_sq_threshold, default 1e-4)")
+    ap.add_argument("--coarse-cosine-threshold", type=float, default=None,
+                    help="... its rotation threshold (registration.coarse_to_fine.coarse.cosine_threshold, default 0.999)")
     ap.add_argument("--ray-report", type=float, default=None, metavar="RANGE",
                     help="the ray report at every aligned pose before the map update: metres a ray is followed (vgicp_hip_map_rays.h)")
     ap.add_argument("--ray-margin", type=float, default=None, help="metres in front of a return within which a hit is near, not blocked")
@@ -139,6 +164,12 @@ def parse_args(argv=None):
             ap.error("--carve-* needs --resident")
         if args.carve_range is None:
             ap.error("--carve-margin, --carve-min-hits and --carve-stride need --carve-range")
+    if any(v is not None for v in (args.levels, args.coarse_max_iteration, args.coarse_translation_sq_threshold,
+                                   args.coarse_cosine_threshold)):
+        if not args.resident:
+            ap.error("--levels and --coarse-* need --resident")
+        if args.levels is None:
+            ap.error("--coarse-* needs --levels")
     args.parser = ap
     return args
 
@@ -163,6 +194,7 @@ def main(argv=None):
     if args.prior_update:
         cfg = dict(cfg, kalman_filter=dict(cfg["kalman_filter"], iterated=True))
     cfg = carve_config(cfg, args)
+    cfg = coarse_to_fine_config(cfg, args)
     truth = None
     if args.bag:
         events = replay.read_rosbag2(args.bag, imu_topic, lidar_topic)
@@ -183,7 +215,7 @@ def main(argv=None):
         backend.set_ray_report(**ray_params)
     odo = replay.Odometry(cfg, backend)
     traj = odo.run(events)
-    summary = dict(poses=len(traj), ray_report=None)
+    summary = dict(poses=len(traj), ray_report=None, trajectory=traj)
     replay.write_tum(args.out, traj)
     print(f"{len(traj)} poses -> {args.out}; Gauss-Newton rounds per frame: {odo.backend.iterations}")
     print(odo.report())
@@ -191,6 +223,9 @@ def main(argv=None):
         cs = [c for _, c in backend.scales]
         print(f"robust scale from the {args.robust_scale_quantile} quantile of d^2 at each predicted pose: "
               f"min {min(cs):.4f}, median {float(np.median(cs)):.4f}, max {max(cs):.4f}")
+    if args.levels is not None:
+        print(f"align in stages against levels {args.levels}: rounds per stage and frame {backend.stage_iterations}; "
+              f"voxels per level {backend.ctx.map_levels_build(max(cfg['registration']['coarse_to_fine']['levels'])).voxels}")
     if args.insert_gate:
         points, refused = backend.ctx.map_gated_totals()
         print(f"map insertion gated at d^2 <= {args.insert_gate}: {refused} of {points} points kept out of the map")
