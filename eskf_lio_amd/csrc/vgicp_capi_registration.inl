@@ -2,10 +2,13 @@
 // vgicp_align / vgicp_align_resident and the single-step hooks (accumulate, solve_step, match, voxel_index).
 namespace {
 // ---- the fused align: vgicp_align of a staged scan in ONE launch ----------------------------------------------------
-// The persistent launch is enqueued before the copy threads start; each workgroup waits for the staged unit(s) that hold
-// its 448 points and reads them over PCIe itself (fused_round0_load), so neither pack_arena_kernel, nor the kernel
-// boundary, nor the re-read of the planes stand between the last unit and round 0.  Where it is taken: plan_align
-// (AlignPath::Fused); everything else keeps the pack launch in front.
+// The persistent launch is enqueued while the copy threads stage the scan; each workgroup waits for the staged unit(s)
+// that hold its 448 points and reads them over PCIe itself (fused_round0_load), so neither pack_arena_kernel, nor the
+// kernel boundary, nor the re-read of the planes stand between the last unit and round 0; the resident copy leaves the
+// launch behind round 0's row publication (fused_leave_resident).  The helpers are posted as soon as the copy job is
+// complete, before the launch is set up, and the launch is followed by the synchronisation alone, without a marker
+// (staged_launch_synchronise).  Where it is taken: plan_align (AlignPath::Fused); everything else keeps the pack launch
+// in front.
 int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* covs, const double* guess,
                 const vgicp_params* params, double* out_pose, vgicp_stats* stats) {
   const double t0 = now_seconds();
@@ -13,8 +16,16 @@ int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   VG_RC(ensure_log(ctx, params->max_iteration));
   UploadJob up;
   VG_RC(scan_upload_stage(ctx, n, points, covs, &up));
+  // the copy job is complete: the helpers start on their first units while this thread sets the launch up (the link is
+  // idle until the first unit is staged)
+  crew_post(ctx, &up.copy);
   PersistArgs a;
-  VG_RC(persistent_args(ctx, guess, params, &a));
+  const int rc_args = persistent_args(ctx, guess, params, &a);
+  if (rc_args != VGICP_OK) {   // no launch: the copy threads still have to let go of the caller's buffers
+    bool held_up = false;
+    const int rc_join = crew_join(ctx, up.copy, &held_up);
+    return rc_join != VGICP_OK ? rc_join : rc_args;
+  }
   FusedUpload f;
   std::memset(&f, 0, sizeof f);
   f.apts = up.copy.dst_a;
@@ -29,7 +40,6 @@ int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   f.asym = ctx->d_ins_counters + 2;
   f.unit_clock = ctx->d_unit_clock;
   const bool trace = trace_align();   // where the host time goes
-  crew_post(ctx, &up.copy);
   const double ta0 = trace ? now_seconds() : 0.0;
   const hipError_t e_launch = launch_persistent_fused(ctx->stream, a, f, ctx->persist_grid);
   const double ta1 = trace ? now_seconds() : 0.0;
@@ -42,12 +52,10 @@ int align_fused(vgicp_ctx* ctx, size_t n, const double* points, const double* co
   }
   if (e_launch != hipSuccess) return fail_hip(ctx, e_launch, "launch_persistent_fused");
   const double ta2 = trace ? now_seconds() : 0.0;
-  VG_HIP(ctx, hipEventRecord(ctx->ev_upload, ctx->stream));
-  ctx->upload_in_flight = true;
   ctx->upload_bytes += n * kScanPlanes * sizeof(double);
   ctx->upload_seconds += now_seconds() - up.t0;  // host side: the staging copy + the enqueue of the launch
   ctx->scan_ready = true;
-  VG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  VG_RC(staged_launch_synchronise(ctx));   // no marker behind the launch: this wait is what frees the staging memory
   const double ta3 = trace ? now_seconds() : 0.0;
   if (trace && ta3 - ta0 > 2e-3)
     std::fprintf(stderr, "[vgicp trace] fused align: enqueue %.3f ms, copy %.3f ms, hipStreamSynchronize %.3f ms\n",

@@ -165,6 +165,20 @@ int scan_upload_stage(vgicp_ctx* ctx, size_t n, const double* points, const doub
   return VGICP_OK;
 }
 
+// The end of a launch that read the staging memory AND is waited for by its caller (the fused align): the
+// synchronisation itself proves that the staging memory is free again, so no marker is recorded behind the launch (one
+// packet less between the kernel's end and the caller's return) and upload_in_flight — "a launch may still be reading
+// the staging memory; ev_upload says when it has" — stays false, which is all that ensure_upload_stage and
+// scan_upload_stage ask.  Only a synchronisation that fails leaves the marker behind after all.  (vgicp_scan_upload's
+// enqueue and the two-launch vgicp_align do not end in a wait of their own: they keep the marker.)
+int staged_launch_synchronise(vgicp_ctx* ctx) {
+  ctx->upload_in_flight = false;
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) return VGICP_OK;
+  if (hipEventRecord(ctx->ev_upload, ctx->stream) == hipSuccess) ctx->upload_in_flight = true;
+  return fail_hip(ctx, e, "hipStreamSynchronize(ctx->stream)");
+}
+
 // pack_arena_kernel over the staging memory of the current scan (wait: behind the copy threads, with the pack's patience)
 hipError_t launch_pack_staged(vgicp_ctx* ctx, bool wait) {
   const uint32_t spin_limit = ctx->dev.pack_spin_limit ? ctx->dev.pack_spin_limit : kPackSpinLimit;

@@ -1261,36 +1261,66 @@ __device__ __forceinline__ uint64_t pinned_clock(double (&x)[N]) {
   return t;
 }
 
+// A staged unit's flag line as the host's copy thread leaves it: flags[16 u] = the sequence number, flags[16 u + 1] = the
+// form of its covariances, stored BEFORE the flag.  Both lie in one naturally aligned 8-byte granule, so one system-scope
+// load brings both over the link: the low word is the flag, and when it says `seq` the high word is that unit's form (a
+// second, dependent load of the form would cost another PCIe read latency per unit).
+__device__ __forceinline__ unsigned long long load_flag_and_form(const uint32_t* flags, uint32_t u) {
+  return __hip_atomic_load((gu64*)(flags + 16 * (size_t)u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Where a workgroup of the fused align leaves the resident copy of its points (fused_leave_resident): written to LDS by
+// fused_round0_load and read back inside round 0, so that none of it occupies registers across the round loop.
+struct FusedLeave {
+  double* plane;     // SoA: plane 0 at the workgroup's first point
+  double* aos_pts;   // AoS copy, at the workgroup's first point
+  double* aos_cov;
+  uint32_t* asym;
+  uint64_t stride;
+  uint32_t seq, cnt; // cnt: the workgroup's points
+};
+
 // The fused align's round-0 load (all threads of the workgroup; one point per worker thread).  The workgroup's 448
 // points lie in one or two staged units: thread 0 waits for their flags with system-scope loads and the pack's patience,
 // then the workgroup reads the points and the covariances over PCIe as pack_arena_kernel does — contiguous 16-byte
 // non-temporal loads into LDS (`lds`: 18 x 448 doubles, the neighbour-prefetch area, unused before round 0), the
-// compact or full form per unit, the odd-count tail read whole (the staging areas are padded).  It leaves behind what
-// the pack left for these points: the 12 SoA planes, the AoS device copy and the asymmetry word.  Each worker thread
-// returns its point in q0, as load_point would have read it from the planes.  false: a unit did not arrive in time.
+// compact or full form per unit, the odd-count tail read whole (the staging areas are padded).  Each worker thread
+// returns its point in q0, as load_point would have read it from the planes; what the pack left behind for these
+// points is stored later, out of lds[0 .. 12 x 448), to the addresses noted in *leave (fused_leave_resident).  false: a
+// unit did not arrive in time.
 __device__ __forceinline__ bool fused_round0_load(const FusedUpload& f, uint64_t stride, uint32_t n_pts, double* lds,
-                                                  double (&q0)[kScanPlanes]) {
+                                                  FusedLeave* leave, double (&q0)[kScanPlanes]) {
   typedef int v4i __attribute__((ext_vector_type(4)));
   constexpr uint32_t B = 512, W = B - 64;   // the persistent workgroup and its worker threads
   __shared__ uint32_t ok_sh, form_sh[2];
   const uint32_t tid = threadIdx.x, p0 = blockIdx.x * W;
   const uint32_t cnt = p0 < n_pts ? min(W, n_pts - p0) : 0u;  // uniform
+  if (tid == 0) {   // read behind round 0's first barrier
+    leave->plane = f.soa + p0;
+    leave->aos_pts = f.aos_pts + 3 * (size_t)p0;
+    leave->aos_cov = f.aos_cov + 9 * (size_t)p0;
+    leave->asym = f.asym;
+    leave->stride = stride;
+    leave->seq = f.seq;
+    leave->cnt = cnt;
+  }
   if (cnt == 0) return true;
   const uint32_t ua = p0 / f.unit, ub = (p0 + cnt - 1) / f.unit;  // W < unit: at most two units
   const uint32_t split = min(p0 + cnt, (ua + 1) * f.unit);         // the first point of unit ub (p0 + cnt: one unit)
   if (tid == 0) {
     uint32_t good = 1;
-    for (uint32_t u = ua; u <= ub && good; ++u)
-      for (uint32_t spins = 0; __hip_atomic_load(f.flags + 16 * u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != f.seq; ++spins) {
+    for (uint32_t u = ua; u <= ub && good; ++u) {
+      unsigned long long w = load_flag_and_form(f.flags, u);
+      for (uint32_t spins = 0; (uint32_t)w != f.seq; ++spins) {
         if (spins >= f.spin_limit) { good = 0; break; }
         __builtin_amdgcn_s_sleep(20);
+        w = load_flag_and_form(f.flags, u);
       }
+      form_sh[u == ua ? 0 : 1] = (uint32_t)(w >> 32);   // the form that came with the flag
+    }
+    if (ua == ub) form_sh[1] = form_sh[0];
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     ok_sh = good;
-    if (good) {
-      form_sh[0] = __hip_atomic_load(f.flags + 16 * ua + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      form_sh[1] = __hip_atomic_load(f.flags + 16 * ub + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
   }
   __syncthreads();
   if (!ok_sh) return false;  // uniform
@@ -1328,33 +1358,48 @@ __device__ __forceinline__ bool fused_round0_load(const FusedUpload& f, uint64_t
   // the workgroup's points have crossed the link: where the registration's device time starts (the two-launch path's
   // persistent launch starts with every point packed)
   if (tid == 0) atomicMax(f.unit_clock, (unsigned long long)wall_clock64());
-  // the AoS device copy, coalesced out of LDS (an odd count leaves one double at the end of each array)
-  {
-    const uint32_t wp = 3 * cnt, wc = 9 * cnt;
-    v4i* dp = reinterpret_cast<v4i*>(f.aos_pts + 3 * (size_t)p0);
-    v4i* dc = reinterpret_cast<v4i*>(f.aos_cov + 9 * (size_t)p0);
-    for (uint32_t k = tid; k < wp / 2; k += B) dp[k] = reinterpret_cast<const v4i*>(lp)[k];
-    for (uint32_t k = tid; k < wc / 2; k += B) dc[k] = reinterpret_cast<const v4i*>(lc)[k];
-    if (tid == 0 && (cnt & 1u)) {
-      f.aos_pts[3 * (size_t)p0 + wp - 1] = lp[wp - 1];
-      f.aos_cov[9 * (size_t)p0 + wc - 1] = lc[wc - 1];
-    }
-  }
   const uint32_t wt = tid - 64u;
   if (tid >= 64u && wt < cnt) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) q0[k] = lp[3 * wt + k];
 #pragma unroll
     for (int k = 0; k < 9; ++k) q0[3 + k] = lc[9 * wt + k];
-    const size_t i = p0 + wt;
-#pragma unroll
-    for (int k = 0; k < kScanPlanes; ++k) f.soa[k * stride + i] = q0[k];
+  }
+  return true;
+}
+
+// The resident copy of the workgroup's points, left behind by its WORKER threads (tid >= 64) once round 0's row is on its
+// way: the 12 SoA planes and the AoS device copy, both coalesced out of the LDS that fused_round0_load filled
+// (lds[0 .. 12 x 448) is untouched until the neighbour look-ahead first writes there, a round later), and the asymmetry
+// word (from q0).  This launch never reads any of it again, so every word is stored write-through: nothing of the
+// 86 KB per workgroup stays dirty in L2 for the end of the launch to write back, and nothing of it stands between the
+// unit's arrival and round 0's voxel probe.  Eight bytes per lane and store: the odd count needs no tail.
+__device__ __forceinline__ void fused_leave_resident(const FusedLeave* leave, const double* lds, const double (&q0)[kScanPlanes]) {
+  constexpr uint32_t W = 512 - 64;
+  // the addresses are made HERE, from the note in LDS (the empty asm keeps the lane's part from being hoisted out of the
+  // round loop): kept in registers through every round they push the solver's constants into scratch
+  uint32_t tid_here = threadIdx.x;
+  asm volatile("" : "+v"(tid_here));
+  const uint32_t wt = tid_here - 64u;
+  const FusedLeave to = *leave;
+  const double* lp = lds;
+  const double* lc = lds + 3 * W;
+  if (wt < to.cnt) {
+    // plane by plane out of LDS, one address at a time
+    double* plane = to.plane + wt;
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k, plane += to.stride) store_through_bits(plane, (unsigned long long)__double_as_longlong(lp[3 * wt + k]));
+#pragma unroll 1
+    for (int k = 0; k < 9; ++k, plane += to.stride) store_through_bits(plane, (unsigned long long)__double_as_longlong(lc[9 * wt + k]));
     const bool same = __double_as_longlong(q0[4]) == __double_as_longlong(q0[6]) &&
                       __double_as_longlong(q0[5]) == __double_as_longlong(q0[9]) &&
                       __double_as_longlong(q0[8]) == __double_as_longlong(q0[10]);
-    if (!same) *f.asym = f.seq;
+    if (!same) *to.asym = to.seq;
   }
-  return true;
+#pragma unroll 1
+  for (uint32_t k = wt; k < 3 * to.cnt; k += W) store_through_bits(to.aos_pts + k, (unsigned long long)__double_as_longlong(lp[k]));
+#pragma unroll 1
+  for (uint32_t k = wt; k < 9 * to.cnt; k += W) store_through_bits(to.aos_cov + k, (unsigned long long)__double_as_longlong(lc[k]));
 }
 
 // MULTI: several GPUs (the rank totals cross xGMI through mailboxes); STAMPS: in-kernel phase clocks
@@ -1391,6 +1436,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
   __shared__ double work[kSolveWork];
   __shared__ double pose_sh[12];
   __shared__ int stop_sh;
+  __shared__ FusedLeave leave_sh;   // FUSED only
   // Scans larger than the grid: a thread owns several points. The first stays in registers; of the
   // others, the first a.memo_points have a 16-byte memo {key, slot} and the first a.stash_points are
   // parked whole after round 0 (plane-major per point: conflict-free), so only the rest is re-read.
@@ -1460,13 +1506,18 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
   for (int k = 0; k < kScanPlanes; ++k) q0[k] = 0.0;
   const bool have = first < end_pts;
   if constexpr (FUSED) {
-    if (!fused_round0_load(up, a.stride, n_pts, reinterpret_cast<double*>(dyn_lds), q0)) {
+    if (!fused_round0_load(up, a.stride, n_pts, reinterpret_cast<double*>(dyn_lds), &leave_sh, q0)) {
       if (tid == 0) a.state->abort_seq = a.seq;   // a unit never came: the host re-packs and re-runs the align
       return;
     }
   } else if (have) {
     load_point(a.scan, a.stride, first, q0);
   }
+
+  // The look-ahead's keys name nothing when a launch starts — no memo survives a launch, the map may change in between —
+  // so a launch's FIRST look-ahead takes every key as unknown and writes it.  That is round 0's; the fused align's is
+  // round 1's, because its round-0 load holds the area through round 0.
+  constexpr int kFirstLook = FUSED ? 1 : 0;
 
   // what the first point used last round: key, hit flag, voxel payload (raw)
   bool spec = false, hit = false;
@@ -1499,7 +1550,7 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
           const int32_t kz = voxel_coord_fast(p[2], a.voxel_size, inv_voxel);
           if (!spec || kx != okx || ky != oky || kz != okz) {
             bool served = false;
-            if (spec && prefetch) {
+            if (spec && prefetch && it > kFirstLook) {   // (nothing has been looked up before the first look-ahead)
               const int4 m = pf_key[tid - 64];
               if (m.x == kx && m.y == ky && m.z == kz && (uint32_t)m.w != kMemoNone) {
                 served = true;
@@ -1601,10 +1652,17 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
     __syncthreads();
     if (STAMPS) { const uint64_t n = wall_clock64(); acc_body += n - t_mark; t_mark = n; }
 
-    if (!MANY && worker && prefetch && have) {
+    if (FUSED && it == 0) {
+      // The fused align's round 0: the workgroup's row is on its way (wave 0 publishes it while the workers get here), so
+      // the resident copy of its points leaves now, beside the exchange, instead of in front of the cold voxel probe.
+      // The look-ahead, which writes the LDS the copy is read from, starts a round later (behind barrier 2).
+      if (worker) fused_leave_resident(&leave_sh, reinterpret_cast<const double*>(dyn_lds), q0);
+    } else if (!MANY && worker && prefetch && have) {
       // While wave 0 exchanges and solves: where is this point inside its voxel?  If a face is nearer than
       // prefetch_margin voxels, look the voxel behind it up now (full probe; 2 dependent round trips that
-      // nobody waits for) so that next round's key change finds the record in LDS.
+      // nobody waits for) so that next round's key change finds the record in LDS.  The map does not change during a
+      // launch: a neighbour that pf_key already names (looked up in an earlier round of THIS launch — the launch's first
+      // look-ahead, kFirstLook, takes no key as known) is not probed again, its record is still what the table holds.
       double p[3], rx, ry, rz;  // r*: distance of the point from the lower face of its voxel, in [0, voxel)
       transform_point(R, t, q0[0], q0[1], q0[2], p);
       (void)voxel_coord_fast(p[0], a.voxel_size, inv_voxel, &rx);
@@ -1617,18 +1675,21 @@ __device__ __forceinline__ void persistent_body(const PersistArgs& a, const Fuse
       if (dx <= dy && dx <= dz) { d = dx; nx += rx < half ? -1 : 1; }
       else if (dy <= dz) { d = dy; ny += ry < half ? -1 : 1; }
       else { d = dz; nz += rz < half ? -1 : 1; }
-      int4 m = make_int4(nx, ny, nz, (int32_t)kMemoNone);
-      if (d < a.prefetch_margin * a.voxel_size) {
-        const VoxelRecord* rec = find_voxel(a.table, a.mask, nx, ny, nz);
-        m.w = rec ? (int32_t)(uint32_t)(rec - a.table) : (int32_t)kMemoMiss;
-        if (rec) {
-          const double2* pay = reinterpret_cast<const double2*>(rec->mean);
-          double2* dst = pf_pay + (tid - 64);
+      const int4 known = pf_key[tid - 64];
+      if (it == kFirstLook || known.x != nx || known.y != ny || known.z != nz || (uint32_t)known.w == kMemoNone) {
+        int4 m = make_int4(nx, ny, nz, (int32_t)kMemoNone);
+        if (d < a.prefetch_margin * a.voxel_size) {
+          const VoxelRecord* rec = find_voxel(a.table, a.mask, nx, ny, nz);
+          m.w = rec ? (int32_t)(uint32_t)(rec - a.table) : (int32_t)kMemoMiss;
+          if (rec) {
+            const double2* pay = reinterpret_cast<const double2*>(rec->mean);
+            double2* dst = pf_pay + (tid - 64);
 #pragma unroll
-          for (int j = 0; j < 6; ++j) dst[j * kWorkers] = pay[j];
+            for (int j = 0; j < 6; ++j) dst[j * kWorkers] = pay[j];
+          }
         }
+        pf_key[tid - 64] = m;
       }
-      pf_key[tid - 64] = m;
     }
     // STAMPS: how long the look-ahead kept this wave (reported in the worker lane's "level-1" column)
     if (STAMPS && !MANY && wave != 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const uint64_t n = wall_clock64(); acc_l1 += n - t_mark; t_mark = n; }
@@ -1959,14 +2020,16 @@ __global__ __launch_bounds__(kPackArenaBlock) void pack_arena_kernel(
     if (u != have_unit) {
       if (t == 0) {
         uint32_t good = 1;
+        unsigned long long w = load_flag_and_form(flags, u);   // flag and form in one load over the link
         if (wait)
-          for (uint32_t spins = 0; __hip_atomic_load(flags + 16 * u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != seq; ++spins) {
+          for (uint32_t spins = 0; (uint32_t)w != seq; ++spins) {
             if (spins >= spin_limit) { good = 0; break; }
             __builtin_amdgcn_s_sleep(20);
+            w = load_flag_and_form(flags, u);
           }
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
         ok = good;
-        form_sh = good ? __hip_atomic_load(flags + 16 * u + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : kArenaFull;
+        form_sh = good ? (uint32_t)(w >> 32) : kArenaFull;
       }
       __syncthreads();
       if (!ok) return;   // uniform
