@@ -83,6 +83,13 @@ MAP_LEVELS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_
 LEVELS_MAX = 4
 LEVEL_STAGES_MAX = 8
 
+# every symbol include/vgicp_hip_map_locate.h declares: likewise, one entry point in a library of its own
+MAP_LOCATE_EXPORTS = ("vgicp_locate_resident",)
+MAP_LOCATE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_locate.so")
+LOCATE_MAX_POSES = 64
+LOCATE_MAX_HALF_WIDTH = 32
+LOCATE_MAX_CELLS = 4096
+
 # every symbol include/vgicp_hip_search_report.h declares: likewise, one entry point (a test hook) in a library of its own
 SEARCH_REPORT_EXPORTS = ("vgicp_prepare_search_report",)
 SEARCH_REPORT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_search_report.so")
@@ -213,6 +220,34 @@ class LevelsBuild:
     voxels: list
     slots: list
     levels: int
+    launches: int
+    seconds: float
+    device_seconds: float
+
+
+class LocateParams(C.Structure):
+    """vgicp_locate_params (vgicp_hip_map_locate.h), 20 bytes."""
+    _fields_ = [("level", C.c_int32), ("window", C.c_int32 * 3), ("stride", C.c_uint32)]
+
+
+class LocateBest(C.Structure):
+    """vgicp_locate_best (vgicp_hip_map_locate.h), 160 bytes."""
+    _fields_ = [("hits", C.c_uint32), ("cell", C.c_uint32), ("offset", C.c_int32 * 3), ("points", C.c_uint32),
+                ("skipped", C.c_uint32), ("reserved", C.c_uint32), ("pose", C.c_double * 16)]
+
+
+class LocateStats(C.Structure):
+    """vgicp_locate_stats (vgicp_hip_map_locate.h), 24 bytes."""
+    _fields_ = [("cells", C.c_int32), ("launches", C.c_int32), ("seconds", C.c_double), ("device_seconds", C.c_double)]
+
+
+@dataclass
+class LocateResult:
+    """What Context.locate_resident returns.  best: one dict per pose (hits, cell, offset: a tuple of 3, points, skipped,
+    pose: 4x4, the input pose moved by offset * the level's voxel size).  hits: uint32 (k, cells), or None."""
+    best: list
+    hits: Optional[np.ndarray]
+    cells: int
     launches: int
     seconds: float
     device_seconds: float
@@ -390,6 +425,13 @@ def load_library() -> C.CDLL:
         for name in MAP_LEVELS_EXPORTS:
             getattr(levels, name).restype = C.c_int
             setattr(lib, name, getattr(levels, name))
+    # locate's library, likewise
+    if os.path.exists(MAP_LOCATE_LIB_PATH):
+        locate = C.CDLL(MAP_LOCATE_LIB_PATH, mode=C.RTLD_GLOBAL)
+        locate.vgicp_locate_resident.argtypes = [vp, dp, sz, C.POINTER(LocateParams), C.POINTER(LocateBest),
+                                                 C.POINTER(C.c_uint32), C.POINTER(LocateStats)]
+        locate.vgicp_locate_resident.restype = C.c_int
+        lib.vgicp_locate_resident = locate.vgicp_locate_resident
     # the neighbour search's path report, likewise
     if os.path.exists(SEARCH_REPORT_LIB_PATH):
         report = C.CDLL(SEARCH_REPORT_LIB_PATH, mode=C.RTLD_GLOBAL)
@@ -1113,6 +1155,28 @@ class Context:
                                       corr_count=counts[i][:it].copy(), normal_eq=neqs[i][:it].copy(), status=rc,
                                       message=self.last_error() if rc else ""))
         return pose_from_abi(out), stages
+
+    def locate_resident(self, poses, level: int, window, stride: int = 1, planes: bool = True) -> "LocateResult":
+        """vgicp_locate_resident (vgicp_hip_map_locate.h): `poses` (one 4x4 pose or k of them) of the resident scan scored
+        over the window of whole-voxel shifts (half-widths wx, wy, wz) on a level of the map, read-only.  planes: also
+        the k x cells array of hits."""
+        ps = np.asarray(poses, dtype=np.float64)
+        ps = ps.reshape(1, 4, 4) if ps.ndim == 2 else ps
+        k = len(ps)
+        g = np.ascontiguousarray(np.stack([pose_to_abi(T) for T in ps]).reshape(k, 16)) if k else np.zeros((0, 16))
+        w = [int(v) for v in window]
+        p = LocateParams(int(level), (C.c_int32 * 3)(*w), int(stride))
+        cells = (2 * w[0] + 1) * (2 * w[1] + 1) * (2 * w[2] + 1)
+        room = cells if all(0 <= v <= LOCATE_MAX_HALF_WIDTH for v in w) and cells <= LOCATE_MAX_CELLS else 1
+        hits = np.zeros((k, room), dtype=np.uint32) if planes else None
+        best = (LocateBest * max(k, 1))()
+        st = LocateStats()
+        self._check(self._lib.vgicp_locate_resident(self._h, _dp(g), k, C.byref(p), best,
+                                                    hits.ctypes.data_as(C.POINTER(C.c_uint32)) if planes else None,
+                                                    C.byref(st)))
+        out = [dict(hits=int(b.hits), cell=int(b.cell), offset=tuple(int(v) for v in b.offset), points=int(b.points),
+                    skipped=int(b.skipped), pose=pose_from_abi(np.array(b.pose))) for b in best[:k]]
+        return LocateResult(out, hits, st.cells, st.launches, st.seconds, st.device_seconds)
 
     def rays_resident(self, poses, params, per_point: bool = True) -> "RayReport":
         """vgicp_rays_resident (vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at `poses`

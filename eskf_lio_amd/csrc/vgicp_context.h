@@ -35,6 +35,7 @@
 #include "../../include/vgicp_hip_map_rays.h"
 #include "../../include/vgicp_hip_search_report.h"
 #include "../../include/vgicp_hip_map_levels.h"
+#include "../../include/vgicp_hip_map_locate.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -43,6 +44,7 @@
 #include "vgicp_map_plan.h"
 #include "vgicp_points_plan.h"
 #include "vgicp_levels_plan.h"
+#include "vgicp_locate_plan.h"
 
 using namespace vgicp;
 
@@ -514,6 +516,10 @@ struct vgicp_ctx {
   PinnedBuf<uint32_t> h_level_counts;    // pinned: the same, copied behind every rebuild
   bool level_counts_pending = false;     // that copy is enqueued and nobody has waited for it yet
   int view_level = 0;                    // != 0 only inside a stage of vgicp_align_resident_levels: resident_view() is that level's
+  // locate (include/vgicp_hip_map_locate.h): read-only, storage of its own and of one size (LocateLayout,
+  // vgicp_capi_map_locate.inl), made by the first call
+  DeviceBuf<char> d_locate;              // the poses, the skipped points per pose, the plane of hits
+  PinnedBuf<char> h_locate;              // pinned: the poses on their way in, the bests (.dev(): where the best launch writes them), the plane on its way out
   // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
   // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
@@ -566,7 +572,7 @@ struct vgicp_ctx {
 };
 
 // The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip, vgicp_map_carve.hip, vgicp_map_rays.hip,
-// vgicp_search_report.hip, vgicp_map_levels.hip): was
+// vgicp_search_report.hip, vgicp_map_levels.hip, vgicp_map_locate.hip): was
 // this context made by the build that reads it?  Reads the stamp only; each library refuses in its own words.
 inline bool same_build(const vgicp_ctx* ctx) { return ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx)); }
 
@@ -719,6 +725,9 @@ int map_level_export(vgicp_ctx* ctx, int level, size_t capacity, int32_t* keys, 
                      size_t* written);
 int align_resident_levels(vgicp_ctx* ctx, const double guess[16], size_t stages, const int32_t* levels, const vgicp_params* params,
                           double out_pose[16], vgicp_stats* stats);
+// The entry point of include/vgicp_hip_map_locate.h behind libvgicp_hip_map_locate.so, likewise (vgicp_capi_map_locate.inl).
+int locate_resident(vgicp_ctx* ctx, const double* poses, size_t k, const vgicp_locate_params* params, vgicp_locate_best* best,
+                    uint32_t* hits, vgicp_locate_stats* stats);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

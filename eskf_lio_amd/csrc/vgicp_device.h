@@ -381,6 +381,25 @@ uint32_t match_blocks(uint32_t n);
 // counters[0] += voxels of the level, counters[1] += probe sequences exhausted.
 hipError_t launch_level_build(hipStream_t s, const VoxelRecord* fine, uint64_t fine_slots, VoxelRecord* coarse,
                               uint64_t coarse_slots, uint32_t* counters);
+// Locate (include/vgicp_hip_map_locate.h has the rule): two launches.  SCORE, grid (chunks of the points that take part,
+// poses): a workgroup makes the keys of its points once, probes the level's table once per point and cell of the window
+// and counts in a histogram in LDS, which it then adds to the plane.  BEST, one workgroup per pose: the maximum with the
+// lowest index, written as vgicp_locate_best.  The table is only read.
+struct LocateArgs {
+  const VoxelRecord* table;    // of the level
+  uint32_t mask;               // its slots - 1
+  uint32_t cells;              // of the window, at most VGICP_LOCATE_MAX_CELLS
+  double voxel_size;           // of the level
+  const double* points_aos;    // n x 3
+  uint32_t n, stride;
+  uint32_t participants;       // points with i % stride == 0
+  int32_t window[3];           // half-widths
+  const double* poses;         // device: 16 per pose, as the ABI lays a transform out
+  uint32_t* skipped;           // per pose, zero before
+  uint32_t* plane;             // poses x cells, zero before
+};
+// best: poses x vgicp_locate_best, where the device writes them (page-locked memory)
+hipError_t launch_locate(hipStream_t s, const LocateArgs& args, uint32_t poses, void* best);
 
 // ---- vgicp_mapupdate.hip: LocalMap::updateLocalMap's insert / evict loops on the device ----
 // Scratch the insertion needs for n points (bytes), and the insertion itself: transform, find-or-claim

@@ -88,6 +88,21 @@ __device__ __forceinline__ void transform_point(const double* R, const double* t
   q[2] = ((R[2] * x + R[5] * y) + R[8] * z) + t[2];
 }
 
+// The key of free-space carving, the ray report and locate (their headers state it): floor(x / h) per axis, the
+// insertion's key (voxel_coord); false unless all three lie within +-2^30 (NaN and the infinities fail)
+__device__ __forceinline__ bool carve_key(const double* x, double h, int32_t* k) {
+#pragma clang fp contract(off)
+  bool defined = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double q = floor(x[a] / h);
+    const bool in = fabs(q) <= 0x1p30;
+    defined = defined && in;
+    k[a] = in ? (int32_t)q : 0;
+  }
+  return defined;
+}
+
 // Probe for the voxel that contains the key. Returns the record or nullptr.  The host keeps at least half of the slots
 // EMPTY (ensure_table), so a walk ends at an EMPTY slot long before it has seen every slot; the bound of mask + 1
 // probes only means that a broken invariant costs a wrong answer ("absent"), never a wave that spins forever.

@@ -11,8 +11,14 @@
 // to the fill launch, which finds its work by the LOCKED state: no scratch array between the two launches, and the fill
 // launch is as large as the LEVEL's table, not as the finer one (a map table is sized for what it may grow to: 2 M slots
 // for 29 000 voxels in the frame chain).
+//
+// Locate (include/vgicp_hip_map_locate.h) reads a level and lives here for the same build: its transform and its key are
+// stated without FMA.  Its two kernels are below the build's.
+#include <cstddef>
+
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
+#include "vgicp_locate_plan.h"
 
 namespace vgicp {
 namespace {
@@ -136,7 +142,112 @@ __global__ __launch_bounds__(256) void level_fill_kernel(const VoxelRecord* __re
   dst->state = SLOT_FULL;   // the kernel boundary publishes
 }
 
+// ---- locate (include/vgicp_hip_map_locate.h states the rule operation by operation; this restates it) ----
+// A workgroup has kLocateChunk points that take part, at one pose.  Their keys are made ONCE, by one lane each, and kept
+// in LDS; then the (point, cell) pairs of the chunk are dealt to the threads in turn, cell fastest, so that the lanes
+// of a wave hold 64 independent probes whatever the window's size (a window of one cell keeps 64 points in flight, one of
+// 3 969 cells 64 cells of one point), and neighbouring lanes probe neighbouring keys.  A thread's pair advances by
+// kLocateBlock pairs per turn: the step is split into the mixed radix (x, y, z, point) once, and a turn is three
+// additions with a carry each, no division.  A probe reads the 16-byte head of a record (find_voxel); a hit is one LDS
+// integer atomic on the window's histogram; the non-zero cells go to the plane as integer atomics without a return.
+// A first version: one probe per lane and turn, the waves of a CU's workgroups hide the probe's latency between them.
+static_assert(sizeof(vgicp_locate_best) == 160 && offsetof(vgicp_locate_best, pose) == 32, "vgicp_locate_best: 160 bytes");
+__global__ __launch_bounds__(kLocateBlock) void locate_score_kernel(LocateArgs a) {
+  __shared__ uint32_t hist[VGICP_LOCATE_MAX_CELLS];
+  __shared__ int4 keys[kLocateChunk];   // w: 1 where the key is defined
+  const uint32_t tid = threadIdx.x, pose = blockIdx.y;
+  for (uint32_t c = tid; c < a.cells; c += kLocateBlock) hist[c] = 0u;
+  const uint32_t first = blockIdx.x * kLocateChunk;
+  const uint32_t count = min(kLocateChunk, a.participants - first);
+  if (tid < kLocateChunk) {   // whole waves
+    bool skip = false;
+    if (tid < count) {
+      const double* m = a.poses + 16 * (size_t)pose;   // column-major 4 x 4
+      const double R[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
+      const double t[3] = {m[12], m[13], m[14]};
+      const double* p = a.points_aos + 3 * ((size_t)(first + tid) * a.stride);
+      double e[3];
+      int32_t k[3];
+      transform_point(R, t, p[0], p[1], p[2], e);
+      skip = !carve_key(e, a.voxel_size, k);
+      keys[tid] = make_int4(k[0], k[1], k[2], skip ? 0 : 1);
+    }
+    wave_count(a.skipped + pose, skip);
+  }
+  __syncthreads();
+  const uint32_t W = 2u * (uint32_t)a.window[0] + 1u, H = 2u * (uint32_t)a.window[1] + 1u, D = 2u * (uint32_t)a.window[2] + 1u;
+  uint32_t x = tid % W, r = tid / W;
+  uint32_t y = r % H;
+  r /= H;
+  uint32_t z = r % D, p = r / D;
+  const uint32_t sx = kLocateBlock % W, r1 = kLocateBlock / W, sy = r1 % H, r2 = r1 / H, sz = r2 % D, sp = r2 / D;
+  while (p < count) {
+    const int4 key = keys[p];
+    if (key.w != 0 &&
+        find_voxel(a.table, a.mask, key.x + ((int32_t)x - a.window[0]), key.y + ((int32_t)y - a.window[1]), key.z + ((int32_t)z - a.window[2])))
+      atomicAdd(&hist[(z * H + y) * W + x], 1u);
+    x += sx;
+    if (x >= W) { x -= W; ++y; }
+    y += sy;
+    if (y >= H) { y -= H; ++z; }
+    z += sz;
+    if (z >= D) { z -= D; ++p; }
+    p += sp;
+  }
+  __syncthreads();
+  uint32_t* plane = a.plane + (size_t)pose * a.cells;
+  for (uint32_t c = tid; c < a.cells; c += kLocateBlock) {
+    const uint32_t v = hist[c];
+    if (v) (void)__hip_atomic_fetch_add(plane + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// One workgroup per pose.  (hits << 32 | ~cell) orders the cells by hits and then by the LOWER index, so the maximum of
+// that word over the plane is the answer; a thread without a cell holds 0, which loses to every cell.
+__global__ __launch_bounds__(kLocateBlock) void locate_best_kernel(LocateArgs a, vgicp_locate_best* out) {
+  __shared__ unsigned long long parts[kLocateBlock / 64];
+  const uint32_t tid = threadIdx.x, pose = blockIdx.x;
+  const uint32_t* plane = a.plane + (size_t)pose * a.cells;
+  unsigned long long best = 0ull;
+  for (uint32_t c = tid; c < a.cells; c += kLocateBlock) {
+    const unsigned long long cand = ((unsigned long long)plane[c] << 32) | (unsigned long long)(0xFFFFFFFFu - c);
+    best = cand > best ? cand : best;
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned long long other = __shfl_down(best, d, 64);
+    best = other > best ? other : best;
+  }
+  if ((tid & 63u) == 0u) parts[tid >> 6] = best;
+  __syncthreads();
+  if (tid != 0u) return;
+  for (uint32_t w = 1; w < kLocateBlock / 64; ++w) best = parts[w] > best ? parts[w] : best;
+  const uint32_t cell = 0xFFFFFFFFu - (uint32_t)best;
+  const uint32_t W = 2u * (uint32_t)a.window[0] + 1u, H = 2u * (uint32_t)a.window[1] + 1u;
+  const int32_t d[3] = {(int32_t)(cell % W) - a.window[0], (int32_t)((cell / W) % H) - a.window[1],
+                        (int32_t)(cell / (W * H)) - a.window[2]};
+  const uint32_t skipped = a.skipped[pose];
+  vgicp_locate_best* o = out + pose;
+  o->hits = (uint32_t)(best >> 32);
+  o->cell = cell;
+  o->points = a.participants - skipped;
+  o->skipped = skipped;
+  o->reserved = 0u;
+  const double* m = a.poses + 16 * (size_t)pose;
+  for (int e = 0; e < 16; ++e) o->pose[e] = m[e];
+  for (int e = 0; e < 3; ++e) {
+    o->offset[e] = d[e];
+    o->pose[12 + e] = __dadd_rn(m[12 + e], __dmul_rn((double)d[e], a.voxel_size));   // one product, one sum
+  }
+}
+
 }  // namespace
+
+hipError_t launch_locate(hipStream_t s, const LocateArgs& a, uint32_t poses, void* best) {
+  if (a.participants != 0u)
+    counted_launch(locate_score_kernel, dim3(locate_chunks(a.participants), poses), dim3(kLocateBlock), 0, s, a);
+  counted_launch(locate_best_kernel, dim3(poses), dim3(kLocateBlock), 0, s, a, static_cast<vgicp_locate_best*>(best));
+  return hipGetLastError();
+}
 
 hipError_t launch_level_build(hipStream_t s, const VoxelRecord* fine, uint64_t fine_slots, VoxelRecord* coarse,
                               uint64_t coarse_slots, uint32_t* counters) {

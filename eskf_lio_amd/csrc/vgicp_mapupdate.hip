@@ -414,19 +414,7 @@ __global__ void evict_kernel(VoxelRecord* table, uint64_t slots, double voxel_si
 }
 
 // ---- free-space carving (include/vgicp_hip_map_carve.h states the rule operation by operation; this restates it) ----
-// floor(x / h) per axis, the insertion's key (voxel_coord); false unless all three lie within +-2^30 (NaN fails)
-__device__ __forceinline__ bool carve_key(const double* x, double h, int32_t* k) {
-#pragma clang fp contract(off)
-  bool defined = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double q = floor(x[a] / h);
-    const bool in = fabs(q) <= 0x1p30;
-    defined = defined && in;
-    k[a] = in ? (int32_t)q : 0;
-  }
-  return defined;
-}
+// (carve_key, the key that is DEFINED within +-2^30, is vgicp_device_fn.h's: vgicp_levels.hip's locate reads it too)
 // The voxel with this key, if it is FULL, takes `mark` into the low half of its spare word (no value comes back).  The
 // probe is find_voxel's: one 16-byte access per slot (key + state), linear, stops at EMPTY, skips TOMB and other keys.
 __device__ __forceinline__ void carve_mark(VoxelRecord* table, uint32_t mask, int32_t kx, int32_t ky, int32_t kz, bool shield) {

@@ -24,11 +24,16 @@
 // alignCoarseToFine / the optional keys registration.coarse_to_fine.{levels, coarse}: the cloud registered in stages against
 // the map's coarser levels (vgicp_hip_map_levels.h; LocalMap::setLevels keeps them), each stage from the pose of the one
 // before it — converges from guesses several voxels off, where align() settles in a neighbouring voxel.
+// yawFan / setLocate / locate / the optional keys registration.locate.{level, window, stride, yaws, keep}: a pose for a cloud
+// whose guess is metres and any yaw off (the first frame against a loaded map, a frame after a stall): a fan of yaws
+// scored over a window of whole-voxel shifts on a level of the map (vgicp_hip_map_locate.h), the best few followed up by
+// the coarse-to-fine chain, the winner chosen by evaluate().
 // pointReport / robustScaleFromQuantile: a cloud at a pose, point by point (vgicp_hip_points.h) — matched or not, |e|^2,
 // d^2, the weight this ICP's robust settings give the point — and order statistics of d^2 to choose a scale or gate by.
 #ifndef ESKF_LIO_SHIM_REGISTRATION_HPP_
 #define ESKF_LIO_SHIM_REGISTRATION_HPP_
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -45,6 +50,7 @@
 #include "../vgicp_hip_prior.h"
 #include "../vgicp_hip_points.h"
 #include "../vgicp_hip_map_levels.h"
+#include "../vgicp_hip_map_locate.h"
 
 // referenced weakly, as LocalMap.hpp references the raw-point store's entry points: a program that links a stand-in of
 // the C ABI without them, or that does not link libvgicp_hip_prior.so beside libvgicp_hip.so, still links, and
@@ -55,6 +61,8 @@
 #pragma weak vgicp_points_resident
 // ... and libvgicp_hip_map_levels.so's: ICP::alignCoarseToFine says so
 #pragma weak vgicp_align_resident_levels
+// ... and libvgicp_hip_map_locate.so's: ICP::locate says so
+#pragma weak vgicp_locate_resident
 
 namespace ESKF_LIO
 {
@@ -79,6 +87,17 @@ struct Matrix6d
 };
 #endif
 
+// What ICP::locate searches and follows up (ICP::setLocate; registration.locate.* in the YAML file).
+struct LocateOptions
+{
+  int level = 3;                            // the level of the map the fan is scored on
+  std::array<int, 3> window{{4, 4, 1}};     // half-widths of the window of shifts, in voxels of that level
+  unsigned stride = 1;                      // every stride-th point of the cloud takes part in the search
+  int yaws = 64;                            // poses of the yaw fan, at most VGICP_LOCATE_MAX_POSES
+  int keep = 4;                             // candidates followed up by the chain, at most 8
+  std::vector<int> schedule;                // of that chain; empty: the ICP's coarse-to-fine schedule
+};
+
 // The keys ICP's YAML constructor reads (config/hilti_config.yaml:50-53).
 struct RegistrationConfig
 {
@@ -97,6 +116,8 @@ struct RegistrationConfig
   int coarseMaxIteration = 30;
   double coarseTranslationSquaredThreshold = 1.0e-4;
   double coarseCosineThreshold = 0.999;
+  // locate (vgicp_hip_map_locate.h; not in the reference's file): registration.locate.{level, window, stride, yaws, keep}
+  LocateOptions locate;
 
   // registration.robust_kernel: none | huber | cauchy
   static int robustKernelFromName(const std::string & name)
@@ -135,6 +156,7 @@ public:
     setCoarseToFine(
       config.coarseToFineLevels, config.coarseMaxIteration, config.coarseTranslationSquaredThreshold,
       config.coarseCosineThreshold);
+    setLocate(config.locate);
   }
 
 #if defined(ESKF_LIO_SHIM_HAVE_YAML)
@@ -165,6 +187,26 @@ public:
       }
       setCoarseToFine(
         c.coarseToFineLevels, c.coarseMaxIteration, c.coarseTranslationSquaredThreshold, c.coarseCosineThreshold);
+    }
+    if (reg["locate"].IsDefined()) {
+      const YAML::Node loc = reg["locate"];
+      // an empty window and a stride, yaws or keep of 0 mean the default, as chunk_iterations: 0 does
+      if (loc["level"].IsDefined()) {c.locate.level = loc["level"].as<int>();}
+      if (loc["window"].IsDefined()) {
+        const std::vector<int> w = loc["window"].as<std::vector<int>>();
+        if (!w.empty() && w.size() != 3) {
+          throw std::invalid_argument("registration.locate.window must have three half-widths");
+        }
+        if (!w.empty()) {c.locate.window = {{w[0], w[1], w[2]}};}
+      }
+      if (loc["stride"].IsDefined()) {
+        const int stride = loc["stride"].as<int>();
+        if (stride < 0) {throw std::invalid_argument("registration.locate.stride must be >= 1");}
+        if (stride > 0) {c.locate.stride = static_cast<unsigned>(stride);}
+      }
+      if (loc["yaws"].IsDefined() && loc["yaws"].as<int>() != 0) {c.locate.yaws = loc["yaws"].as<int>();}
+      if (loc["keep"].IsDefined() && loc["keep"].as<int>() != 0) {c.locate.keep = loc["keep"].as<int>();}
+      setLocate(c.locate);
     }
   }
 #endif
@@ -212,41 +254,7 @@ public:
     applyPrior(ctx);
     lastUsedResidentScan_ = residentScanOrUpload(ctx, cloud, "alignCoarseToFine");
     shim::TraceScope tsCall(shim::Trace::AlignCall);
-    const size_t stages = schedule.size();
-    std::vector<int32_t> levels(schedule.begin(), schedule.end());
-    std::vector<vgicp_params> params(stages, paramsOf());
-    for (size_t i = 0; i + 1 < stages; ++i) {
-      params[i].max_iteration = coarseMaxIteration_;
-      params[i].translation_sq_threshold = coarseTranslationSquaredThreshold_;
-      params[i].cosine_threshold = coarseCosineThreshold_;
-    }
-    std::vector<std::vector<uint64_t>> counts(stages);
-    std::vector<vgicp_stats> stats(stages);
-    for (size_t i = 0; i < stages; ++i) {
-      counts[i].assign(static_cast<size_t>(params[i].max_iteration > 0 ? params[i].max_iteration : 1), 0);
-      stats[i] = vgicp_stats{};
-      stats[i].corr_count = counts[i].data();
-    }
-    double pose[16];
-    const int rc = vgicp_align_resident_levels(
-      ctx, shim::poseData(guess), stages, levels.data(), params.data(), pose, stats.data());
-    shim::check(ctx, rc, "vgicp_align_resident_levels");
-    lastStages_.assign(stages, StageStats{});
-    for (size_t i = 0; i < stages; ++i) {
-      StageStats & s = lastStages_[i];
-      s.level = schedule[i];
-      s.stats.iterations = stats[i].iterations;
-      s.stats.converged = stats[i].converged != 0;
-      s.stats.seconds = stats[i].seconds;
-      s.stats.deviceSeconds = stats[i].device_seconds;
-      counts[i].resize(static_cast<size_t>(stats[i].iterations));
-      s.stats.correspondenceCounts = counts[i];
-    }
-    lastStats_ = lastStages_.back().stats;
-    if (!lastStats_.converged) {
-      std::cout << "ICP not converged!\n";
-    }
-    return shim::poseFromData(pose);
+    return chainResidentScan(ctx, guess, schedule);
   }
   // ... with the schedule this ICP was given (setCoarseToFine, registration.coarse_to_fine.levels); none: align()
   Isometry3d alignCoarseToFine(const PointCloud & cloud, const LocalMap & localMap, const Isometry3d & guess)
@@ -564,6 +572,144 @@ public:
     return evaluateResidentScan(ctx, poses);
   }
 
+  // ---- locate (vgicp_hip_map_locate.h): a pose for a cloud that has no guess an align converges from ----
+  using LocateOptions = ESKF_LIO::LocateOptions;
+
+  // count poses about the sensor's position at `guess`: pose j is [Rz(2 pi j / count) R_guess | t_guess], a rotation about
+  // the world's z through that position.
+  static std::vector<Isometry3d> yawFan(const Isometry3d & guess, int count)
+  {
+    if (count < 1) {throw std::invalid_argument("ICP::yawFan: count < 1");}
+    const double * g = shim::poseData(guess);
+    std::vector<Isometry3d> fan;
+    fan.reserve(static_cast<size_t>(count));
+    for (int j = 0; j < count; ++j) {
+      const double a = 2.0 * 3.14159265358979323846 * static_cast<double>(j) / static_cast<double>(count);
+      const double c = std::cos(a), s = std::sin(a);
+      double m[16];
+      for (int e = 0; e < 16; ++e) {m[e] = g[e];}
+      for (int col = 0; col < 3; ++col) {          // Rz(a) R: rows x and y of every column of R
+        m[0 + 4 * col] = c * g[0 + 4 * col] - s * g[1 + 4 * col];
+        m[1 + 4 * col] = s * g[0 + 4 * col] + c * g[1 + 4 * col];
+      }
+      fan.push_back(shim::poseFromData(m));
+    }
+    return fan;
+  }
+
+  // What locate() searches and follows up.  Throws std::invalid_argument for anything the library would refuse, and
+  // changes nothing then.  An empty schedule means this ICP's coarse-to-fine schedule (setCoarseToFine).
+  void setLocate(const LocateOptions & options)
+  {
+    if (options.level < 0 || options.level > VGICP_LEVELS_MAX) {
+      throw std::invalid_argument("ICP::setLocate: level must be 0 .. VGICP_LEVELS_MAX");
+    }
+    long cells = 1;
+    for (const int w : options.window) {
+      if (w < 0 || w > VGICP_LOCATE_MAX_HALF_WIDTH) {
+        throw std::invalid_argument("ICP::setLocate: a half-width of the window must be 0 .. VGICP_LOCATE_MAX_HALF_WIDTH");
+      }
+      cells *= 2 * w + 1;
+    }
+    if (cells > VGICP_LOCATE_MAX_CELLS) {
+      throw std::invalid_argument("ICP::setLocate: the window has more than VGICP_LOCATE_MAX_CELLS cells");
+    }
+    if (options.stride < 1) {throw std::invalid_argument("ICP::setLocate: stride < 1");}
+    if (options.yaws < 1 || options.yaws > VGICP_LOCATE_MAX_POSES) {
+      throw std::invalid_argument("ICP::setLocate: yaws must be 1 .. VGICP_LOCATE_MAX_POSES");
+    }
+    if (options.keep < 1 || options.keep > kLocateKeepMax) {throw std::invalid_argument("ICP::setLocate: keep must be 1 .. 8");}
+    checkSchedule(options.schedule);
+    locate_ = options;
+  }
+  const LocateOptions & locateOptions() const {return locate_;}
+
+  // One candidate of the last locate(): a pose of the fan, what vgicp_locate_resident found for it, where the chain from
+  // there ended and how the cloud scores at that end.
+  struct LocateCandidate
+  {
+    int poseIndex = 0;               // in the yaw fan
+    uint32_t hits = 0;               // of the pose's best cell
+    std::array<int, 3> offset{};     // that cell's shift, in voxels of the level
+    Isometry3d start;                // the fan's pose moved by the shift: where the chain started
+    Isometry3d pose;                 // where it ended
+    Evaluation evaluation;           // of the cloud at `pose`
+  };
+
+  // Finds a pose for `cloud` from a guess that may be metres and any yaw off: ONE call of vgicp_locate_resident on the yaw
+  // fan about `guess`; the poses ranked by the hits of their best cell (descending, ties to the lower index); the first
+  // `keep` of them followed up by the coarse-to-fine chain (alignCoarseToFine's stages) from the located pose; the ends
+  // scored by one evaluate; the one with the most correspondences (ties: the lower cost, then the better rank) returned.
+  // The map must keep the level searched and the levels of the schedule (LocalMap::setLevels).  The cloud is the
+  // resident scan when it still is what CloudPreprocessor::process left on the device, else ONE upload of it.
+  // lastLocation() lists the candidates in rank order, lastLocationWinner() the index of the one returned; lastStats()
+  // and lastStages() describe the last chain run, lastEvaluation() the winner.
+  Isometry3d locate(const PointCloud & cloud, const LocalMap & localMap, const Isometry3d & guess)
+  {
+    if (!vgicp_locate_resident) {
+      throw std::runtime_error(
+              "ICP::locate: the linked vgicp module has no vgicp_locate_resident (libvgicp_hip_map_locate.so)");
+    }
+    if (!vgicp_align_resident_levels) {
+      throw std::runtime_error(
+              "ICP::locate: the linked vgicp module has no vgicp_align_resident_levels (libvgicp_hip_map_levels.so)");
+    }
+    const std::vector<int> & schedule = locate_.schedule.empty() ? schedule_ : locate_.schedule;
+    if (schedule.empty()) {
+      throw std::invalid_argument("ICP::locate: no schedule (LocateOptions::schedule or setCoarseToFine)");
+    }
+    vgicp_ctx * ctx = localMap.context();
+    applyRobust(ctx);
+    applyPrior(ctx);
+    lastUsedResidentScan_ = residentScanOrUpload(ctx, cloud, "locate");
+    shim::TraceScope tsCall(shim::Trace::AlignCall);
+    const std::vector<Isometry3d> fan = yawFan(guess, locate_.yaws);
+    const size_t k = fan.size();
+    std::vector<double> in(16 * k);
+    for (size_t h = 0; h < k; ++h) {
+      const double * g = shim::poseData(fan[h]);
+      for (int e = 0; e < 16; ++e) {in[16 * h + static_cast<size_t>(e)] = g[e];}
+    }
+    vgicp_locate_params params{};
+    params.level = locate_.level;
+    for (size_t a = 0; a < 3; ++a) {params.window[a] = locate_.window[a];}
+    params.stride = locate_.stride;
+    std::vector<vgicp_locate_best> best(k);
+    shim::check(
+      ctx, vgicp_locate_resident(ctx, in.data(), k, &params, best.data(), nullptr, nullptr), "vgicp_locate_resident");
+    std::vector<size_t> order(k);
+    for (size_t h = 0; h < k; ++h) {order[h] = h;}
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {return best[a].hits > best[b].hits;});
+    const size_t keep = std::min(k, static_cast<size_t>(locate_.keep));
+    std::vector<LocateCandidate> found(keep);
+    std::vector<Isometry3d> ends(keep);
+    for (size_t c = 0; c < keep; ++c) {
+      const vgicp_locate_best & b = best[order[c]];
+      found[c].poseIndex = static_cast<int>(order[c]);
+      found[c].hits = b.hits;
+      for (size_t a = 0; a < 3; ++a) {found[c].offset[a] = b.offset[a];}
+      found[c].start = shim::poseFromData(b.pose);
+      found[c].pose = ends[c] = chainResidentScan(ctx, found[c].start, schedule);
+    }
+    const std::vector<Evaluation> scores = evaluateResidentScan(ctx, ends);
+    size_t winner = 0;
+    for (size_t c = 0; c < keep; ++c) {
+      found[c].evaluation = scores[c];
+      const Evaluation & w = scores[winner];
+      if (scores[c].correspondences > w.correspondences ||
+        (scores[c].correspondences == w.correspondences && scores[c].cost < w.cost))
+      {
+        winner = c;
+      }
+    }
+    lastLocation_ = found;
+    lastLocationWinner_ = winner;
+    lastEvaluation_ = scores[winner];
+    return found[winner].pose;
+  }
+  const std::vector<LocateCandidate> & lastLocation() const {return lastLocation_;}     // of the last locate(), in rank order
+  size_t lastLocationWinner() const {return lastLocationWinner_;}
+
   // A cloud at a pose, point by point (one call of vgicp_points_resident).
   struct PointReport
   {
@@ -828,6 +974,47 @@ private:
     return true;
   }
 
+  // vgicp_align_resident_levels on whatever scan is resident, over a checked, non-empty schedule: the stages' parameters,
+  // the call, the per-stage report (alignCoarseToFine, and locate once per candidate)
+  Isometry3d chainResidentScan(vgicp_ctx * ctx, const Isometry3d & guess, const std::vector<int> & schedule)
+  {
+    const size_t stages = schedule.size();
+    std::vector<int32_t> levels(schedule.begin(), schedule.end());
+    std::vector<vgicp_params> params(stages, paramsOf());
+    for (size_t i = 0; i + 1 < stages; ++i) {
+      params[i].max_iteration = coarseMaxIteration_;
+      params[i].translation_sq_threshold = coarseTranslationSquaredThreshold_;
+      params[i].cosine_threshold = coarseCosineThreshold_;
+    }
+    std::vector<std::vector<uint64_t>> counts(stages);
+    std::vector<vgicp_stats> stats(stages);
+    for (size_t i = 0; i < stages; ++i) {
+      counts[i].assign(static_cast<size_t>(params[i].max_iteration > 0 ? params[i].max_iteration : 1), 0);
+      stats[i] = vgicp_stats{};
+      stats[i].corr_count = counts[i].data();
+    }
+    double pose[16];
+    const int rc = vgicp_align_resident_levels(
+      ctx, shim::poseData(guess), stages, levels.data(), params.data(), pose, stats.data());
+    shim::check(ctx, rc, "vgicp_align_resident_levels");
+    lastStages_.assign(stages, StageStats{});
+    for (size_t i = 0; i < stages; ++i) {
+      StageStats & s = lastStages_[i];
+      s.level = schedule[i];
+      s.stats.iterations = stats[i].iterations;
+      s.stats.converged = stats[i].converged != 0;
+      s.stats.seconds = stats[i].seconds;
+      s.stats.deviceSeconds = stats[i].device_seconds;
+      counts[i].resize(static_cast<size_t>(stats[i].iterations));
+      s.stats.correspondenceCounts = counts[i];
+    }
+    lastStats_ = lastStages_.back().stats;
+    if (!lastStats_.converged) {
+      std::cout << "ICP not converged!\n";
+    }
+    return shim::poseFromData(pose);
+  }
+
   // vgicp_evaluate_resident on whatever scan is resident (1 <= poses.size() <= VGICP_EVAL_MAX)
   static std::vector<Evaluation> evaluateResidentScan(vgicp_ctx * ctx, const std::vector<Isometry3d> & poses)
   {
@@ -863,6 +1050,10 @@ private:
   double coarseTranslationSquaredThreshold_ = 1.0e-4;
   double coarseCosineThreshold_ = 0.999;
   std::vector<StageStats> lastStages_;
+  static constexpr int kLocateKeepMax = 8;
+  LocateOptions locate_;               // of locate(cloud, map, guess)
+  std::vector<LocateCandidate> lastLocation_;
+  size_t lastLocationWinner_ = 0;
   bool priorOn_ = false;
   std::array<double, 16> priorPose_{};
   std::array<double, 36> priorInformation_{};
