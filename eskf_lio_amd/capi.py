@@ -50,49 +50,37 @@ BATCH_MAX = 64
 EVALUATE_EXPORTS = ("vgicp_evaluate_resident",)
 EVAL_MAX = 64
 
-# every symbol include/vgicp_hip_prior.h declares: an extension header whose two entry points live in a library of their
-# own beside the module (PRIOR_LIB_PATH), so that libvgicp_hip.so exports exactly the lists above
+# The entry points of the later extension headers live in small libraries of their own beside the module, so that
+# libvgicp_hip.so exports exactly the lists above: include/vgicp_hip_<name>.h is libvgicp_hip_<name>.so (side_lib_path),
+# for every name of SIDE_EXPORTS (csrc/Makefile's SIDE).  Each tuple: every symbol its header declares
 PRIOR_EXPORTS = ("vgicp_set_pose_prior", "vgicp_pose_prior_chart")
-PRIOR_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_prior.so")
-
-# every symbol include/vgicp_hip_points.h declares: likewise an entry point in a library of its own beside the module
 POINTS_EXPORTS = ("vgicp_points_resident",)
-POINTS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_points.so")
+MAP_GATED_EXPORTS = ("vgicp_map_insert_resident_gated", "vgicp_map_insert_resident_gated_async", "vgicp_map_gated_totals")
+MAP_CARVE_EXPORTS = ("vgicp_map_carve_resident", "vgicp_map_carve_resident_async", "vgicp_map_carve_totals")
+MAP_RAYS_EXPORTS = ("vgicp_rays_resident",)
+SEARCH_REPORT_EXPORTS = ("vgicp_prepare_search_report",)   # a test hook
+MAP_LEVELS_EXPORTS = ("vgicp_map_levels_build", "vgicp_map_level_size", "vgicp_map_level_export", "vgicp_align_resident_levels")
+MAP_LOCATE_EXPORTS = ("vgicp_locate_resident",)
+SIDE_EXPORTS = {"prior": PRIOR_EXPORTS, "points": POINTS_EXPORTS, "map_gated": MAP_GATED_EXPORTS,
+                "map_carve": MAP_CARVE_EXPORTS, "map_rays": MAP_RAYS_EXPORTS, "search_report": SEARCH_REPORT_EXPORTS,
+                "map_levels": MAP_LEVELS_EXPORTS, "map_locate": MAP_LOCATE_EXPORTS}
+
+
+def side_lib_path(name: str) -> str:
+    return os.path.join(os.path.dirname(LIB_PATH), f"libvgicp_hip_{name}.so")
+
+
 POINT_QUANTILES_MAX = 16
 POINT_MATCHED, POINT_NEGATIVE, POINT_NOT_FINITE = 1, 2, 4
-
-# every symbol include/vgicp_hip_map_gated.h declares: likewise, three entry points in a library of their own
-MAP_GATED_EXPORTS = ("vgicp_map_insert_resident_gated", "vgicp_map_insert_resident_gated_async", "vgicp_map_gated_totals")
-MAP_GATED_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_gated.so")
-
-# every symbol include/vgicp_hip_map_carve.h declares: likewise, three entry points in a library of their own
-MAP_CARVE_EXPORTS = ("vgicp_map_carve_resident", "vgicp_map_carve_resident_async", "vgicp_map_carve_totals")
-MAP_CARVE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_carve.so")
 CARVE_MAX_STEPS = 4096
-
-# every symbol include/vgicp_hip_map_rays.h declares: likewise, one entry point in a library of its own
-MAP_RAYS_EXPORTS = ("vgicp_rays_resident",)
-MAP_RAYS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_rays.so")
 RAYS_MAX_POSES = 64
 RAY_NO_RAY, RAY_OPEN, RAY_OWN, RAY_BEHIND, RAY_CONFIRMED, RAY_BLOCKED, RAY_NEAR = range(7)
 RAY_CLASS_NAMES = ("no_ray", "open", "own", "behind", "confirmed", "blocked", "near")
-
-# every symbol include/vgicp_hip_map_levels.h declares: likewise, four entry points in a library of their own
-MAP_LEVELS_EXPORTS = ("vgicp_map_levels_build", "vgicp_map_level_size", "vgicp_map_level_export", "vgicp_align_resident_levels")
-MAP_LEVELS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_levels.so")
 LEVELS_MAX = 4
 LEVEL_STAGES_MAX = 8
-
-# every symbol include/vgicp_hip_map_locate.h declares: likewise, one entry point in a library of its own
-MAP_LOCATE_EXPORTS = ("vgicp_locate_resident",)
-MAP_LOCATE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_map_locate.so")
 LOCATE_MAX_POSES = 64
 LOCATE_MAX_HALF_WIDTH = 32
 LOCATE_MAX_CELLS = 4096
-
-# every symbol include/vgicp_hip_search_report.h declares: likewise, one entry point (a test hook) in a library of its own
-SEARCH_REPORT_EXPORTS = ("vgicp_prepare_search_report",)
-SEARCH_REPORT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libvgicp_hip_search_report.so")
 # the fourteen paths of the neighbour search, in the order of the struct's fields (and of the kernel's bits)
 SEARCH_PATHS = ("home", "crowded", "no_own_cell", "window_is_k", "whole_scan", "clipped", "open2", "open1", "leaf",
                 "finest", "compacted", "spilled", "waited", "reranked")
@@ -297,6 +285,84 @@ class RayReport:
     device_seconds: float
 
 
+# every entry point's argument types, the module's own and the side libraries'; each returns int but those of RESTYPES
+vp, dp, ip, sz = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_size_t
+PROTOTYPES = {
+    "vgicp_abi_version": [],
+    "vgicp_create": [C.c_int, C.POINTER(vp)],
+    "vgicp_create_multi": [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)],
+    "vgicp_destroy": [vp],
+    "vgicp_last_error": [vp],
+    "vgicp_device_info": [vp, C.c_char_p, sz, ip, C.POINTER(C.c_uint64)],
+    "vgicp_get_counter": [vp, C.c_int, C.POINTER(C.c_uint64)],
+    "vgicp_map_reset": [vp, C.c_double, sz],
+    "vgicp_map_upsert": [vp, sz, ip, dp, dp],
+    "vgicp_map_erase": [vp, sz, ip],
+    "vgicp_map_size": [vp, C.POINTER(sz), C.POINTER(sz)],
+    "vgicp_map_insert_scan": [vp, sz, dp, dp, dp, sz, C.POINTER(sz)],
+    "vgicp_map_insert_resident": [vp, dp, sz, C.POINTER(sz)],
+    "vgicp_map_evict": [vp, dp, C.c_double, C.POINTER(sz)],
+    "vgicp_map_export": [vp, sz, ip, dp, dp, C.POINTER(C.c_uint64), C.POINTER(sz)],
+    "vgicp_align": [vp, sz, dp, dp, dp, C.POINTER(Params), dp, C.POINTER(Stats)],
+    "vgicp_scan_upload": [vp, sz, dp, dp],
+    "vgicp_align_resident": [vp, dp, C.POINTER(Params), dp, C.POINTER(Stats)],
+    "vgicp_accumulate": [vp, sz, dp, dp, dp, dp, dp, C.POINTER(C.c_uint64)],
+    "vgicp_solve_step": [vp, dp, dp, C.c_double, C.c_double, C.c_uint32, dp, dp, ip, ip],
+    "vgicp_match": [vp, sz, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_uint64), C.POINTER(sz)],
+    "vgicp_voxel_index": [vp, sz, dp, ip],
+    "vgicp_scan_prepare": [vp, sz, dp, dp, sz, dp, dp, C.c_double, C.c_int, C.POINTER(sz), C.POINTER(C.c_int64)],
+    "vgicp_scan_download": [vp, sz, dp, dp, C.POINTER(sz)],
+    "vgicp_scan_prepare_async": [vp, sz, dp, dp, sz, dp, dp, C.c_double, C.c_int],
+    "vgicp_sweep_stage": [vp, sz, dp, dp, C.POINTER(C.c_uint64)],
+    "vgicp_sweep_stage_cloud2": [vp, sz, vp, sz, sz, sz, sz, sz, C.POINTER(C.c_uint64)],
+    "vgicp_sweep_unstage": [vp, C.c_uint64],
+    "vgicp_scan_fetch_begin": [vp, C.POINTER(sz)],
+    "vgicp_scan_fetch_end": [vp, sz, dp, dp, C.POINTER(sz)],
+    "vgicp_scan_fetch_sums": [vp, C.POINTER(C.c_uint64)],
+    "vgicp_peer_status": [vp],
+    "vgicp_scan_prepare_staged_async": [vp, C.c_uint64, sz, dp, dp, C.c_double, C.c_int],
+    "vgicp_scan_info": [vp, C.POINTER(sz), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)],
+    "vgicp_map_insert_resident_async": [vp, dp, sz],
+    "vgicp_get_frame_stats": [vp, C.POINTER(FrameStats), C.c_int],
+    "vgicp_set_option": [vp, C.c_int, C.c_int],
+    "vgicp_host_register": [vp, vp, sz],
+    "vgicp_host_unregister": [vp, vp],
+    "vgicp_deskew": [vp, sz, dp, dp, sz, dp, C.POINTER(C.c_int64)],
+    "vgicp_preprocess": [vp, sz, dp, C.c_double, C.c_int, sz, dp, dp, C.POINTER(C.c_uint64), C.POINTER(sz)],
+    "vgicp_comm_unique_id": [vp, vp],
+    "vgicp_comm_init": [vp, C.c_int, C.c_int, vp],
+    "vgicp_comm_destroy": [vp],
+    "vgicp_peer_export": [vp, vp],
+    "vgicp_peer_connect": [vp, C.c_int, C.c_int, vp],
+    "vgicp_peer_disconnect": [vp],
+    "vgicp_map_points_size": [vp, C.POINTER(sz), C.POINTER(sz)],
+    "vgicp_map_points_export": [vp, sz, ip, dp, C.POINTER(sz)],
+    "vgicp_align_resident_batch": [vp, sz, dp, C.POINTER(Params), dp, C.POINTER(BatchStats)],
+    "vgicp_align_batch_width": [vp, C.POINTER(sz)],
+    "vgicp_evaluate_resident": [vp, sz, dp, C.POINTER(Evaluation), C.POINTER(EvalStats)],
+    "vgicp_set_pose_prior": [vp, dp, dp],
+    "vgicp_pose_prior_chart": [dp, dp, dp, dp],
+    "vgicp_points_resident": [vp, dp, sz, dp, dp, dp, C.POINTER(C.c_uint8), sz, dp, C.POINTER(PointSummary),
+                             C.POINTER(PointStats)],
+    "vgicp_map_insert_resident_gated": [vp, dp, sz, C.c_double, sz, C.POINTER(C.c_uint8), C.POINTER(GatedInsertStats)],
+    "vgicp_map_insert_resident_gated_async": [vp, dp, sz, C.c_double],
+    "vgicp_map_gated_totals": [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "vgicp_map_carve_resident": [vp, dp, C.POINTER(CarveParams), sz, ip, C.POINTER(sz), C.POINTER(CarveStats)],
+    "vgicp_map_carve_resident_async": [vp, dp, C.POINTER(CarveParams)],
+    "vgicp_map_carve_totals": [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "vgicp_rays_resident": [vp, dp, sz, C.POINTER(RayParams), C.POINTER(RayOutputs), C.POINTER(RayCounts),
+                           C.POINTER(RayStats)],
+    "vgicp_map_levels_build": [vp, C.c_int, C.POINTER(LevelsStats)],
+    "vgicp_map_level_size": [vp, C.c_int, C.POINTER(sz), C.POINTER(sz), dp],
+    "vgicp_map_level_export": [vp, C.c_int, sz, ip, dp, dp, C.POINTER(C.c_uint64), C.POINTER(sz)],
+    "vgicp_align_resident_levels": [vp, dp, sz, ip, C.POINTER(Params), dp, C.POINTER(Stats)],
+    "vgicp_locate_resident": [vp, dp, sz, C.POINTER(LocateParams), C.POINTER(LocateBest), C.POINTER(C.c_uint32),
+                             C.POINTER(LocateStats)],
+    "vgicp_prepare_search_report": [vp, C.POINTER(SearchReport)],
+}
+RESTYPES = {"vgicp_last_error": C.c_char_p, "vgicp_peer_status": C.c_char_p}
+del vp, dp, ip, sz
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -311,133 +377,19 @@ def load_library() -> C.CDLL:
             "(python -c 'import __graft_entry__ as g; g.build()' or make -C eskf_lio_amd/csrc). "
             "There is no CPU fallback for this path.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    sz = C.c_size_t
-    lib.vgicp_abi_version.restype = C.c_int
-    lib.vgicp_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.vgicp_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    lib.vgicp_destroy.argtypes = [vp]
-    lib.vgicp_last_error.argtypes = [vp]
-    lib.vgicp_last_error.restype = C.c_char_p
-    lib.vgicp_device_info.argtypes = [vp, C.c_char_p, sz, ip, C.POINTER(C.c_uint64)]
-    lib.vgicp_get_counter.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
-    lib.vgicp_map_reset.argtypes = [vp, C.c_double, sz]
-    lib.vgicp_map_upsert.argtypes = [vp, sz, ip, dp, dp]
-    lib.vgicp_map_erase.argtypes = [vp, sz, ip]
-    lib.vgicp_map_size.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
-    lib.vgicp_map_insert_scan.argtypes = [vp, sz, dp, dp, dp, sz, C.POINTER(sz)]
-    lib.vgicp_map_insert_resident.argtypes = [vp, dp, sz, C.POINTER(sz)]
-    lib.vgicp_map_evict.argtypes = [vp, dp, C.c_double, C.POINTER(sz)]
-    lib.vgicp_map_export.argtypes = [vp, sz, ip, dp, dp, C.POINTER(C.c_uint64), C.POINTER(sz)]
-    lib.vgicp_align.argtypes = [vp, sz, dp, dp, dp, C.POINTER(Params), dp, C.POINTER(Stats)]
-    lib.vgicp_scan_upload.argtypes = [vp, sz, dp, dp]
-    lib.vgicp_align_resident.argtypes = [vp, dp, C.POINTER(Params), dp, C.POINTER(Stats)]
-    lib.vgicp_accumulate.argtypes = [vp, sz, dp, dp, dp, dp, dp, C.POINTER(C.c_uint64)]
-    lib.vgicp_solve_step.argtypes = [vp, dp, dp, C.c_double, C.c_double, C.c_uint32, dp, dp, ip, ip]
-    lib.vgicp_match.argtypes = [vp, sz, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_uint64), C.POINTER(sz)]
-    lib.vgicp_voxel_index.argtypes = [vp, sz, dp, ip]
-    lib.vgicp_scan_prepare.argtypes = [vp, sz, dp, dp, sz, dp, dp, C.c_double, C.c_int, C.POINTER(sz),
-                                       C.POINTER(C.c_int64)]
-    lib.vgicp_scan_download.argtypes = [vp, sz, dp, dp, C.POINTER(sz)]
-    lib.vgicp_scan_prepare_async.argtypes = [vp, sz, dp, dp, sz, dp, dp, C.c_double, C.c_int]
-    lib.vgicp_sweep_stage.argtypes = [vp, sz, dp, dp, C.POINTER(C.c_uint64)]
-    lib.vgicp_sweep_stage_cloud2.argtypes = [vp, sz, vp, sz, sz, sz, sz, sz, C.POINTER(C.c_uint64)]
-    lib.vgicp_sweep_unstage.argtypes = [vp, C.c_uint64]
-    lib.vgicp_scan_fetch_begin.argtypes = [vp, C.POINTER(sz)]
-    lib.vgicp_scan_fetch_end.argtypes = [vp, sz, dp, dp, C.POINTER(sz)]
-    lib.vgicp_scan_fetch_sums.argtypes = [vp, C.POINTER(C.c_uint64)]
-    lib.vgicp_peer_status.argtypes = [vp]
-    lib.vgicp_peer_status.restype = C.c_char_p
-    lib.vgicp_scan_prepare_staged_async.argtypes = [vp, C.c_uint64, sz, dp, dp, C.c_double, C.c_int]
-    lib.vgicp_scan_info.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
-    lib.vgicp_map_insert_resident_async.argtypes = [vp, dp, sz]
-    lib.vgicp_get_frame_stats.argtypes = [vp, C.POINTER(FrameStats), C.c_int]
-    lib.vgicp_set_option.argtypes = [vp, C.c_int, C.c_int]
-    lib.vgicp_host_register.argtypes = [vp, vp, sz]
-    lib.vgicp_host_unregister.argtypes = [vp, vp]
-    lib.vgicp_deskew.argtypes = [vp, sz, dp, dp, sz, dp, C.POINTER(C.c_int64)]
-    lib.vgicp_preprocess.argtypes = [vp, sz, dp, C.c_double, C.c_int, sz, dp, dp, C.POINTER(C.c_uint64),
-                                     C.POINTER(sz)]
-    lib.vgicp_comm_unique_id.argtypes = [vp, vp]
-    lib.vgicp_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
-    lib.vgicp_comm_destroy.argtypes = [vp]
-    lib.vgicp_peer_export.argtypes = [vp, vp]
-    lib.vgicp_peer_connect.argtypes = [vp, C.c_int, C.c_int, vp]
-    lib.vgicp_peer_disconnect.argtypes = [vp]
-    lib.vgicp_map_points_size.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
-    lib.vgicp_map_points_export.argtypes = [vp, sz, ip, dp, C.POINTER(sz)]
-    lib.vgicp_align_resident_batch.argtypes = [vp, sz, dp, C.POINTER(Params), dp, C.POINTER(BatchStats)]
-    lib.vgicp_align_batch_width.argtypes = [vp, C.POINTER(sz)]
-    lib.vgicp_evaluate_resident.argtypes = [vp, sz, dp, C.POINTER(Evaluation), C.POINTER(EvalStats)]
-    for name in EXPORTS + MAP_POINTS_EXPORTS + BATCH_EXPORTS + EVALUATE_EXPORTS:
-        fn = getattr(lib, name)
-        if name not in ("vgicp_last_error", "vgicp_peer_status"):
-            fn.restype = C.c_int
-    # the pose prior's library, where it was built beside the module (a module of an earlier commit, loaded through
-    # VGICP_LIB_PATH for a comparison, has none): its two entry points are reached through the same object
-    if os.path.exists(PRIOR_LIB_PATH):
-        prior = C.CDLL(PRIOR_LIB_PATH, mode=C.RTLD_GLOBAL)
-        prior.vgicp_set_pose_prior.argtypes = [vp, dp, dp]
-        prior.vgicp_pose_prior_chart.argtypes = [dp, dp, dp, dp]
-        for name in PRIOR_EXPORTS:
-            getattr(prior, name).restype = C.c_int
-            setattr(lib, name, getattr(prior, name))
-    # the per-point report's library, likewise
-    if os.path.exists(POINTS_LIB_PATH):
-        points = C.CDLL(POINTS_LIB_PATH, mode=C.RTLD_GLOBAL)
-        points.vgicp_points_resident.argtypes = [vp, dp, sz, dp, dp, dp, C.POINTER(C.c_uint8), sz, dp,
-                                                 C.POINTER(PointSummary), C.POINTER(PointStats)]
-        points.vgicp_points_resident.restype = C.c_int
-        lib.vgicp_points_resident = points.vgicp_points_resident
-    # the gated map insertion's library, likewise
-    if os.path.exists(MAP_GATED_LIB_PATH):
-        gated = C.CDLL(MAP_GATED_LIB_PATH, mode=C.RTLD_GLOBAL)
-        gated.vgicp_map_insert_resident_gated.argtypes = [vp, dp, sz, C.c_double, sz, C.POINTER(C.c_uint8),
-                                                          C.POINTER(GatedInsertStats)]
-        gated.vgicp_map_insert_resident_gated_async.argtypes = [vp, dp, sz, C.c_double]
-        gated.vgicp_map_gated_totals.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        for name in MAP_GATED_EXPORTS:
-            getattr(gated, name).restype = C.c_int
-            setattr(lib, name, getattr(gated, name))
-    # free-space carving's library, likewise
-    if os.path.exists(MAP_CARVE_LIB_PATH):
-        carve = C.CDLL(MAP_CARVE_LIB_PATH, mode=C.RTLD_GLOBAL)
-        carve.vgicp_map_carve_resident.argtypes = [vp, dp, C.POINTER(CarveParams), sz, ip, C.POINTER(sz), C.POINTER(CarveStats)]
-        carve.vgicp_map_carve_resident_async.argtypes = [vp, dp, C.POINTER(CarveParams)]
-        carve.vgicp_map_carve_totals.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        for name in MAP_CARVE_EXPORTS:
-            getattr(carve, name).restype = C.c_int
-            setattr(lib, name, getattr(carve, name))
-    # the ray report's library, likewise
-    if os.path.exists(MAP_RAYS_LIB_PATH):
-        rays = C.CDLL(MAP_RAYS_LIB_PATH, mode=C.RTLD_GLOBAL)
-        rays.vgicp_rays_resident.argtypes = [vp, dp, sz, C.POINTER(RayParams), C.POINTER(RayOutputs), C.POINTER(RayCounts),
-                                             C.POINTER(RayStats)]
-        rays.vgicp_rays_resident.restype = C.c_int
-        lib.vgicp_rays_resident = rays.vgicp_rays_resident
-    # the map levels' library, likewise
-    if os.path.exists(MAP_LEVELS_LIB_PATH):
-        levels = C.CDLL(MAP_LEVELS_LIB_PATH, mode=C.RTLD_GLOBAL)
-        levels.vgicp_map_levels_build.argtypes = [vp, C.c_int, C.POINTER(LevelsStats)]
-        levels.vgicp_map_level_size.argtypes = [vp, C.c_int, C.POINTER(sz), C.POINTER(sz), dp]
-        levels.vgicp_map_level_export.argtypes = [vp, C.c_int, sz, ip, dp, dp, C.POINTER(C.c_uint64), C.POINTER(sz)]
-        levels.vgicp_align_resident_levels.argtypes = [vp, dp, sz, ip, C.POINTER(Params), dp, C.POINTER(Stats)]
-        for name in MAP_LEVELS_EXPORTS:
-            getattr(levels, name).restype = C.c_int
-            setattr(lib, name, getattr(levels, name))
-    # locate's library, likewise
-    if os.path.exists(MAP_LOCATE_LIB_PATH):
-        locate = C.CDLL(MAP_LOCATE_LIB_PATH, mode=C.RTLD_GLOBAL)
-        locate.vgicp_locate_resident.argtypes = [vp, dp, sz, C.POINTER(LocateParams), C.POINTER(LocateBest),
-                                                 C.POINTER(C.c_uint32), C.POINTER(LocateStats)]
-        locate.vgicp_locate_resident.restype = C.c_int
-        lib.vgicp_locate_resident = locate.vgicp_locate_resident
-    # the neighbour search's path report, likewise
-    if os.path.exists(SEARCH_REPORT_LIB_PATH):
-        report = C.CDLL(SEARCH_REPORT_LIB_PATH, mode=C.RTLD_GLOBAL)
-        report.vgicp_prepare_search_report.argtypes = [vp, C.POINTER(SearchReport)]
-        report.vgicp_prepare_search_report.restype = C.c_int
-        lib.vgicp_prepare_search_report = report.vgicp_prepare_search_report
+
+    def declare(handle, names):   # ... and every name is reached through the one object
+        for name in names:
+            fn = getattr(handle, name)
+            fn.argtypes, fn.restype = PROTOTYPES[name], RESTYPES.get(name, C.c_int)
+            setattr(lib, name, fn)
+
+    declare(lib, EXPORTS + MAP_POINTS_EXPORTS + BATCH_EXPORTS + EVALUATE_EXPORTS)
+    # the side libraries that were built beside the module (a module of an earlier commit, loaded through VGICP_LIB_PATH
+    # for a comparison, has fewer)
+    for side, names in SIDE_EXPORTS.items():
+        if os.path.exists(side_lib_path(side)):
+            declare(C.CDLL(side_lib_path(side), mode=C.RTLD_GLOBAL), names)
     _lib = lib
     return lib
 

@@ -571,11 +571,6 @@ struct vgicp_ctx {
   int rank = 0;
 };
 
-// The layout handshake of the libraries beside the module (vgicp_prior.hip, vgicp_points.hip, vgicp_map_gated.hip, vgicp_map_carve.hip, vgicp_map_rays.hip,
-// vgicp_search_report.hip, vgicp_map_levels.hip, vgicp_map_locate.hip): was
-// this context made by the build that reads it?  Reads the stamp only; each library refuses in its own words.
-inline bool same_build(const vgicp_ctx* ctx) { return ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx)); }
-
 // The facts plan_align (vgicp_align_plan.h) decides by, as this context and this call have them: the ONE place where a
 // single-device align's plan meets the context (a multi-device context fills its own: group_facts, vgicp_multi.hip).
 // n: the caller's count (AlignCall::Upload), else the resident scan's.
@@ -667,6 +662,17 @@ inline int fail_hip(const vgicp_ctx* ctx, hipError_t e, const char* what) {
   } while (0)
 // ... and a call of this library's own that returns a status: anything but VGICP_OK is returned as it is
 #define VG_RC(call) do { const int rc__ = (call); if (rc__ != VGICP_OK) return rc__; } while (0)
+
+// The layout handshake of the libraries beside the module (vgicp_<name>.hip for every name of the Makefile's SIDE): was
+// this context made by the build that reads it?  Reads the stamp only.
+inline bool same_build(const vgicp_ctx* ctx) { return ctx->layout == (vgicp_ctx::kLayoutMark | (uint64_t)sizeof(vgicp_ctx)); }
+// ... as every entry point of those libraries makes it, under VG_RC, before anything else of the context is read or
+// written: a NULL context leaves no text, one of another build leaves `refusal` (the library's own words) where a failed
+// vgicp_create's text goes (vgicp_last_error(NULL)).
+inline int layout_handshake(const vgicp_ctx* ctx, const char* refusal) {
+  if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
+  return same_build(ctx) ? VGICP_OK : vgicp::fail(nullptr, VGICP_ERR_BAD_ARGUMENT, refusal);
+}
 
 // ---- what vgicp_multi.hip needs from vgicp_capi.hip besides the public entry points ----
 namespace vgicp_internal {

@@ -5,34 +5,24 @@
 // vgicp_context.h as the module (one Makefile, one rule set) and linked against it.
 #include "vgicp_context.h"
 
-namespace {
-// rules 1 and 2 of the header's list: nothing of the context is read or written unless its layout is this build's (the
-// text goes where a failed vgicp_create's goes).  *rc: the status to return when the handshake fails.
-bool handshake(const vgicp_ctx* ctx, int* rc) {
-  *rc = VGICP_ERR_BAD_ARGUMENT;
-  if (ctx && !same_build(ctx)) fail(nullptr, *rc, "context and libvgicp_hip_map_carve.so are not from one build of the module");
-  return ctx && same_build(ctx);
-}
-}  // namespace
+// rules 1 and 2 of the header's list are the handshake; what it leaves for a context of another build
+static const char kOtherBuild[] = "context and libvgicp_hip_map_carve.so are not from one build of the module";
 
 extern "C" {
 
 int vgicp_map_carve_resident(vgicp_ctx* ctx, const double transform[16], const vgicp_carve_params* params, size_t capacity,
                              int32_t* removed_keys, size_t* removed, vgicp_carve_stats* stats) {
-  int rc = VGICP_OK;
-  if (!handshake(ctx, &rc)) return rc;
+  VG_RC(layout_handshake(ctx, kOtherBuild));
   return vgicp_internal::map_carve_resident(ctx, transform, params, capacity, removed_keys, removed, stats);
 }
 
 int vgicp_map_carve_resident_async(vgicp_ctx* ctx, const double transform[16], const vgicp_carve_params* params) {
-  int rc = VGICP_OK;
-  if (!handshake(ctx, &rc)) return rc;
+  VG_RC(layout_handshake(ctx, kOtherBuild));
   return vgicp_internal::map_carve_resident_async(ctx, transform, params);
 }
 
 int vgicp_map_carve_totals(vgicp_ctx* ctx, uint64_t* rays, uint64_t* removed) {
-  int rc = VGICP_OK;
-  if (!handshake(ctx, &rc)) return rc;
+  VG_RC(layout_handshake(ctx, kOtherBuild));
   return vgicp_internal::map_carve_totals(ctx, rays, removed);
 }
 }  // extern "C"

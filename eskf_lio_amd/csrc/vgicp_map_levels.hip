@@ -5,41 +5,30 @@
 // same vgicp_context.h as the module (one Makefile, one rule set) and linked against it.
 #include "vgicp_context.h"
 
-namespace {
-// rule 1 of the header's list: nothing of the context is read or written unless its layout is this build's (the text
-// goes where a failed vgicp_create's goes).  *rc: the status to return when the handshake fails.
-bool handshake(const vgicp_ctx* ctx, int* rc) {
-  *rc = VGICP_ERR_BAD_ARGUMENT;
-  if (ctx && !same_build(ctx)) fail(nullptr, *rc, "context and libvgicp_hip_map_levels.so are not from one build of the module");
-  return ctx && same_build(ctx);
-}
-}  // namespace
+// rule 1 of the header's list is the handshake; what it leaves for a context of another build
+static const char kOtherBuild[] = "context and libvgicp_hip_map_levels.so are not from one build of the module";
 
 extern "C" {
 
 int vgicp_map_levels_build(vgicp_ctx* ctx, int levels, vgicp_levels_stats* stats) {
-  int rc = VGICP_OK;
-  if (!handshake(ctx, &rc)) return rc;
+  VG_RC(layout_handshake(ctx, kOtherBuild));
   return vgicp_internal::map_levels_build(ctx, levels, stats);
 }
 
 int vgicp_map_level_size(vgicp_ctx* ctx, int level, size_t* voxels, size_t* table_slots, double* voxel_size) {
-  int rc = VGICP_OK;
-  if (!handshake(ctx, &rc)) return rc;
+  VG_RC(layout_handshake(ctx, kOtherBuild));
   return vgicp_internal::map_level_size(ctx, level, voxels, table_slots, voxel_size);
 }
 
 int vgicp_map_level_export(vgicp_ctx* ctx, int level, size_t capacity, int32_t* keys, double* means, double* covs,
                            uint64_t* counts, size_t* written) {
-  int rc = VGICP_OK;
-  if (!handshake(ctx, &rc)) return rc;
+  VG_RC(layout_handshake(ctx, kOtherBuild));
   return vgicp_internal::map_level_export(ctx, level, capacity, keys, means, covs, counts, written);
 }
 
 int vgicp_align_resident_levels(vgicp_ctx* ctx, const double guess[16], size_t stages, const int32_t* levels,
                                 const vgicp_params* params, double out_pose[16], vgicp_stats* stats) {
-  int rc = VGICP_OK;
-  if (!handshake(ctx, &rc)) return rc;
+  VG_RC(layout_handshake(ctx, kOtherBuild));
   return vgicp_internal::align_resident_levels(ctx, guess, stages, levels, params, out_pose, stats);
 }
 }  // extern "C"

@@ -9,11 +9,8 @@ extern "C" {
 
 int vgicp_locate_resident(vgicp_ctx* ctx, const double* poses, size_t k, const vgicp_locate_params* params,
                           vgicp_locate_best* best, uint32_t* hits, vgicp_locate_stats* stats) {
-  // rule 1 of the header's list: nothing of the context is read or written unless its layout is this build's (the text
-  // goes where a failed vgicp_create's goes)
-  if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (!same_build(ctx))
-    return fail(nullptr, VGICP_ERR_BAD_ARGUMENT, "context and libvgicp_hip_map_locate.so are not from one build of the module");
+  // rule 1 of the header's list
+  VG_RC(layout_handshake(ctx, "context and libvgicp_hip_map_locate.so are not from one build of the module"));
   return vgicp_internal::locate_resident(ctx, poses, k, params, best, hits, stats);
 }
 }  // extern "C"

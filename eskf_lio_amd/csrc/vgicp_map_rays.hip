@@ -9,10 +9,8 @@ extern "C" {
 
 int vgicp_rays_resident(vgicp_ctx* ctx, const double* poses, size_t n_poses, const vgicp_ray_params* params,
                         const vgicp_ray_outputs* per_point, vgicp_ray_counts* counts, vgicp_ray_stats* stats) {
-  // rules 1 and 2 of the header's list: nothing of the context is read or written unless its layout is this build's (the
-  // text goes where a failed vgicp_create's goes)
-  if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (!same_build(ctx)) return fail(nullptr, VGICP_ERR_BAD_ARGUMENT, "context and libvgicp_hip_map_rays.so are not from one build of the module");
+  // rules 1 and 2 of the header's list
+  VG_RC(layout_handshake(ctx, "context and libvgicp_hip_map_rays.so are not from one build of the module"));
   return vgicp_internal::rays_resident(ctx, poses, n_poses, params, per_point, counts, stats);
 }
 }  // extern "C"

@@ -433,6 +433,65 @@ __device__ __forceinline__ double carve_boundary(int32_t k, double d, double o, 
   if (d == 0.0) return __builtin_inf();
   return ((double)(k + (d > 0.0 ? 1 : 0)) * h - o) / d;
 }
+// THE walk of a ray through the voxels, carving's and the ray report's: from the voxel of the origin o (key k0) along d
+// (len: its length) while the parameter of the next boundary is below t_end.  visit(kx, ky, kz) is called for the
+// origin's voxel and for every voxel entered; true stops the walk.  What comes back: the voxels visited, the last one's
+// key and the parameter at which the ray entered it (0 in the origin's).
+struct RayWalk {
+  uint32_t visits;
+  int32_t kx, ky, kz;
+  double t_in;
+};
+template <class Visit>
+__device__ __forceinline__ RayWalk walk_ray(const int32_t* k0, double dx, double dy, double dz, const double* o, double h,
+                                            double t_end, double len, Visit visit) {
+#pragma clang fp contract(off)
+  // the walk's hard bound: what vgicp_map_plan.h lets through keeps the ceiling at kCarveMaxSteps + 1
+  constexpr double kCellsMax = 4097.0;
+  double cells = ceil((t_end * len) / h);
+  if (!(cells <= kCellsMax)) cells = kCellsMax;   // (a NaN too)
+  const uint32_t max_steps = 3u * (uint32_t)cells + 3u;
+  RayWalk w{1u, k0[0], k0[1], k0[2], 0.0};
+  const int32_t sx = dx > 0.0 ? 1 : -1, sy = dy > 0.0 ? 1 : -1, sz = dz > 0.0 ? 1 : -1;
+  double tx = carve_boundary(w.kx, dx, o[0], h), ty = carve_boundary(w.ky, dy, o[1], h), tz = carve_boundary(w.kz, dz, o[2], h);
+  bool stop = visit(w.kx, w.ky, w.kz);
+  for (uint32_t step = 0; step < max_steps && !stop; ++step) {
+    if (tx <= ty && tx <= tz) {
+      if (!(tx < t_end)) break;
+      w.t_in = tx;
+      w.kx += sx;
+      tx = carve_boundary(w.kx, dx, o[0], h);
+    } else if (ty <= tz) {
+      if (!(ty < t_end)) break;
+      w.t_in = ty;
+      w.ky += sy;
+      ty = carve_boundary(w.ky, dy, o[1], h);
+    } else {
+      if (!(tz < t_end)) break;
+      w.t_in = tz;
+      w.kz += sz;
+      tz = carve_boundary(w.kz, dz, o[2], h);
+    }
+    stop = visit(w.kx, w.ky, w.kz);
+    ++w.visits;
+  }
+  return w;
+}
+// The workgroup's 64-bit sum of every lane's `visits`, for thread 0 (every thread of a kBlock workgroup calls this).
+__device__ __forceinline__ unsigned long long block_visits(uint32_t visits) {
+  __shared__ unsigned long long wave_visits[kBlock / 64];
+  unsigned long long sum = visits;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, (unsigned int)d, 64);
+  if ((threadIdx.x & 63u) == 0u) wave_visits[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  unsigned long long total = 0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (uint32_t w = 0; w < kBlock / 64; ++w) total += wave_visits[w];
+  }
+  return total;
+}
 
 __global__ void __launch_bounds__(kBlock) carve_mark_kernel(CarveArgs a) {
 #pragma clang fp contract(off)
@@ -456,47 +515,17 @@ __global__ void __launch_bounds__(kBlock) carve_mark_kernel(CarveArgs a) {
       const bool finite = isfinite(dx) && isfinite(dy) && isfinite(dz);
       if (t_stop > 0.0 && finite && carve_key(o, h, k)) {
         ray = true;
-        // the walk's hard bound: what vgicp_map_plan.h lets through keeps the ceiling at kCarveMaxSteps + 1
-        double cells = ceil((t_stop * len) / h);
-        if (!(cells <= 4097.0)) cells = 4097.0;
-        const uint32_t max_steps = 3u * (uint32_t)cells + 3u;
-        int32_t kx = k[0], ky = k[1], kz = k[2];
-        const int32_t sx = dx > 0.0 ? 1 : -1, sy = dy > 0.0 ? 1 : -1, sz = dz > 0.0 ? 1 : -1;
-        double tx = carve_boundary(kx, dx, o[0], h), ty = carve_boundary(ky, dy, o[1], h), tz = carve_boundary(kz, dz, o[2], h);
-        carve_mark(a.table, mask, kx, ky, kz, false);
-        visits = 1;
-        for (uint32_t step = 0; step < max_steps; ++step) {
-          if (tx <= ty && tx <= tz) {
-            if (!(tx < t_stop)) break;
-            kx += sx;
-            tx = carve_boundary(kx, dx, o[0], h);
-          } else if (ty <= tz) {
-            if (!(ty < t_stop)) break;
-            ky += sy;
-            ty = carve_boundary(ky, dy, o[1], h);
-          } else {
-            if (!(tz < t_stop)) break;
-            kz += sz;
-            tz = carve_boundary(kz, dz, o[2], h);
-          }
-          carve_mark(a.table, mask, kx, ky, kz, false);
-          ++visits;
-        }
+        visits = walk_ray(k, dx, dy, dz, o, h, t_stop, len, [&](int32_t kx, int32_t ky, int32_t kz) {
+                   carve_mark(a.table, mask, kx, ky, kz, false);
+                   return false;   // carving marks every voxel up to t_stop
+                 }).visits;
       }
     }
   }
   // one atomic per workgroup and counter
   const int cast = __syncthreads_count(ray ? 1 : 0);
-  __shared__ unsigned long long wave_visits[kBlock / 64];
-  unsigned long long sum = visits;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, (unsigned int)d, 64);
-  if ((threadIdx.x & 63u) == 0u) wave_visits[threadIdx.x >> 6] = sum;
-  __syncthreads();
+  const unsigned long long total = block_visits(visits);
   if (threadIdx.x == 0) {
-    unsigned long long total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kBlock / 64; ++w) total += wave_visits[w];
     if (a.rays && cast) atomicAdd(a.rays, (uint32_t)cast);
     if (a.visits && total) atomicAdd(a.visits, total);
   }
@@ -536,7 +565,7 @@ __global__ void __launch_bounds__(kBlock) carve_sweep_kernel(CarveArgs a) {
 }
 
 // ---- the ray report (include/vgicp_hip_map_rays.h states the rule operation by operation; this restates it).  The key,
-// the boundary, the transform and the probe are carving's above: one definition of the step serves both ----
+// the boundary, the walk (walk_ray), the transform and the probe are carving's above: one definition serves both ----
 // CONFIRM: one lane per point and pose.  The slot of the point's own voxel, if FULL, gets its bit in the pose's bitmap
 // (test before set, as carve_mark does for the shield: a scan puts many points into one voxel).
 __global__ void __launch_bounds__(kBlock) rays_confirm_kernel(RayArgs a) {
@@ -561,7 +590,6 @@ __global__ void __launch_bounds__(kBlock) rays_confirm_kernel(RayArgs a) {
 __global__ void __launch_bounds__(kBlock) rays_walk_kernel(RayArgs a) {
 #pragma clang fp contract(off)
   __shared__ uint32_t by_class[8];
-  __shared__ unsigned long long wave_visits[kBlock / 64];
   if (threadIdx.x < 8u) by_class[threadIdx.x] = 0u;
   __syncthreads();
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -590,35 +618,13 @@ __global__ void __launch_bounds__(kBlock) rays_walk_kernel(RayArgs a) {
       const bool finite = isfinite(dx) && isfinite(dy) && isfinite(dz);
       if (len > 0.0 && t_end > 0.0 && finite && carve_key(o, h, k)) {
         ray = true;
-        // the walk's hard bound, carving's: what vgicp_map_plan.h lets through keeps the ceiling at kCarveMaxSteps + 1
-        double cells = ceil((t_end * len) / h);
-        if (!(cells <= 4097.0)) cells = 4097.0;
-        const uint32_t max_steps = 3u * (uint32_t)cells + 3u;
-        kx = k[0]; ky = k[1]; kz = k[2];
-        const int32_t sx = dx > 0.0 ? 1 : -1, sy = dy > 0.0 ? 1 : -1, sz = dz > 0.0 ? 1 : -1;
-        double tx = carve_boundary(kx, dx, o[0], h), ty = carve_boundary(ky, dy, o[1], h), tz = carve_boundary(kz, dz, o[2], h);
-        hit = find_voxel(a.table, mask, kx, ky, kz);
-        visits = 1;
-        for (uint32_t step = 0; step < max_steps && !hit; ++step) {
-          if (tx <= ty && tx <= tz) {
-            if (!(tx < t_end)) break;
-            t_in = tx;
-            kx += sx;
-            tx = carve_boundary(kx, dx, o[0], h);
-          } else if (ty <= tz) {
-            if (!(ty < t_end)) break;
-            t_in = ty;
-            ky += sy;
-            ty = carve_boundary(ky, dy, o[1], h);
-          } else {
-            if (!(tz < t_end)) break;
-            t_in = tz;
-            kz += sz;
-            tz = carve_boundary(kz, dz, o[2], h);
-          }
-          hit = find_voxel(a.table, mask, kx, ky, kz);
-          ++visits;
-        }
+        const RayWalk w = walk_ray(k, dx, dy, dz, o, h, t_end, len, [&](int32_t x, int32_t y, int32_t z) {
+          hit = find_voxel(a.table, mask, x, y, z);
+          return hit != nullptr;   // the report ends at the first FULL voxel
+        });
+        visits = w.visits;
+        kx = w.kx; ky = w.ky; kz = w.kz;
+        t_in = w.t_in;
         // the class, in the header's order
         if (!hit) {
           cls = 1u;   // OPEN
@@ -643,16 +649,9 @@ __global__ void __launch_bounds__(kBlock) rays_walk_kernel(RayArgs a) {
   }
   // at most one global atomic per workgroup and counter
   const int cast = __syncthreads_count(ray ? 1 : 0);   // (also the barrier behind the histogram's adds)
-  unsigned long long sum = visits;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, (unsigned int)d, 64);
-  if ((threadIdx.x & 63u) == 0u) wave_visits[threadIdx.x >> 6] = sum;
-  __syncthreads();
+  const unsigned long long total = block_visits(visits);
   unsigned long long* counts = a.counts + (size_t)kRayCountWords * blockIdx.y;
   if (threadIdx.x == 0) {
-    unsigned long long total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kBlock / 64; ++w) total += wave_visits[w];
     if (cast) atomicAdd(counts, (unsigned long long)cast);
     if (total) atomicAdd(counts + 1, total);
   }

@@ -10,14 +10,10 @@ extern "C" {
 int vgicp_points_resident(vgicp_ctx* ctx, const double pose[16], size_t capacity, double* d2, double* sq_error,
                           double* weight, uint8_t* status, size_t n_quantiles, const double* q,
                           vgicp_point_summary* summary, vgicp_point_stats* stats) {
-  // rules 1 and 2 of the header's list (plan_points decides them from these two facts alone): nothing of the context is
-  // read or written unless its layout is this build's (the text goes where a failed vgicp_create's goes)
-  PointsFacts f;
-  f.ctx = ctx != nullptr;
-  f.same_build = ctx && same_build(ctx);
-  const PointsVerdict v = plan_points(f);
-  if (v.rule == 1) return v.status;
-  if (v.rule == 2) return fail(nullptr, v.status, v.text);
+  // rules 1 and 2 of the header's list; rule 2's words are the ones plan_points keeps for it
+  PointsFacts other_build;
+  other_build.same_build = false;
+  VG_RC(layout_handshake(ctx, plan_points(other_build).text));
   return vgicp_internal::points_resident(ctx, pose, capacity, d2, sq_error, weight, status, n_quantiles, q, summary, stats);
 }
 }  // extern "C"

@@ -42,12 +42,7 @@ bool prior_info_is_psd(const double* L, double tol) {
 extern "C" {
 
 int vgicp_set_pose_prior(vgicp_ctx* ctx, const double prior_pose[16], const double information[36]) {
-  if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  // the handshake with the module that made the context: nothing of it is read or written unless its layout is this
-  // build's (the text goes where a failed vgicp_create's goes: vgicp_last_error(NULL))
-  if (!same_build(ctx))
-    return fail(nullptr, VGICP_ERR_BAD_ARGUMENT,
-                "libvgicp_hip_prior.so and the libvgicp_hip.so that created this context are not from one build");
+  VG_RC(layout_handshake(ctx, "libvgicp_hip_prior.so and the libvgicp_hip.so that created this context are not from one build"));
   if (!prior_pose || !information) {   // a clear: never refused, and vgicp_last_error keeps its text
     ctx->prior_on = false;
     return VGICP_OK;

@@ -8,10 +8,7 @@
 extern "C" {
 
 int vgicp_prepare_search_report(vgicp_ctx* ctx, vgicp_search_report* report) {
-  // nothing of the context is read or written unless its layout is this build's (the text goes where a failed
-  // vgicp_create's goes)
-  if (!ctx) return VGICP_ERR_BAD_ARGUMENT;
-  if (!same_build(ctx)) return fail(nullptr, VGICP_ERR_BAD_ARGUMENT, "context and libvgicp_hip_search_report.so are not from one build of the module");
+  VG_RC(layout_handshake(ctx, "context and libvgicp_hip_search_report.so are not from one build of the module"));
   return vgicp_internal::prepare_search_report(ctx, report);
 }
 }  // extern "C"

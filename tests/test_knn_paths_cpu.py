@@ -31,7 +31,7 @@ def test_header_declares_the_one_function_and_the_library_exports_it():
     assert tuple(fields[10:]) == capi.SEARCH_PATHS == kp.PATHS
     import ctypes as C
     assert C.sizeof(capi.SearchReport) == 96
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.SEARCH_REPORT_LIB_PATH], capture_output=True, text=True,
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.side_lib_path("search_report")], capture_output=True, text=True,
                          check=True).stdout
     assert set(re.findall(r" T (vgicp_[a-z_0-9]+)", out)) == set(capi.SEARCH_REPORT_EXPORTS)
     assert hasattr(lib, "vgicp_prepare_search_report")

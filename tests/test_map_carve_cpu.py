@@ -29,7 +29,7 @@ def test_header_declares_exactly_the_three_functions_and_the_library_exports_the
     assert '#include "vgicp_hip.h"' in text and "libvgicp_hip_map_carve.so" in text
     assert not re.search(r"#define\s+VGICP_OPTION_", text)           # no new vgicp_set_option number
     assert re.search(r"#define\s+VGICP_CARVE_MAX_STEPS\s+%d\b" % capi.CARVE_MAX_STEPS, text) and mc.MAX_STEPS == capi.CARVE_MAX_STEPS
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.MAP_CARVE_LIB_PATH], capture_output=True, text=True,
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.side_lib_path("map_carve")], capture_output=True, text=True,
                          check=True).stdout
     assert set(re.findall(r" T (vgicp_[a-z_0-9]+)", out)) == set(capi.MAP_CARVE_EXPORTS)
     assert all(hasattr(lib, name) for name in CARVE)

@@ -29,7 +29,7 @@ def test_header_declares_exactly_the_three_functions_and_the_library_exports_the
     text = open(os.path.join(ROOT, "include", "vgicp_hip_map_gated.h")).read()
     assert '#include "vgicp_hip.h"' in text and "libvgicp_hip_map_gated.so" in text
     assert not re.search(r"#define\s+VGICP_OPTION_", text)           # no new vgicp_set_option number
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.MAP_GATED_LIB_PATH], capture_output=True, text=True,
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.side_lib_path("map_gated")], capture_output=True, text=True,
                          check=True).stdout
     assert set(re.findall(r" T (vgicp_[a-z_0-9]+)", out)) == set(capi.MAP_GATED_EXPORTS)
     assert all(hasattr(lib, name) for name in GATED)

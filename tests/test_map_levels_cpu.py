@@ -30,7 +30,7 @@ def test_header_declares_exactly_the_four_functions_and_the_library_exports_them
     assert re.search(r"#define\s+VGICP_LEVELS_MAX\s+%d\b" % capi.LEVELS_MAX, text) and ml.LEVELS_MAX == capi.LEVELS_MAX == 4
     assert re.search(r"#define\s+VGICP_LEVEL_STAGES_MAX\s+%d\b" % capi.LEVEL_STAGES_MAX, text)
     assert ml.LEVEL_STAGES_MAX == capi.LEVEL_STAGES_MAX == 8
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.MAP_LEVELS_LIB_PATH], capture_output=True, text=True,
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.side_lib_path("map_levels")], capture_output=True, text=True,
                          check=True).stdout
     assert set(re.findall(r" T (vgicp_[a-z_0-9]+)", out)) == set(capi.MAP_LEVELS_EXPORTS)
     assert all(hasattr(lib, name) for name in LEVELS)

@@ -36,7 +36,7 @@ def test_header_declares_exactly_the_one_function_and_the_library_exports_it():
                                 ("VGICP_LOCATE_MAX_CELLS", capi.LOCATE_MAX_CELLS, lo.MAX_CELLS)):
         assert re.search(r"#define\s+%s\s+%d\b" % (name, value), text) and value == mirror, name
     assert (capi.LOCATE_MAX_POSES, capi.LOCATE_MAX_HALF_WIDTH, capi.LOCATE_MAX_CELLS) == (64, 32, 4096)
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.MAP_LOCATE_LIB_PATH], capture_output=True, text=True,
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.side_lib_path("map_locate")], capture_output=True, text=True,
                          check=True).stdout
     assert set(re.findall(r" T (vgicp_[a-z_0-9]+)", out)) == set(capi.MAP_LOCATE_EXPORTS)
     assert hasattr(lib, "vgicp_locate_resident")

@@ -33,7 +33,7 @@ def test_header_declares_exactly_the_one_function_and_the_library_exports_it():
     assert re.search(r"#define\s+VGICP_RAYS_MAX_POSES\s+%d\b" % capi.RAYS_MAX_POSES, text)
     for value, name in enumerate(("NO_RAY", "OPEN", "OWN", "BEHIND", "CONFIRMED", "BLOCKED", "NEAR")):
         assert re.search(r"VGICP_RAY_%s = %d\b" % (name, value), text) and getattr(capi, "RAY_" + name) == getattr(mr, name) == value
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.MAP_RAYS_LIB_PATH], capture_output=True, text=True,
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.side_lib_path("map_rays")], capture_output=True, text=True,
                          check=True).stdout
     assert set(re.findall(r" T (vgicp_[a-z_0-9]+)", out)) == set(capi.MAP_RAYS_EXPORTS)
     assert hasattr(lib, "vgicp_rays_resident")

@@ -36,7 +36,7 @@ def test_header_declares_the_entry_point_and_its_library_exports_it():
     assert (define("VGICP_POINT_MATCHED"), define("VGICP_POINT_NEGATIVE"), define("VGICP_POINT_NOT_FINITE")) == \
         (capi.POINT_MATCHED, capi.POINT_NEGATIVE, capi.POINT_NOT_FINITE) == (1, 2, 4)
     assert not re.search(r"#define\s+VGICP_OPTION_", text)           # no new vgicp_set_option number
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.POINTS_LIB_PATH], capture_output=True, text=True,
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.side_lib_path("points")], capture_output=True, text=True,
                          check=True).stdout
     assert set(re.findall(r" T (vgicp_[a-z_0-9]+)", out)) == set(capi.POINTS_EXPORTS)
     assert hasattr(lib, "vgicp_points_resident")

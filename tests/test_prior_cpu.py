@@ -73,8 +73,8 @@ def test_header_declares_exactly_the_two_functions_and_the_library_exports_them(
     assert set(names) <= set(declared("vgicp_hip_prior.h"))
     lib = capi.load_library()
     # the library of this header, beside the module (whose own exports stay the pinned lists): exactly the two
-    assert os.path.dirname(capi.PRIOR_LIB_PATH) == os.path.dirname(capi.LIB_PATH)
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.PRIOR_LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert os.path.dirname(capi.side_lib_path("prior")) == os.path.dirname(capi.LIB_PATH)
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.side_lib_path("prior")], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r" T (vgicp_[a-z_0-9]+)", out))
     assert exported == set(names)
     for name in names:

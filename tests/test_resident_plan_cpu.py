@@ -40,8 +40,17 @@ def test_the_shared_pieces_are_written_once():
             assert "peers_connected" not in text, name
     for name in ("vgicp_capi_evaluate.inl", "vgicp_capi_batch.inl"):
         assert "no voxel map" not in source(name) and "no scan resident" not in source(name), name
-    # the layout handshake: one comparison, in vgicp_context.h, used by the three libraries beside the module
+    # the layout handshake: one comparison and one function that refuses by it, in vgicp_context.h, used by every
+    # library beside the module (the Makefile's list)
     sources = [f for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".inl"))]
     assert sum(len(re.findall(r"kLayoutMark \|", source(f))) for f in sources) == 2          # the stamp and same_build
-    for lib in ("vgicp_prior.hip", "vgicp_points.hip", "vgicp_map_gated.hip"):
-        assert "same_build(ctx)" in source(lib) and "kLayoutMark" not in source(lib)
+    assert len(re.findall(r"same_build\(ctx\)", source("vgicp_context.h"))) == 1             # in layout_handshake
+    side = re.search(r"^SIDE := (.+)$", source("Makefile"), re.M).group(1).split()
+    assert len(side) >= 8 and {"prior", "points", "map_locate"} <= set(side)
+    for lib in ("vgicp_%s.hip" % name for name in side):
+        text = source(lib)
+        assert "VG_RC(layout_handshake(ctx, " in text or "same_build(ctx)" in text, lib
+        assert "kLayoutMark" not in text and not re.search(r"\bhandshake\s*\([^;{]*\)\s*\{", text), lib
+    # the ray walk of carving and of the ray report: the step's comparison and the step bound's cap, once each
+    everything = "".join(source(f) for f in sources)
+    assert everything.count("tx <= ty && tx <= tz") == 1 and everything.count("4097.0") == 1
