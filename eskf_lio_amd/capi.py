@@ -61,9 +61,10 @@ MAP_RAYS_EXPORTS = ("vgicp_rays_resident",)
 SEARCH_REPORT_EXPORTS = ("vgicp_prepare_search_report",)   # a test hook
 MAP_LEVELS_EXPORTS = ("vgicp_map_levels_build", "vgicp_map_level_size", "vgicp_map_level_export", "vgicp_align_resident_levels")
 MAP_LOCATE_EXPORTS = ("vgicp_locate_resident",)
+MAP_SUBMAP_EXPORTS = ("vgicp_scan_from_map", "vgicp_scan_from_map_keys")
 SIDE_EXPORTS = {"prior": PRIOR_EXPORTS, "points": POINTS_EXPORTS, "map_gated": MAP_GATED_EXPORTS,
                 "map_carve": MAP_CARVE_EXPORTS, "map_rays": MAP_RAYS_EXPORTS, "search_report": SEARCH_REPORT_EXPORTS,
-                "map_levels": MAP_LEVELS_EXPORTS, "map_locate": MAP_LOCATE_EXPORTS}
+                "map_levels": MAP_LEVELS_EXPORTS, "map_locate": MAP_LOCATE_EXPORTS, "map_submap": MAP_SUBMAP_EXPORTS}
 
 
 def side_lib_path(name: str) -> str:
@@ -241,6 +242,31 @@ class LocateResult:
     device_seconds: float
 
 
+class SubmapParams(C.Structure):
+    """vgicp_submap_params (vgicp_hip_map_submap.h), 176 bytes."""
+    _fields_ = [("center", C.c_double * 3), ("radius", C.c_double), ("frame", C.c_double * 16), ("min_count", C.c_uint64),
+                ("level", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SubmapStats(C.Structure):
+    """vgicp_submap_stats (vgicp_hip_map_submap.h), 56 bytes."""
+    _fields_ = [("voxels", C.c_uint64), ("points", C.c_uint64), ("too_far", C.c_uint64), ("too_few", C.c_uint64),
+                ("launches", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double), ("device_seconds", C.c_double)]
+
+
+@dataclass
+class SubmapResult:
+    """What Context.scan_from_map returns: the counts of vgicp_submap_stats and how the call ran.  points is the size of
+    the resident scan now; 0 means that there is none."""
+    voxels: int
+    points: int
+    too_far: int
+    too_few: int
+    launches: int
+    seconds: float
+    device_seconds: float
+
+
 class RayParams(C.Structure):
     """vgicp_ray_params (vgicp_hip_map_rays.h), 56 bytes."""
     _fields_ = [("origin", C.c_double * 3), ("margin", C.c_double), ("beyond", C.c_double), ("max_range", C.c_double),
@@ -358,6 +384,8 @@ PROTOTYPES = {
     "vgicp_align_resident_levels": [vp, dp, sz, ip, C.POINTER(Params), dp, C.POINTER(Stats)],
     "vgicp_locate_resident": [vp, dp, sz, C.POINTER(LocateParams), C.POINTER(LocateBest), C.POINTER(C.c_uint32),
                              C.POINTER(LocateStats)],
+    "vgicp_scan_from_map": [vp, vp, C.POINTER(SubmapParams), C.POINTER(SubmapStats)],
+    "vgicp_scan_from_map_keys": [vp, sz, ip, C.POINTER(C.c_uint64), C.POINTER(sz)],
     "vgicp_prepare_search_report": [vp, C.POINTER(SearchReport)],
 }
 RESTYPES = {"vgicp_last_error": C.c_char_p, "vgicp_peer_status": C.c_char_p}
@@ -1129,6 +1157,33 @@ class Context:
         out = [dict(hits=int(b.hits), cell=int(b.cell), offset=tuple(int(v) for v in b.offset), points=int(b.points),
                     skipped=int(b.skipped), pose=pose_from_abi(np.array(b.pose))) for b in best[:k]]
         return LocateResult(out, hits, st.cells, st.launches, st.seconds, st.device_seconds)
+
+    # -- submap as scan (vgicp_hip_map_submap.h) --
+    def scan_from_map(self, src: "Context", center, radius: float, frame=None, min_count: int = 0,
+                      level: int = 0) -> "SubmapResult":
+        """vgicp_scan_from_map: this context's resident scan becomes the voxels of `src`'s map (or of its level `level`)
+        whose centres lie within `radius` of `center` (the source map's frame; math.inf: all of them) and whose count is
+        at least min_count, each moved by `frame` (4x4, default the identity), in ascending slot order.  src may be self."""
+        p = SubmapParams((C.c_double * 3)(*[float(v) for v in center]), float(radius),
+                         (C.c_double * 16)(*pose_to_abi(np.eye(4) if frame is None else frame)), int(min_count), int(level), 0)
+        st = SubmapStats()
+        self._check(self._lib.vgicp_scan_from_map(self._h, src._h, C.byref(p), C.byref(st)))
+        return SubmapResult(int(st.voxels), int(st.points), int(st.too_far), int(st.too_few), st.launches, st.seconds,
+                            st.device_seconds)
+
+    def scan_from_map_keys(self):
+        """vgicp_scan_from_map_keys: (keys n x 3 int32, counts n uint64) of the voxels behind the resident scan that
+        scan_from_map made, in scan order; VgicpError (NOT_READY) once the scan has been replaced."""
+        w = C.c_size_t()
+        rc = self._lib.vgicp_scan_from_map_keys(self._h, 0, None, None, C.byref(w))   # size query
+        if rc != OK and not (rc == ERR_BAD_ARGUMENT and w.value > 0):
+            self._check(rc)
+        n = w.value
+        keys, counts = np.zeros((n, 3), dtype=np.int32), np.zeros(n, dtype=np.uint64)
+        self._check(self._lib.vgicp_scan_from_map_keys(self._h, n, keys.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(w)))
+        assert w.value == n, (w.value, n)
+        return keys, counts
 
     def rays_resident(self, poses, params, per_point: bool = True) -> "RayReport":
         """vgicp_rays_resident (vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at `poses`

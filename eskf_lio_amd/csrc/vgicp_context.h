@@ -36,6 +36,7 @@
 #include "../../include/vgicp_hip_search_report.h"
 #include "../../include/vgicp_hip_map_levels.h"
 #include "../../include/vgicp_hip_map_locate.h"
+#include "../../include/vgicp_hip_map_submap.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -45,6 +46,7 @@
 #include "vgicp_points_plan.h"
 #include "vgicp_levels_plan.h"
 #include "vgicp_locate_plan.h"
+#include "vgicp_submap_plan.h"
 
 using namespace vgicp;
 
@@ -520,6 +522,14 @@ struct vgicp_ctx {
   // vgicp_capi_map_locate.inl), made by the first call
   DeviceBuf<char> d_locate;              // the poses, the skipped points per pose, the plane of hits
   PinnedBuf<char> h_locate;              // pinned: the poses on their way in, the bests (.dev(): where the best launch writes them), the plane on its way out
+  // submap as scan (include/vgicp_hip_map_submap.h), as the DESTINATION of vgicp_scan_from_map; made by the first call,
+  // grow-only
+  DeviceBuf<char> d_submap_work;         // the call's scratch (submap_work_bytes): ballots, the groups' counts, the totals
+  DeviceBuf<char> d_submap_keys;         // per point of the scan: the counts (8 bytes each), then the keys (12 bytes each)
+  size_t submap_capacity = 0;            // points d_submap_keys holds
+  PinnedBuf<unsigned long long> h_submap;   // pinned, 4 words; .dev(): where the scan launch writes the totals
+  uint64_t submap_generation = 0;        // the scan_generation vgicp_scan_from_map left (0: it never ran): the keys are that scan's
+  EventHandle ev_submap;                 // as the SOURCE of a call between two contexts: behind this stream's work, for dst's stream to wait on
   // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
   // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
@@ -734,6 +744,9 @@ int align_resident_levels(vgicp_ctx* ctx, const double guess[16], size_t stages,
 // The entry point of include/vgicp_hip_map_locate.h behind libvgicp_hip_map_locate.so, likewise (vgicp_capi_map_locate.inl).
 int locate_resident(vgicp_ctx* ctx, const double* poses, size_t k, const vgicp_locate_params* params, vgicp_locate_best* best,
                     uint32_t* hits, vgicp_locate_stats* stats);
+// The entry points of include/vgicp_hip_map_submap.h behind libvgicp_hip_map_submap.so, likewise (vgicp_capi_map_submap.inl).
+int scan_from_map(vgicp_ctx* dst, vgicp_ctx* src, const vgicp_submap_params* params, vgicp_submap_stats* stats);
+int scan_from_map_keys(vgicp_ctx* dst, size_t capacity, int32_t* keys, uint64_t* counts, size_t* written);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

@@ -646,6 +646,31 @@ struct RayArgs {
   uint32_t* steps;
 };
 hipError_t launch_map_rays(hipStream_t s, const RayArgs& args);
+// Submap as scan (include/vgicp_hip_map_submap.h has the rule): three launches over the source table in groups of
+// kSubmapGroupSlots slots (vgicp_submap_plan.h).  MARK decides per slot and leaves a ballot per 64 slots and three
+// counts per group; SCAN (one workgroup) turns the groups' selected counts into exclusive offsets and writes the totals
+// {selected, too far, too few} to `totals` and to totals_host (page-locked memory); EMIT writes the selected voxels,
+// transformed, at their ranks: both layouts of a resident scan, the keys and the counts.  The table is only read.
+struct SubmapArgs {
+  const VoxelRecord* table;
+  uint64_t slots;
+  double voxel_size;             // of the source table
+  double center[3], radius;
+  uint64_t min_count;
+  double pose[12];               // the frame: R column-major (9), t (3)
+  unsigned long long* ballots;   // kSubmapGroupWords per group
+  uint32_t* group_counts;        // [3][groups]: selected (after SCAN: the exclusive offsets), too far, too few
+  uint32_t groups;
+  uint32_t capacity;             // points the outputs hold: ranks at or beyond it are dropped
+  unsigned long long* totals;    // 3 words
+  double* aos_points;            // capacity x 3
+  double* aos_covs;              // capacity x 9
+  double* planes;                // kScanPlanes planes of `stride` doubles
+  uint64_t stride;
+  int32_t* keys;                 // capacity x 3
+  unsigned long long* counts;    // capacity
+};
+hipError_t launch_submap(hipStream_t s, const SubmapArgs& args, unsigned long long* totals_host);
 // Append every FULL record to the output arrays (unordered); counters[0] = records written.
 hipError_t launch_map_export(hipStream_t s, const VoxelRecord* table, uint64_t slots, uint32_t capacity,
                              int32_t* keys, double* means, double* covs, uint64_t* counts,

@@ -88,6 +88,18 @@ __device__ __forceinline__ void transform_point(const double* R, const double* t
   q[2] = ((R[2] * x + R[5] * y) + R[8] * z) + t[2];
 }
 
+// LocalMap::needsPointRemoval (src/LocalMap.cpp:149-154): |(index + 0.5) * voxelSize - position| > d, every product and
+// sum rounded once.  Eviction removes the voxels it is true for; the submap (include/vgicp_hip_map_submap.h) selects
+// among those it is false for, so a NaN distance (there is none behind the entry points' checks) keeps a voxel.
+__device__ __forceinline__ bool voxel_beyond(int32_t kx, int32_t ky, int32_t kz, double voxel_size, double px, double py,
+                                             double pz, double distance) {
+#pragma clang fp contract(off)
+  const double dx = ((double)kx + 0.5) * voxel_size - px;
+  const double dy = ((double)ky + 0.5) * voxel_size - py;
+  const double dz = ((double)kz + 0.5) * voxel_size - pz;
+  return sqrt((dx * dx + dy * dy) + dz * dz) > distance;
+}
+
 // The key of free-space carving, the ray report and locate (their headers state it): floor(x / h) per axis, the
 // insertion's key (voxel_coord); false unless all three lie within +-2^30 (NaN and the infinities fail)
 __device__ __forceinline__ bool carve_key(const double* x, double h, int32_t* k) {

@@ -26,6 +26,8 @@ struct LocateFacts {
   ResidentFacts at;
 };
 using LocateVerdict = ResidentVerdict;
+// a level nobody asked for: locate's words, and the submap's (vgicp_submap_plan.h)
+constexpr const char* kLevelNotAskedText = "level is above the number of levels asked for: call vgicp_map_levels_build first";
 
 inline LocateVerdict plan_locate(const LocateFacts& f) {
   if (!f.ctx) return {1, VGICP_ERR_BAD_ARGUMENT};
@@ -38,8 +40,7 @@ inline LocateVerdict plan_locate(const LocateFacts& f) {
   if (locate_cells(f.window) > VGICP_LOCATE_MAX_CELLS)
     return {2, VGICP_ERR_BAD_ARGUMENT, "the window has more than VGICP_LOCATE_MAX_CELLS cells"};
   if (f.stride < 1) return {2, VGICP_ERR_BAD_ARGUMENT, "stride must be >= 1"};
-  if (f.level > f.requested)
-    return {3, VGICP_ERR_NOT_READY, "level is above the number of levels asked for: call vgicp_map_levels_build first"};
+  if (f.level > f.requested) return {3, VGICP_ERR_NOT_READY, kLevelNotAskedText};
   if (!f.poses_finite) return {4, VGICP_ERR_BAD_ARGUMENT, "an entry of a pose is not finite"};
   if (f.at.several_devices)
     return {5, VGICP_ERR_BAD_ARGUMENT, "vgicp_locate_resident is not available on multi-device contexts, communicators "

@@ -40,9 +40,13 @@
 // The ray report (include/vgicp_hip_map_rays.h) is the read-only query made of the same step: rays_confirm_kernel sets a
 // bit per slot that holds a return (a bitmap beside the table, not the spare word), rays_walk_kernel walks every ray up
 // to its first FULL voxel and classes it, for several poses in one grid.
+//
+// Submap as scan (include/vgicp_hip_map_submap.h) makes a resident scan of the table's voxels: eviction's distance test,
+// the insertion's transform, and a compaction by ballots and a prefix sum that keeps the slots' order.  Three launches.
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
 #include "vgicp_sort.h"
+#include "vgicp_submap_plan.h"
 
 namespace vgicp {
 namespace {
@@ -394,18 +398,14 @@ __global__ void insert_apply_list_kernel(VoxelRecord* table, const uint32_t* __r
   rec->reserved = 0;  // the list is empty again
 }
 
-// LocalMap::needsPointRemoval (src/LocalMap.cpp:149-154): |(index + 0.5) * voxelSize - position| > d
+// LocalMap::needsPointRemoval (voxel_beyond, vgicp_device_fn.h: the submap's selection asks the same question)
 __global__ void evict_kernel(VoxelRecord* table, uint64_t slots, double voxel_size, double px,
                              double py, double pz, double distance, uint32_t* counters) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool far = false;
   if (i < slots && table[i].state == SLOT_FULL) {
-#pragma clang fp contract(off)
     VoxelRecord* rec = table + i;
-    const double dx = ((double)rec->key[0] + 0.5) * voxel_size - px;
-    const double dy = ((double)rec->key[1] + 0.5) * voxel_size - py;
-    const double dz = ((double)rec->key[2] + 0.5) * voxel_size - pz;
-    far = sqrt((dx * dx + dy * dy) + dz * dz) > distance;
+    far = voxel_beyond(rec->key[0], rec->key[1], rec->key[2], voxel_size, px, py, pz, distance);
     if (far) rec->state = SLOT_TOMB;
   }
   // one atomic per workgroup: a mass eviction (788k of 1M voxels) was bound by 16 000 waves adding to one word
@@ -730,6 +730,150 @@ __global__ void raw_scatter_kernel(const RawPoint* __restrict__ log, uint32_t up
   }
 }
 
+// ---- submap as scan (include/vgicp_hip_map_submap.h states the rule operation by operation; this restates it) ----
+// MARK.  As the levels' claim launch: a thread issues the loads of its kSubmapPer slot heads together (one 16-byte read
+// out of every 128-byte line of a mostly EMPTY table; what it costs is how many are in flight).  Turn k of wave w covers
+// the 64 consecutive slots of ballot word k * 4 + w of the group.
+__global__ __launch_bounds__(kSubmapBlock) void submap_mark_kernel(SubmapArgs a) {
+  __shared__ uint32_t sums[3];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (tid < 3u) sums[tid] = 0u;
+  __syncthreads();
+  const uint64_t first_slot = (uint64_t)blockIdx.x * kSubmapGroupSlots + tid;
+  int4 heads[kSubmapPer];
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {
+    const uint64_t i = first_slot + kSubmapBlock * k;
+    heads[k] = i < a.slots ? *reinterpret_cast<const int4*>(a.table + i) : make_int4(0, 0, 0, SLOT_EMPTY);
+  }
+  uint32_t taken = 0, far = 0, few = 0;   // lane 0's: the wave's counts
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {
+    const int4 head = heads[k];
+    const bool full = head.w == SLOT_FULL;
+    const bool beyond = full && voxel_beyond(head.x, head.y, head.z, a.voxel_size, a.center[0], a.center[1], a.center[2], a.radius);
+    const bool inside = full && !beyond;
+    bool enough = true;
+    if (inside && a.min_count > 1ull) enough = a.table[first_slot + kSubmapBlock * k].count >= a.min_count;
+    const unsigned long long ballot = __ballot(inside && enough);
+    const unsigned long long b_far = __ballot(beyond), b_few = __ballot(inside && !enough);
+    if (lane == 0u) {
+      a.ballots[(size_t)blockIdx.x * kSubmapGroupWords + k * (kSubmapBlock / 64u) + wave] = ballot;
+      taken += (uint32_t)__popcll(ballot);
+      far += (uint32_t)__popcll(b_far);
+      few += (uint32_t)__popcll(b_few);
+    }
+  }
+  if (lane == 0u) {   // integers: the order of the four waves does not matter
+    if (taken) atomicAdd(&sums[0], taken);
+    if (far) atomicAdd(&sums[1], far);
+    if (few) atomicAdd(&sums[2], few);
+  }
+  __syncthreads();
+  if (tid < 3u) a.group_counts[(size_t)tid * a.groups + blockIdx.x] = sums[tid];
+}
+
+// SCAN.  One workgroup: the exclusive prefix sum of the groups' selected counts in place, 1 024 at a time with a carry,
+// and the three totals.
+__global__ __launch_bounds__(1024) void submap_scan_kernel(uint32_t* counts, uint32_t groups, unsigned long long* totals,
+                                                          unsigned long long* totals_host) {
+  __shared__ uint32_t wave_sum[16];
+  __shared__ unsigned long long wave_left[2][16];
+  __shared__ uint32_t carry;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (tid == 0u) carry = 0u;
+  __syncthreads();
+  unsigned long long far = 0ull, few = 0ull;
+  for (uint32_t base = 0; base < groups; base += 1024u) {
+    const uint32_t idx = base + tid;
+    const uint32_t val = idx < groups ? counts[idx] : 0u;
+    if (idx < groups) {
+      far += counts[(size_t)groups + idx];
+      few += counts[2 * (size_t)groups + idx];
+    }
+    uint32_t incl = val;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t up = __shfl_up(incl, d, 64);
+      if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63u) wave_sum[wave] = incl;
+    __syncthreads();
+    uint32_t before = carry;
+    for (uint32_t w = 0; w < wave; ++w) before += wave_sum[w];
+    if (idx < groups) counts[idx] = before + incl - val;
+    __syncthreads();
+    if (tid == 1023u) carry = before + incl;
+    __syncthreads();
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    far += __shfl_down(far, d, 64);
+    few += __shfl_down(few, d, 64);
+  }
+  if (lane == 0u) {
+    wave_left[0][wave] = far;
+    wave_left[1][wave] = few;
+  }
+  __syncthreads();
+  if (tid != 0u) return;
+  for (uint32_t w = 1; w < 16u; ++w) {
+    far += wave_left[0][w];
+    few += wave_left[1][w];
+  }
+  const unsigned long long out[3] = {carry, far, few};
+  for (int k = 0; k < 3; ++k) totals[k] = totals_host[k] = out[k];
+}
+
+// EMIT.  The group's kSubmapGroupWords ballots sit in the first lanes of every wave; their popcounts' prefix gives what
+// lies before each word.  A group that selected nothing leaves at once, a zero word touches no table line.
+__global__ __launch_bounds__(kSubmapBlock) void submap_emit_kernel(SubmapArgs a) {
+  static_assert(kSubmapGroupWords <= 64u, "a wave holds its group's ballots, one per lane");
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const unsigned long long mine = lane < kSubmapGroupWords ? a.ballots[(size_t)blockIdx.x * kSubmapGroupWords + lane] : 0ull;
+  const uint32_t pc = (uint32_t)__popcll(mine);
+  uint32_t incl = pc;
+#pragma unroll
+  for (int d = 1; d < (int)kSubmapGroupWords; d <<= 1) {
+    const uint32_t up = __shfl_up(incl, d, 64);
+    if (lane >= (uint32_t)d) incl += up;
+  }
+  if (__shfl(incl, (int)kSubmapGroupWords - 1, 64) == 0u) return;   // the whole group, so the whole workgroup
+  const uint32_t excl = incl - pc;
+  const uint32_t base = a.group_counts[blockIdx.x];
+  unsigned long long word[kSubmapPer];
+  uint32_t before[kSubmapPer];
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {   // every lane takes part in the cross-lane reads
+    const int q = (int)(k * (kSubmapBlock / 64u) + wave);
+    word[k] = __shfl(mine, q, 64);
+    before[k] = __shfl(excl, q, 64);
+  }
+#pragma unroll 1
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {
+    if (!((word[k] >> lane) & 1ull)) continue;
+    const size_t rank = (size_t)base + before[k] + (uint32_t)__popcll(word[k] & ((1ull << lane) - 1ull));
+    if (rank >= a.capacity) continue;   // the host sizes the outputs for every voxel of the table; this is the belt
+    const VoxelRecord* rec = a.table + ((uint64_t)blockIdx.x * kSubmapGroupSlots + kSubmapBlock * k + tid);
+    const int4 head = *reinterpret_cast<const int4*>(rec);
+    const double2* pay = reinterpret_cast<const double2*>(rec->mean);   // 16-byte aligned
+    const double2 p0 = pay[0], p1 = pay[1], p2 = pay[2], p3 = pay[3], p4 = pay[4], p5 = pay[5];
+    const unsigned long long count = rec->count;
+    const double C[9] = {p1.y, p2.x, p2.y, p3.x, p3.y, p4.x, p4.y, p5.x, p5.y};
+    double v[kScanPlanes];
+    transform_point(a.pose, a.pose + 9, p0.x, p0.y, p1.x, v);
+    rotate_cov_exact(a.pose, C, v + 3);
+#pragma unroll
+    for (int e = 0; e < 3; ++e) a.aos_points[3 * rank + e] = v[e];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.aos_covs[9 * rank + e] = v[3 + e];
+#pragma unroll
+    for (int e = 0; e < kScanPlanes; ++e) a.planes[(size_t)e * a.stride + rank] = v[e];   // consecutive ranks: contiguous
+    a.keys[3 * rank] = head.x;
+    a.keys[3 * rank + 1] = head.y;
+    a.keys[3 * rank + 2] = head.z;
+    a.counts[rank] = count;
+  }
+}
 
 }  // namespace
 
@@ -813,6 +957,13 @@ hipError_t launch_map_export(hipStream_t s, const VoxelRecord* table, uint64_t s
                              uint32_t* counters) {
   counted_launch(export_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, s, table, slots, capacity, keys, means, covs, counts,
                  counters);
+  return hipGetLastError();
+}
+
+hipError_t launch_submap(hipStream_t s, const SubmapArgs& a, unsigned long long* totals_host) {
+  counted_launch(submap_mark_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
+  counted_launch(submap_scan_kernel, dim3(1), dim3(1024), 0, s, a.group_counts, a.groups, a.totals, totals_host);
+  counted_launch(submap_emit_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
   return hipGetLastError();
 }
 

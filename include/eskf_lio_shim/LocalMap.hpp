@@ -42,6 +42,7 @@
 #include "../vgicp_hip_map_carve.h"
 #include "../vgicp_hip_map_rays.h"
 #include "../vgicp_hip_map_levels.h"
+#include "../vgicp_hip_map_submap.h"
 
 // The raw-point store's entry points (vgicp_hip_map_points.h, and vgicp_set_option for its option) are referenced
 // weakly, so a program that links a stand-in of the C ABI without them (tests/native/shadow_stress.cpp) still links: a
@@ -63,6 +64,9 @@
 #pragma weak vgicp_rays_resident
 // ... and the map levels' (vgicp_hip_map_levels.h, in libvgicp_hip_map_levels.so): without that library setLevels(n > 0) refuses.
 #pragma weak vgicp_map_levels_build
+// ... and the submap's (vgicp_hip_map_submap.h, in libvgicp_hip_map_submap.so): without that library scanFromMap refuses.
+#pragma weak vgicp_scan_from_map
+#pragma weak vgicp_scan_from_map_keys
 #include "ShimTypes.hpp"
 #include "ShimSupport.hpp"
 #include "ResidentScan.hpp"
@@ -591,6 +595,60 @@ public:
     levels_ = levels;
   }
   int levels() const {return levels_;}
+
+  // Submap as scan (include/vgicp_hip_map_submap.h): the resident scan of THIS map's context becomes the voxels of
+  // `source` (this map itself, or another map on the same device; with level > 0 that level of it, LocalMap::setLevels)
+  // whose centres lie within `radius` of `center` (in source's frame; infinity: all of them) and that hold at least
+  // minCount points, each moved by `frame` — on the device, in the order of source's table.  Every call over the
+  // resident scan then registers, scores or inserts a piece of map (ICP::alignSubmap is the loop-closure recipe).  The
+  // cloud CloudPreprocessor::process left on the device is no longer resident afterwards: an align of it uploads it.
+  // points == 0: nothing was selected and no scan is resident.  Both maps must keep their voxels on the device.
+  struct SubmapStats
+  {
+    uint64_t voxels = 0, points = 0, tooFar = 0, tooFew = 0;
+    double seconds = 0.0, deviceSeconds = 0.0;
+  };
+  SubmapStats scanFromMap(
+    const LocalMap & source, const Vector3d & center, double radius, const Isometry3d & frame, size_t minCount = 0,
+    int level = 0)
+  {
+    if (!vgicp_scan_from_map) {
+      throw std::runtime_error("LocalMap::scanFromMap: the linked vgicp module has no vgicp_scan_from_map (libvgicp_hip_map_submap.so)");
+    }
+    if (!deviceResident_ || !source.deviceResident_) {
+      throw std::runtime_error("LocalMap::scanFromMap: both maps must be device-resident");
+    }
+    vgicp_submap_params p{};
+    for (int a = 0; a < 3; ++a) {p.center[a] = center.data()[a];}
+    p.radius = radius;
+    const double * f = shim::poseData(frame);
+    for (int e = 0; e < 16; ++e) {p.frame[e] = f[e];}
+    p.min_count = minCount;
+    p.level = level;
+    vgicp_submap_stats st{};
+    shim::check(ctx_, vgicp_scan_from_map(ctx_, source.ctx_, &p, &st), "vgicp_scan_from_map");
+    SubmapStats out;
+    out.voxels = st.voxels;
+    out.points = st.points;
+    out.tooFar = st.too_far;
+    out.tooFew = st.too_few;
+    out.seconds = st.seconds;
+    out.deviceSeconds = st.device_seconds;
+    return out;
+  }
+  // The keys (3 per point) and counts of the voxels behind the resident scan scanFromMap made, in scan order.
+  void scanFromMapKeys(std::vector<int32_t> & keys, std::vector<uint64_t> & counts) const
+  {
+    if (!vgicp_scan_from_map_keys) {
+      throw std::runtime_error("LocalMap::scanFromMapKeys: the linked vgicp module has no vgicp_scan_from_map_keys (libvgicp_hip_map_submap.so)");
+    }
+    size_t n = 0;
+    const int rc = vgicp_scan_from_map_keys(ctx_, 0, nullptr, nullptr, &n);   // size query
+    if (rc != VGICP_OK && !(rc == VGICP_ERR_BAD_ARGUMENT && n > 0)) {shim::check(ctx_, rc, "vgicp_scan_from_map_keys");}
+    keys.assign(3 * n, 0);
+    counts.assign(n, 0);
+    shim::check(ctx_, vgicp_scan_from_map_keys(ctx_, n, keys.data(), counts.data(), &n), "vgicp_scan_from_map_keys");
+  }
 
   // The ray report (include/vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at a pose,
   // read-only — which returns appeared in front of the map's surface (VGICP_RAY_BEHIND), which rays the map blocks

@@ -263,6 +263,52 @@ public:
   }
   const std::vector<StageStats> & lastStages() const {return lastStages_;}          // of the last alignCoarseToFine()
 
+  // Where is this piece of `source` in `target`?  (Loop closure, the merge of two sessions, the re-entry into a loaded
+  // map with more than one sweep.)  The voxels of source within `radius` of anchor's translation become target's
+  // resident scan in the frame anchor^-1 (LocalMap::scanFromMap; minCount and level as there), i.e. as the cloud a sensor
+  // at `anchor` would have prepared, and are registered on target from `guess`, the anchor's pose in target's map as far
+  // as it is known (the anchor itself when the two maps are believed to share a frame) — through the coarse-to-fine
+  // chain when this ICP has a schedule (setCoarseToFine; target must keep the levels), else by one align.  Returns the
+  // anchor's pose in target's map; lastStats() / lastStages() describe the registration, lastSubmap() the selection.
+  // Throws std::runtime_error when nothing was selected.
+  Isometry3d alignSubmap(
+    LocalMap & source, LocalMap & target, const Isometry3d & anchor, double radius, const Isometry3d & guess,
+    size_t minCount = 0, int level = 0)
+  {
+    lastSubmap_ = target.scanFromMap(source, anchor.translation(), radius, anchor.inverse(), minCount, level);
+    if (lastSubmap_.points == 0) {throw std::runtime_error("ICP::alignSubmap: no voxel of the source was selected");}
+    vgicp_ctx * ctx = target.context();
+    applyRobust(ctx);
+    applyPrior(ctx);
+    lastUsedResidentScan_ = true;
+    shim::TraceScope tsCall(shim::Trace::AlignCall);
+    if (!schedule_.empty()) {
+      if (!vgicp_align_resident_levels) {
+        throw std::runtime_error(
+                "ICP::alignSubmap: the linked vgicp module has no vgicp_align_resident_levels (libvgicp_hip_map_levels.so)");
+      }
+      return chainResidentScan(ctx, guess, schedule_);
+    }
+    const vgicp_params params = paramsOf();
+    std::vector<uint64_t> counts(static_cast<size_t>(maxIteration_ > 0 ? maxIteration_ : 1), 0);
+    vgicp_stats stats{};
+    stats.corr_count = counts.data();
+    double pose[16];
+    const int rc = vgicp_align_resident(ctx, shim::poseData(guess), &params, pose, &stats);
+    if (rc != VGICP_OK && rc != VGICP_ERR_DEGENERATE) {shim::check(ctx, rc, "vgicp_align_resident");}
+    lastStats_.iterations = stats.iterations;
+    lastStats_.converged = stats.converged != 0;
+    lastStats_.seconds = stats.seconds;
+    lastStats_.deviceSeconds = stats.device_seconds;
+    counts.resize(static_cast<size_t>(stats.iterations));
+    lastStats_.correspondenceCounts = counts;
+    if (!lastStats_.converged) {
+      std::cout << "ICP not converged!\n";
+    }
+    return shim::poseFromData(pose);
+  }
+  const LocalMap::SubmapStats & lastSubmap() const {return lastSubmap_;}          // of the last alignSubmap()
+
   // The robust round of every later align / alignHypotheses of this ICP (vgicp_hip_robust.h): kind = VGICP_ROBUST_NONE,
   // _HUBER or _CAUCHY, its scale c, and the gate on the squared Mahalanobis residual (0 = none), in the library's
   // regularised units.  The library takes millionths: scale and gate are rounded to them.  Throws std::invalid_argument
@@ -1050,6 +1096,7 @@ private:
   double coarseTranslationSquaredThreshold_ = 1.0e-4;
   double coarseCosineThreshold_ = 0.999;
   std::vector<StageStats> lastStages_;
+  LocalMap::SubmapStats lastSubmap_;
   static constexpr int kLocateKeepMax = 8;
   LocateOptions locate_;               // of locate(cloud, map, guess)
   std::vector<LocateCandidate> lastLocation_;
