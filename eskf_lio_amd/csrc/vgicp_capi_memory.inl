@@ -406,6 +406,8 @@ int begin_scan(vgicp_ctx* ctx, size_t n, double prep_voxel, bool with_deskew) {
   ctx->prep_voxel = prep_voxel;
   ctx->prep_with_deskew = with_deskew;
   ctx->prep_deskewed = ctx->prep_indefinite = 0;
+  ctx->scan_deskewed = 0;
+  ctx->scan_indefinite = 0;
   ctx->stride = ctx->scan_capacity;
   return VGICP_OK;
 }

@@ -206,6 +206,8 @@ int settle_scan(vgicp_ctx* ctx) {
     return rc;
   }
   ctx->n = m;
+  ctx->scan_deskewed = ctx->prep_deskewed;
+  ctx->scan_indefinite = ctx->prep_indefinite;
   return VGICP_OK;
 }
 
@@ -816,8 +818,8 @@ int vgicp_scan_info(vgicp_ctx* ctx, size_t* kept, int64_t* deskewed, uint64_t* i
   if (rc != VGICP_OK) return rc;
   if (!ctx->scan_ready) return fail(ctx, VGICP_ERR_NOT_READY, "no scan resident");
   if (kept) *kept = ctx->n;
-  if (deskewed) *deskewed = ctx->prep_with_deskew ? ctx->prep_deskewed : 0;
-  if (indefinite) *indefinite = ctx->prep_indefinite;
+  if (deskewed) *deskewed = ctx->prep_with_deskew ? ctx->scan_deskewed : 0;
+  if (indefinite) *indefinite = ctx->scan_indefinite;
   return VGICP_OK;
 }
 
@@ -839,7 +841,7 @@ int vgicp_scan_prepare(vgicp_ctx* ctx, size_t n, const double* points, const dou
   rc = settle(ctx);  // one synchronisation
   if (rc != VGICP_OK) return rc;
   *kept = ctx->n;
-  if (deskewed && ctx->prep_with_deskew) *deskewed = ctx->prep_deskewed;
+  if (deskewed && ctx->prep_with_deskew) *deskewed = ctx->scan_deskewed;
   return VGICP_OK;
 }
 

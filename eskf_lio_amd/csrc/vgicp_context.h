@@ -413,6 +413,10 @@ struct vgicp_ctx {
   uint32_t scan_seq = 0;             // uploads so far; pack_scan_kernel marks an asymmetric covariance with it
   bool scan_sym_known = false;       // the resident scan went through pack_scan_kernel (not a scan prepared on the device)
   int64_t prep_deskewed = 0;
+  // what vgicp_scan_info answers for the RESIDENT scan: its own preparation's counts, taken when that is settled.  prep_deskewed
+  // and prep_indefinite are the LAST preparation's, vgicp_preprocess included, which leaves the resident scan alone
+  int64_t scan_deskewed = 0;
+  uint64_t scan_indefinite = 0;
   // the robust round (include/vgicp_hip_robust.h), as vgicp_set_option left it; kernel 0 and gate 0 = the plain round
   int robust_kernel = 0;             // VGICP_OPTION_ROBUST_KERNEL
   int robust_scale_micro = 1000000;  // VGICP_OPTION_ROBUST_SCALE_MICRO: c = value / 1e6

@@ -119,7 +119,8 @@ enum {
   VGICP_COUNTER_PREP_INDEFINITE = 4,  /* kept points of the LAST vgicp_preprocess / vgicp_scan_prepare whose
                                          regularised covariance has a negative eigenvalue (see vgicp_preprocess) */
   VGICP_COUNTER_SCAN_GENERATION = 5   /* goes up whenever the RESIDENT scan is replaced (vgicp_align, vgicp_scan_upload,
-                                         vgicp_scan_prepare*, vgicp_accumulate): a host object that remembers "my cloud is
+                                         vgicp_scan_prepare*, vgicp_accumulate, a side header's call that makes the
+                                         scan — also by a preparation that is refused, which leaves no scan): a host object that remembers "my cloud is
                                          the resident scan" (the shim's CloudPreprocessor / ICP pair) checks it; no
                                          synchronisation */,
   VGICP_COUNTER_UPLOAD_SLOW = 6       /* staged uploads whose copy threads were held up for so long (> 0.1 s) that the
@@ -289,8 +290,14 @@ int vgicp_scan_prepare(vgicp_ctx* ctx, size_t n, const double* points, const dou
  *   vgicp_map_insert_resident_async   LocalMap::updateLocalMap (:86): enqueued, counts read at the next
  *                                 synchronisation (a failure of the insertion is reported by the next call that
  *                                 synchronises: vgicp_align_resident, vgicp_map_size, ...).
- * vgicp_scan_info returns what the last preparation found (it synchronises if that is still pending). Any other
- * entry point first brings a pending preparation / insertion up to date.
+ * vgicp_scan_info returns what the preparation of the RESIDENT scan found (it synchronises if that is still pending): a
+ * vgicp_preprocess or vgicp_deskew in between changes nothing of it, and for a resident scan that no preparation made
+ * (vgicp_scan_upload, vgicp_align, vgicp_accumulate, a scan made from a voxel map) it answers (n, 0, 0).  Any other
+ * entry point first brings a pending preparation / insertion up to date — vgicp_scan_upload, vgicp_align,
+ * vgicp_accumulate and vgicp_scan_prepare too, although they replace the scan: a refusal that is still pending is
+ * reported by the first entry that settles, which then does nothing else (no scan is resident afterwards; the call is
+ * repeated).  Only vgicp_scan_prepare_async / _staged_async, the staging calls, vgicp_scan_fetch_sums, vgicp_solve_step
+ * and vgicp_get_counter (but for VGICP_COUNTER_PREP_INDEFINITE) settle nothing.
  * Lifetime of the caller's buffers: a sweep of up to 16 MB (points + capture times; VGICP_STAGE_LIMIT bytes in the
  * environment) is copied into page-locked staging memory of the context before the call returns — the caller's
  * buffers are free again at once, and the runtime never registers the caller's pages.  (A registered range that the

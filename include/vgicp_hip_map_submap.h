@@ -32,7 +32,9 @@
  *
  * WHAT THE CALL LEAVES IN dst.  Both layouts of the resident scan are written (the AoS copy and the twelve planes); the
  * scan counts as one whose covariances' symmetry is unknown (all twelve planes are read); the scan generation counter
- * advances by one; everything else is as after vgicp_scan_upload of the same points.  When nothing is selected the call
+ * advances by one; everything else is as after vgicp_scan_upload of the same points: vgicp_scan_info answers (n, 0, 0),
+ * a fetch that was open and its checksums are void, and what is pending in dst is settled first — a preparation's
+ * refusal that is still pending there is reported by this call, which then does nothing else.  When nothing is selected the call
  * returns VGICP_OK with points == 0 and dst has NO resident scan afterwards: resident calls answer VGICP_ERR_NOT_READY.
  * The key and the count of every selected voxel, in scan order, stay in device memory of dst;
  * vgicp_scan_from_map_keys delivers them while the scan generation is still the one the call produced.
