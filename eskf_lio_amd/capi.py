@@ -62,9 +62,11 @@ SEARCH_REPORT_EXPORTS = ("vgicp_prepare_search_report",)   # a test hook
 MAP_LEVELS_EXPORTS = ("vgicp_map_levels_build", "vgicp_map_level_size", "vgicp_map_level_export", "vgicp_align_resident_levels")
 MAP_LOCATE_EXPORTS = ("vgicp_locate_resident",)
 MAP_SUBMAP_EXPORTS = ("vgicp_scan_from_map", "vgicp_scan_from_map_keys")
+MAP_CHECKPOINT_EXPORTS = ("vgicp_map_checkpoint_size", "vgicp_map_checkpoint", "vgicp_map_checkpoint_info", "vgicp_map_restore")
 SIDE_EXPORTS = {"prior": PRIOR_EXPORTS, "points": POINTS_EXPORTS, "map_gated": MAP_GATED_EXPORTS,
                 "map_carve": MAP_CARVE_EXPORTS, "map_rays": MAP_RAYS_EXPORTS, "search_report": SEARCH_REPORT_EXPORTS,
-                "map_levels": MAP_LEVELS_EXPORTS, "map_locate": MAP_LOCATE_EXPORTS, "map_submap": MAP_SUBMAP_EXPORTS}
+                "map_levels": MAP_LEVELS_EXPORTS, "map_locate": MAP_LOCATE_EXPORTS, "map_submap": MAP_SUBMAP_EXPORTS,
+                "map_checkpoint": MAP_CHECKPOINT_EXPORTS}
 
 
 def side_lib_path(name: str) -> str:
@@ -267,6 +269,59 @@ class SubmapResult:
     device_seconds: float
 
 
+CHECKPOINT_FORMAT, CHECKPOINT_HEADER_BYTES, CHECKPOINT_RAW_POINTS, CHECKPOINT_RULES = 1, 128, 1, 14
+
+
+class CheckpointInfo(C.Structure):
+    """vgicp_checkpoint_info (vgicp_hip_map_checkpoint.h), 80 bytes."""
+    _fields_ = [("format", C.c_uint32), ("header_bytes", C.c_uint32), ("total_bytes", C.c_uint64), ("voxel_size", C.c_double),
+                ("slots", C.c_uint64), ("voxels", C.c_uint64), ("tombstones", C.c_uint64), ("raw_points", C.c_uint64),
+                ("flags", C.c_uint32), ("record_bytes", C.c_uint32), ("checksum", C.c_uint64), ("rule", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class CheckpointStats(C.Structure):
+    """vgicp_checkpoint_stats (vgicp_hip_map_checkpoint.h), 56 bytes."""
+    _fields_ = [("bytes", C.c_uint64), ("voxels", C.c_uint64), ("tombstones", C.c_uint64), ("raw_points", C.c_uint64),
+                ("launches", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double), ("device_seconds", C.c_double)]
+
+
+@dataclass
+class CheckpointResult:
+    """What Context.map_restore returns (and Context.last_checkpoint holds): vgicp_checkpoint_stats."""
+    bytes: int
+    voxels: int
+    tombstones: int
+    raw_points: int
+    launches: int
+    seconds: float
+    device_seconds: float
+
+
+def _blob_bytes(blob) -> np.ndarray:
+    """A blob as a contiguous uint8 array; of a file's content (a shim file: the blob, then a trailer) the blob alone,
+    by the header's total_bytes."""
+    b = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    if b.size >= CHECKPOINT_HEADER_BYTES and bytes(b[:8]) == b"VGICPMAP":
+        total = int(b[16:24].view("<u8")[0])
+        if CHECKPOINT_HEADER_BYTES <= total < b.size and bytes(b[total:total + 8]) == b"VGICPTRJ":
+            b = b[:total]
+    return np.ascontiguousarray(b)
+
+
+def map_checkpoint_info(blob) -> dict:
+    """vgicp_map_checkpoint_info (host only): the header's fields and `rule`, 0 when the blob passes the check, else the
+    number of the first rule it fails, with `message` naming it."""
+    lib = load_library()
+    b = _blob_bytes(blob)
+    info = CheckpointInfo()
+    rc = lib.vgicp_map_checkpoint_info(b.ctypes.data_as(C.c_void_p), b.size, C.byref(info))
+    out = {name: getattr(info, name) for name, _ in CheckpointInfo._fields_ if name != "reserved"}
+    out["message"] = "" if rc == OK else lib.vgicp_last_error(None).decode()
+    return out
+
+
 class RayParams(C.Structure):
     """vgicp_ray_params (vgicp_hip_map_rays.h), 56 bytes."""
     _fields_ = [("origin", C.c_double * 3), ("margin", C.c_double), ("beyond", C.c_double), ("max_range", C.c_double),
@@ -387,6 +442,10 @@ PROTOTYPES = {
     "vgicp_scan_from_map": [vp, vp, C.POINTER(SubmapParams), C.POINTER(SubmapStats)],
     "vgicp_scan_from_map_keys": [vp, sz, ip, C.POINTER(C.c_uint64), C.POINTER(sz)],
     "vgicp_prepare_search_report": [vp, C.POINTER(SearchReport)],
+    "vgicp_map_checkpoint_size": [vp, C.POINTER(sz)],
+    "vgicp_map_checkpoint": [vp, sz, vp, C.POINTER(sz), C.POINTER(CheckpointStats)],
+    "vgicp_map_checkpoint_info": [vp, sz, C.POINTER(CheckpointInfo)],
+    "vgicp_map_restore": [vp, vp, sz, C.POINTER(CheckpointStats)],
 }
 RESTYPES = {"vgicp_last_error": C.c_char_p, "vgicp_peer_status": C.c_char_p}
 del vp, dp, ip, sz
@@ -1184,6 +1243,32 @@ class Context:
                                                        counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(w)))
         assert w.value == n, (w.value, n)
         return keys, counts
+
+    # -- map checkpoint (vgicp_hip_map_checkpoint.h) --
+    def map_checkpoint_size(self) -> int:
+        w = C.c_size_t()
+        self._check(self._lib.vgicp_map_checkpoint_size(self._h, C.byref(w)))
+        return w.value
+
+    def map_checkpoint(self) -> np.ndarray:
+        """vgicp_map_checkpoint: the map as one blob (uint8 array), packed on the device; read-only.  The call's stats
+        stay in self.last_checkpoint."""
+        blob = np.zeros(self.map_checkpoint_size(), dtype=np.uint8)
+        w, st = C.c_size_t(), CheckpointStats()
+        self._check(self._lib.vgicp_map_checkpoint(self._h, blob.size, blob.ctypes.data_as(C.c_void_p), C.byref(w), C.byref(st)))
+        assert w.value == blob.size, (w.value, blob.size)
+        self.last_checkpoint = CheckpointResult(int(st.bytes), int(st.voxels), int(st.tombstones), int(st.raw_points),
+                                                st.launches, st.seconds, st.device_seconds)
+        return blob
+
+    def map_restore(self, blob) -> "CheckpointResult":
+        """vgicp_map_restore: this context's map becomes the blob's, slot for slot.  blob: a uint8 array or bytes; the
+        content of a file the shim's saveCheckpoint wrote is read by total_bytes, its trailer ignored."""
+        b = _blob_bytes(blob)
+        st = CheckpointStats()
+        self._check(self._lib.vgicp_map_restore(self._h, b.ctypes.data_as(C.c_void_p), b.size, C.byref(st)))
+        return CheckpointResult(int(st.bytes), int(st.voxels), int(st.tombstones), int(st.raw_points), st.launches,
+                                st.seconds, st.device_seconds)
 
     def rays_resident(self, poses, params, per_point: bool = True) -> "RayReport":
         """vgicp_rays_resident (vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at `poses`

@@ -37,6 +37,7 @@
 #include "../../include/vgicp_hip_map_levels.h"
 #include "../../include/vgicp_hip_map_locate.h"
 #include "../../include/vgicp_hip_map_submap.h"
+#include "../../include/vgicp_hip_map_checkpoint.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -47,6 +48,7 @@
 #include "vgicp_levels_plan.h"
 #include "vgicp_locate_plan.h"
 #include "vgicp_submap_plan.h"
+#include "vgicp_checkpoint_plan.h"
 
 using namespace vgicp;
 
@@ -534,6 +536,11 @@ struct vgicp_ctx {
   PinnedBuf<unsigned long long> h_submap;   // pinned, 4 words; .dev(): where the scan launch writes the totals
   uint64_t submap_generation = 0;        // the scan_generation vgicp_scan_from_map left (0: it never ran): the keys are that scan's
   EventHandle ev_submap;                 // as the SOURCE of a call between two contexts: behind this stream's work, for dst's stream to wait on
+  // the map checkpoint (include/vgicp_hip_map_checkpoint.h); made by the first call, grow-only.  The device side of a
+  // call is carved out of the staging area (d_stage)
+  PinnedBuf<char> h_checkpoint;          // pinned: the blob on its way out (header room, then the payload) or in
+  size_t checkpoint_capacity = 0;        // bytes h_checkpoint holds
+  PinnedBuf<unsigned long long> h_checkpoint_totals;   // pinned, 4 words; .dev(): where the scan launch writes {FULL, TOMB, raw points}
   // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
   // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
@@ -751,6 +758,11 @@ int locate_resident(vgicp_ctx* ctx, const double* poses, size_t k, const vgicp_l
 // The entry points of include/vgicp_hip_map_submap.h behind libvgicp_hip_map_submap.so, likewise (vgicp_capi_map_submap.inl).
 int scan_from_map(vgicp_ctx* dst, vgicp_ctx* src, const vgicp_submap_params* params, vgicp_submap_stats* stats);
 int scan_from_map_keys(vgicp_ctx* dst, size_t capacity, int32_t* keys, uint64_t* counts, size_t* written);
+// The entry points of include/vgicp_hip_map_checkpoint.h behind libvgicp_hip_map_checkpoint.so, likewise
+// (vgicp_capi_map_checkpoint.inl); vgicp_map_checkpoint_info needs no context and stays in its library.
+int map_checkpoint_size(vgicp_ctx* ctx, size_t* bytes);
+int map_checkpoint(vgicp_ctx* ctx, size_t capacity, void* blob, size_t* written, vgicp_checkpoint_stats* stats);
+int map_restore(vgicp_ctx* ctx, const void* blob, size_t bytes, vgicp_checkpoint_stats* stats);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

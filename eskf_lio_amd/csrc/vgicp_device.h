@@ -671,6 +671,52 @@ struct SubmapArgs {
   unsigned long long* counts;    // capacity
 };
 hipError_t launch_submap(hipStream_t s, const SubmapArgs& args, unsigned long long* totals_host);
+// Map checkpoint (include/vgicp_hip_map_checkpoint.h has the format): the submap's three launches over the same groups,
+// with two ballots per 64 slots (FULL, TOMB).  MARK leaves the ballots, per ballot word the sum of its FULL records'
+// counts (word_raw, raw points only) and three counts per group; SCAN (one workgroup) turns the groups' counts into
+// exclusive offsets and writes the totals {FULL, TOMB, raw points} to `totals` and to totals_host (page-locked memory);
+// EMIT writes the ascending slot lists, the records at their ranks (eight lanes per record; the spare word as zero) and
+// per FULL slot the offset of its points in the raw section.  The table is only read.
+struct CheckpointArgs {
+  const VoxelRecord* table;
+  uint64_t slots;
+  unsigned long long* ballots;   // [groups][2][kSubmapGroupWords]
+  uint32_t* word_raw;            // [groups][kSubmapGroupWords], or nullptr: no raw points
+  uint32_t* group_counts;        // [3][groups]: FULL, TOMB, raw (after SCAN: the exclusive offsets)
+  uint32_t groups;
+  uint32_t full_capacity, tomb_capacity;   // entries the lists (and `records`) hold: ranks at or beyond are dropped
+  unsigned long long* totals;    // 4 words
+  uint32_t* full_slots;
+  uint32_t* tomb_slots;
+  VoxelRecord* records;
+  uint32_t* offsets;             // [slots], written at FULL slots; or nullptr
+};
+hipError_t launch_checkpoint(hipStream_t s, const CheckpointArgs& args, unsigned long long* totals_host);
+// ... and every live entry of the log to points[offsets[slot] + ordinal] (3 doubles; positions at or beyond `capacity`
+// are dropped)
+hipError_t launch_checkpoint_raw(hipStream_t s, const RawPoint* log, uint32_t upper, const uint32_t* ctr, const VoxelRecord* table,
+                                 uint64_t slots, const uint32_t* offsets, uint32_t capacity, double* points);
+// The restore: records[j] to table[full_slots[j]] (eight lanes per record), the state of table[tomb_slots[j]] to
+// SLOT_TOMB; with raw points (log != nullptr) three more launches rebuild the log in canonical order — the sums of the
+// counts per block of 1 024 records, their exclusive prefix sum, and the entries {xyz, full_slots[j], o} at offset[j] + o,
+// ctr[0] = raw_points.  A slot at or beyond `slots` and a position at or beyond raw_points are dropped.  The table was
+// cleared on the same stream.
+struct RestoreArgs {
+  VoxelRecord* table;
+  uint64_t slots;
+  const uint32_t* full_slots;
+  const uint32_t* tomb_slots;
+  const VoxelRecord* records;
+  uint32_t voxels, tombstones;
+  const double* raw;             // raw_points x 3
+  uint32_t raw_points;
+  RawPoint* log;                 // or nullptr
+  uint32_t log_capacity;
+  uint32_t* ctr;                 // RawLog::ctr
+  uint32_t* block_sums;          // one word per 1 024 records
+  unsigned long long* totals;    // 4 words
+};
+hipError_t launch_restore(hipStream_t s, const RestoreArgs& args);
 // Append every FULL record to the output arrays (unordered); counters[0] = records written.
 hipError_t launch_map_export(hipStream_t s, const VoxelRecord* table, uint64_t slots, uint32_t capacity,
                              int32_t* keys, double* means, double* covs, uint64_t* counts,

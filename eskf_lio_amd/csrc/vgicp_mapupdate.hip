@@ -43,10 +43,14 @@
 //
 // Submap as scan (include/vgicp_hip_map_submap.h) makes a resident scan of the table's voxels: eviction's distance test,
 // the insertion's transform, and a compaction by ballots and a prefix sum that keeps the slots' order.  Three launches.
+//
+// The map checkpoint (include/vgicp_hip_map_checkpoint.h) packs the table into a blob with the same three launches and two
+// ballots per word (FULL, TOMB), and the restore scatters a blob back slot for slot.
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
 #include "vgicp_sort.h"
 #include "vgicp_submap_plan.h"
+#include "vgicp_checkpoint_plan.h"
 
 namespace vgicp {
 namespace {
@@ -875,6 +879,250 @@ __global__ __launch_bounds__(kSubmapBlock) void submap_emit_kernel(SubmapArgs a)
   }
 }
 
+// ---- map checkpoint (include/vgicp_hip_map_checkpoint.h has the format) ----
+// MARK.  The submap's, with two ballots per turn and no decision but the state; with raw points the wave also sums its
+// FULL records' counts (one 8-byte read out of the line the head came from).
+__global__ __launch_bounds__(kSubmapBlock) void checkpoint_mark_kernel(CheckpointArgs a) {
+  __shared__ uint32_t sums[3];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (tid < 3u) sums[tid] = 0u;
+  __syncthreads();
+  const uint64_t first_slot = (uint64_t)blockIdx.x * kSubmapGroupSlots + tid;
+  int4 heads[kSubmapPer];
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {
+    const uint64_t i = first_slot + kSubmapBlock * k;
+    heads[k] = i < a.slots ? *reinterpret_cast<const int4*>(a.table + i) : make_int4(0, 0, 0, SLOT_EMPTY);
+  }
+  uint32_t n_full = 0, n_tomb = 0, n_raw = 0;   // lane 0's: the wave's counts
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {
+    const bool full = heads[k].w == SLOT_FULL;
+    const unsigned long long b_full = __ballot(full), b_tomb = __ballot(heads[k].w == SLOT_TOMB);
+    uint32_t points = 0;
+    if (a.word_raw) {   // the same for every lane
+      points = full ? (uint32_t)a.table[first_slot + kSubmapBlock * k].count : 0u;
+      for (int d = 32; d > 0; d >>= 1) points += __shfl_down(points, d, 64);
+    }
+    if (lane == 0u) {
+      const uint32_t q = k * (kSubmapBlock / 64u) + wave;
+      a.ballots[((size_t)blockIdx.x * 2) * kSubmapGroupWords + q] = b_full;
+      a.ballots[((size_t)blockIdx.x * 2 + 1) * kSubmapGroupWords + q] = b_tomb;
+      if (a.word_raw) a.word_raw[(size_t)blockIdx.x * kSubmapGroupWords + q] = points;
+      n_full += (uint32_t)__popcll(b_full);
+      n_tomb += (uint32_t)__popcll(b_tomb);
+      n_raw += points;
+    }
+  }
+  if (lane == 0u) {   // integers: the order of the four waves does not matter
+    if (n_full) atomicAdd(&sums[0], n_full);
+    if (n_tomb) atomicAdd(&sums[1], n_tomb);
+    if (n_raw) atomicAdd(&sums[2], n_raw);
+  }
+  __syncthreads();
+  if (tid < 3u) a.group_counts[(size_t)tid * a.groups + blockIdx.x] = sums[tid];
+}
+
+// SCAN.  One workgroup: the exclusive prefix sum of each of `arrays` rows of `groups` counts in place, 1 024 at a time
+// with a carry, and each row's total (to both places; totals_host may be nullptr).
+__global__ __launch_bounds__(1024) void checkpoint_scan_kernel(uint32_t* counts, uint32_t groups, uint32_t arrays,
+                                                              unsigned long long* totals, unsigned long long* totals_host) {
+  __shared__ uint32_t wave_sum[16];
+  __shared__ uint32_t carry;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  for (uint32_t r = 0; r < arrays; ++r) {
+    uint32_t* row = counts + (size_t)r * groups;
+    if (tid == 0u) carry = 0u;
+    __syncthreads();
+    for (uint32_t base = 0; base < groups; base += 1024u) {
+      const uint32_t idx = base + tid;
+      const uint32_t val = idx < groups ? row[idx] : 0u;
+      uint32_t incl = val;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+      }
+      if (lane == 63u) wave_sum[wave] = incl;
+      __syncthreads();
+      uint32_t before = carry;
+      for (uint32_t w = 0; w < wave; ++w) before += wave_sum[w];
+      if (idx < groups) row[idx] = before + incl - val;
+      __syncthreads();
+      if (tid == 1023u) carry = before + incl;
+      __syncthreads();
+    }
+    if (tid == 0u) {
+      totals[r] = carry;
+      if (totals_host) totals_host[r] = carry;
+    }
+    __syncthreads();
+  }
+}
+
+// EMIT.  A wave holds its group's ballots and sums, one per lane: lanes 0 .. 15 the FULL words, 16 .. 31 the TOMB words,
+// 32 .. 47 the raw sums; a prefix sum inside each run of 16 lanes gives what lies before each word.  A lane's slot and
+// rank as in the submap's EMIT; the records are then copied eight lanes to a record, 16 bytes each: every read and every
+// write is a whole line.  The last 16 bytes are the count and the spare word, which goes out as zero.
+__global__ __launch_bounds__(kSubmapBlock) void checkpoint_emit_kernel(CheckpointArgs a) {
+  static_assert(kSubmapGroupWords == 16u, "three runs of 16 lanes hold a group's ballots and sums");
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, seg = lane >> 4, in_seg = lane & 15u;
+  const size_t g = blockIdx.x;
+  unsigned long long mine = 0ull;
+  if (seg < 2u) mine = a.ballots[(g * 2 + seg) * kSubmapGroupWords + in_seg];
+  uint32_t val = (uint32_t)__popcll(mine);
+  if (seg == 2u && a.word_raw) val = a.word_raw[g * kSubmapGroupWords + in_seg];
+  uint32_t incl = val;
+#pragma unroll
+  for (int d = 1; d < 16; d <<= 1) {
+    const uint32_t up = __shfl_up(incl, d, 64);
+    if (in_seg >= (uint32_t)d) incl += up;
+  }
+  if (__shfl(incl, 15, 64) == 0u && __shfl(incl, 31, 64) == 0u) return;   // the whole group, so the whole workgroup
+  const uint32_t excl = incl - val;
+  const uint32_t base_full = a.group_counts[g], base_tomb = a.group_counts[(size_t)a.groups + g];
+  const uint32_t base_raw = a.offsets ? a.group_counts[2 * (size_t)a.groups + g] : 0u;
+  unsigned long long w_full[kSubmapPer], w_tomb[kSubmapPer];
+  uint32_t b_full[kSubmapPer], b_tomb[kSubmapPer], b_raw[kSubmapPer];
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {   // every lane takes part in the cross-lane reads
+    const int q = (int)(k * (kSubmapBlock / 64u) + wave);
+    w_full[k] = __shfl(mine, q, 64);
+    w_tomb[k] = __shfl(mine, 16 + q, 64);
+    b_full[k] = __shfl(excl, q, 64);
+    b_tomb[k] = __shfl(excl, 16 + q, 64);
+    b_raw[k] = __shfl(excl, 32 + q, 64);
+  }
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {
+    if ((w_full[k] | w_tomb[k]) == 0ull) continue;   // the wave's 64 slots of this turn: nothing here (the same for every lane)
+    const uint64_t wave_slot = (uint64_t)g * kSubmapGroupSlots + kSubmapBlock * k + 64u * wave;
+    const uint32_t slot = (uint32_t)(wave_slot + lane);
+    const bool full = (w_full[k] >> lane) & 1ull;
+    if ((w_tomb[k] >> lane) & 1ull) {
+      const uint32_t rank = base_tomb + b_tomb[k] + (uint32_t)__popcll(w_tomb[k] & below);
+      if (rank < a.tomb_capacity) a.tomb_slots[rank] = slot;
+    }
+    const uint32_t first = base_full + b_full[k];
+    if (full) {
+      const uint32_t rank = first + (uint32_t)__popcll(w_full[k] & below);
+      if (rank < a.full_capacity) a.full_slots[rank] = slot;
+    }
+    if (w_full[k] == 0ull) continue;
+    if (a.offsets) {   // the same for every lane: the prefix sum of the counts in slot order
+      const uint32_t c = full ? (uint32_t)a.table[slot].count : 0u;
+      uint32_t upto = c;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(upto, d, 64);
+        if (lane >= (uint32_t)d) upto += up;
+      }
+      if (full) a.offsets[slot] = base_raw + b_raw[k] + upto - c;
+    }
+    const uint32_t part = lane & 7u;
+#pragma unroll 1
+    for (uint32_t pass = 0; pass < 8u; ++pass) {
+      const uint32_t r = pass * 8u + (lane >> 3);   // which of the wave's 64 slots
+      if (!((w_full[k] >> r) & 1ull)) continue;
+      const uint32_t rank = first + (uint32_t)__popcll(w_full[k] & ((1ull << r) - 1ull));
+      if (rank >= a.full_capacity) continue;   // the host sizes the outputs for every voxel it knows of; this is the belt
+      uint4 v = reinterpret_cast<const uint4*>(a.table + wave_slot + r)[part];
+      if (part == 7u) v.z = v.w = 0u;          // {count, spare}: the spare word is the launches' scratch, zero in a blob
+      reinterpret_cast<uint4*>(a.records + rank)[part] = v;
+    }
+  }
+}
+
+// The live entries of the log to their places in the raw section (raw_scatter_kernel without the keys).
+__global__ void checkpoint_raw_kernel(const RawPoint* __restrict__ log, uint32_t upper, const uint32_t* ctr,
+                                      const VoxelRecord* __restrict__ table, uint64_t slots,
+                                      const uint32_t* __restrict__ offsets, uint32_t capacity, double* __restrict__ points) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t used = ctr[0] < upper ? ctr[0] : upper;
+  if (e >= used) return;
+  const RawPoint p = log[e];
+  if ((uint64_t)p.slot >= slots) return;   // see raw_compact_kernel
+  const VoxelRecord* rec = table + p.slot;
+  if (rec->state != SLOT_FULL || p.ordinal >= rec->count) return;  // dead (evicted / erased voxel)
+  const uint64_t pos = (uint64_t)offsets[p.slot] + p.ordinal;
+  if (pos >= capacity) return;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) points[3 * pos + k] = p.xyz[k];
+}
+
+// ---- the restore ----
+// SCATTER.  Eight lanes per record, 16 bytes each; behind them one lane per tombstone writes a head whose state is
+// SLOT_TOMB (nothing reads a tombstone's other bytes).  Every slot passed the host's check; the compare is the belt.
+__global__ void restore_scatter_kernel(RestoreArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t parts = 8ull * a.voxels;
+  if (i < parts) {
+    const uint64_t j = i >> 3;
+    const uint32_t part = (uint32_t)i & 7u, slot = a.full_slots[j];
+    if ((uint64_t)slot >= a.slots) return;
+    reinterpret_cast<uint4*>(a.table + slot)[part] = reinterpret_cast<const uint4*>(a.records + j)[part];
+    return;
+  }
+  const uint64_t t = i - parts;
+  if (t >= a.tombstones) return;
+  const uint32_t slot = a.tomb_slots[t];
+  if ((uint64_t)slot >= a.slots) return;
+  *reinterpret_cast<int4*>(a.table + slot) = make_int4(0, 0, 0, SLOT_TOMB);
+}
+// a record's count as the log's rebuild takes it: never beyond the points the blob holds (rule 14 says their sum is that)
+__device__ __forceinline__ uint32_t restore_count(const RestoreArgs& a, uint64_t j) {
+  if (j >= a.voxels) return 0u;
+  const uint64_t c = a.records[j].count;
+  return c < a.raw_points ? (uint32_t)c : a.raw_points;
+}
+// the sum over a workgroup of kRestoreBlock lanes of v (to every lane), and what lies before this lane's
+__device__ __forceinline__ uint32_t restore_block_scan(uint32_t v, uint32_t* wave_sum, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t up = __shfl_up(incl, d, 64);
+    if (lane >= (uint32_t)d) incl += up;
+  }
+  if (lane == 63u) wave_sum[wave] = incl;
+  __syncthreads();
+  uint32_t before = 0u, all = 0u;
+  for (uint32_t w = 0; w < kRestoreBlock / 64u; ++w) {
+    if (w < wave) before += wave_sum[w];
+    all += wave_sum[w];
+  }
+  *total = all;
+  return before + incl - v;
+}
+__global__ __launch_bounds__(kRestoreBlock) void restore_raw_count_kernel(RestoreArgs a) {
+  __shared__ uint32_t wave_sum[kRestoreBlock / 64u];
+  uint32_t total;
+  (void)restore_block_scan(restore_count(a, (uint64_t)blockIdx.x * kRestoreBlock + threadIdx.x), wave_sum, &total);
+  if (threadIdx.x == 0u) a.block_sums[blockIdx.x] = total;
+}
+// block_sums are exclusive offsets by now: record j's points go to offset[j] .. offset[j] + count
+__global__ __launch_bounds__(kRestoreBlock) void restore_raw_fill_kernel(RestoreArgs a) {
+  __shared__ uint32_t wave_sum[kRestoreBlock / 64u];
+  const uint64_t j = (uint64_t)blockIdx.x * kRestoreBlock + threadIdx.x;
+  const uint32_t c = restore_count(a, j);
+  uint32_t total;
+  const uint32_t at = a.block_sums[blockIdx.x] + restore_block_scan(c, wave_sum, &total);
+  if (blockIdx.x == 0u && threadIdx.x == 0u) a.ctr[0] = a.raw_points;
+  if (c == 0u) return;
+  const uint32_t slot = a.full_slots[j];
+  for (uint32_t o = 0; o < c; ++o) {
+    const uint64_t pos = (uint64_t)at + o;
+    if (pos >= a.raw_points || pos >= a.log_capacity) return;
+    RawPoint p;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p.xyz[k] = a.raw[3 * pos + k];
+    p.slot = slot;
+    p.ordinal = o;
+    a.log[pos] = p;
+  }
+}
+
 }  // namespace
 
 size_t map_insert_scratch_bytes(uint32_t n) {
@@ -964,6 +1212,34 @@ hipError_t launch_submap(hipStream_t s, const SubmapArgs& a, unsigned long long*
   counted_launch(submap_mark_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
   counted_launch(submap_scan_kernel, dim3(1), dim3(1024), 0, s, a.group_counts, a.groups, a.totals, totals_host);
   counted_launch(submap_emit_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_checkpoint(hipStream_t s, const CheckpointArgs& a, unsigned long long* totals_host) {
+  if (!a.table || a.groups == 0 || a.slots != (uint64_t)a.groups * kSubmapGroupSlots) return hipErrorInvalidValue;
+  counted_launch(checkpoint_mark_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
+  counted_launch(checkpoint_scan_kernel, dim3(1), dim3(1024), 0, s, a.group_counts, a.groups, a.word_raw ? 3u : 2u, a.totals, totals_host);
+  counted_launch(checkpoint_emit_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_checkpoint_raw(hipStream_t s, const RawPoint* log, uint32_t upper, const uint32_t* ctr, const VoxelRecord* table,
+                                 uint64_t slots, const uint32_t* offsets, uint32_t capacity, double* points) {
+  if (upper == 0) return hipSuccess;
+  counted_launch(checkpoint_raw_kernel, dim3(blocks_for(upper, 256)), dim3(256), 0, s, log, upper, ctr, table, slots, offsets,
+                 capacity, points);
+  return hipGetLastError();
+}
+
+hipError_t launch_restore(hipStream_t s, const RestoreArgs& a) {
+  const uint64_t lanes = 8ull * a.voxels + a.tombstones;
+  if (lanes > 0) counted_launch(restore_scatter_kernel, dim3(blocks_for(lanes, 256)), dim3(256), 0, s, a);
+  if (a.log && a.voxels > 0) {
+    const uint32_t blocks = restore_blocks(a.voxels);
+    counted_launch(restore_raw_count_kernel, dim3(blocks), dim3(kRestoreBlock), 0, s, a);
+    counted_launch(checkpoint_scan_kernel, dim3(1), dim3(1024), 0, s, a.block_sums, blocks, 1u, a.totals, (unsigned long long*)nullptr);
+    counted_launch(restore_raw_fill_kernel, dim3(blocks), dim3(kRestoreBlock), 0, s, a);
+  }
   return hipGetLastError();
 }
 

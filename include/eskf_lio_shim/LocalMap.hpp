@@ -23,7 +23,10 @@
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <cstring>
 #include <fstream>
+#include <iterator>
 #include <iostream>
 #include <limits>
 #include <stdexcept>
@@ -43,6 +46,7 @@
 #include "../vgicp_hip_map_rays.h"
 #include "../vgicp_hip_map_levels.h"
 #include "../vgicp_hip_map_submap.h"
+#include "../vgicp_hip_map_checkpoint.h"
 
 // The raw-point store's entry points (vgicp_hip_map_points.h, and vgicp_set_option for its option) are referenced
 // weakly, so a program that links a stand-in of the C ABI without them (tests/native/shadow_stress.cpp) still links: a
@@ -67,6 +71,11 @@
 // ... and the submap's (vgicp_hip_map_submap.h, in libvgicp_hip_map_submap.so): without that library scanFromMap refuses.
 #pragma weak vgicp_scan_from_map
 #pragma weak vgicp_scan_from_map_keys
+// ... and the map checkpoint's (vgicp_hip_map_checkpoint.h, in libvgicp_hip_map_checkpoint.so): without that library
+// saveCheckpoint and loadCheckpoint refuse.
+#pragma weak vgicp_map_checkpoint_size
+#pragma weak vgicp_map_checkpoint
+#pragma weak vgicp_map_restore
 #include "ShimTypes.hpp"
 #include "ShimSupport.hpp"
 #include "ResidentScan.hpp"
@@ -650,6 +659,98 @@ public:
     shim::check(ctx_, vgicp_scan_from_map_keys(ctx_, n, keys.data(), counts.data(), &n), "vgicp_scan_from_map_keys");
   }
 
+  // The map checkpoint (include/vgicp_hip_map_checkpoint.h): the device map as one blob, restored slot for slot, so that a
+  // stopped session goes on with the bits it would have produced.  The file is the blob verbatim, then a trailer:
+  // "VGICPTRJ", u64 n, the n trajectory poses and prevTransform_ as 16 doubles each (column-major).  Written to
+  // path + ".tmp" and renamed.  Beside the drop-in calls: none of them changes its route.  Where the map's points live in
+  // the host's shadow grid (no deviceResident, or keepRawPoints without rawPointsOnDevice) both methods throw: the shadow
+  // grid is not restored.  A file whose raw-points flag or voxel_size is not this map's (voxel_size bit for bit) is
+  // refused before anything is loaded.  The trailer does not carry whether prevTransform_ was ever set by an insertion
+  // (hasPrevTransform_, which updateLocalMap sets with its first insertion): a load takes it to be set exactly when the
+  // trajectory is not empty, which is what it is after every update that inserted — every first update does.
+  void saveCheckpoint(const std::string & path)
+  {
+    requireCheckpoint("saveCheckpoint");
+    size_t bytes = 0;
+    shim::check(ctx_, vgicp_map_checkpoint_size(ctx_, &bytes), "vgicp_map_checkpoint_size");
+    std::vector<char> blob(bytes);
+    shim::check(ctx_, vgicp_map_checkpoint(ctx_, blob.size(), blob.data(), &bytes, nullptr), "vgicp_map_checkpoint");
+    const std::string tmp = path + ".tmp";
+    {
+      std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
+      out.write(blob.data(), static_cast<std::streamsize>(bytes));
+      out.write("VGICPTRJ", 8);
+      const uint64_t n = trajectory_.size();
+      out.write(reinterpret_cast<const char *>(&n), 8);
+      for (const Isometry3d & pose : trajectory_) {out.write(reinterpret_cast<const char *>(shim::poseData(pose)), 128);}
+      out.write(reinterpret_cast<const char *>(shim::poseData(prevTransform_)), 128);
+      out.flush();
+      if (!out) {throw std::runtime_error("LocalMap::saveCheckpoint: cannot write " + tmp);}
+    }
+    if (std::rename(tmp.c_str(), path.c_str()) != 0) {
+      throw std::runtime_error("LocalMap::saveCheckpoint: cannot rename " + tmp + " to " + path);
+    }
+  }
+  void loadCheckpoint(const std::string & path)
+  {
+    requireCheckpoint("loadCheckpoint");
+    std::ifstream in(path, std::ios::binary | std::ios::ate);
+    if (!in) {throw std::runtime_error("LocalMap::loadCheckpoint: cannot read " + path);}
+    const std::streamoff size = in.tellg();
+    std::vector<char> data(size > 0 ? static_cast<size_t>(size) : 0);
+    in.seekg(0);
+    if (!data.empty() && !in.read(data.data(), static_cast<std::streamsize>(data.size()))) {
+      throw std::runtime_error("LocalMap::loadCheckpoint: cannot read " + path);
+    }
+    uint64_t total = 0;
+    uint32_t flags = 0;
+    double voxel = 0.0;
+    if (data.size() >= VGICP_CHECKPOINT_HEADER_BYTES) {
+      std::memcpy(&total, data.data() + 16, 8);
+      std::memcpy(&voxel, data.data() + 24, 8);
+      std::memcpy(&flags, data.data() + 64, 4);
+    }
+    if (total < VGICP_CHECKPOINT_HEADER_BYTES || total > data.size()) {
+      throw std::runtime_error("LocalMap::loadCheckpoint: " + path + " holds no whole checkpoint");
+    }
+    // the trailer, if there is one, in full
+    uint64_t n = 0;
+    const bool trailer = data.size() > total;
+    if (trailer) {
+      const size_t rest = data.size() - static_cast<size_t>(total);
+      if (rest < 16 || std::memcmp(data.data() + total, "VGICPTRJ", 8) != 0) {
+        throw std::runtime_error("LocalMap::loadCheckpoint: " + path + " has no trajectory trailer behind the checkpoint");
+      }
+      std::memcpy(&n, data.data() + total + 8, 8);
+      if (n > (rest - 16) / 128 || rest != 16 + 128 * (static_cast<size_t>(n) + 1)) {
+        throw std::runtime_error("LocalMap::loadCheckpoint: the trajectory trailer of " + path + " is cut short");
+      }
+    }
+    if (((flags & VGICP_CHECKPOINT_RAW_POINTS) != 0) != rawOnDevice_) {
+      throw std::invalid_argument("LocalMap::loadCheckpoint: the checkpoint's raw-points flag is not this map's rawPointsOnDevice");
+    }
+    if (!(voxel == voxelSize_)) {
+      throw std::invalid_argument("LocalMap::loadCheckpoint: the checkpoint's voxel_size is not this map's voxelSize");
+    }
+    shim::check(ctx_, vgicp_map_restore(ctx_, data.data(), static_cast<size_t>(total), nullptr), "vgicp_map_restore");
+    if (!trailer) {return;}
+    const auto poseAt = [&data, total](uint64_t i) {
+        double m[16];
+        std::memcpy(m, data.data() + total + 16 + 128 * i, 128);
+        Isometry3d pose = Isometry3d::Identity();
+        for (int c = 0; c < 4; ++c) {
+          for (int r = 0; r < 4; ++r) {pose.matrix()(r, c) = m[4 * c + r];}
+        }
+        return pose;
+      };
+    trajectory_.clear();
+    for (uint64_t i = 0; i < n; ++i) {trajectory_.push_back(poseAt(i));}
+    prevTransform_ = poseAt(n);
+    hasPrevTransform_ = n > 0;
+  }
+  const std::vector<Isometry3d> & trajectory() const {return trajectory_;}
+  const Isometry3d & prevTransform() const {return prevTransform_;}
+
   // The ray report (include/vgicp_hip_map_rays.h): the first map voxel on every ray of the resident scan at a pose,
   // read-only — which returns appeared in front of the map's surface (VGICP_RAY_BEHIND), which rays the map blocks
   // (VGICP_RAY_BLOCKED: what carving would see through), per point and counted.  Like ICP::pointReport and carveTotals a
@@ -736,6 +837,18 @@ private:
     shim::check(
       ctx_, vgicp_set_option(ctx_, VGICP_OPTION_MAP_RAW_POINTS, rawOnDevice_ ? 1 : 0),
       "vgicp_set_option(VGICP_OPTION_MAP_RAW_POINTS)");
+  }
+  void requireCheckpoint(const char * method) const
+  {
+    const std::string who = std::string("LocalMap::") + method;
+    if (!vgicp_map_checkpoint_size || !vgicp_map_checkpoint || !vgicp_map_restore) {
+      throw std::runtime_error(who + ": the linked vgicp module has no map checkpoint (libvgicp_hip_map_checkpoint.so)");
+    }
+    if (!deviceResident_ || (keepRawPoints_ && !rawOnDevice_)) {
+      throw std::runtime_error(
+              who + ": the map's points live in the host's shadow grid, which a checkpoint does not restore "
+              "(deviceResident, and with keepRawPoints also rawPointsOnDevice)");
+    }
   }
   static double now()
   {
