@@ -7,6 +7,7 @@ not been built, importing the library raises; if there is no gfx950 device, `Con
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Optional
@@ -63,10 +64,11 @@ MAP_LEVELS_EXPORTS = ("vgicp_map_levels_build", "vgicp_map_level_size", "vgicp_m
 MAP_LOCATE_EXPORTS = ("vgicp_locate_resident",)
 MAP_SUBMAP_EXPORTS = ("vgicp_scan_from_map", "vgicp_scan_from_map_keys")
 MAP_CHECKPOINT_EXPORTS = ("vgicp_map_checkpoint_size", "vgicp_map_checkpoint", "vgicp_map_checkpoint_info", "vgicp_map_restore")
+MAP_MERGE_EXPORTS = ("vgicp_map_merge",)
 SIDE_EXPORTS = {"prior": PRIOR_EXPORTS, "points": POINTS_EXPORTS, "map_gated": MAP_GATED_EXPORTS,
                 "map_carve": MAP_CARVE_EXPORTS, "map_rays": MAP_RAYS_EXPORTS, "search_report": SEARCH_REPORT_EXPORTS,
                 "map_levels": MAP_LEVELS_EXPORTS, "map_locate": MAP_LOCATE_EXPORTS, "map_submap": MAP_SUBMAP_EXPORTS,
-                "map_checkpoint": MAP_CHECKPOINT_EXPORTS}
+                "map_checkpoint": MAP_CHECKPOINT_EXPORTS, "map_merge": MAP_MERGE_EXPORTS}
 
 
 def side_lib_path(name: str) -> str:
@@ -269,6 +271,35 @@ class SubmapResult:
     device_seconds: float
 
 
+class MergeParams(C.Structure):
+    """vgicp_merge_params (vgicp_hip_map_merge.h), 184 bytes."""
+    _fields_ = [("center", C.c_double * 3), ("radius", C.c_double), ("frame", C.c_double * 16), ("min_count", C.c_uint64),
+                ("max_count", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class MergeStats(C.Structure):
+    """vgicp_merge_stats (vgicp_hip_map_merge.h), 88 bytes."""
+    _fields_ = [("voxels", C.c_uint64), ("selected", C.c_uint64), ("too_far", C.c_uint64), ("too_few", C.c_uint64),
+                ("created", C.c_uint64), ("updated", C.c_uint64), ("frozen", C.c_uint64), ("points", C.c_uint64),
+                ("launches", C.c_int32), ("reserved", C.c_int32), ("seconds", C.c_double), ("device_seconds", C.c_double)]
+
+
+@dataclass
+class MergeResult:
+    """What Context.map_merge returns: the counts of vgicp_merge_stats and how the call ran."""
+    voxels: int
+    selected: int
+    too_far: int
+    too_few: int
+    created: int
+    updated: int
+    frozen: int
+    points: int
+    launches: int
+    seconds: float
+    device_seconds: float
+
+
 CHECKPOINT_FORMAT, CHECKPOINT_HEADER_BYTES, CHECKPOINT_RAW_POINTS, CHECKPOINT_RULES = 1, 128, 1, 14
 
 
@@ -441,6 +472,7 @@ PROTOTYPES = {
                              C.POINTER(LocateStats)],
     "vgicp_scan_from_map": [vp, vp, C.POINTER(SubmapParams), C.POINTER(SubmapStats)],
     "vgicp_scan_from_map_keys": [vp, sz, ip, C.POINTER(C.c_uint64), C.POINTER(sz)],
+    "vgicp_map_merge": [vp, vp, C.POINTER(MergeParams), C.POINTER(MergeStats)],
     "vgicp_prepare_search_report": [vp, C.POINTER(SearchReport)],
     "vgicp_map_checkpoint_size": [vp, C.POINTER(sz)],
     "vgicp_map_checkpoint": [vp, sz, vp, C.POINTER(sz), C.POINTER(CheckpointStats)],
@@ -1243,6 +1275,20 @@ class Context:
                                                        counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(w)))
         assert w.value == n, (w.value, n)
         return keys, counts
+
+    # -- map merge (vgicp_hip_map_merge.h) --
+    def map_merge(self, src: "Context", center=None, radius: float = math.inf, frame=None, min_count: int = 0,
+                  max_count: int = 0) -> "MergeResult":
+        """vgicp_map_merge: the voxels of `src`'s map whose centres lie within `radius` of `center` (the source map's
+        frame; default: all of them) and whose count is at least min_count, each moved by `frame` (4x4, source map ->
+        this map, default the identity), are folded into this context's map, weighted by their counts, in ascending slot
+        order of the source.  A voxel of this map that holds max_count points or more accepts nothing (0: no cap)."""
+        p = MergeParams((C.c_double * 3)(*[float(v) for v in ((0.0, 0.0, 0.0) if center is None else center)]), float(radius),
+                        (C.c_double * 16)(*pose_to_abi(np.eye(4) if frame is None else frame)), int(min_count), int(max_count), 0)
+        st = MergeStats()
+        self._check(self._lib.vgicp_map_merge(self._h, src._h, C.byref(p), C.byref(st)))
+        return MergeResult(int(st.voxels), int(st.selected), int(st.too_far), int(st.too_few), int(st.created), int(st.updated),
+                           int(st.frozen), int(st.points), st.launches, st.seconds, st.device_seconds)
 
     # -- map checkpoint (vgicp_hip_map_checkpoint.h) --
     def map_checkpoint_size(self) -> int:

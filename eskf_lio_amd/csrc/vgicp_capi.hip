@@ -41,5 +41,6 @@ std::atomic<uint64_t> g_context_ids{0};
 #include "vgicp_capi_map_locate.inl"
 #include "vgicp_capi_map_submap.inl"
 #include "vgicp_capi_map_checkpoint.inl"
+#include "vgicp_capi_map_merge.inl"
 #include "vgicp_capi_peers.inl"
 #include "vgicp_capi_multi_support.inl"

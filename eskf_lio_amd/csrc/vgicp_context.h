@@ -38,6 +38,7 @@
 #include "../../include/vgicp_hip_map_locate.h"
 #include "../../include/vgicp_hip_map_submap.h"
 #include "../../include/vgicp_hip_map_checkpoint.h"
+#include "../../include/vgicp_hip_map_merge.h"
 #include "vgicp_device.h"
 #include "vgicp_owned.h"
 #include "vgicp_align_plan.h"
@@ -49,6 +50,7 @@
 #include "vgicp_locate_plan.h"
 #include "vgicp_submap_plan.h"
 #include "vgicp_checkpoint_plan.h"
+#include "vgicp_merge_plan.h"
 
 using namespace vgicp;
 
@@ -541,6 +543,9 @@ struct vgicp_ctx {
   PinnedBuf<char> h_checkpoint;          // pinned: the blob on its way out (header room, then the payload) or in
   size_t checkpoint_capacity = 0;        // bytes h_checkpoint holds
   PinnedBuf<unsigned long long> h_checkpoint_totals;   // pinned, 4 words; .dev(): where the scan launch writes {FULL, TOMB, raw points}
+  // map merge (include/vgicp_hip_map_merge.h), as the DESTINATION of vgicp_map_merge; made by the first call.  The device
+  // side of a call is carved out of the staging area (d_stage); as the SOURCE a context lends ev_submap
+  PinnedBuf<unsigned long long> h_merge;   // pinned, kMergeTotalWords; .dev(): where the scan launch writes {selected, too far, too few}
   // raw points of the map (VGICP_OPTION_MAP_RAW_POINTS): the device append log of vgicp_device.h's RawLog.  Its three
   // device words sit behind the insertion's totals (d_ins_counters + 4), so the copy that brings those to the host in
   // the frame chain brings the log's fill too: the bound below is made exact at every synchronisation that settles an
@@ -763,6 +768,8 @@ int scan_from_map_keys(vgicp_ctx* dst, size_t capacity, int32_t* keys, uint64_t*
 int map_checkpoint_size(vgicp_ctx* ctx, size_t* bytes);
 int map_checkpoint(vgicp_ctx* ctx, size_t capacity, void* blob, size_t* written, vgicp_checkpoint_stats* stats);
 int map_restore(vgicp_ctx* ctx, const void* blob, size_t bytes, vgicp_checkpoint_stats* stats);
+// The entry point of include/vgicp_hip_map_merge.h behind libvgicp_hip_map_merge.so, likewise (vgicp_capi_map_merge.inl).
+int map_merge(vgicp_ctx* dst, vgicp_ctx* src, const vgicp_merge_params* params, vgicp_merge_stats* stats);
 bool align_needs_allocation(const vgicp_ctx* ctx, size_t n, int max_it);
 int reserve_for_align(vgicp_ctx* ctx, size_t n, int max_it);
 }  // namespace vgicp_internal

@@ -671,6 +671,31 @@ struct SubmapArgs {
   unsigned long long* counts;    // capacity
 };
 hipError_t launch_submap(hipStream_t s, const SubmapArgs& args, unsigned long long* totals_host);
+// Map merge (include/vgicp_hip_map_merge.h has the rule): the submap's MARK and SCAN over the source table as they are
+// (sub: its selection, frame, ballots, group counts and totals; sub.capacity = n), then MOVE-AND-CLAIM (a selected lane
+// transforms its record, finds or claims the slot in `table` and writes moved[rank], slot_in[rank], idx_in[rank] = rank;
+// ranks from the selected total up to n get kNoSlot), the library's stable sort of (slot, rank) and APPLY (the head of a
+// segment folds its contributors in rank order and writes the record once).  counters[0] += voxels created, counters[1]
+// += contributors that found the table full; totals (64-bit, kMergeTotalWords, zero before): [4] += voxels updated,
+// [5] += contributors frozen out, [6] += points accepted.  The source table is only read.
+struct MergeMoved;   // vgicp_merge_plan.h
+struct MergeArgs {
+  SubmapArgs sub;
+  VoxelRecord* table;            // the destination's
+  uint32_t mask;                 // its slots - 1
+  uint32_t n;                    // contributors the scratch holds: the source's voxel count as the host knows it
+  double voxel_size;             // the destination's
+  uint64_t max_count;            // 0: no cap
+  MergeMoved* moved;             // n
+  uint32_t* slot_in;             // n each; the sort leaves its result in (slot_out, idx_out)
+  uint32_t* idx_in;
+  uint32_t* slot_out;
+  uint32_t* idx_out;
+  void* split;                   // merge_sort_split_bytes(n)
+  uint32_t* counters;
+  unsigned long long* totals;
+};
+hipError_t launch_map_merge(hipStream_t s, const MergeArgs& args, unsigned long long* totals_host);
 // Map checkpoint (include/vgicp_hip_map_checkpoint.h has the format): the submap's three launches over the same groups,
 // with two ballots per 64 slots (FULL, TOMB).  MARK leaves the ballots, per ballot word the sum of its FULL records'
 // counts (word_raw, raw points only) and three counts per group; SCAN (one workgroup) turns the groups' counts into

@@ -46,11 +46,16 @@
 //
 // The map checkpoint (include/vgicp_hip_map_checkpoint.h) packs the table into a blob with the same three launches and two
 // ballots per word (FULL, TOMB), and the restore scatters a blob back slot for slot.
+//
+// Map merge (include/vgicp_hip_map_merge.h) folds the selected voxels of one table into another, weighted by their
+// counts: the submap's MARK and SCAN, a move-and-claim launch that shares the insertion's claim loop (claim_slot), the
+// insertion's sort of (slot, rank) and an apply launch that folds a voxel's contributors in the source's slot order.
 #include "vgicp_device.h"
 #include "vgicp_device_fn.h"
 #include "vgicp_sort.h"
 #include "vgicp_submap_plan.h"
 #include "vgicp_checkpoint_plan.h"
+#include "vgicp_merge_plan.h"
 
 namespace vgicp {
 namespace {
@@ -105,25 +110,9 @@ struct Pose12 {
   double v[12];
 };
 
-// One point of insert_prepare_kernel: transform, key, find-or-claim the slot. fresh: this thread created the
-// voxel; returns the slot or kNoSlot (table full).
-__device__ __forceinline__ uint32_t prepare_point(VoxelRecord* table, uint32_t mask, double voxel_size,
-                                                  const double* __restrict__ pts, const double* __restrict__ covs,
-                                                  uint32_t i, const Pose12& pose, double* __restrict__ wpts,
-                                                  double* __restrict__ wcovs, bool& fresh) {
-  double p[3], C[9], W[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) C[k] = covs[9 * (size_t)i + k];
-  transform_point(pose.v, pose.v + 9, pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], p);
-  rotate_cov_exact(pose.v, C, W);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) wpts[3 * (size_t)i + k] = p[k];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) wcovs[9 * (size_t)i + k] = W[k];
-  const int32_t kx = voxel_coord(p[0], voxel_size);
-  const int32_t ky = voxel_coord(p[1], voxel_size);
-  const int32_t kz = voxel_coord(p[2], voxel_size);
-
+// THE bounded claim loop, the insertion's and the merge's: the slot of the voxel with this key, found or claimed.  fresh:
+// this thread created the voxel; returns the slot or kNoSlot (table full).
+__device__ __forceinline__ uint32_t claim_slot(VoxelRecord* table, uint32_t mask, int32_t kx, int32_t ky, int32_t kz, bool& fresh) {
   uint32_t slot = voxel_hash(kx, ky, kz) & mask;
   uint32_t found = kNoSlot;
   // `spins` bounds the waits on LOCKED words so that a bug can only fail the call, never hang the GPU
@@ -157,6 +146,27 @@ __device__ __forceinline__ uint32_t prepare_point(VoxelRecord* table, uint32_t m
     ++probes;
   }
   return found;
+}
+
+// One point of insert_prepare_kernel: transform, key, find-or-claim the slot. fresh: this thread created the
+// voxel; returns the slot or kNoSlot (table full).
+__device__ __forceinline__ uint32_t prepare_point(VoxelRecord* table, uint32_t mask, double voxel_size,
+                                                  const double* __restrict__ pts, const double* __restrict__ covs,
+                                                  uint32_t i, const Pose12& pose, double* __restrict__ wpts,
+                                                  double* __restrict__ wcovs, bool& fresh) {
+  double p[3], C[9], W[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) C[k] = covs[9 * (size_t)i + k];
+  transform_point(pose.v, pose.v + 9, pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], p);
+  rotate_cov_exact(pose.v, C, W);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) wpts[3 * (size_t)i + k] = p[k];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) wcovs[9 * (size_t)i + k] = W[k];
+  const int32_t kx = voxel_coord(p[0], voxel_size);
+  const int32_t ky = voxel_coord(p[1], voxel_size);
+  const int32_t kz = voxel_coord(p[2], voxel_size);
+  return claim_slot(table, mask, kx, ky, kz, fresh);
 }
 
 // LISTS: idx_of receives the point's `next` on its voxel's list (index + 1 of the point that headed the list before;
@@ -1123,6 +1133,193 @@ __global__ __launch_bounds__(kRestoreBlock) void restore_raw_fill_kernel(Restore
   }
 }
 
+// ---- map merge (include/vgicp_hip_map_merge.h states the rule operation by operation; this restates it).  MARK and SCAN
+// are the submap's above, launched as they are ----
+// MOVE-AND-CLAIM.  The ranks as in the submap's EMIT, taken densely (below); the record moved by the same two device
+// functions; the key of the moved mean at the destination's voxel size; the insertion's claim loop; one 128-byte line per
+// contributor at its rank.
+// Before that every workgroup helps to fill the sort's input behind the last rank: SCAN's total is on the device only.
+__global__ __launch_bounds__(kSubmapBlock) void merge_move_kernel(MergeArgs m) {
+  static_assert(kSubmapGroupWords <= 64u, "a wave holds its group's ballots, one per lane");
+  static_assert(kSubmapGroupSlots <= 65536u, "a slot's place in its group fits 16 bits");
+  __shared__ uint32_t sums[2];
+  __shared__ uint16_t list[kSubmapGroupSlots];
+  const SubmapArgs& a = m.sub;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (tid < 2u) sums[tid] = 0u;
+  const unsigned long long total = a.totals[0];
+  const uint64_t selected = total < (unsigned long long)m.n ? total : m.n;
+  for (uint64_t t = selected + (uint64_t)blockIdx.x * kSubmapBlock + tid; t < m.n; t += (uint64_t)gridDim.x * kSubmapBlock) {
+    m.slot_in[t] = kNoSlot;
+    m.idx_in[t] = (uint32_t)t;
+  }
+  const unsigned long long mine = lane < kSubmapGroupWords ? a.ballots[(size_t)blockIdx.x * kSubmapGroupWords + lane] : 0ull;
+  const uint32_t pc = (uint32_t)__popcll(mine);
+  uint32_t incl = pc;
+#pragma unroll
+  for (int d = 1; d < (int)kSubmapGroupWords; d <<= 1) {
+    const uint32_t up = __shfl_up(incl, d, 64);
+    if (lane >= (uint32_t)d) incl += up;
+  }
+  if (__shfl(incl, (int)kSubmapGroupWords - 1, 64) == 0u) return;   // the whole group, so the whole workgroup
+  const uint32_t excl = incl - pc;
+  const uint32_t base = a.group_counts[blockIdx.x];
+  unsigned long long word[kSubmapPer];
+  uint32_t before[kSubmapPer];
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k) {   // every lane takes part in the cross-lane reads
+    const int q = (int)(k * (kSubmapBlock / 64u) + wave);
+    word[k] = __shfl(mine, q, 64);
+    before[k] = __shfl(excl, q, 64);
+  }
+  // The group's selected slots, in rank order, into LDS; then the lanes take them DENSELY, one contributor per lane: the
+  // claim is a chain of dependent memory round trips per wave, and a table is mostly empty slots — taken where the bits
+  // stand (a wave per 64 slots and turn) a wave would run that chain for one or a few lanes at a time
+#pragma unroll
+  for (uint32_t k = 0; k < kSubmapPer; ++k)
+    if ((word[k] >> lane) & 1ull)
+      list[before[k] + (uint32_t)__popcll(word[k] & ((1ull << lane) - 1ull))] = (uint16_t)(kSubmapBlock * k + tid);
+  const uint32_t group_total = __shfl(incl, (int)kSubmapGroupWords - 1, 64);   // <= kSubmapGroupSlots
+  __syncthreads();   // behind the list, and behind the zeroing of sums
+  uint32_t created = 0, lost = 0;
+#pragma unroll 1
+  for (uint32_t at = tid; at < group_total; at += kSubmapBlock) {
+    const size_t rank = (size_t)base + at;
+    if (rank >= m.n) continue;   // the host sizes the scratch for every voxel of the source; this is the belt
+    const VoxelRecord* rec = a.table + ((uint64_t)blockIdx.x * kSubmapGroupSlots + list[at]);
+    const double2* pay = reinterpret_cast<const double2*>(rec->mean);   // 16-byte aligned
+    const double2 p0 = pay[0], p1 = pay[1], p2 = pay[2], p3 = pay[3], p4 = pay[4], p5 = pay[5];
+    const unsigned long long count = rec->count;
+    const double C[9] = {p1.y, p2.x, p2.y, p3.x, p3.y, p4.x, p4.y, p5.x, p5.y};
+    double v[kScanPlanes];
+    transform_point(a.pose, a.pose + 9, p0.x, p0.y, p1.x, v);
+    rotate_cov_exact(a.pose, C, v + 3);
+    bool fresh = false;
+    const uint32_t found = claim_slot(m.table, m.mask, voxel_coord(v[0], m.voxel_size), voxel_coord(v[1], m.voxel_size),
+                                      voxel_coord(v[2], m.voxel_size), fresh);
+    created += fresh ? 1u : 0u;
+    lost += found == kNoSlot ? 1u : 0u;
+    double2* out = reinterpret_cast<double2*>(m.moved + rank);   // the line: 6 x 16 bytes of statistics, then {count, slot}
+#pragma unroll
+    for (int e = 0; e < 6; ++e) out[e] = make_double2(v[2 * e], v[2 * e + 1]);
+    m.moved[rank].count = count;
+    m.moved[rank].slot = found;
+    m.slot_in[rank] = found;
+    m.idx_in[rank] = (uint32_t)rank;
+  }
+  // one atomic per workgroup and counter
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    created += __shfl_down(created, d, 64);
+    lost += __shfl_down(lost, d, 64);
+  }
+  if (lane == 0u) {
+    if (created) atomicAdd(&sums[0], created);
+    if (lost) atomicAdd(&sums[1], lost);
+  }
+  __syncthreads();
+  if (tid < 2u && sums[tid]) atomicAdd(&m.counters[tid], sums[tid]);
+}
+
+// one entry of the fold: (nn * x + cc * y) / n1, every operation rounded once
+__device__ __forceinline__ double merge_entry(double nn, double x, double cc, double y, double n1) {
+#pragma clang fp contract(off)
+  const double a = nn * x, b = cc * y;
+  const double s = a + b;
+  return s / n1;
+}
+// The workgroup's 64-bit sums of every lane's two values, for thread 0 (every thread of a kBlock workgroup calls this).
+__device__ __forceinline__ void merge_block_sums(unsigned long long& u, unsigned long long& v) {
+  __shared__ unsigned long long part[2][kBlock / 64];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    u += __shfl_down(u, (unsigned int)d, 64);
+    v += __shfl_down(v, (unsigned int)d, 64);
+  }
+  if ((threadIdx.x & 63u) == 0u) {
+    part[0][threadIdx.x >> 6] = u;
+    part[1][threadIdx.x >> 6] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0u) return;
+  u = v = 0ull;
+#pragma unroll
+  for (uint32_t w = 0; w < kBlock / 64; ++w) {
+    u += part[0][w];
+    v += part[1][w];
+  }
+}
+// APPLY.  The head of the segment that starts at sorted position j folds its contributors, in rank order, into the
+// destination record's state in registers and writes the record once — not at all when nothing was accepted.  Every slot
+// and every rank read from the sort's output is checked against its capacity before it indexes anything.
+__global__ __launch_bounds__(kBlock) void merge_apply_kernel(MergeArgs m) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t slot = kNoSlot;
+  bool head = false;
+  if (j < m.n) {
+    slot = m.slot_out[j];
+    head = slot != kNoSlot && slot <= m.mask && !(j > 0 && m.slot_out[j - 1] == slot);
+  }
+  bool updated = false;
+  unsigned long long frozen = 0ull, points = 0ull;
+  if (head) {
+    VoxelRecord* rec = m.table + slot;
+    const uint64_t before = rec->count;
+    uint64_t count = before;
+    double s[12];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = rec->mean[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[3 + k] = rec->cov[k];
+    bool accepted = false;
+    for (uint32_t q = j; q < m.n && m.slot_out[q] == slot; ++q) {
+      const uint32_t i = m.idx_out[q];
+      if (i >= m.n) continue;
+      if (m.max_count != 0ull && count >= m.max_count) {   // frozen: the contributor's line is not read
+        ++frozen;
+        continue;
+      }
+      const double2* in = reinterpret_cast<const double2*>(m.moved + i);
+      double c[12];
+#pragma unroll
+      for (int e = 0; e < 6; ++e) {
+        const double2 p = in[e];
+        c[2 * e] = p.x;
+        c[2 * e + 1] = p.y;
+      }
+      const uint64_t cnt = m.moved[i].count;
+      if (count == 0) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) s[k] = c[k];
+        count = cnt;
+      } else {
+        const double nn = (double)count, cc = (double)cnt, n1 = (double)(count + cnt);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) s[k] = merge_entry(nn, s[k], cc, c[k], n1);
+        count += cnt;
+      }
+      points += cnt;
+      accepted = true;
+    }
+    if (accepted) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) rec->mean[k] = s[k];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) rec->cov[k] = s[3 + k];
+      rec->count = count;
+      updated = before != 0;
+    }
+  }
+  // one atomic per workgroup and counter
+  const int n_updated = __syncthreads_count(updated ? 1 : 0);
+  merge_block_sums(frozen, points);
+  if (threadIdx.x == 0u) {
+    if (n_updated) atomicAdd(&m.totals[4], (unsigned long long)n_updated);
+    if (frozen) atomicAdd(&m.totals[5], frozen);
+    if (points) atomicAdd(&m.totals[6], points);
+  }
+}
+
 }  // namespace
 
 size_t map_insert_scratch_bytes(uint32_t n) {
@@ -1212,6 +1409,24 @@ hipError_t launch_submap(hipStream_t s, const SubmapArgs& a, unsigned long long*
   counted_launch(submap_mark_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
   counted_launch(submap_scan_kernel, dim3(1), dim3(1024), 0, s, a.group_counts, a.groups, a.totals, totals_host);
   counted_launch(submap_emit_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_merge(hipStream_t s, const MergeArgs& m, unsigned long long* totals_host) {
+  const SubmapArgs& a = m.sub;
+  if (!m.table || !a.table || m.n == 0 || a.groups == 0 || ((uint64_t)m.mask & ((uint64_t)m.mask + 1)) != 0) return hipErrorInvalidValue;
+  // the plan sizes the splitters' room without the sort's header: it must hold what the sort asks for
+  if (merge_sort_split_bytes(m.n) < sortk::split_bytes(m.n, sizeof(uint32_t))) return hipErrorInvalidValue;
+  counted_launch(submap_mark_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, a);
+  counted_launch(submap_scan_kernel, dim3(1), dim3(1024), 0, s, a.group_counts, a.groups, a.totals, totals_host);
+  counted_launch(merge_move_kernel, dim3(a.groups), dim3(kSubmapBlock), 0, s, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // stable: equal slots keep ascending rank = the source's slot order (the inputs are scratch from here on)
+  e = sortk::sort_pairs(m.slot_in, m.idx_in, m.slot_out, m.idx_out, m.split, m.n, s);
+  if (e != hipSuccess) return e;
+  g_kernel_launches += sortk::launches_for(m.n);
+  counted_launch(merge_apply_kernel, dim3(blocks_for(m.n, kBlock)), dim3(kBlock), 0, s, m);
   return hipGetLastError();
 }
 

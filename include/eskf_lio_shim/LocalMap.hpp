@@ -47,6 +47,7 @@
 #include "../vgicp_hip_map_levels.h"
 #include "../vgicp_hip_map_submap.h"
 #include "../vgicp_hip_map_checkpoint.h"
+#include "../vgicp_hip_map_merge.h"
 
 // The raw-point store's entry points (vgicp_hip_map_points.h, and vgicp_set_option for its option) are referenced
 // weakly, so a program that links a stand-in of the C ABI without them (tests/native/shadow_stress.cpp) still links: a
@@ -76,6 +77,8 @@
 #pragma weak vgicp_map_checkpoint_size
 #pragma weak vgicp_map_checkpoint
 #pragma weak vgicp_map_restore
+// ... and the map merge's (vgicp_hip_map_merge.h, in libvgicp_hip_map_merge.so): without that library mergeFrom refuses.
+#pragma weak vgicp_map_merge
 #include "ShimTypes.hpp"
 #include "ShimSupport.hpp"
 #include "ResidentScan.hpp"
@@ -657,6 +660,57 @@ public:
     keys.assign(3 * n, 0);
     counts.assign(n, 0);
     shim::check(ctx_, vgicp_scan_from_map_keys(ctx_, n, keys.data(), counts.data(), &n), "vgicp_scan_from_map_keys");
+  }
+
+  // Map merge (include/vgicp_hip_map_merge.h): the voxels of `source` whose centres lie within `radius` of `center` (in
+  // source's frame; infinity: all of them) and that hold at least minCount points are moved by `frame` (source's map ->
+  // this map: the pose ICP::alignSubmap returned, times the anchor's inverse) and folded into THIS map, each weighted by
+  // its count, on the device.  A voxel of this map that holds maxCount points or more accepts nothing (0: no cap).
+  // Beside the drop-in calls: none of them changes its route, and the resident scan stays.  Both maps must keep their
+  // voxels on the device; where this map's points live in the host's shadow grid (no deviceResident, or keepRawPoints
+  // without rawPointsOnDevice) the method throws, as loadCheckpoint does: the shadow grid would not see the merged voxels
+  // (with rawPointsOnDevice the module refuses: a merged voxel has no point list to keep).
+  struct MergeStats
+  {
+    uint64_t voxels = 0, selected = 0, tooFar = 0, tooFew = 0, created = 0, updated = 0, frozen = 0, points = 0;
+    double seconds = 0.0, deviceSeconds = 0.0;
+  };
+  MergeStats mergeFrom(
+    const LocalMap & source, const Isometry3d & frame, const Vector3d & center, double radius, size_t minCount = 0,
+    size_t maxCount = 0)
+  {
+    if (!vgicp_map_merge) {
+      throw std::runtime_error("LocalMap::mergeFrom: the linked vgicp module has no vgicp_map_merge (libvgicp_hip_map_merge.so)");
+    }
+    if (!deviceResident_ || !source.deviceResident_) {
+      throw std::runtime_error("LocalMap::mergeFrom: both maps must be device-resident");
+    }
+    if (keepRawPoints_ && !rawOnDevice_) {
+      throw std::runtime_error(
+              "LocalMap::mergeFrom: the map's points live in the host's shadow grid, which a merge does not reach "
+              "(deviceResident, and without keepRawPoints)");
+    }
+    vgicp_merge_params p{};
+    for (int a = 0; a < 3; ++a) {p.center[a] = center.data()[a];}
+    p.radius = radius;
+    const double * f = shim::poseData(frame);
+    for (int e = 0; e < 16; ++e) {p.frame[e] = f[e];}
+    p.min_count = minCount;
+    p.max_count = maxCount;
+    vgicp_merge_stats st{};
+    shim::check(ctx_, vgicp_map_merge(ctx_, source.ctx_, &p, &st), "vgicp_map_merge");
+    MergeStats out;
+    out.voxels = st.voxels;
+    out.selected = st.selected;
+    out.tooFar = st.too_far;
+    out.tooFew = st.too_few;
+    out.created = st.created;
+    out.updated = st.updated;
+    out.frozen = st.frozen;
+    out.points = st.points;
+    out.seconds = st.seconds;
+    out.deviceSeconds = st.device_seconds;
+    return out;
   }
 
   // The map checkpoint (include/vgicp_hip_map_checkpoint.h): the device map as one blob, restored slot for slot, so that a
